@@ -15,10 +15,19 @@ tests/test_parity_gpu.py::test_sampler_end_to_end_vs_golden and tests/test_scale
 VQ codes stay bit-exact because the encoder always runs in the fp32 mode).  bf16 is faster by ~1 % and outside
 the gate (2.6e-3); fp32 (3-term split MFMA) is the 5e-6 parity mode.
 
-`--gpus N` with N > 1 and no torchrun environment re-executes itself under `python -m torch.distributed.run
---nproc-per-node N` (one rank per GPU, RCCL); a line is printed only if the process group really has N ranks.
+`--gpus N` with N > 1 and no torchrun environment starts itself again as a child under `python -m torch.distributed.run
+--nproc-per-node N` (one rank per GPU, RCCL) and exits with its status; a line is printed only if the process group really has
+N ranks.
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line: `metric`, `value` (clips/s over the `--steps` timed steps), `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` (wall milliseconds of one timed step) and the run's configuration.  A plain run does nothing else: it sets up,
+warms up, times the steps and prints the line.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step computed -- the finished clips rank 0 receives -- as
+DIR/x0.npy (float32 [clips, 1, T]; beyond 60 MiB a fixed, seeded sample of whole clips).  The inputs of a step depend only on the
+arguments, so two builds can be compared output for output.
+
+`--full` adds the measurements below (each still switched off by its own --no-* option):
   roofline     - the dominant kernel (fused MFMA conv): algorithmic bytes of all its launches in one
                  forward / their summed duration, measured live with hipEvents on the launch stream
                  (per-launch brackets minus the measured bracket overhead = the launches back to back, what
@@ -65,7 +74,32 @@ def parse():
     ap.add_argument("--no-other-configs", action="store_true", help="skip BASELINE configs 2, 4 and 5 (one timed batch each)")
     ap.add_argument("--init-only", action="store_true", help="stop after process-group initialisation (launch-path self test)")
     ap.add_argument("--T", type=int, default=64000)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure roofline, CPU baseline, other modes and other configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's clips to DIR/x0.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_BYTES = 60 * 2 ** 20  # --dump-outputs budget (the .npy header comes on top)
+
+
+def dump_outputs(d: str, x0) -> None:
+    """The finished clips of the last timed step as d/x0.npy, float32.  A batch larger than DUMP_BYTES keeps a fixed, seeded sample
+    of whole clips in clip order (a clip longer than the budget: its first DUMP_BYTES / 4 samples)."""
+    import numpy as np
+
+    x = x0.detach().float().cpu()
+    per_clip = x[0].numel() * 4
+    keep = DUMP_BYTES // per_clip
+    if keep == 0:
+        x = x[:1].reshape(1, -1)[:, : DUMP_BYTES // 4].reshape(1, x.shape[1], -1)
+    elif x.shape[0] > keep:
+        idx = torch.randperm(x.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        x = x[idx]
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "x0.npy"), x.contiguous().numpy())
 
 
 def cpu_baseline(base: int, T: int, sample_steps: int):
@@ -185,14 +219,18 @@ def free_port() -> int:
 
 
 def relaunch(n: int) -> None:
-    """`python bench.py --gpus N` outside torchrun: become `python -m torch.distributed.run --nproc-per-node N bench.py ...`
-    (same arguments, same stdout), one rank per GPU."""
+    """`python bench.py --gpus N` outside torchrun: run `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child
+    process (same arguments, same stdout), one rank per GPU, and exit with its status."""
+    import subprocess
+
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC: what RCCL needs on this driver
-    os.environ.setdefault("OMP_NUM_THREADS", "8")
+    env = dict(os.environ)
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC: what RCCL needs on this driver
+    env.setdefault("OMP_NUM_THREADS", "8")
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    rc = subprocess.run(cmd, env=env).returncode
+    sys.exit(rc if rc >= 0 else 128 - rc)
 
 
 def main():
@@ -202,7 +240,7 @@ def main():
     if not launched and a.gpus > 1:
         if backend == "nccl" and torch.cuda.device_count() < a.gpus:
             sys.exit(f"bench.py: --gpus {a.gpus} but only {torch.cuda.device_count()} GPU(s) are visible")
-        relaunch(a.gpus)  # does not return
+        relaunch(a.gpus)  # exits with the child's status
     world = int(os.environ.get("WORLD_SIZE", "1")) if launched else 1
     rank = int(os.environ.get("RANK", "0")) if launched else 0
     local_rank = int(os.environ.get("LOCAL_RANK", "0")) if launched else 0
@@ -292,6 +330,8 @@ def main():
         dt = float(tt.item())
     if rank == 0:
         assert out is not None and out.shape == (n_total, 1, a.T) and bool(torch.isfinite(out).all())
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, out)
 
     # ---- live per-kernel timing of one forward (hipEvents on the launch stream), rank 0 ----
     def kernel_roofline(prec):
@@ -400,9 +440,10 @@ def main():
                 "mfma_tflops": round(conv["flops"] / (conv_ms * 1e-3) / 1e12, 1)}
         return h, per_kind, roof
 
+    # everything below up to the line is --full only: a plain run reports the timed steps and nothing else
     roof = None
     extra = {}
-    if rank == 0:
+    if rank == 0 and a.full:
         h, per_kind, roof = kernel_roofline(a.precision)
         B = end - begin
         fwd_ms = sum(d["ms"] for d in per_kind.values())
@@ -417,12 +458,12 @@ def main():
         }
 
     cpu = None
-    if rank == 0 and not a.no_cpu_baseline and n_gpus == 1:
+    if rank == 0 and a.full and not a.no_cpu_baseline and n_gpus == 1:
         cpu = cpu_baseline(base, a.T, a.sample_steps)
 
     # the same workload in the other two precision modes (--other-steps samples each), so that all three are on record side by side
     others = None
-    if rank == 0 and n_gpus == 1 and not a.no_other_modes:
+    if rank == 0 and a.full and n_gpus == 1 and not a.no_other_modes:
         # (accuracy is NOT measured in this run: the modes are held to the gate by the -m gpu tests, on this very workload by
         #  tests/test_scale_gpu.py::test_headline_workload_vs_reference_fixture, fixture F6b made from the reference)
         notes = {"fp32": "parity mode: fp32 storage, 3-term bf16-split MFMA (gate: tests, fixture F6b)",
@@ -451,7 +492,7 @@ def main():
     # BASELINE.json's other configurations (2, 4, 5) at their per-GPU share, in the headline's precision mode: one timed batch each
     # after one warm-up batch (tools/bench_configs.py is the builder-run form of the same measurement, profiles/r06_configs_1gpu.json)
     other_cfgs = None
-    if rank == 0 and n_gpus == 1 and not a.no_other_configs and a.T == 64000:
+    if rank == 0 and a.full and n_gpus == 1 and not a.no_other_configs and a.T == 64000:
         other_cfgs = other_configs(dev, a.precision, a.T)
 
     if rank == 0:

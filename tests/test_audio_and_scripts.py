@@ -225,7 +225,7 @@ def test_bench_distributed_branch_two_ranks_on_one_gpu():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--model", "unet32", "--batch", "3", "--sample-steps", "2",
-                        "--steps", "2", "--warmup", "1", "--T", "4096", "--no-cpu-baseline", "--no-other-modes"],
+                        "--steps", "2", "--warmup", "1", "--T", "4096", "--full", "--no-cpu-baseline", "--no-other-modes"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -233,3 +233,32 @@ def test_bench_distributed_branch_two_ranks_on_one_gpu():
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["config"]["global_batch"] == 6 and out["steps"] == 2 and out["value"] > 0
     assert out["dtype"] == "fp16" and out["scaling"] == "weak" and out["roofline"]["frac"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run reports the timed steps only (no --full objects), and --dump-outputs writes the last timed step's clips:
+    float32 [clips, 1, T], finite, bitwise the same in two runs with the same arguments."""
+    import json
+    import subprocess
+    import sys
+
+    got = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--model", "unet32", "--batch", "3",
+                            "--sample-steps", "2", "--steps", "3", "--warmup", "1", "--T", "4096", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+        assert out["unit"] == "clips/s" and out["higher_is_better"] is True and out["dtype"] == "fp16"
+        assert abs(out["value"] - 3 * 1e3 / out["ms_per_step"]) < 0.02 * out["value"]
+        assert out["roofline"] is None and out["cpu_baseline"] is None and out["other_modes"] is None and out["other_configs"] is None
+        assert sorted(os.listdir(d)) == ["x0.npy"]
+        x = np.load(d / "x0.npy")
+        assert x.dtype == np.float32 and x.shape == (3, 1, 4096) and np.isfinite(x).all() and np.abs(x).max() > 0
+        got.append(x)
+    assert np.array_equal(got[0], got[1])

@@ -216,6 +216,27 @@ def test_bench_refuses_world_size_mismatch():
     assert "refusing to report" in r.stderr
 
 
+def test_bench_dump_outputs_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 clips as they are while they fit the budget, else a fixed, seeded sample of whole clips in clip order."""
+    import numpy as np
+
+    import bench
+
+    x = torch.randn(10, 1, 100, generator=torch.Generator().manual_seed(5), dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "all"), x)
+    y = np.load(tmp_path / "all" / "x0.npy")
+    assert y.dtype == np.float32 and np.array_equal(y, x.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 3 * 100 * 4)
+    samples = []
+    for tag in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / tag), x)
+        samples.append(np.load(tmp_path / tag / "x0.npy"))
+        assert os.path.getsize(tmp_path / tag / "x0.npy") <= 3 * 100 * 4 + 128
+    assert samples[0].shape == (3, 1, 100) and np.array_equal(samples[0], samples[1])
+    rows = [int(np.flatnonzero((y == s).all(axis=(1, 2)))[0]) for s in samples[0]]
+    assert rows == sorted(set(rows))
+
+
 def test_weight_snapshot_token_and_copies():
     """The device snapshot key follows in-place parameter updates (the reference reads live parameters), and
     modules deep-copy / pickle without a handle; index validation raises like nn.Embedding."""

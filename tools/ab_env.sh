@@ -10,7 +10,7 @@ for i in $(seq $R); do
 done
 for i in $(seq $R); do
   for v in $A $B; do
-    env $VAR=$v python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-modes --no-other-configs 2>/dev/null | python -c "
+    env $VAR=$v python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-other-modes --no-other-configs 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$VAR=$v', d['value'], 'clips/s  conv', r['conv_ms_per_forward'], 'ms  frac', r['frac'])"
   done
 done

@@ -4,15 +4,16 @@
 # summary of the same bench command (labelled by mode: the bench runs ONLY that mode, --no-other-modes), and the per-launch
 # HBM traffic from two separate --pmc passes (FETCH_SIZE, WRITE_SIZE; MI355X_MICROARCH.md: never combined with other traces).
 PREC=${1:-fp16}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 TAG=${2:-meas_$PREC}
 cd $GRAFT_REPO_ROOT
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-timeout 900 python bench.py --precision $PREC > $OUT/bench_$PREC.json 2> $OUT/bench_$PREC.err; tail -c 400 $OUT/bench_$PREC.json
+timeout 900 python bench.py --full --precision $PREC > $OUT/bench_$PREC.json 2> $OUT/bench_$PREC.err; tail -c 400 $OUT/bench_$PREC.json
 timeout 300 python tools/profile_ops.py --precision $PREC > $OUT/ops_unet64_$PREC.txt 2>&1
 cd /tmp && rm -rf /tmp/prof_stats
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o stats -- python $GRAFT_REPO_ROOT/bench.py --precision $PREC --steps 2 --warmup 0 --no-cpu-baseline --no-other-modes --no-other-configs > $OUT/bench_under_rocprof_$PREC.json 2> $OUT/bench_under_rocprof_$PREC.err
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o stats -- python $REPO/bench.py --full --precision $PREC --steps 2 --warmup 0 --no-cpu-baseline --no-other-modes --no-other-configs > $OUT/bench_under_rocprof_$PREC.json 2> $OUT/bench_under_rocprof_$PREC.err
 cp $(find /tmp/prof_stats -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats_$PREC.csv
 head -5 $OUT/kernel_stats_$PREC.csv
 if [ "$3" != "nopmc" ]; then
