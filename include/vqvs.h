@@ -178,6 +178,22 @@ int vqvs_classifier_forward(vqvs_model* m, const float* d_x, const float* d_ts, 
  *   d_labels [B] int64, d_grad [B,1,T] f32 out, d_logits [B,num_labels] f32 out or NULL */
 int vqvs_classifier_guidance(vqvs_model* m, const float* d_x, const float* d_ts, const int64_t* d_labels, float scale,
                              float* d_grad, float* d_logits, int B, int T, void* stream);
+/* feat = Classifier.stem(x, ts), the vector reference stat_generate.py:36-38 collects: the attention pool's c_proj output at
+ * the query token (models/classifier.py:111-121, 153-158), before the head's GELU and Linear.  Forward schedule only (never
+ * the backward phase); all three precision modes.  F = output_mult * base_channels.
+ *   d_x [B,1,T] f32, d_ts [B] f32 -> d_feat [B,F] f32, d_logits [B,num_labels] f32 or NULL,
+ *   d_probs [B,num_labels] f32 (softmax of the logits, stat_generate.py:39) or NULL */
+int vqvs_classifier_features(vqvs_model* m, const float* d_x, const float* d_ts, float* d_feat,
+                             float* d_logits, float* d_probs, int B, int T, void* stream);
+
+/* ---- feature statistics (reference stat_generate.py:44-45: np.mean / np.cov over every clip's features) ---------------
+ * Streaming moments about a shift K (handle-less):
+ *   d_s1[F] += sum_b (f_b - K);  d_s2[F*F] += sum_b (f_b - K)(f_b - K)^T   (double accumulators, full symmetric matrix)
+ *   d_feat [B,F] f32, d_shift [F] f32, d_s1 [F] f64 in/out, d_s2 [F,F] f64 in/out; B >= 1, F in 1..8192.
+ * f64 throughout (differences formed in f64 from the f32 inputs, f64 MFMA products and sums).  Deterministic: every output
+ * element is owned by one workgroup that walks b in a fixed order (no atomics), so the same sequence of calls gives
+ * bitwise-identical accumulators.  Null pointers and bad sizes return VQVS_ERR_ARG before touching the device. */
+int vqvs_feature_moments(const float* d_feat, int B, int F, const float* d_shift, double* d_s1, double* d_s2, void* stream);
 
 /* ---- encoder-predictor guidance ---------------------------------------------------
  * logits = EncoderPredictor.forward(x, ts)   reference models/encoder_predictor.py:43-58: UNetPredictor with a

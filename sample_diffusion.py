@@ -4,7 +4,9 @@ Sample waveforms from a diffusion model on MI355X.  Counterpart of the reference
 (same flags; reference sample_diffusion.py:125-141), running on the gfx950 library: x_T ~ N(0,1), optional
 class labels (uniform or --target-class), `ddpm_sample`, one 16 kHz mono s16 WAV per clip.
 Differences: WAV files are written directly (no ffmpeg); `--schedule` accepts "lambda t: t" / "lambda t: t**P"
-without eval; `--seed`, `--precision` are new.  Classifier guidance (`--classifier-path`, reference
+without eval; `--seed`, `--precision` are new; so are `--stats-classifier`, `--stats-path`, `--stats-precision`, which score the run in
+line: every written clip, as the WAV file holds it, goes through the classifier's stem at t = 0 and into the feature
+statistics that stat_generate.py computes from the files (same npz).  Classifier guidance (`--classifier-path`, reference
 sample_diffusion.py:30-42) runs on the same library: the classifier forward and the gradient of log p(y | x_t)
 are `vqvs_classifier_guidance` (explicit HIP backward schedule, no autograd).
 """
@@ -18,7 +20,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from vq_voice_swap_amd import Classifier, DiffusionModel, randn_clips  # noqa: E402
+from vq_voice_swap_amd import Classifier, DiffusionModel, FeatureStats, randn_clips, wav_roundtrip  # noqa: E402
 from vq_voice_swap_amd.audio import ChunkWriter, parse_time_schedule  # noqa: E402
 
 
@@ -38,7 +40,20 @@ def arg_parser():
     p.add_argument("--encoding", default="linear", type=str)
     p.add_argument("--seed", default=None, type=int)
     p.add_argument("--precision", default="fp32", choices=["fp32", "fp16", "bf16"])
+    p.add_argument("--stats-classifier", default=None, type=str, help="classifier checkpoint for in-line feature statistics")
+    p.add_argument("--stats-path", default=None, type=str, help="npz of the in-line statistics (stat_generate.py's format)")
+    p.add_argument("--stats-precision", default="fp32", choices=["fp32", "fp16", "bf16"])
     return p
+
+
+def parse_args(argv=None):
+    parser = arg_parser()
+    args = parser.parse_args(argv)
+    if (args.stats_classifier is None) != (args.stats_path is None):
+        parser.error("--stats-classifier and --stats-path must be given together")
+    if args.stats_path is not None and (args.num_samples is None or args.num_samples < 2):
+        parser.error("--stats-path needs --num-samples of at least 2 (a covariance needs two clips)")
+    return args
 
 
 def sample_labels(args, num_labels, n, device, gen):
@@ -76,7 +91,7 @@ def write_clip(path, seq, encoding):
 
 
 def main(argv=None):
-    args = arg_parser().parse_args(argv)
+    args = parse_args(argv)
     schedule = parse_time_schedule(args.schedule)
     model = DiffusionModel.load(args.checkpoint_path)
     if not torch.cuda.is_available():
@@ -95,15 +110,28 @@ def main(argv=None):
     if args.num_samples is None:
         write_clip(args.sample_path, sample_batch(args, model, classifier, device, 1, seed, 0, schedule, gen)[0], args.encoding)
         return
+    stats_clf = stats = None
+    if args.stats_path is not None:
+        stats_clf = Classifier.load(args.stats_classifier).to(device)
+        stats_clf.eval()
+        stats_clf.set_precision(args.stats_precision)
+        stats = FeatureStats(stats_clf.feature_dim, device)
     os.mkdir(args.sample_path)
     count = 0
     for b in range(int(math.ceil(args.num_samples / args.batch_size))):
         sample = sample_batch(args, model, classifier, device, args.batch_size, seed, b * args.batch_size, schedule, gen)
+        if stats is not None:  # the clips this batch contributes, as their WAV files will hold them (stat_generate.py reads those)
+            feat, probs = stats_clf.features(wav_roundtrip(sample[: args.num_samples - count], args.encoding), return_probs=True)
+            stats.update(feat)
+            stats.add_probs(probs)
         for seq in sample:
             if count == args.num_samples:
                 break
             write_clip(os.path.join(args.sample_path, f"sample_{count:06}.wav"), seq, args.encoding)
             count += 1
+    if stats is not None:
+        print(f"classifier score: {stats.class_score()}")
+        stats.save(args.stats_path)
 
 
 if __name__ == "__main__":

@@ -13,6 +13,7 @@ from .conv_encoder import ConvMFCCEncoder
 from .diffusion import CosSchedule, Diffusion, ExpSchedule, Schedule, make_schedule, randn_clips
 from .diffusion_model import DiffusionModel
 from .encoder_predictor import EncoderPredictor
+from .stats import FeatureStats, class_score, frechet_distance, wav_roundtrip
 from .unet import ResBlockModule, UNetEncoder, UNetPredictor
 from .vq import VQ
 from .vq_vae import VQVAE
@@ -20,4 +21,5 @@ from .vq_vae import VQVAE
 __all__ = [
     "Savable", "atomic_save", "CosSchedule", "Diffusion", "ExpSchedule", "Schedule", "make_schedule", "randn_clips",
     "DiffusionModel", "Classifier", "ConvMFCCEncoder", "EncoderPredictor", "ResBlockModule", "UNetEncoder", "UNetPredictor", "VQ", "VQVAE",
+    "FeatureStats", "class_score", "frechet_distance", "wav_roundtrip",
 ]

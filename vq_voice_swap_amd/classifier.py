@@ -79,7 +79,8 @@ class Classifier(_NativeModule, Savable):
         check_topology(self.stem.base_channels, self.stem.channel_mult, self.stem.depth_mult, ())  # (classifier.py:52-58: any of these)
         if int(self.stem.output_mult) != self.stem.output_mult or not 1 <= self.stem.output_mult * self.stem.base_channels <= 4096:
             raise ValueError(f"output_mult={self.stem.output_mult}: the feature width must be in 1..4096")
-        self.out = _seq(None, _scaled(nn.Linear(self.stem.out_channels, num_labels), 0.0))
+        # (a real GELU, parameter-free: `clf.out(clf.features(x, ts))` is the reference's classifier.out(fv), stat_generate.py:39)
+        self.out = _seq(nn.GELU(), _scaled(nn.Linear(self.stem.out_channels, num_labels), 0.0))
 
     def save_kwargs(self) -> Dict[str, Any]:
         s = self.stem
@@ -123,6 +124,29 @@ class Classifier(_NativeModule, Savable):
             _native.check(_native.lib().vqvs_classifier_forward(h.ptr, x.data_ptr(), ts.data_ptr(), logits.data_ptr(), B, T,
                                                                _native._stream_ptr()))
         return logits
+
+    @property
+    def feature_dim(self) -> int:
+        return self.stem.out_channels
+
+    def features(self, x: torch.Tensor, ts: torch.Tensor = None, return_logits: bool = False, return_probs: bool = False):
+        """ClassifierStem.forward (classifier.py:111-121): the c_proj output at the query token, [N, output_mult * base_channels],
+        through `vqvs_classifier_features` (forward schedule only).  ts=None means t = 0, as stat_generate.py:33.  With
+        return_logits / return_probs, the head's logits and their softmax (stat_generate.py:39) come out of the same pass:
+        returns feat, or a tuple (feat[, logits][, probs])."""
+        if ts is None:
+            ts = torch.zeros(x.shape[0], device=x.device)
+        x, ts, B, T = self._prepare(x, ts)
+        h = self.handle(x.device, B, T)
+        feat = torch.empty(B, self.feature_dim, device=x.device, dtype=torch.float32)
+        logits = torch.empty(B, self.num_labels, device=x.device, dtype=torch.float32) if return_logits else None
+        probs = torch.empty(B, self.num_labels, device=x.device, dtype=torch.float32) if return_probs else None
+        with torch.cuda.device(x.device):
+            _native.check(_native.lib().vqvs_classifier_features(h.ptr, x.data_ptr(), ts.data_ptr(), feat.data_ptr(), _native._ptr(logits),
+                                                                _native._ptr(probs), B, T, _native._stream_ptr()))
+        if not (return_logits or return_probs):
+            return feat
+        return (feat,) + ((logits,) if return_logits else ()) + ((probs,) if return_probs else ())
 
     def log_prob_grad(self, x: torch.Tensor, ts: torch.Tensor, labels: torch.Tensor, scale: float = 1.0, return_logits: bool = False):
         """scale * d/dx log_softmax(self(x, ts))[labels] through `vqvs_classifier_guidance` (forward + explicit backward)."""

@@ -256,6 +256,29 @@ int vqvs_classifier_forward(vqvs_model* m, const float* d_x, const float* d_ts, 
   return run_model(m, c);
 }
 
+int vqvs_classifier_features(vqvs_model* m, const float* d_x, const float* d_ts, float* d_feat, float* d_logits, float* d_probs, int B,
+                             int T, void* stream) {
+  if (int e = check_run(m, VQVS_KIND_CLASSIFIER, B, T)) return e;
+  if (!d_x || !d_ts || !d_feat) VQVS_FAIL(VQVS_ERR_ARG, "x, ts and feat must be non-NULL");
+  RunCtx c;
+  c.B = B;
+  c.Lbase = T;
+  c.x = d_x;
+  c.ts = d_ts;
+  c.out = d_logits;  // (NULL: the head does not store them)
+  c.feat = d_feat;
+  c.probs = d_probs;
+  c.st = reinterpret_cast<hipStream_t>(stream);
+  return run_model(m, c);  // (phase 0 only: c.backward stays false)
+}
+
+int vqvs_feature_moments(const float* d_feat, int B, int F, const float* d_shift, double* d_s1, double* d_s2, void* stream) {
+  if (!d_feat || !d_shift || !d_s1 || !d_s2) VQVS_FAIL(VQVS_ERR_ARG, "feat, shift, s1 and s2 must be non-NULL");
+  if (B < 1) VQVS_FAIL(VQVS_ERR_ARG, "batch %d must be at least 1", B);
+  if (F < 1 || F > 8192) VQVS_FAIL(VQVS_ERR_ARG, "feature width %d outside 1..8192", F);
+  return launch_feature_moments(d_feat, B, F, d_shift, d_s1, d_s2, reinterpret_cast<hipStream_t>(stream));
+}
+
 int vqvs_classifier_guidance(vqvs_model* m, const float* d_x, const float* d_ts, const int64_t* d_labels, float scale, float* d_grad,
                              float* d_logits, int B, int T, void* stream) {
   if (int e = check_run(m, VQVS_KIND_CLASSIFIER, B, T)) return e;

@@ -468,6 +468,7 @@ __global__ __launch_bounds__(HEAD_NT) void cls_head_kernel(const HeadArgs a) {
     const float v = ((a0 + a1) + (a2 + a3)) + a.bc[f];
     feat[f] = v;
     gl[f] = gelu_f(v);
+    if (a.feat) a.feat[(size_t)b * F + f] = v;
   }
   __syncthreads();
   for (int n = tid; n < NL; n += HEAD_NT) {
@@ -481,7 +482,28 @@ __global__ __launch_bounds__(HEAD_NT) void cls_head_kernel(const HeadArgs a) {
     }
     const float v = ((a0 + a1) + (a2 + a3)) + a.bl[n];
     lg[n] = v;
-    a.logits[(size_t)b * NL + n] = v;
+    if (a.logits) a.logits[(size_t)b * NL + n] = v;
+  }
+  if (a.probs) {  // softmax over up to 8192 logits: block max, then block sum of exp (accurate expf: these are reported, not steered by)
+    __syncthreads();
+    float m = -3.0e38f;
+    for (int n = tid; n < NL; n += HEAD_NT) m = fmaxf(m, lg[n]);
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) m = fmaxf(m, __shfl_xor(m, k));
+    if (lane == 0) redm[wv] = m;
+    __syncthreads();
+    m = redm[0];
+    for (int k = 1; k < NW; ++k) m = fmaxf(m, redm[k]);
+    float sum = 0.f;
+    for (int n = tid; n < NL; n += HEAD_NT) sum += expf(lg[n] - m);
+    sum = wave_sum_f(sum);
+    if (lane == 0) reds[wv] = sum;
+    __syncthreads();
+    sum = 0.f;
+    for (int k = 0; k < NW; ++k) sum += reds[k];
+    const float inv = 1.0f / sum;
+    for (int n = tid; n < NL; n += HEAD_NT) a.probs[(size_t)b * NL + n] = expf(lg[n] - m) * inv;
+    __syncthreads();  // (redm / reds are reused by the backward below)
   }
   if (!a.labels) return;
   __syncthreads();

@@ -254,12 +254,18 @@ struct HeadArgs {
   const float* wl;     // [NL][F] out.1
   const float* wlT;    // [F][NL]
   const float* bl;     // [NL]
-  float* logits;       // [B][NL] out
+  float* logits;       // [B][NL] out or nullptr
+  float* feat;         // [B][F] c_proj output at the query token (ClassifierStem.forward, classifier.py:111-121) or nullptr
+  float* probs;        // [B][NL] softmax of the logits or nullptr
   const int64_t* labels;  // [B] or nullptr = forward only
   float gscale;
   void* dh;            // [B][L][C] out (gradient), when labels
 };
 int launch_cls_head(const HeadArgs& a, int B, int precision, hipStream_t st);
+
+// Streaming feature moments (vqvs_feature_moments): s1[F] += sum_b (f_b - K), s2[F][F] += sum_b (f_b - K)(f_b - K)^T in f64 on the
+// f64 MFMA.  One workgroup per 64 x 64 tile of the upper triangle, mirrored; no atomics, so repeated calls are bitwise reproducible.
+int launch_feature_moments(const float* feat, int B, int F, const float* shift, double* s1, double* s2, hipStream_t st);
 
 // EncoderPredictor head (encoder_predictor.py:53-58, 60-64; vq_vae.py:125-130): nearest down-sampling of the UNet
 // output by `rate`, 1x1 convolution to `D` logits per latent position, and -- with targets -- the gradient of

@@ -1575,6 +1575,8 @@ int build_model(vqvs_model* m, const float* const* hp) {
       a.wl = reinterpret_cast<const float*>(bp->wp(wl_off));
       a.bl = reinterpret_cast<const float*>(bp->wp(bl_off));
       a.logits = r.out;
+      a.feat = r.feat;
+      a.probs = r.probs;
       a.labels = r.backward ? r.labels : nullptr;
       a.gscale = grad_scale(prec);  // (the caller's scale multiplies the finished gradient in fp32, in_conv_bw: the 2-byte gradient tensors never see it)
       a.dh = bp->act(dh.off);

@@ -49,6 +49,9 @@ struct RunCtx {
   bool backward = false;
   float gscale = 1.0f;
   float* grad_out = nullptr;
+  // classifier handles, vqvs_classifier_features: [B][F] features and [B][num_labels] probabilities, or nullptr (out may be too)
+  float* feat = nullptr;
+  float* probs = nullptr;
   hipStream_t st = nullptr;
 };
 
