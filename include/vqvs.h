@@ -229,6 +229,28 @@ int vqvs_ddpm_guided_eps(const float* d_x_t, const float* d_mean, const float* d
 /* x_T ~ N(0,1) from the same counter-based generator (replaces torch.randn, sample_diffusion.py:86) */
 int vqvs_randn(float* d_out, int B, int T, uint64_t seed, uint64_t clip_offset, uint32_t stream_id, void* stream);
 
+/* ---- forward process and denoising loss (handle-less) ------------------------------------
+ * x_t = Diffusion.sample_q(x_0, ts, epsilon) = sqrt(a) * x_0 + sqrt(1 - a) * eps   reference diffusion/diffusion.py:17-26
+ *   d_x0    [x0_rows,T] f32, x0_rows = B or 1 (one clip broadcast to every row: speaker search)
+ *   d_alpha [B] f32: schedule(ts), evaluated by the caller as for vqvs_ddpm_step
+ *   d_eps   [eps_rows,T] f32 with eps_rows = B or 1 (one noise row broadcast), or NULL to draw N(0,1) in the kernel from the
+ *           Philox generator of vqvs_ddpm_step / vqvs_randn on stream id 2, keyed by (seed, index of the row) with
+ *           index = d_noise_index[b] (int64 [B]) or, when d_noise_index is NULL, clip_offset + b.  Rows with equal indices get
+ *           equal noise -- the reference's "fix a noise seed for every example" (voice_search_vqvae.py:79-80) without a tensor
+ *           of copies.  eps_rows is not read when d_eps is NULL (0, 1 or B are accepted).
+ *   d_x_t   [B,T] f32 out.  Any T in 1..2^30; B in 1..65535.  16-byte accesses when T % 4 == 0 and the buffers are 16-byte
+ *           aligned, scalar ones otherwise: the values do not depend on which. */
+int vqvs_ddpm_noise(const float* d_x0, int x0_rows, const float* d_alpha, const float* d_eps, int eps_rows,
+                    const int64_t* d_noise_index, float* d_x_t, int B, int T, uint64_t seed, uint64_t clip_offset, void* stream);
+/* loss[b] = mean_t (eps[b,t] - pred[b,t])^2   reference diffusion.py:151, voice_search_vqvae.py:98
+ *   d_pred [B,T] f32; the noise arguments of vqvs_ddpm_noise -- given, broadcast, or REGENERATED from the same counters, so the
+ *   noise of a generated batch is never written to memory; d_loss [B] f32 out.
+ * Differences and squares in f32, sums in f64 in a fixed order: a workgroup folds 4096 consecutive samples of one row, one
+ * thread adds the row's chunk sums in chunk order and is the row's only writer (no atomics).  Equal rows give bitwise-equal
+ * losses whatever B and the row's position are.  Keeps B * ceil(T / 4096) doubles in the per-(device, stream) scratch buffer. */
+int vqvs_ddpm_sqerr(const float* d_pred, const float* d_eps, int eps_rows, const int64_t* d_noise_index, float* d_loss,
+                    int B, int T, uint64_t seed, uint64_t clip_offset, void* stream);
+
 /* ---- vector quantisation -------------------------------------------------------
  * idx = argmin_k ((-2 z.e_k) + |e_k|^2) + |z|^2, first index on ties
  * reference vq.py:112-143, 199-243.   d_z [B,Cd,T1] f32 NCT, d_dict [K,Cd] f32 -> d_idx [B,T1] int64 */

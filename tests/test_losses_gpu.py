@@ -1,0 +1,286 @@
+"""Denoising-loss evals on the device: the noising and squared-error kernels against the reference and float64, their
+determinism and sharding invariance, `denoising_losses` / `speaker_search_losses` end to end against fixture F16 (written by
+tools/gen_loss_golden.py from the reference), and the two scripts as child processes.
+
+Measured on MI355X (profiles/loss_parity_margins.jsonl): noise kernel 8.6e-8 (bound 2e-6), loss kernel at most 3.9e-8 (5e-7),
+end-to-end rows of fixtures A and B at most 4.6e-7 in fp32 (bounds ~5.8e-5) and 3.2e-5 in fp16 (bounds ~2.3e-3)."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from vq_voice_swap_amd import DiffusionModel, LossTracker, VQVAE, _native, create_data_loader, randn_clips, speaker_search_losses
+from vq_voice_swap_amd.audio import ChunkWriter
+from vq_voice_swap_amd.det_init import det_init_
+
+from util import seeded
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the project's per-forward relative-RMS bounds of the two gate modes (tests/test_parity_gpu.py: FP32_REL, FP16_REL)
+RHO = {"fp32": 1e-4, "fp16": 4e-3}
+T16 = 16384
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    return torch.device("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def f16(golden):
+    return golden("f16_denoising_losses")
+
+
+def det_model(m):
+    det_init_(m.state_dict().items())
+    m.eval()
+    return m
+
+
+def loss_bound(r, rho):
+    """|loss - ref| / ref <= 2 rho r + (rho r)^2 with r = |pred| / |noise - pred|: Cauchy-Schwarz on |d + delta|^2 - |d|^2 for a
+    prediction error |delta| <= rho |pred|."""
+    return 2 * rho * r + (rho * r) ** 2
+
+
+def record(name, value, bound):
+    rec = {"test": name, "rel_err": float(value), "bound": float(bound), "fraction_of_bound": float(value / bound)}
+    print(f"[margin] {name}: rel err {value:.3e} (bound {bound:.3e})")
+    path = os.environ.get("VQVS_LOSS_MARGINS")  # a .jsonl file to append to (profiles/loss_parity_margins.jsonl is such a run)
+    if path:
+        with open(path, "a") as f:
+            f.write(json.dumps(rec) + "\n")
+
+
+def noise_call(x0, alpha, *, eps=None, idx=None, B=None, seed=0, clip_offset=0):
+    B = B if B is not None else alpha.numel()
+    T = x0[0].numel()
+    out = torch.empty((B,) + tuple(x0.shape[1:]), device=x0.device)
+    _native.check(_native.lib().vqvs_ddpm_noise(x0.data_ptr(), x0.shape[0], alpha.data_ptr(), _native._ptr(eps), 0 if eps is None else eps.shape[0],
+                                                _native._ptr(idx), out.data_ptr(), B, T, seed, clip_offset, _native._stream_ptr()))
+    return out
+
+
+def sqerr_call(pred, *, eps=None, idx=None, seed=0, clip_offset=0):
+    B, T = pred.shape[0], pred[0].numel()
+    loss = torch.empty(B, device=pred.device)
+    _native.check(_native.lib().vqvs_ddpm_sqerr(pred.data_ptr(), _native._ptr(eps), 0 if eps is None else eps.shape[0], _native._ptr(idx),
+                                                loss.data_ptr(), B, T, seed, clip_offset, _native._stream_ptr()))
+    return loss
+
+
+# ---------------------------------------------------------------- noise kernel
+def test_noise_kernel_vs_reference_sample_q(f16, dev):
+    model = DiffusionModel("unet", 32)
+    x = (float(f16["a_x_scale"]) * seeded((4, 1, T16), int(f16["a_x_seed"]))).to(dev)
+    noise = seeded((4, 1, T16), int(f16["a_noise_seed"])).to(dev)
+    alpha = model.diffusion.schedule(torch.from_numpy(f16["a_ts"])).to(dev)
+    got = noise_call(x, alpha, eps=noise)[0, 0].cpu()
+    want = torch.from_numpy(f16["a_x_t_row0"])
+    err = ((got - want).abs().max() / want.abs().max()).item()
+    record("A noise kernel row 0 vs reference sample_q (max abs / max |row|)", err, 2e-6)
+    assert err <= 2e-6
+
+
+@pytest.mark.parametrize("T", [16384, 1001])
+def test_noise_kernel_broadcast_forms_are_bitwise(dev, T):
+    B = 5
+    x = seeded((B, 1, T), 1).to(dev)
+    eps = seeded((B, 1, T), 2).to(dev)
+    alpha = torch.linspace(0.05, 0.95, B).to(dev)
+    one_x, one_e = x[2:3].contiguous(), eps[3:4].contiguous()
+    assert torch.equal(noise_call(one_x, alpha, eps=eps), noise_call(one_x.expand(B, -1, -1).contiguous(), alpha, eps=eps))
+    assert torch.equal(noise_call(x, alpha, eps=one_e), noise_call(x, alpha, eps=one_e.expand(B, -1, -1).contiguous()))
+    assert torch.equal(noise_call(one_x, alpha, eps=one_e),
+                       noise_call(one_x.expand(B, -1, -1).contiguous(), alpha, eps=one_e.expand(B, -1, -1).contiguous()))
+    # against the tensor expression (float64), every row and the odd tail included
+    a = alpha.double().reshape(-1, 1, 1)
+    want = a.sqrt() * x.double() + (1 - a).sqrt() * eps.double()
+    assert ((noise_call(x, alpha, eps=eps).double() - want).abs().max() / want.abs().max()).item() <= 2e-6
+    # generated noise is what vqvs_randn writes on stream id 2 for the same indices
+    z = randn_clips(B, T, dev, seed=9, clip_offset=40, stream_id=2)
+    assert torch.equal(noise_call(x, alpha, seed=9, clip_offset=40), noise_call(x, alpha, eps=z))
+
+
+# ---------------------------------------------------------------- loss kernel
+@pytest.mark.parametrize("shape", [(5, 64000), (3, 1001)])
+def test_sqerr_kernel_vs_float64(dev, shape):
+    pred, eps = seeded(shape, 11), seeded(shape, 12)
+    want = ((eps.double().numpy() - pred.double().numpy()) ** 2).mean(axis=1)
+    got = sqerr_call(pred.to(dev), eps=eps.to(dev)).cpu().double().numpy()
+    err = np.abs(got - want) / want
+    for b, e in enumerate(err):
+        record(f"sqerr kernel {shape} row {b} vs float64", e, 5e-7)
+    assert err.max() < 5e-7
+    # one noise row for every prediction row
+    got1 = sqerr_call(pred.to(dev), eps=eps[1:2].to(dev).contiguous()).cpu().double().numpy()
+    want1 = ((eps[1:2].double().numpy() - pred.double().numpy()) ** 2).mean(axis=1)
+    assert (np.abs(got1 - want1) / want1).max() < 5e-7
+
+
+@pytest.mark.parametrize("T", [16384, 1001])
+def test_regenerated_noise_determinism_and_sharding(dev, T):
+    B, seed, off = 8, 1234, 1 << 33  # (an offset past 32 bits: the high word is part of the counter)
+    pred = seeded((B, 1, T), 21).to(dev)
+    z = randn_clips(B, T, dev, seed=seed, clip_offset=off, stream_id=2)
+    whole = sqerr_call(pred, seed=seed, clip_offset=off)
+    assert torch.equal(whole, sqerr_call(pred, eps=z))  # regenerated == read back, bitwise
+    assert torch.equal(whole, sqerr_call(pred, seed=seed, clip_offset=off))  # run to run
+    # sharding: rows [0:3] and [3:8] on their own, keyed by the global index
+    parts = torch.cat([sqerr_call(pred[:3].contiguous(), seed=seed, clip_offset=off),
+                       sqerr_call(pred[3:].contiguous(), seed=seed, clip_offset=off + 3)])
+    assert torch.equal(whole, parts)
+    # row order: a permutation of rows with their indices
+    perm = torch.tensor([5, 0, 7, 2, 1, 6, 3, 4], device=dev)
+    idx = perm + off
+    assert torch.equal(whole[perm], sqerr_call(pred[perm].contiguous(), idx=idx, seed=seed))
+    # equal indices, equal noise (and another seed, other noise)
+    same = torch.full((B,), off + 2, dtype=torch.int64, device=dev)
+    x0, alpha = torch.zeros(1, 1, T, device=dev), torch.zeros(B, device=dev)  # alpha = 0: x_t is the noise itself
+    rows = noise_call(x0, alpha, idx=same, seed=seed)
+    assert torch.equal(rows, z[2:3].expand(B, -1, -1))
+    assert not torch.equal(noise_call(x0, alpha, idx=same, seed=seed + 1), rows)
+    assert abs(rows[0].mean().item()) < 5 / T ** 0.5 and abs(rows[0].std().item() - 1) < 5 / T ** 0.5  # N(0, 1)
+
+
+# ---------------------------------------------------------------- end to end (fixtures A and B)
+@pytest.mark.parametrize("prec", ["fp32", "fp16"])
+def test_denoising_losses_vs_reference(f16, dev, prec):
+    model = det_model(DiffusionModel("unet", 32))
+    model.set_precision(prec)
+    x = (float(f16["a_x_scale"]) * seeded((4, 1, T16), int(f16["a_x_seed"]))).to(dev)
+    noise = seeded((4, 1, T16), int(f16["a_noise_seed"])).to(dev)
+    ts = torch.from_numpy(f16["a_ts"]).to(dev)
+    got = model.diffusion.denoising_losses(x, model.predictor, ts, noise=noise).cpu().double().numpy()
+    want, r = f16["a_losses"].astype(np.float64), f16["a_r"]
+    assert got.shape == want.shape
+    err, bound = np.abs(got - want) / want, loss_bound(r, RHO[prec])
+    for b in range(4):
+        record(f"A denoising_losses {prec} row {b} (t = {f16['a_ts'][b]:.2f})", err[b], bound[b])
+    assert (err <= bound).all(), (prec, err, bound)
+    # the tensor-expression path (held to the same bound by the same argument) computes the same thing
+    old = model.diffusion.ddpm_losses(x, model.predictor, ts, noise).cpu().double().numpy()
+    assert (np.abs(got - old) / want <= 2 * bound).all(), (prec, got, old)
+
+
+def search_setup(f16, dev):
+    model = det_model(VQVAE(base_channels=32, pred_name="unet", num_labels=5))
+    with torch.no_grad():
+        model.vq.dictionary.copy_(seeded(model.vq.dictionary.shape, int(f16["b_dict_seed"]), float(f16["b_dict_scale"])))
+    target = (float(f16["b_x_scale"]) * seeded((1, 1, T16), int(f16["b_x_seed"]))).clamp(-1, 1).to(dev)
+    encoded = model.vq.embed(torch.from_numpy(f16["b_codes"]).to(dev))
+    labels, ts = torch.from_numpy(f16["b_labels"]).to(dev), torch.from_numpy(f16["b_ts"]).to(dev)
+    noise = torch.from_numpy(f16["b_noise"]).to(dev)  # [num_seeds, 1, T]
+    return model, target, encoded, labels, ts, noise
+
+
+@pytest.mark.parametrize("prec", ["fp32", "fp16"])
+def test_speaker_search_vs_reference(f16, dev, prec):
+    model, target, encoded, labels, ts, noise = search_setup(f16, dev)
+    model.set_precision(prec)
+    seeds, bs = int(f16["b_num_seeds"]), int(f16["b_batch_size"])
+    got = speaker_search_losses(model, target, encoded, labels, ts, bs, seeds, 0, noise=noise).cpu().double().numpy()
+    want, r = f16["b_losses"].astype(np.float64), f16["b_r"]
+    err, bound = np.abs(got - want) / want, loss_bound(r, RHO[prec])
+    for b in range(len(want)):
+        record(f"B speaker search {prec} row {b} (label {int(labels[b])}, t = {f16['b_ts'][b]:.2f})", err[b], bound[b])
+    assert (err <= bound).all(), (prec, err, bound)
+    if prec != "fp32":
+        return
+    # per-label means within the rows' bounds, and the reference's ordering wherever it is resolvable
+    n_t = len(want) // 5
+    means, ref_means = got.reshape(5, n_t).mean(-1), f16["b_label_means"].astype(np.float64)
+    mean_bound = (bound * want).reshape(5, n_t).mean(-1)
+    assert (np.abs(means - ref_means) <= mean_bound + 1e-7 * ref_means).all()  # (+ the fixture's own float32 rounding of the means)
+    pairs = 0
+    for i in range(5):
+        for j in range(5):
+            if ref_means[j] - ref_means[i] > 2 * max(mean_bound[i], mean_bound[j]):
+                pairs += 1
+                assert means[i] < means[j], (i, j, means, ref_means)
+    order = np.argsort(ref_means)
+    assert ref_means[order[1]] - ref_means[order[0]] > 2 * max(mean_bound[order[0]], mean_bound[order[1]])  # the generator's assertion
+    assert pairs >= 1 and np.argmin(means) == order[0]
+
+
+def test_speaker_search_micro_batch_invariance(f16, dev):
+    model, target, encoded, labels, ts, noise = search_setup(f16, dev)
+    model.set_precision("fp32")
+    a = speaker_search_losses(model, target, encoded, labels, ts, 8, 2, 5)
+    b = speaker_search_losses(model, target, encoded, labels, ts, 20, 2, 5)
+    assert torch.equal(a, b)
+    assert torch.equal(a, speaker_search_losses(model, target, encoded, labels, ts, 8, 2, 5))
+    assert not torch.equal(a, speaker_search_losses(model, target, encoded, labels, ts, 8, 2, 6))
+    # the generated draws are rows 0 and 1 of stream 2: the same call with that noise given
+    z = randn_clips(2, T16, dev, seed=5, clip_offset=0, stream_id=2)
+    assert torch.equal(a, speaker_search_losses(model, target, encoded, labels, ts, 8, 2, 5, noise=z))
+
+
+# ---------------------------------------------------------------- scripts
+def run_script(args, seconds):
+    """One fresh child process under its own time limit; a failing child fails the test at once."""
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    r = subprocess.run(["timeout", "-k", "10", str(seconds), sys.executable] + [str(a) for a in args], capture_output=True, text=True,
+                       env=env, cwd=ROOT)
+    assert r.returncode == 0, f"exit status {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}"
+    return r.stdout
+
+
+def test_eval_diffusion_script(tmp_path, dev):
+    model = det_model(DiffusionModel("unet", 32))
+    ckpt = tmp_path / "unet32.pt"
+    model.save(str(ckpt))
+    cmd = [os.path.join(ROOT, "eval_diffusion.py"), ckpt, "tones", "--batch-size", "3", "--seed", "1"]
+    out = run_script(cmd, 300)
+    lines = [ln for ln in out.splitlines() if " samples: " in ln]
+    assert len(lines) == 10 and lines[-1].startswith("30 samples: ")
+    assert [ln.split(" ")[0] for ln in lines] == [str(3 * (i + 1)) for i in range(10)]
+    # the same pass, driven directly
+    tracker = LossTracker(avg_size=1_000_000)
+    loader, _ = create_data_loader("tones", batch_size=3, seed=1)
+    for i, batch in enumerate(loader):
+        ts = model.diffusion.draw_ts(3, 1, 3 * i)
+        tracker.add(ts, model.diffusion.denoising_losses(batch["samples"][:, None].to(dev), model.predictor, ts, seed=1, clip_offset=3 * i))
+    want = " ".join(f"{k}={v:.06f}" for k, v in tracker.log_dict().items())
+    assert lines[-1] == f"30 samples: {want}"
+    assert run_script(cmd, 300) == out  # two runs, identical text
+    # --max-samples ends the pass early
+    short = run_script(cmd + ["--max-samples", "7"], 300)
+    assert [ln for ln in short.splitlines() if " samples: " in ln] == lines[:2]
+
+
+def test_voice_search_script(tmp_path, f16, dev):
+    model, _, _, _, _, _ = search_setup(f16, dev)
+    ckpt = tmp_path / "vqvae32.pt"
+    model.save(str(ckpt))
+    wav = tmp_path / "clip.wav"
+    w = ChunkWriter(str(wav), 16000)
+    w.write((0.1 * seeded((64000,), 3)).clamp(-1, 1).numpy())
+    w.close()
+    out = run_script([os.path.join(ROOT, "voice_search_vqvae.py"), "--input-file", wav, "--num-timesteps", "3", "--batch-size", "4",
+                      "--top-k", "3", "--seed", "2", ckpt], 300)
+    lines = out.splitlines()
+    at = lines.index("top 3 sorted losses")
+    assert lines[at + 1] == "-------"
+    rows = [ln.split("\t\t") for ln in lines[at + 2:]]
+    assert len(rows) == 3
+    # the same search, driven directly
+    import voice_search_vqvae as script
+    from vq_voice_swap_amd.audio import ChunkReader
+
+    reader = ChunkReader(str(wav), 16000)
+    clip = torch.from_numpy(reader.read(64000)[None, None]).to(dev)
+    reader.close()
+    encoded = model.vq.embed(model.encode(clip))
+    labels, ts = script.search_grid(5, 3, dev)
+    losses = speaker_search_losses(model, clip, encoded, labels, ts, 4, 1, 2).reshape(5, 3).mean(-1).cpu().numpy().tolist()
+    want = sorted(enumerate(losses), key=lambda x: x[1])[:3]
+    assert [(int(a), b) for a, b in rows] == [(i, f"{v:.6f}") for i, v in want]
+    assert [float(b) for _, b in rows] == sorted(float(b) for _, b in rows)

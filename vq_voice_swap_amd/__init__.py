@@ -10,9 +10,11 @@ DiffusionModel / VQVAE API of unixpickle/vq-voice-swap.  See DESIGN.md.
 from .base import Savable, atomic_save
 from .classifier import Classifier
 from .conv_encoder import ConvMFCCEncoder
+from .dataset import create_data_loader
 from .diffusion import CosSchedule, Diffusion, ExpSchedule, Schedule, make_schedule, randn_clips
 from .diffusion_model import DiffusionModel
 from .encoder_predictor import EncoderPredictor
+from .losses import LossTracker, speaker_search_losses
 from .stats import FeatureStats, class_score, frechet_distance, wav_roundtrip
 from .unet import ResBlockModule, UNetEncoder, UNetPredictor
 from .vq import VQ
@@ -21,5 +23,5 @@ from .vq_vae import VQVAE
 __all__ = [
     "Savable", "atomic_save", "CosSchedule", "Diffusion", "ExpSchedule", "Schedule", "make_schedule", "randn_clips",
     "DiffusionModel", "Classifier", "ConvMFCCEncoder", "EncoderPredictor", "ResBlockModule", "UNetEncoder", "UNetPredictor", "VQ", "VQVAE",
-    "FeatureStats", "class_score", "frechet_distance", "wav_roundtrip",
+    "FeatureStats", "class_score", "frechet_distance", "wav_roundtrip", "LossTracker", "speaker_search_losses", "create_data_loader",
 ]

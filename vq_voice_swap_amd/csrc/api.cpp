@@ -365,6 +365,35 @@ int vqvs_randn(float* d_out, int B, int T, uint64_t seed, uint64_t clip_offset, 
   return run_randn(d_out, B, T, seed, clip_offset, stream_id, reinterpret_cast<hipStream_t>(stream));
 }
 
+// shared argument rules of the two forward-process entry points: B rows of T samples, noise given as 1 or B rows or generated
+static int check_noise_args(const float* d_eps, int eps_rows, int B, int T) {
+  if (B < 1 || B > 65535) VQVS_FAIL(VQVS_ERR_ARG, "batch %d outside 1..65535", B);
+  if (T < 1 || T > (1 << 30)) VQVS_FAIL(VQVS_ERR_ARG, "row length %d outside 1..2^30", T);
+  if (d_eps && eps_rows != 1 && eps_rows != B) VQVS_FAIL(VQVS_ERR_ARG, "eps_rows %d must be 1 or the batch %d", eps_rows, B);
+  if (!d_eps && eps_rows != 0 && eps_rows != 1 && eps_rows != B)
+    VQVS_FAIL(VQVS_ERR_ARG, "eps_rows %d must be 0, 1 or the batch %d when the noise is generated", eps_rows, B);
+  return 0;
+}
+
+int vqvs_ddpm_noise(const float* d_x0, int x0_rows, const float* d_alpha, const float* d_eps, int eps_rows, const int64_t* d_noise_index,
+                    float* d_x_t, int B, int T, uint64_t seed, uint64_t clip_offset, void* stream) {
+  if (!d_x0 || !d_alpha || !d_x_t) VQVS_FAIL(VQVS_ERR_ARG, "x0, alpha and x_t must be non-NULL");
+  if (int e = check_noise_args(d_eps, eps_rows, B, T)) return e;
+  if (x0_rows != 1 && x0_rows != B) VQVS_FAIL(VQVS_ERR_ARG, "x0_rows %d must be 1 or the batch %d", x0_rows, B);
+  return run_ddpm_noise(d_x0, x0_rows, d_alpha, d_eps, eps_rows, d_noise_index, d_x_t, B, T, seed, clip_offset,
+                        reinterpret_cast<hipStream_t>(stream));
+}
+
+int vqvs_ddpm_sqerr(const float* d_pred, const float* d_eps, int eps_rows, const int64_t* d_noise_index, float* d_loss, int B, int T,
+                    uint64_t seed, uint64_t clip_offset, void* stream) {
+  if (!d_pred || !d_loss) VQVS_FAIL(VQVS_ERR_ARG, "pred and loss must be non-NULL");
+  if (int e = check_noise_args(d_eps, eps_rows, B, T)) return e;
+  ScratchLease lease;
+  if (int e = scratch_get((size_t)sqerr_scratch_doubles(B, T) * 8, stream, lease)) return e;
+  return run_ddpm_sqerr(d_pred, d_eps, eps_rows, d_noise_index, d_loss, reinterpret_cast<double*>(lease.p), B, T, seed, clip_offset,
+                        reinterpret_cast<hipStream_t>(stream));
+}
+
 int vqvs_vq_argmin(const float* d_z, const float* d_dict, int64_t* d_idx, int B, int Cd, int T1, int K, void* stream) {
   if (!d_z || !d_dict || !d_idx) VQVS_FAIL(VQVS_ERR_ARG, "NULL argument");
   if (B < 1 || Cd < 1 || T1 < 1 || K < 1) VQVS_FAIL(VQVS_ERR_ARG, "bad shape");

@@ -11,6 +11,12 @@ int run_ddpm_step(const float* x_t, const float* eps, const float* noise, const 
 int run_ddpm_mean(const float* x_t, const float* eps, const float* a_t, const float* a_prev, float* out, int B, int T, hipStream_t st);
 int run_ddpm_guided_eps(const float* x_t, const float* mean, const float* grad, const float* a_t, const float* a_prev, float* out,
                         int B, int T, uint32_t flags, hipStream_t st);
+// forward process and denoising loss (loss_kernels.hip)
+int sqerr_scratch_doubles(int B, int T);
+int run_ddpm_noise(const float* x0, int x0_rows, const float* alpha, const float* eps, int eps_rows, const int64_t* noise_index,
+                   float* x_t, int B, int T, uint64_t seed, uint64_t clip_offset, hipStream_t st);
+int run_ddpm_sqerr(const float* pred, const float* eps, int eps_rows, const int64_t* noise_index, float* loss, double* scratch, int B,
+                   int T, uint64_t seed, uint64_t clip_offset, hipStream_t st);
 int run_vq_argmin(const float* z, const float* dict, float* en_scratch, int64_t* idx, int B, int Cd, int T1, int K, hipStream_t st);
 int run_vq_embed(const int64_t* idx, const float* dict, float* out, int B, int Cd, int T1, int K, hipStream_t st);
 }  // namespace vqvs

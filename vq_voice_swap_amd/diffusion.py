@@ -110,6 +110,82 @@ class Diffusion:
         pred = predictor(self.sample_q(x, ts, epsilon=noise), ts)
         return ((noise - pred) ** 2).flatten(1).mean(dim=1)
 
+    # ---- denoising loss (evaluation side; fused HIP kernels) ---------------------------------
+    @staticmethod
+    def draw_ts(n: int, seed: int, clip_offset: int = 0) -> torch.Tensor:
+        """n uniform times in [0, 1) from a host generator seeded by (seed, clip_offset): what `denoising_losses(ts=None)` uses."""
+        g = torch.Generator().manual_seed((int(seed) + 0x9E3779B97F4A7C15 * (int(clip_offset) + 1)) % (2 ** 63))
+        return torch.rand(n, generator=g)
+
+    def denoising_losses(self, x_0: torch.Tensor, predictor: Callable, ts: Optional[torch.Tensor] = None, *,
+                         noise: Optional[torch.Tensor] = None, seed: Optional[int] = None,
+                         noise_index: Optional[torch.Tensor] = None, clip_offset: int = 0, alpha: Optional[torch.Tensor] = None,
+                         check: bool = True, **predictor_kwargs) -> torch.Tensor:
+        """Per-row noise-prediction MSE, [B] float32: what `ddpm_losses` computes (reference diffusion.py:135-151), as
+        `vqvs_ddpm_noise` -> `predictor(x_t, ts, **predictor_kwargs)` -> `vqvs_ddpm_sqerr`.
+
+        `x_0` is [B, ..., T], or [1, ..., T] with `ts` of length B: one clip scored at B settings without B copies of it.
+        `noise` is a tensor of B rows or of one (broadcast); `noise=None` draws it in the kernels from the counter-based
+        generator keyed by (seed, noise_index[b]) -- `noise_index=None` means clip_offset + b, the GLOBAL clip index, so a clip's
+        loss does not depend on the batch it is scored in -- and the loss kernel regenerates it instead of reading it back.
+        `ts=None` draws B uniform values from a host generator seeded by (seed, clip_offset).
+        A caller that scores many micro-batches in a row (`speaker_search_losses`) passes `alpha` = schedule(ts) of the rows, evaluated
+        once for all of them, and `check=False`, and calls the predictor's `check_status()` itself once at the end: neither the
+        host-side schedule nor the range guard then synchronises per micro-batch."""
+        _native.require_cuda(x_0, noise, noise_index)
+        if x_0.dim() < 2:
+            raise ValueError("x_0 must be [N, ..., T]")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        x0 = x_0.detach().to(torch.float32).contiguous()
+        if ts is None:
+            ts = self.draw_ts(x0.shape[0], seed, clip_offset)
+        ts = ts.detach().to(device=x0.device, dtype=torch.float32).contiguous()
+        if ts.dim() != 1 or ts.numel() < 1:
+            raise ValueError(f"ts must be a non-empty vector, got shape {tuple(ts.shape)}")
+        B, T = ts.numel(), x0[0].numel()
+        if x0.shape[0] not in (1, B):
+            raise ValueError(f"x_0 has {x0.shape[0]} rows: expected {B} (one per entry of ts) or 1")
+        eps, eps_rows = None, 0
+        if noise is not None:
+            eps = noise.detach().to(torch.float32).contiguous()
+            eps_rows = eps.shape[0]
+            if eps_rows not in (1, B) or tuple(eps.shape[1:]) != tuple(x0.shape[1:]):
+                raise ValueError(f"noise of shape {tuple(eps.shape)} does not match {B} (or 1) rows of {tuple(x0.shape[1:])}")
+        idx = None
+        if noise_index is not None:
+            idx = noise_index.detach().to(device=x0.device, dtype=torch.int64).contiguous()
+            if idx.shape != (B,):
+                raise ValueError(f"expected noise_index of shape [{B}], got {tuple(idx.shape)}")
+        # alpha_bar(t) on the HOST, as ddpm_sample evaluates its tables: the reference's float32 expressions on the CPU's own exp / cos
+        if alpha is None:
+            alpha = self.schedule(ts.cpu())
+        alpha = alpha.detach().to(device=x0.device, dtype=torch.float32).contiguous()
+        if alpha.shape != (B,):
+            raise ValueError(f"expected alpha of shape [{B}], got {tuple(alpha.shape)}")
+        x_t = torch.empty((B,) + tuple(x0.shape[1:]), device=x0.device, dtype=torch.float32)
+        loss = torch.empty(B, device=x0.device, dtype=torch.float32)
+        L = _native.lib()
+        with torch.cuda.device(x0.device):
+            _native.check(L.vqvs_ddpm_noise(x0.data_ptr(), x0.shape[0], alpha.data_ptr(), _native._ptr(eps), eps_rows, _native._ptr(idx),
+                                            x_t.data_ptr(), B, T, int(seed), int(clip_offset), _native._stream_ptr()))
+            with torch.no_grad():
+                pred = predictor(x_t, ts, **predictor_kwargs)
+            _native.require_cuda(pred)
+            if tuple(pred.shape) != tuple(x_t.shape):
+                raise ValueError(f"the predictor returned shape {tuple(pred.shape)} for an input of shape {tuple(x_t.shape)}")
+            pred = pred.detach().to(torch.float32).contiguous()
+            _native.check(L.vqvs_ddpm_sqerr(pred.data_ptr(), _native._ptr(eps), eps_rows, _native._ptr(idx), loss.data_ptr(), B, T,
+                                            int(seed), int(clip_offset), _native._stream_ptr()))
+        if check:
+            chk = getattr(predictor, "check_status", None)  # range guard of a native predictor, as in ddpm_sample
+            if chk is None:
+                mods = _native_modules(predictor)
+                chk = mods[0].check_status if mods else None
+            if chk is not None:
+                chk()
+        return loss
+
     # ---- hot path -------------------------------------------------------------------------
     def ddpm_previous(
         self,
