@@ -1,6 +1,10 @@
 """Randomised ResBlock parity sweep (HIP vs oracle): random channel counts, lengths (incl. tile-boundary cases),
 dilations, resizes, FiLM on/off, batch sizes, all three precision modes.  Developer tool; tests/ hold the fixed cases.
-    python tools/fuzz_resblock.py [seed] [cases] [big]      ("big": every fourth case is a long, many-clip launch)"""
+    python tools/fuzz_resblock.py [seed] [cases] [big|walk]   ("big": every fourth case is a long, many-clip launch;
+    "walk": every fourth case has few steps per clip and many clips -- L in 255 .. 1100 at widths 32 / 64 / 96 / 128, six clips per
+    workgroup (VQVS_WS_GRID is honoured, so a small grid keeps the oracle cheap) -- the band where the (scale, shift) ring rule of
+    conv_ws_kernel has its case boundaries; those cases are also checked per clip and, bitwise, against batches of two;
+    tests/test_ws_walk_gpu.py pins the seeded list)"""
 import os
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in device memory: a process-level HIP switch, before the runtime starts
 import os, random, sys
@@ -16,6 +20,8 @@ dev = torch.device("cuda:0")
 rng = random.Random(int(sys.argv[1]) if len(sys.argv) > 1 else 0)
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 40
 BIG = len(sys.argv) > 3 and sys.argv[3] == "big"
+WALK = len(sys.argv) > 3 and sys.argv[3] == "walk"
+WALK_GRID = int(os.environ.get("VQVS_WS_GRID", "0")) or 256  # workgroups per launch (default: one per CU of an MI355X)
 worst = {"fp32": 0.0, "fp16": 0.0, "bf16": 0.0}
 bad = 0
 for i in range(N):
@@ -33,6 +39,14 @@ for i in range(N):
         B = rng.choice([24, 37, 48])
         cin = rng.choice([64, 128])
         cout = cin if scale != 1.0 else rng.choice([cin, 64, 128])
+    walk = WALK and i % 4 == 0
+    if walk:  # few steps per clip, every workgroup walks six clips (and starts in the middle of one when B is not a multiple of the grid)
+        scale = 1.0
+        cin = rng.choice([32, 64, 96, 128])
+        cout = rng.choice([cin, 32, 64, 128])
+        dil = rng.choice([1, 2, 4])
+        L = rng.randrange(255, 1101)
+        B = 6 * WALK_GRID - rng.choice([0, 1, 3])
     m = ResBlockModule(cin, emb, cout if cout != cin else None, scale, dil)
     det_init_((f"fz{i}." + k, v) for k, v in m.block.state_dict().items())
     x = seeded((B, cin, L), 5000 + i)
@@ -43,6 +57,13 @@ for i in range(N):
         m.set_precision(prec)
         got = m(x.to(dev), None if e is None else e.to(dev)).cpu()
         err = rel_rms(got, want) if got.shape == want.shape else float("inf")
+        if walk and got.shape == want.shape:  # one clip's wrong table must not hide in the batch RMS, and a clip's bits must not depend on the batch
+            per_clip = ((got - want).pow(2).mean(dim=(1, 2)).sqrt() / want.pow(2).mean(dim=(1, 2)).sqrt()).max().item()
+            pairs = torch.cat([m(x[j:j + 2].to(dev), None if e is None else e[j:j + 2].to(dev)) for j in range(0, B, 2)]).cpu()
+            if not per_clip < 5 * tol or not torch.equal(got, pairs):
+                bad += 1
+                print("MISMATCH (walk)", prec, dict(cin=cin, cout=cout, dil=dil, emb=emb, L=L, B=B), "per clip", per_clip, "clips differing from the batch-of-two run",
+                      int((got != pairs).flatten(1).any(dim=1).sum()), flush=True)
         worst[prec] = max(worst[prec], err)
         if not err < tol:
             bad += 1

@@ -858,7 +858,7 @@ int launch_conv(const ConvArgs& a, int B, int precision, hipStream_t st) {
     if (r != 0) return r < 0 ? r : 0;
   }
   if (a.gn != nullptr) VQVS_FAIL(-1, "conv: a fused GroupNorm is only taken where ws_fuses_gn() says so (Cout=%d)", a.Cout);
-  static const int trace = getenv("VQVS_WS_TRACE") ? atoi(getenv("VQVS_WS_TRACE")) : 0;  // (which launches conv_ws_kernel declined)
+  static const int trace = getenv("VQVS_WS_TRACE") ? atoi(getenv("VQVS_WS_TRACE")) : 0;  // (which launches conv_ws_kernel declined; ws_launch prints the accepted plans)
   if (trace)
     fprintf(stderr, "conv_mfma: Cout=%d Lout=%d nseg=%d seg0(C=%d taps=%d dil=%d rsz=%d xf=%d) skip=%d epi_gelu=%d nbw=%d out_f32=%d prec=%d\n", a.Cout, a.Lout,
             a.nseg, a.seg[0].C, a.seg[0].ntaps, a.seg[0].dil, a.seg[0].resize, a.seg[0].ss != nullptr, a.skip != nullptr, a.epi_gelu, a.nbw, a.out_f32, precision);

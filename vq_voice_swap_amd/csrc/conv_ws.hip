@@ -18,7 +18,12 @@
 // ds_write_b128) and weights (lane-linear DMA image, swizzle applied to the source address) alike: ds_read_b128 conflict-free.
 #include <atomic>
 #include <cstddef>
+#include <cstdio>
 #include <cstdlib>
+#include <mutex>
+#include <set>
+#include <string>
+#include <type_traits>
 
 #include "kernels.hpp"
 
@@ -171,12 +176,50 @@ struct WsArgs {
   int Cout, Lout, TTO, ntx, nty, ntiles, ntiles_stat;
   int wres_bytes;  // resident-weights form: bytes of all segments' weights
   int ss_bytes;    // bytes of one clip's (scale, shift) table (all prologue segments), ss_ring copies of it live in LDS
-  int ss_ring;     // 2, 4 or 8 (power of two): clips whose chunks can be in flight at once
+  int ss_ring;     // 2, 4 or 8 (ws_ss_ring): more than the clips between a chunk being staged and the load cursor WS_LOOKAHEAD chunks on
   int rev;         // 1: the launch walks its tiles from the last to the first (ConvArgs.rev)
   int zp;          // 1: whole-clip tiles (template flag ZP): a clip of at most 255 rows is ONE tile whatever the dilation
 };
 static_assert(offsetof(WsArgs, gn) == 0, "gn_table reads WsGn through the kernarg segment pointer: it must stay the first member");
 #define WS_SEGF(s, f) ((s) == 0 ? a.seg[0].f : ((s) == 1 ? a.seg[1].f : ((s) == 2 ? a.seg[2].f : a.seg[3].f)))
+
+#ifndef VQVS_WS_PREP_EARLY
+#define VQVS_WS_PREP_EARLY 1  // (0: the cursor runs behind the barrier, as through round 5 -- A/B)
+#endif
+// The (scale, shift) ring.  While some producer wave still stages chunk q (and reads the table of q's clip), the fastest one has
+// staged q, issued q + 3 and moved its load cursor on -- into chunk q + 5 when prepare() runs in front of the step barrier
+// (VQVS_WS_PREP_EARLY, the default), into q + 4 when it runs behind it -- and a table is WRITTEN when the cursor enters its clip
+// (refresh_ss).  Tables live in slot clip & (ring - 1), so the ring must be larger than the number of clip boundaries between a
+// staged chunk and the cursor WS_LOOKAHEAD chunks ahead of it, for every position of the staged chunk inside its clip.
+constexpr int ws_lookahead(bool prep_early) { return prep_early ? 5 : 4; }
+constexpr int WS_LOOKAHEAD = ws_lookahead(VQVS_WS_PREP_EARLY != 0);
+// spc = steps (chunks) per clip: 2 slots when the cursor can be at most one clip ahead, 4 up to three clips, 8 at one step per clip
+constexpr int ws_ss_ring(long long spc, int lookahead) { return spc >= lookahead ? 2 : (spc >= 2 ? 4 : 8); }
+// The proof, by walking chunks rather than by the closed form: the largest clip distance between a staged chunk at offset `o` of
+// its clip and the chunk `lookahead` steps on, over every offset.
+constexpr int ws_ss_span(int spc, int lookahead) {
+  int worst = 0;
+  for (int o = 0; o < spc; ++o) {
+    int clip = 0, pos = o;
+    for (int i = 0; i < lookahead; ++i)
+      if (++pos == spc) {
+        pos = 0;
+        ++clip;
+      }
+    worst = clip > worst ? clip : worst;
+  }
+  return worst;
+}
+constexpr bool ws_ss_ring_holds(int lookahead) {
+  for (int spc = 1; spc <= 64; ++spc) {
+    const int ring = ws_ss_ring(spc, lookahead);
+    if ((ring & (ring - 1)) != 0 || ws_ss_span(spc, lookahead) >= ring) return false;
+  }
+  return true;
+}
+static_assert(ws_ss_ring_holds(ws_lookahead(true)) && ws_ss_ring_holds(ws_lookahead(false)),
+              "the (scale, shift) ring is overwritten while a producer wave still reads it: ws_ss_ring vs. the load cursor's lookahead");
+static_assert(ws_ss_ring(4, ws_lookahead(true)) == 4 && ws_ss_ring(4, ws_lookahead(false)) == 2, "ring at four steps per clip");
 
 struct TileCo {
   int b, tx, ty;
@@ -368,8 +411,8 @@ __global__ __launch_bounds__((ws_threads<T, ROWS>())) void conv_ws_kernel(const 
     bool ss_defer = true;  // start-up: the first clip's table is copied AFTER the first three chunk loads are on their way (below)
     auto refresh_ss = [&](int clip) {
       // first chunk of a new clip: its (scale, shift) rows (every prologue segment's) go to LDS once -- the producers then read
-      // them with ds_read instead of four more global loads per chunk and thread.  Slot b % ring: chunks of at most `ring`
-      // clips are in flight (host: ring = 4 when a clip can take fewer than four steps).
+      // them with ds_read instead of four more global loads per chunk and thread.  Slot b % ring: the cursor that calls this is
+      // up to WS_LOOKAHEAD chunks ahead of a chunk another wave still stages, fewer than `ring` clips (host: ws_ss_ring).
       char* const tab = smem + SS_OFF + (clip & (a.ss_ring - 1)) * a.ss_bytes;
       if (a.gn.nsrc > 0) return;  // (the consumers build the tables of a launch with a fused GroupNorm)
       for (int sg = 0; sg < a.nseg; ++sg) {
@@ -637,10 +680,7 @@ __global__ __launch_bounds__((ws_threads<T, ROWS>())) void conv_ws_kernel(const 
     sync_lds();
     int q = 0;
     WS_TMARK(2)
-#ifndef VQVS_WS_PREP_EARLY
-#define VQVS_WS_PREP_EARLY 1  // (0: the cursor runs behind the barrier, as through round 5 -- A/B)
-#endif
-#if VQVS_WS_PREP_EARLY
+#if VQVS_WS_PREP_EARLY  // (default 1, set above WS_LOOKAHEAD)
     // the parameters of the loads a step issues are computed at the END of the step before it, in front of the barrier -- scalar work
     // that would otherwise run right behind the barrier, beside the consumers' MFMA burst, now fills the wait for the other waves
     Prep prn = prepare();
@@ -1368,6 +1408,18 @@ int ws_launch(const WsArgs& w, hipStream_t st) {
   constexpr int NT = ws_threads<T, ROWS>();
   const int nwg = (grid_env > 0 ? grid_env : ws_num_cus()) * (1024 / NT);  // persistent workgroups: one (two) per CU
   const int grid = w.ntiles < nwg ? w.ntiles : nwg;
+  // VQVS_WS_TRACE: one stderr line per distinct accepted plan and process (conv_mfma.hip prints the declined launches)
+  static const int trace = getenv("VQVS_WS_TRACE") ? atoi(getenv("VQVS_WS_TRACE")) : 0;
+  if (trace) {
+    char line[320];
+    snprintf(line, sizeof line, "conv_ws: prec=%s Cout=%d Lout=%d B=%d rows=%d CT=%d res=%d avg=%d zp=%d ntx=%d nty=%d nchunks=%d spc=%d ss_ring=%d la=%d ss_bytes=%d gn=%d rev=%d ntiles=%d grid=%d lds=%d",
+             X3 ? "fp32" : (sizeof(T) == 2 && std::is_same<T, half_t>::value ? "fp16" : "bf16"), w.Cout, w.Lout, w.ntiles / (w.ntx * w.nty), ROWS, CT, RES ? 1 : 0,
+             AVG ? 1 : 0, w.zp, w.ntx, w.nty, w.nchunks, w.ntx * w.nty * w.nchunks, w.ss_ring, WS_LOOKAHEAD, w.ss_bytes, w.gn.nsrc > 0 ? 1 : 0, w.rev, w.ntiles, grid, lds);
+    static std::mutex mu;
+    static std::set<std::string> seen;
+    std::lock_guard<std::mutex> lk(mu);
+    if (seen.insert(line).second) fprintf(stderr, "%s\n", line);
+  }
   hipLaunchKernelGGL((conv_ws_kernel<T, ROWS, CT, RES, AVG, ZP>), dim3(grid), dim3(NT), lds, st, w);
   VQVS_HIP(hipGetLastError());
   return 0;
@@ -1555,11 +1607,12 @@ bool ws_plan(const ConvArgs& a, int B, int precision, WsPlan& plan) {
   // resident weights: one channel tile per launch and everything fits the CU's LDS
   static const int res_env = getenv("VQVS_WS_RES") ? atoi(getenv("VQVS_WS_RES")) : 1;  // 0: always stream the weights (A/B measurements)
   if (w.ss_bytes > 8192) return 0;  // (one 16-byte piece per producer thread)
-  // (scale, shift) tables in LDS: the producers' load cursor runs up to four chunks ahead of the chunk being staged, and a table is
-  // written when the cursor ENTERS its clip -- so the ring must hold every clip between the staged chunk and the cursor:
-  // 2 clips when a clip takes at least four steps, 3 at two or three steps, 5 when a clip is a single step (32 x 3 -> 32, L <= 254)
+  // (scale, shift) tables in LDS: the producers' load cursor runs up to WS_LOOKAHEAD (five) chunks ahead of a chunk that is still
+  // being staged, and a table is written when the cursor ENTERS its clip -- so the ring must hold every clip between the staged
+  // chunk and the cursor: 2 clips when a clip takes at least five steps, up to 4 at two to four steps, 6 when a clip is a single
+  // step (32 x 3 -> 32, L <= 254).  ws_ss_ring, proved against the walk by the static_assert beside it.
   const long long spc = (long long)w.ntx * w.nty * n;  // steps per clip
-  w.ss_ring = spc >= 4 ? 2 : (spc >= 2 ? 4 : 8);
+  w.ss_ring = ws_ss_ring(spc, WS_LOOKAHEAD);
   const int ss_total = w.ss_ring * w.ss_bytes;
   if (ws_fixed_lds(rows, CT, false, x3) + ss_total > ws_lds_cap(rows, x3)) return 0;
   // (avg-pooled launches stream their weights: resident weights + four loads per chunk do not fit 128 VGPRs without spills, and
