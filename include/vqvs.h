@@ -255,6 +255,23 @@ int vqvs_ddpm_sqerr(const float* d_pred, const float* d_eps, int eps_rows, const
  * idx = argmin_k ((-2 z.e_k) + |e_k|^2) + |z|^2, first index on ties
  * reference vq.py:112-143, 199-243.   d_z [B,Cd,T1] f32 NCT, d_dict [K,Cd] f32 -> d_idx [B,T1] int64 */
 int vqvs_vq_argmin(const float* d_z, const float* d_dict, int64_t* d_idx, int B, int Cd, int T1, int K, void* stream);
+/* Quantise and score in one pass (handle-less): what VQ.forward and StandardVQLoss need of z (reference vq.py:45-51, 112-143),
+ * plus the code counts of an evaluation pass.
+ *   d_z [B,Cd,T1] f32 NCT, d_dict [K,Cd] f32; the limits of vqvs_vq_argmin (Cd a multiple of 4), B in 1..65535
+ *   d_idx      [B,T1] int64 out: bit-identical to vqvs_vq_argmin on the same inputs (the two kernels call one search routine:
+ *              same distance formula, same fmaf order, first index on ties)
+ *   d_embedded [B,Cd,T1] f32 NCT out, or NULL: d_embedded[b,:,t] = d_dict[idx[b,t],:], an exact copy, written along time
+ *   d_sqerr    [B] f64 out, or NULL: sum over c,t of (z[b,c,t] - e[b,c,t])^2.  Differences and squares in f32, sums in f64 in a
+ *              fixed order: a workgroup folds its 32 positions x Cd channels, one thread adds the clip's tile sums in tile order
+ *              and is the clip's only writer (no floating-point atomics).  A clip's value is bitwise the same whatever B and
+ *              its row are; a clip whose columns are dictionary rows scores exactly 0.
+ *   d_hist     [K] int64 in/out, or NULL: d_hist[k] += number of positions of THIS call that chose code k (integer atomics:
+ *              exact in any order).  The caller zeroes it once and passes it to every call of a pass.
+ * z is not fetched from HBM again: the epilogue re-reads the workgroup's own tile, which the search has just walked K / 128
+ * times, from L2.  Keeps B * ceil(T1 / 32) doubles and K floats in the per-(device, stream) scratch buffer.  Asynchronous on
+ * `stream`; NULL d_z / d_dict / d_idx or non-positive sizes return VQVS_ERR_ARG before the device is touched. */
+int vqvs_vq_quantize(const float* d_z, const float* d_dict, int64_t* d_idx, float* d_embedded, double* d_sqerr, int64_t* d_hist,
+                     int B, int Cd, int T1, int K, void* stream);
 /* out[b,:,t] = dict[idx[b,t],:]   reference vq.py:98-110 */
 int vqvs_vq_embed(const int64_t* d_idx, const float* d_dict, float* d_out, int B, int Cd, int T1, int K, void* stream);
 

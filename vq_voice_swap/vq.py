@@ -1,1 +1,1 @@
-from vq_voice_swap_amd.vq import VQ  # noqa: F401
+from vq_voice_swap_amd.vq import VQ, StandardVQLoss, VQLoss  # noqa: F401

@@ -17,11 +17,12 @@ from .encoder_predictor import EncoderPredictor
 from .losses import LossTracker, speaker_search_losses
 from .stats import FeatureStats, class_score, frechet_distance, wav_roundtrip
 from .unet import ResBlockModule, UNetEncoder, UNetPredictor
-from .vq import VQ
+from .vq import VQ, StandardVQLoss, VQLoss, code_usage
 from .vq_vae import VQVAE
 
 __all__ = [
     "Savable", "atomic_save", "CosSchedule", "Diffusion", "ExpSchedule", "Schedule", "make_schedule", "randn_clips",
     "DiffusionModel", "Classifier", "ConvMFCCEncoder", "EncoderPredictor", "ResBlockModule", "UNetEncoder", "UNetPredictor", "VQ", "VQVAE",
     "FeatureStats", "class_score", "frechet_distance", "wav_roundtrip", "LossTracker", "speaker_search_losses", "create_data_loader",
+    "StandardVQLoss", "VQLoss", "code_usage",
 ]

@@ -403,6 +403,17 @@ int vqvs_vq_argmin(const float* d_z, const float* d_dict, int64_t* d_idx, int B,
   return run_vq_argmin(d_z, d_dict, reinterpret_cast<float*>(lease.p), d_idx, B, Cd, T1, K, reinterpret_cast<hipStream_t>(stream));
 }
 
+int vqvs_vq_quantize(const float* d_z, const float* d_dict, int64_t* d_idx, float* d_embedded, double* d_sqerr, int64_t* d_hist, int B,
+                     int Cd, int T1, int K, void* stream) {
+  if (!d_z || !d_dict || !d_idx) VQVS_FAIL(VQVS_ERR_ARG, "z, dict and idx must be non-NULL");
+  if (B < 1 || Cd < 1 || T1 < 1 || K < 1) VQVS_FAIL(VQVS_ERR_ARG, "bad shape B=%d Cd=%d T1=%d K=%d", B, Cd, T1, K);
+  if (B > 65535) VQVS_FAIL(VQVS_ERR_ARG, "batch %d outside 1..65535", B);
+  if (Cd % 4) VQVS_FAIL(VQVS_ERR_ARG, "Cd must be a multiple of 4 (got %d)", Cd);
+  ScratchLease lease;
+  if (int e = scratch_get(vq_quantize_scratch_bytes(B, T1, K), stream, lease)) return e;
+  return run_vq_quantize(d_z, d_dict, lease.p, d_idx, d_embedded, d_sqerr, d_hist, B, Cd, T1, K, reinterpret_cast<hipStream_t>(stream));
+}
+
 int vqvs_vq_embed(const int64_t* d_idx, const float* d_dict, float* d_out, int B, int Cd, int T1, int K, void* stream) {
   if (!d_idx || !d_dict || !d_out) VQVS_FAIL(VQVS_ERR_ARG, "NULL argument");
   return run_vq_embed(d_idx, d_dict, d_out, B, Cd, T1, K, reinterpret_cast<hipStream_t>(stream));

@@ -148,16 +148,13 @@ __global__ void vq_norms_kernel(const float* dict, float* en, int K, int Cd) {
   en[k] = s;
 }
 
-__global__ __launch_bounds__(256) void vq_argmin_kernel(const float* z, const float* dict, const float* en, int64_t* idx_out, int Cd,
-                                                        int T1, int K) {
-  __shared__ __attribute__((aligned(16))) float xs[VQ_KC][VQ_POS];
-  __shared__ __attribute__((aligned(16))) float ds[VQ_TILE][VQ_DS];
-  __shared__ float bd[8][VQ_POS];
-  __shared__ int bi[8][VQ_POS];
+// The search itself, shared by vq_argmin_kernel and vq_quantize_kernel: after the call thread tid < VQ_POS holds the winning code
+// of position t0 + tid (every other thread's return value is meaningless).  The four LDS arrays belong to the caller, which may
+// reuse them once it has passed a barrier of its own.
+__device__ __forceinline__ int vq_search(const float* zb, const float* dict, const float* en, int Cd, int T1, int K, int t0,
+                                         float (*xs)[VQ_POS], float (*ds)[VQ_DS], float (*bd)[VQ_POS], int (*bi)[VQ_POS]) {
   const int tid = threadIdx.x;
   const int pos = tid & 31, cg = tid >> 5;
-  const int b = blockIdx.y, t0 = blockIdx.x * VQ_POS;
-  const float* zb = z + (size_t)b * Cd * T1;
   float best = INFINITY;
   int best_i = 0;
   float xn = 0.f;
@@ -218,9 +215,10 @@ __global__ __launch_bounds__(256) void vq_argmin_kernel(const float* z, const fl
   bd[cg][pos] = best;
   bi[cg][pos] = best_i;
   __syncthreads();
-  if (tid < VQ_POS && t0 + tid < T1) {
+  int i = 0;
+  if (tid < VQ_POS) {
     float d = bd[0][tid];
-    int i = bi[0][tid];
+    i = bi[0][tid];
     for (int g = 1; g < 8; ++g) {
       const float dg = bd[g][tid];
       const int ig = bi[g][tid];
@@ -229,8 +227,114 @@ __global__ __launch_bounds__(256) void vq_argmin_kernel(const float* z, const fl
         i = ig;
       }
     }
-    idx_out[(size_t)b * T1 + t0 + tid] = i;
   }
+  return i;
+}
+
+__global__ __launch_bounds__(256) void vq_argmin_kernel(const float* z, const float* dict, const float* en, int64_t* idx_out, int Cd,
+                                                        int T1, int K) {
+  __shared__ __attribute__((aligned(16))) float xs[VQ_KC][VQ_POS];
+  __shared__ __attribute__((aligned(16))) float ds[VQ_TILE][VQ_DS];
+  __shared__ float bd[8][VQ_POS];
+  __shared__ int bi[8][VQ_POS];
+  const int tid = threadIdx.x;
+  const int b = blockIdx.y, t0 = blockIdx.x * VQ_POS;
+  const int i = vq_search(z + (size_t)b * Cd * T1, dict, en, Cd, T1, K, t0, xs, ds, bd, bi);
+  if (tid < VQ_POS && t0 + tid < T1) idx_out[(size_t)b * T1 + t0 + tid] = i;
+}
+
+// ---------------------------------------------------------------------------------
+// Quantise and score: the search above, then -- in the same workgroup, on the same 32 positions -- the winners' rows written
+// out in NCT, the tile's sum of (z - e)^2 and the tile's code counts.
+//   * The winners' rows are staged through LDS (the search's dictionary tile, now free) with the row-contiguous 16-byte loads
+//     of the search, and leave along time: 32 lanes write 128 contiguous bytes of one channel.
+//   * z is read again from global memory.  The workgroup has just read these Cd x 32 floats K / 128 times in the search, so
+//     they are L2 lines of its own XCD, not HBM traffic; keeping them in LDS instead would cost Cd x 128 bytes per workgroup
+//     (64 KB at Cd = 512: one workgroup per CU instead of three; 128 KB at Cd = 1024: with the 35 KB dictionary tile, past the
+//     160 KB of a CU) and bound Cd by the LDS size.
+//   * Thread (pos, cg) owns channels cg * 8 .. cg * 8 + 7 of every 64-channel chunk: differences and squares in fp32 (the square
+//     rounded before it meets the sum), one fp64 accumulator in channel order, then the fixed tree of ddpm_sqerr_partial_kernel
+//     (xor-shuffles inside each wave, the four waves in order).  Nothing depends on B or on the clip's row.
+//   * Counts: lane p < 32 adds the number of the tile's positions that chose its code, if it is the first of them, with one
+//     64-bit integer atomic -- integer sums are order-free, so the histogram is exact and reproducible.
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void vq_quantize_kernel(const float* z, const float* dict, const float* en, int64_t* idx_out,
+                                                          float* emb_out, double* partial, int64_t* hist, int Cd, int T1, int K,
+                                                          int ntile) {
+  __shared__ __attribute__((aligned(16))) float xs[VQ_KC][VQ_POS];
+  __shared__ __attribute__((aligned(16))) float ds[VQ_TILE][VQ_DS];
+  __shared__ float bd[8][VQ_POS];
+  __shared__ int bi[8][VQ_POS];
+  __shared__ int win[VQ_POS];
+  __shared__ double red[4];
+  const int tid = threadIdx.x;
+  const int pos = tid & 31, cg = tid >> 5;
+  const int b = blockIdx.y, t0 = blockIdx.x * VQ_POS;
+  const float* zb = z + (size_t)b * Cd * T1;
+  const int w = vq_search(zb, dict, en, Cd, T1, K, t0, xs, ds, bd, bi);
+  if (tid < VQ_POS) {
+    const bool live = t0 + tid < T1;
+    win[tid] = live ? w : -1;
+    if (live) idx_out[(size_t)b * T1 + t0 + tid] = w;
+  }
+  __syncthreads();
+  if (hist && tid < VQ_POS && win[tid] >= 0) {
+    int count = 0;
+    bool first = true;
+    for (int p = 0; p < VQ_POS; ++p) {
+      if (win[p] == win[tid]) {
+        ++count;
+        if (p < tid) first = false;
+      }
+    }
+    if (first) atomicAdd(reinterpret_cast<unsigned long long*>(hist) + win[tid], (unsigned long long)count);
+  }
+  if (!emb_out && !partial) return;
+  const bool live = t0 + pos < T1;
+  double s = 0.0;
+  for (int c0 = 0; c0 < Cd; c0 += VQ_KC) {
+    __syncthreads();
+    for (int i = tid; i < VQ_POS * (VQ_KC / 4); i += 256) {
+      const int r = i / (VQ_KC / 4), c4 = (i % (VQ_KC / 4)) * 4;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (win[r] >= 0 && c0 + c4 + 3 < Cd) v = *reinterpret_cast<const f32x4*>(dict + (size_t)win[r] * Cd + c0 + c4);
+      *reinterpret_cast<f32x4*>(&ds[r][c4]) = v;
+    }
+    __syncthreads();
+    if (live) {
+      const f32x4 e0 = *reinterpret_cast<const f32x4*>(&ds[pos][cg * 8]);
+      const f32x4 e1 = *reinterpret_cast<const f32x4*>(&ds[pos][cg * 8 + 4]);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int c = c0 + cg * 8 + j;
+        if (c < Cd) {
+          const float e = j < 4 ? e0[j] : e1[j - 4];
+          const size_t at = (size_t)c * T1 + t0 + pos;
+          if (emb_out) emb_out[(size_t)b * Cd * T1 + at] = e;
+          if (partial) {
+            const float d = zb[at] - e;
+            const float d2 = __fmul_rn(d, d);  // (rounded to fp32 before it meets the fp64 sum: never contracted)
+            s += (double)d2;
+          }
+        }
+      }
+    }
+  }
+  if (!partial) return;
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+  if ((tid & 63) == 0) red[tid >> 6] = s;
+  __syncthreads();
+  if (tid == 0) partial[(size_t)b * ntile + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// sqerr[b] = sum of the clip's tile partials in tile order: one thread -- one writer -- per clip
+__global__ __launch_bounds__(64) void vq_sqerr_finish_kernel(const double* partial, double* sqerr, int B, int ntile) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  double s = 0.0;
+  for (int i = 0; i < ntile; ++i) s += partial[(size_t)b * ntile + i];
+  sqerr[b] = s;
 }
 
 __global__ __launch_bounds__(256) void vq_embed_kernel(const int64_t* idx, const float* dict, float* out, int Cd, int T1, int K) {
@@ -283,6 +387,22 @@ int run_ddpm_guided_eps(const float* x_t, const float* mean, const float* grad, 
 int run_vq_argmin(const float* z, const float* dict, float* en_scratch, int64_t* idx, int B, int Cd, int T1, int K, hipStream_t st) {
   hipLaunchKernelGGL(vq_norms_kernel, dim3((K + 255) / 256), dim3(256), 0, st, dict, en_scratch, K, Cd);
   hipLaunchKernelGGL(vq_argmin_kernel, dim3((T1 + VQ_POS - 1) / VQ_POS, B), dim3(256), 0, st, z, dict, en_scratch, idx, Cd, T1, K);
+  VQVS_HIP(hipGetLastError());
+  return 0;
+}
+
+size_t vq_quantize_scratch_bytes(int B, int T1, int K) { return ((size_t)B * ((T1 + VQ_POS - 1) / VQ_POS)) * 8 + (size_t)K * 4; }
+
+// scratch: [B * ntile] fp64 tile partials, then [K] fp32 code norms
+int run_vq_quantize(const float* z, const float* dict, void* scratch, int64_t* idx, float* embedded, double* sqerr, int64_t* hist, int B,
+                    int Cd, int T1, int K, hipStream_t st) {
+  const int ntile = (T1 + VQ_POS - 1) / VQ_POS;
+  double* partial = reinterpret_cast<double*>(scratch);
+  float* en = reinterpret_cast<float*>(partial + (size_t)B * ntile);
+  hipLaunchKernelGGL(vq_norms_kernel, dim3((K + 255) / 256), dim3(256), 0, st, dict, en, K, Cd);
+  hipLaunchKernelGGL(vq_quantize_kernel, dim3(ntile, B), dim3(256), 0, st, z, dict, en, idx, embedded, sqerr ? partial : nullptr, hist,
+                     Cd, T1, K, ntile);
+  if (sqerr) hipLaunchKernelGGL(vq_sqerr_finish_kernel, dim3((B + 63) / 64), dim3(64), 0, st, partial, sqerr, B, ntile);
   VQVS_HIP(hipGetLastError());
   return 0;
 }

@@ -18,5 +18,9 @@ int run_ddpm_noise(const float* x0, int x0_rows, const float* alpha, const float
 int run_ddpm_sqerr(const float* pred, const float* eps, int eps_rows, const int64_t* noise_index, float* loss, double* scratch, int B,
                    int T, uint64_t seed, uint64_t clip_offset, hipStream_t st);
 int run_vq_argmin(const float* z, const float* dict, float* en_scratch, int64_t* idx, int B, int Cd, int T1, int K, hipStream_t st);
+// fused search + embedding + per-clip sum of (z - e)^2 + code counts; scratch holds vq_quantize_scratch_bytes(B, T1, K) bytes
+size_t vq_quantize_scratch_bytes(int B, int T1, int K);
+int run_vq_quantize(const float* z, const float* dict, void* scratch, int64_t* idx, float* embedded, double* sqerr, int64_t* hist, int B,
+                    int Cd, int T1, int K, hipStream_t st);
 int run_vq_embed(const int64_t* idx, const float* dict, float* out, int B, int Cd, int T1, int K, hipStream_t st);
 }  // namespace vqvs

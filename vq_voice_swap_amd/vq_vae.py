@@ -54,6 +54,41 @@ class VQVAE(DiffusionModel):
         with torch.no_grad():
             return self.vq.encode(self.encoder(inputs))
 
+    def losses(self, vq_loss, inputs: torch.Tensor, labels: Optional[torch.Tensor] = None, jitter: float = 0.0, no_vq_prob: float = 0.0,
+               *, ts: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, seed: Optional[int] = None,
+               clip_offset: int = 0, hist: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """The losses of reference vq_vae.py:34-80 as an EVALUATION: {"vq_loss", "mse", "ts", "mses"} as there, plus "idxs"
+        [N,T1], "sq_err" [N] float64 (the clip's sum of (z - e)^2) and "embedded" [N,C,T1] (the conditioning, for a caller
+        that scores the decoder again).  Encoder (its own mode, fp32 unless `set_precision` was told otherwise) ->
+        `VQ.quantize` (one kernel: codes, embedding, error sums, counts into `hist`) -> `Diffusion.denoising_losses` with the
+        embedding as conditioning: the embedding is computed once and serves both losses.  `ts`, `noise`, `seed` and
+        `clip_offset` are those of `denoising_losses`; the t of a clip comes back unchanged.  `vq_loss` is a `StandardVQLoss`
+        (read from the kernel's sums) or any callable (inputs, embedded, dictionary) -> scalar.  `jitter` and `no_vq_prob`
+        are training-only regularisers and must be zero; a module in training mode is refused."""
+        if jitter or no_vq_prob:
+            raise ValueError(f"jitter={jitter!r} and no_vq_prob={no_vq_prob!r} are training-only regularisers (reference vq_vae.py:58-72); "
+                             "VQVAE.losses here is an evaluation and accepts only 0 for both")
+        if self.training or self.vq.training:
+            raise RuntimeError("VQVAE.losses is evaluation-only (no gradients, no usage tracking / revival); call .eval()")
+        from . import _native
+
+        _native.require_cuda(inputs, labels, noise, hist)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        if ts is None:
+            ts = self.diffusion.draw_ts(inputs.shape[0], seed, clip_offset)
+        with torch.no_grad():
+            z = self.encoder(inputs)
+            q = self.vq.quantize(z, hist=hist)
+            if hasattr(vq_loss, "from_sq_err"):
+                vq_value = vq_loss.from_sq_err(q["sq_err"], z.numel())
+            else:
+                vq_value = vq_loss(z, q["embedded"], self.vq.dictionary.detach().to(z))
+            mses = self.diffusion.denoising_losses(inputs, self.predictor, ts, noise=noise, seed=seed, clip_offset=clip_offset,
+                                                   cond=q["embedded"], labels=labels)
+        return {"vq_loss": vq_value, "mse": mses.mean(), "ts": ts, "mses": mses, "idxs": q["idxs"], "sq_err": q["sq_err"],
+                "embedded": q["embedded"]}
+
     def decode(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, steps: int = 100, progress: bool = False,
                constrain: bool = False, enc_pred=None, enc_pred_scale: float = 1.0, x_T: Optional[torch.Tensor] = None,
                **kwargs) -> torch.Tensor:
