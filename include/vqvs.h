@@ -275,6 +275,30 @@ int vqvs_vq_quantize(const float* d_z, const float* d_dict, int64_t* d_idx, floa
 /* out[b,:,t] = dict[idx[b,t],:]   reference vq.py:98-110 */
 int vqvs_vq_embed(const int64_t* d_idx, const float* d_dict, float* d_out, int B, int Cd, int T1, int K, void* stream);
 
+/* ---- guidance-model scores (handle-less) -------------------------------------------------
+ * Cross-entropy, accuracy, top-k and confusion counts of classification logits in one call: what the reference logs while it
+ * trains its two guidance models (train_loop.py:551-561 the classifier's NLL of the label, :602-613 the encoder predictor's code
+ * cross-entropy), plus the counts an evaluation wants.
+ *   d_logits  [B,K,L] f32, NCT with L contiguous: what vqvs_encpred_forward writes; a classifier's [B,K] logits are L = 1
+ *   d_targets [B,L] int64.  B in 1..65535, K in 1..8192, L in 1..2^24
+ * For a position (b, l) with target y:  rank = #{j : logit_j > logit_y} + #{j < y : logit_j == logit_y}, on the raw f32 logits:
+ * ties go to the first index, as in vqvs_vq_argmin; a NaN target logit ranks K.  A count: exact, whatever order it is taken in.
+ *   d_nll       [B] f64 out: sum over l of (logsumexp_j logit_j - logit_y).  The maximum is found in f32, the differences from
+ *               it are formed in f64 from the f32 inputs, exp and log are f64, and all sums are f64 in a fixed order: a
+ *               workgroup folds 64 positions, one thread adds the clip's tile sums in tile order and is the clip's only writer
+ *               (no floating-point atomics).  A clip's value is bitwise the same whatever B and its row are.
+ *   d_top1      [B] int64 out, or NULL: number of positions with rank 0
+ *   d_topk      [B] int64 out, or NULL: number of positions with rank < k; k in 1..K when given (k is not read otherwise)
+ *   d_confusion [K,K] int64 in/out, or NULL: d_confusion[y, argmax] += 1 per position, argmax = first index of the maximum
+ *               (integer atomics: exact in any order).  The caller zeroes it once and passes it to every call of a pass.
+ * A target outside 0..K-1 is never used as an index: that clip's d_nll becomes NaN and the position is counted nowhere.
+ * L > 1: lanes run along L (coalesced rows), eight waves split K and meet in LDS; keeps 16 bytes per (clip, 64-position tile)
+ * in the per-(device, stream) scratch buffer.  L = 1: lanes run along K, one workgroup (one wave up to K = 256) per row.
+ * Asynchronous on `stream`; NULL d_logits / d_targets / d_nll, sizes outside the limits or k out of range return VQVS_ERR_ARG
+ * before the device is touched. */
+int vqvs_xent_score(const float* d_logits, const int64_t* d_targets, double* d_nll, int64_t* d_top1, int64_t* d_topk, int k,
+                    int64_t* d_confusion, int B, int K, int L, void* stream);
+
 /* ---- test / profiling hooks ------------------------------------------------------ */
 int vqvs_debug_tap_count(const vqvs_model* m);
 int vqvs_debug_tap_info(const vqvs_model* m, int i, char* name_out, int name_cap, int* channels, int* length_shift);

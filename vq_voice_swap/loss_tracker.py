@@ -1,1 +1,1 @@
-from vq_voice_swap_amd.losses import LossTracker  # noqa: F401
+from vq_voice_swap_amd.losses import LossTracker, classification_scores  # noqa: F401

@@ -125,6 +125,14 @@ class Classifier(_NativeModule, Savable):
                                                                _native._stream_ptr()))
         return logits
 
+    def scores(self, x: torch.Tensor, ts: torch.Tensor, labels: torch.Tensor, *, topk=None, confusion=None):
+        """`classification_scores` of self(x, ts) against `labels` [N]: the NLL of the label the reference logs while training
+        (train_loop.py:551-561), with accuracy, top-k and confusion counts; forward and scoring on the same stream."""
+        from .losses import classification_scores
+
+        _native.require_cuda(labels)
+        return classification_scores(self(x, ts), labels.to(x.device), topk=topk, confusion=confusion)
+
     @property
     def feature_dim(self) -> int:
         return self.stem.out_channels

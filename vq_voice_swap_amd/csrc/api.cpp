@@ -414,6 +414,20 @@ int vqvs_vq_quantize(const float* d_z, const float* d_dict, int64_t* d_idx, floa
   return run_vq_quantize(d_z, d_dict, lease.p, d_idx, d_embedded, d_sqerr, d_hist, B, Cd, T1, K, reinterpret_cast<hipStream_t>(stream));
 }
 
+int vqvs_xent_score(const float* d_logits, const int64_t* d_targets, double* d_nll, int64_t* d_top1, int64_t* d_topk, int k,
+                    int64_t* d_confusion, int B, int K, int L, void* stream) {
+  if (!d_logits || !d_targets || !d_nll) VQVS_FAIL(VQVS_ERR_ARG, "logits, targets and nll must be non-NULL");
+  if (B < 1 || B > 65535) VQVS_FAIL(VQVS_ERR_ARG, "batch %d outside 1..65535", B);
+  if (K < 1 || K > 8192) VQVS_FAIL(VQVS_ERR_ARG, "class count %d outside 1..8192", K);
+  if (L < 1 || L > (1 << 24)) VQVS_FAIL(VQVS_ERR_ARG, "positions per clip %d outside 1..2^24", L);
+  if (d_topk && (k < 1 || k > K)) VQVS_FAIL(VQVS_ERR_ARG, "k=%d outside 1..%d", k, K);
+  ScratchLease lease;
+  if (L > 1)
+    if (int e = scratch_get(xent_score_scratch_bytes(B, L), stream, lease)) return e;
+  return run_xent_score(d_logits, d_targets, lease.p, d_nll, d_top1, d_topk, d_topk ? k : 0, d_confusion, B, K, L,
+                        reinterpret_cast<hipStream_t>(stream));
+}
+
 int vqvs_vq_embed(const int64_t* d_idx, const float* d_dict, float* d_out, int B, int Cd, int T1, int K, void* stream) {
   if (!d_idx || !d_dict || !d_out) VQVS_FAIL(VQVS_ERR_ARG, "NULL argument");
   return run_vq_embed(d_idx, d_dict, d_out, B, Cd, T1, K, reinterpret_cast<hipStream_t>(stream));

@@ -22,5 +22,9 @@ int run_vq_argmin(const float* z, const float* dict, float* en_scratch, int64_t*
 size_t vq_quantize_scratch_bytes(int B, int T1, int K);
 int run_vq_quantize(const float* z, const float* dict, void* scratch, int64_t* idx, float* embedded, double* sqerr, int64_t* hist, int B,
                     int Cd, int T1, int K, hipStream_t st);
+// cross-entropy scores of logits [B, K, L] against targets [B, L] (score_kernels.hip); scratch holds xent_score_scratch_bytes(B, L) bytes
+size_t xent_score_scratch_bytes(int B, int L);
+int run_xent_score(const float* logits, const int64_t* targets, void* scratch, double* nll, int64_t* top1, int64_t* topk, int k,
+                   int64_t* confusion, int B, int K, int L, hipStream_t st);
 int run_vq_embed(const int64_t* idx, const float* dict, float* out, int B, int Cd, int T1, int K, hipStream_t st);
 }  // namespace vqvs

@@ -117,6 +117,25 @@ class Diffusion:
         g = torch.Generator().manual_seed((int(seed) + 0x9E3779B97F4A7C15 * (int(clip_offset) + 1)) % (2 ** 63))
         return torch.rand(n, generator=g)
 
+    def sample_q_seeded(self, x_0: torch.Tensor, ts: torch.Tensor, *, seed: int, clip_offset: int = 0) -> torch.Tensor:
+        """`sample_q` with the noise drawn inside `vqvs_ddpm_noise` from the counter-based generator keyed by (seed, clip_offset +
+        row): the noising half of `denoising_losses`.  Row b is clip number clip_offset + b of a pass, so a clip's x_t does not
+        depend on the batch it is noised in.  alpha_bar(t) is evaluated on the host, as there."""
+        _native.require_cuda(x_0)
+        if x_0.dim() < 2:
+            raise ValueError("x_0 must be [N, ..., T]")
+        x0 = x_0.detach().to(torch.float32).contiguous()
+        B, T = x0.shape[0], x0[0].numel()
+        ts = ts.detach().to(dtype=torch.float32)
+        if ts.shape != (B,):
+            raise ValueError(f"expected ts of shape [{B}], got {tuple(ts.shape)}")
+        alpha = self.schedule(ts.cpu()).to(device=x0.device, dtype=torch.float32).contiguous()
+        x_t = torch.empty_like(x0)
+        with torch.cuda.device(x0.device):
+            _native.check(_native.lib().vqvs_ddpm_noise(x0.data_ptr(), B, alpha.data_ptr(), None, 0, None, x_t.data_ptr(), B, T,
+                                                        int(seed), int(clip_offset), _native._stream_ptr()))
+        return x_t
+
     def denoising_losses(self, x_0: torch.Tensor, predictor: Callable, ts: Optional[torch.Tensor] = None, *,
                          noise: Optional[torch.Tensor] = None, seed: Optional[int] = None,
                          noise_index: Optional[torch.Tensor] = None, clip_offset: int = 0, alpha: Optional[torch.Tensor] = None,

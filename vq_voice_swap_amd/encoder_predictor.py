@@ -83,6 +83,15 @@ class EncoderPredictor(_NativeModule, Savable):
         """Per-clip mean cross-entropy (encoder_predictor.py:60-64); values only -- the gradient path is `guidance_grad`."""
         return F.cross_entropy(self(x, ts), targets, reduction="none").mean(-1)
 
+    def scores(self, x: torch.Tensor, ts: torch.Tensor, targets: torch.Tensor, *, topk=None, confusion=None):
+        """`classification_scores` of self(x, ts) against `targets` [N, T // downsample_rate]: per clip the SUMMED code
+        cross-entropy (`losses` is its mean over "positions"), correct and top-k position counts, confusion counts; forward and
+        scoring on the same stream."""
+        from .losses import classification_scores
+
+        _native.require_cuda(targets)
+        return classification_scores(self(x, ts), targets.to(x.device), topk=topk, confusion=confusion)
+
     def guidance_grad(self, x: torch.Tensor, ts: torch.Tensor, targets: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
         """-scale * d/dx sum_{n,i} cross_entropy(logits[n,:,i], targets[n,i])   (vq_vae.py:125-130)."""
         x, ts, B, T = self._prepare(x, ts)

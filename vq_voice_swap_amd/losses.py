@@ -1,7 +1,9 @@
 """
 Denoising-loss evaluation: the per-quartile loss averages of the reference's eval_diffusion.py (its LossTracker,
 vq_voice_swap/loss_tracker.py:8-41) and the speaker search of voice_search_vqvae.py:68-103, both on
-`Diffusion.denoising_losses` (the fused noising / squared-error kernels).
+`Diffusion.denoising_losses` (the fused noising / squared-error kernels); and the scores of the two guidance models
+(`classification_scores`: the NLL the reference logs at train_loop.py:551-561 and :602-613, with accuracy, top-k and confusion
+counts, from one fused kernel).
 """
 
 from __future__ import annotations
@@ -10,6 +12,8 @@ from typing import Dict, List, Optional
 
 import numpy as np
 import torch
+
+from . import _native
 
 
 def _as_f64(v) -> np.ndarray:
@@ -123,3 +127,48 @@ def speaker_search_losses(model, target: torch.Tensor, encoded: torch.Tensor, la
         out.append(torch.stack(per_seed).mean(0))
     model.predictor.check_status()  # range guard of the decoder's mode, once per search
     return torch.cat(out)
+
+
+def classification_scores(logits: torch.Tensor, targets: torch.Tensor, *, topk: Optional[int] = None,
+                          confusion: Optional[torch.Tensor] = None) -> Dict[str, object]:
+    """Scores of classification logits against integer targets through `vqvs_xent_score`, on the current stream.
+
+    `logits` is float32 [B, K] with `targets` int64 [B] (a classifier), or [B, K, L] with targets [B, L] (an encoder predictor).
+    Returns {"nll": float64 [B], the clip's SUMMED negative log-likelihood; "top1": int64 [B], positions whose target holds the
+    first maximum; "topk": int64 [B], positions whose target ranks among the first `topk` (None when topk is None);
+    "positions": L}.  `confusion`, an int64 [K, K] tensor on the logits' device, gets [target, argmax] += 1 per position: zero it
+    once and pass it to every call of a pass.  Sums are deterministic float64 and counts exact, so a clip scores the same
+    whatever batch it is in.  Targets outside 0..K-1 raise IndexError before anything is launched."""
+    if not (torch.is_tensor(logits) and torch.is_tensor(targets)):
+        raise ValueError("logits and targets must be tensors")
+    if logits.dim() not in (2, 3):
+        raise ValueError(f"expected logits of shape [B, K] or [B, K, L], got {tuple(logits.shape)}")
+    B, K = int(logits.shape[0]), int(logits.shape[1])
+    L = int(logits.shape[2]) if logits.dim() == 3 else 1
+    want = (B, L) if logits.dim() == 3 else (B,)
+    if tuple(targets.shape) != want:
+        raise ValueError(f"expected targets of shape {want} for logits of shape {tuple(logits.shape)}, got {tuple(targets.shape)}")
+    if logits.dtype != torch.float32:
+        raise ValueError(f"logits must be float32, got {logits.dtype}")
+    if targets.dtype != torch.int64:
+        raise ValueError(f"targets must be int64, got {targets.dtype}")
+    if not (1 <= B <= 65535 and 1 <= K <= 8192 and 1 <= L <= 2 ** 24):
+        raise ValueError(f"B={B}, K={K}, L={L} outside the limits 1..65535, 1..8192, 1..2^24")
+    if topk is not None and not 1 <= int(topk) <= K:
+        raise ValueError(f"topk={topk} outside 1..{K}")
+    if confusion is not None:
+        if not torch.is_tensor(confusion) or confusion.dtype != torch.int64 or tuple(confusion.shape) != (K, K) or not confusion.is_contiguous():
+            raise ValueError(f"confusion must be a contiguous int64 tensor of shape {(K, K)}")
+    _native.require_cuda(logits, targets, confusion)
+    if targets.device != logits.device or (confusion is not None and confusion.device != logits.device):
+        raise ValueError("logits, targets and confusion must be on one device")
+    logits, targets = logits.detach().contiguous(), targets.detach().contiguous()
+    _native.check_index_range(targets, K, "classification_scores: targets")
+    nll = torch.empty(B, device=logits.device, dtype=torch.float64)
+    top1 = torch.empty(B, device=logits.device, dtype=torch.int64)
+    topk_out = torch.empty(B, device=logits.device, dtype=torch.int64) if topk is not None else None
+    with torch.cuda.device(logits.device):
+        _native.check(_native.lib().vqvs_xent_score(logits.data_ptr(), targets.data_ptr(), nll.data_ptr(), top1.data_ptr(),
+                                                    _native._ptr(topk_out), int(topk or 0), _native._ptr(confusion), B, K, L,
+                                                    _native._stream_ptr()))
+    return {"nll": nll, "top1": top1, "topk": topk_out, "positions": L}
