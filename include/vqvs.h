@@ -19,8 +19,8 @@
  *   - return value 0 = success, negative = error (vqvs_last_error() describes
  *     it, thread-local).  Nothing here falls back to a CPU path.
  *   - a handle is not thread-safe (one scratch arena); different handles are
- *     independent.  The handle-less entry points (vqvs_ddpm_step with CONSTRAIN,
- *     vqvs_vq_argmin) keep one small scratch buffer per (device, stream): calls on
+ *     independent.  The handle-less entry points (vqvs_ddpm_step and
+ *     vqvs_ddpm_step_windows with CONSTRAIN, vqvs_vq_argmin) keep one small scratch buffer per (device, stream): calls on
  *     different streams never share it and may run concurrently; calls on one
  *     stream are ordered by the stream.  One process per GPU.
  */
@@ -221,6 +221,29 @@ int vqvs_encpred_guidance(vqvs_model* m, const float* d_x, const float* d_ts, co
 int vqvs_ddpm_step(const float* d_x_t, const float* d_eps, const float* d_noise, const float* d_alpha_t,
                    const float* d_alpha_prev, float* d_x_prev, int B, int T, uint32_t flags, float noise_scale,
                    uint64_t seed, uint64_t clip_offset, uint32_t step_index, void* stream);
+/* The reverse step of ONE long signal whose predictions came from overlapping windows of the trained length (handle-less; the
+ * reference has no counterpart).  n windows of W samples, one every H: sample j of window b is absolute position p = b * H + j of a
+ * signal of Np = (n - 1) * H + W samples, and V = W - H is the overlap.
+ *   d_x [Np] f32 the long state; d_eps [n,W] f32 the predictor's output on the windows
+ *   d_alpha_t, d_alpha_prev: ONE float each (all windows of a recording share t)
+ *   d_noise [Np] f32, one value per absolute position, or NULL to draw philox_normal4(seed, quad = p / 4, clip, step_index, stream 0):
+ *     exactly what vqvs_ddpm_step draws for ONE row of length Np at clip_offset = clip, shared by the windows that overlap
+ *   d_x_prev [Np] f32 out; d_windows [n,W] f32 out or NULL: d_windows[b,j] = d_x_prev[b * H + j], the next forward's input, written
+ *     in the same pass (both copies of an overlap sample are the same value)
+ *   flags, noise_scale: as for vqvs_ddpm_step
+ * Per sample p, with the coefficients of vqvs_ddpm_step: a window b that covers p contributes e_b = eps[b,j], with CONSTRAIN
+ * re-derived as there, x0 = clamp((x[p] - sqrt(1-a_t) e_b) / sqrt(a_t) - mean_b, -1, 1), about window b's OWN mean of x0 over its W
+ * samples (fp64 partials per 4096 samples added in chunk order: n * ceil(W / 4096) doubles of the per-(device, stream) scratch
+ * buffer).  One window: e = e_b.  Two, left b and right b + 1: u = p - (b + 1) * H in [0, V), w = (u + 1/2) / V,
+ * e = fmaf(w, e_right - e_left, e_left).  Then x_prev[p] = c1 * (x[p] - c2 * e) + sigma * noise: means are blended and the noise is
+ * shared, so the step has the variance of a single clip's and the windows agree on their common samples at every step.  At n = 1 the
+ * result equals vqvs_ddpm_step(B = 1, T = W, clip_offset = clip) bit for bit.
+ * Limits (VQVS_ERR_ARG before the device is touched): n in 1..65535; W and H positive multiples of 4 (every access is 16 bytes wide:
+ * a quad never straddles a window boundary); 0 <= V <= H, so at most two windows cover a sample; Np < 2^31; NULL d_x, d_eps,
+ * d_alpha_t, d_alpha_prev or d_x_prev; d_x_prev overlapping d_x. */
+int vqvs_ddpm_step_windows(const float* d_x, const float* d_eps, const float* d_noise, const float* d_alpha_t,
+                           const float* d_alpha_prev, float* d_x_prev, float* d_windows, int n, int W, int H, uint32_t flags,
+                           float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index, void* stream);
 /* mean = eps_to_prev(eps)  and  eps' = prev_to_eps(mean + sigma^2 * grad)   (diffusion.py:69-83) */
 int vqvs_ddpm_mean(const float* d_x_t, const float* d_eps, const float* d_alpha_t, const float* d_alpha_prev,
                    float* d_mean, int B, int T, void* stream);

@@ -3,6 +3,7 @@
 Encode a clip with a VQ-VAE and decode it as another speaker, on MI355X.  Counterpart of the reference's
 sample_vqvae.py (same flags and positionals; reference sample_vqvae.py:76-92): read 4 s of 16 kHz audio,
 `encode`, `decode(labels, constrain=True)`, clamp, write WAV; `--check-vq` re-encodes the result.
+`--whole-file` (not in the reference) converts the whole input instead: `encode_long` / `decode_long` on overlapping windows.
 Differences: WAV in/out directly (no ffmpeg); the model is put in eval mode (the reference's train-mode VQ
 bookkeeping crashes on current numpy; outputs are identical).  `--enc-pred-path` loads an
 EncoderPredictor whose guidance gradient comes from the library's explicit backward schedule (no autograd).
@@ -13,6 +14,7 @@ import sys
 
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in device memory: a process-level HIP switch, set before the runtime starts
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -34,6 +36,11 @@ def arg_parser():
     p.add_argument("--check-vq", action="store_true")
     p.add_argument("--seed", default=None, type=int)
     p.add_argument("--precision", default="fp32", choices=["fp32", "fp16", "bf16"])
+    p.add_argument("--whole-file", action="store_true",
+                   help="convert the whole input, not its first --seconds: overlapping windows of one long signal, blended at every step")
+    p.add_argument("--window-seconds", type=float, default=None, help="window length with --whole-file (default: --seconds)")
+    p.add_argument("--overlap-seconds", type=float, default=0.4, help="overlap of neighbouring windows with --whole-file")
+    p.add_argument("--window-batch", type=int, default=64, help="windows per forward with --whole-file")
     p.add_argument("checkpoint_path", type=str)
     p.add_argument("output_file", type=str)
     return p
@@ -57,6 +64,9 @@ def main(argv=None):
         enc_pred.eval()
         enc_pred.set_precision(args.precision)
 
+    if args.whole_file:
+        return convert_whole_file(args, model, enc_pred, device)
+
     print(f"loading waveform from {args.input_file}...")
     reader = ChunkReader(args.input_file, sample_rate=args.sample_rate, encoding=args.encoding)
     try:
@@ -78,6 +88,46 @@ def main(argv=None):
     if args.check_vq:
         assert not args.no_vq
         count = (encoded == model.encode(sample)).float().mean()
+        print(f"fraction of consistent VQ codes: {count}")
+
+    print(f"saving result to {args.output_file}...")
+    writer = ChunkWriter(args.output_file, sample_rate=args.sample_rate, encoding=args.encoding)
+    try:
+        writer.write(sample.clamp(-1, 1).cpu().numpy().flatten())
+    finally:
+        writer.close()
+
+
+def convert_whole_file(args, model, enc_pred, device):
+    """--whole-file: every sample of the input, through `encode_long` / `decode_long`; the output has the input's length."""
+    if args.no_vq:
+        raise SystemExit("--no-vq is not available with --whole-file")
+    window = round((args.seconds if args.window_seconds is None else args.window_seconds) * args.sample_rate)
+    hop = window - round(args.overlap_seconds * args.sample_rate)
+    print(f"loading waveform from {args.input_file}...")
+    reader = ChunkReader(args.input_file, sample_rate=args.sample_rate, encoding=args.encoding)
+    try:
+        chunks = []
+        while (chunk := reader.read(1 << 20)) is not None:
+            chunks.append(chunk)
+    finally:
+        reader.close()
+    if not chunks:
+        raise SystemExit(f"{args.input_file} holds no samples")
+    wave = torch.from_numpy(np.concatenate(chunks)[None, None]).to(device)
+    num_samples = wave.shape[-1]
+
+    print(f"encoding {num_samples} samples in windows of {window} every {hop}...")
+    encoded = model.encode_long(wave, window, hop, args.window_batch)
+
+    print(f"decoding {encoded.shape[0]} windows...")
+    labels = torch.tensor([args.label]).long().to(device)
+    sample = model.decode_long(encoded, labels, num_samples=num_samples, window=window, hop=hop, steps=args.sample_steps, progress=True,
+                               constrain=True, seed=args.seed, enc_pred=enc_pred, enc_pred_scale=args.enc_pred_scale,
+                               window_batch=args.window_batch)
+
+    if args.check_vq:
+        count = (encoded == model.encode_long(sample, window, hop, args.window_batch)).float().mean()
         print(f"fraction of consistent VQ codes: {count}")
 
     print(f"saving result to {args.output_file}...")

@@ -14,6 +14,7 @@ from .dataset import create_data_loader
 from .diffusion import CosSchedule, Diffusion, ExpSchedule, Schedule, make_schedule, randn_clips
 from .diffusion_model import DiffusionModel
 from .encoder_predictor import EncoderPredictor
+from .longform import plan_windows
 from .losses import LossTracker, classification_scores, speaker_search_losses
 from .stats import FeatureStats, class_score, frechet_distance, wav_roundtrip
 from .unet import ResBlockModule, UNetEncoder, UNetPredictor
@@ -24,5 +25,5 @@ __all__ = [
     "Savable", "atomic_save", "CosSchedule", "Diffusion", "ExpSchedule", "Schedule", "make_schedule", "randn_clips",
     "DiffusionModel", "Classifier", "ConvMFCCEncoder", "EncoderPredictor", "ResBlockModule", "UNetEncoder", "UNetPredictor", "VQ", "VQVAE",
     "FeatureStats", "class_score", "frechet_distance", "wav_roundtrip", "LossTracker", "speaker_search_losses", "create_data_loader",
-    "StandardVQLoss", "VQLoss", "code_usage", "classification_scores",
+    "StandardVQLoss", "VQLoss", "code_usage", "classification_scores", "plan_windows",
 ]

@@ -348,6 +348,23 @@ int vqvs_ddpm_step(const float* d_x_t, const float* d_eps, const float* d_noise,
                        noise_scale, seed, clip_offset, step_index, reinterpret_cast<hipStream_t>(stream));
 }
 
+int vqvs_ddpm_step_windows(const float* d_x, const float* d_eps, const float* d_noise, const float* d_alpha_t, const float* d_alpha_prev,
+                           float* d_x_prev, float* d_windows, int n, int W, int H, uint32_t flags, float noise_scale, uint64_t seed,
+                           uint64_t clip, uint32_t step_index, void* stream) {
+  if (!d_x || !d_eps || !d_alpha_t || !d_alpha_prev || !d_x_prev) VQVS_FAIL(VQVS_ERR_ARG, "x, eps, alpha_t, alpha_prev and x_prev must be non-NULL");
+  if (n < 1 || n > 65535) VQVS_FAIL(VQVS_ERR_ARG, "window count %d outside 1..65535", n);
+  if (W < 4 || H < 4 || W % 4 || H % 4) VQVS_FAIL(VQVS_ERR_ARG, "window %d and hop %d must be positive multiples of 4", W, H);
+  if (W < H || W - H > H) VQVS_FAIL(VQVS_ERR_ARG, "overlap %d (window %d - hop %d) outside 0..hop: at most two windows may cover a sample", W - H, W, H);
+  const int64_t Np = (int64_t)(n - 1) * H + W;
+  if (Np >= ((int64_t)1 << 31)) VQVS_FAIL(VQVS_ERR_ARG, "%d windows every %d samples span %lld samples: 2^31 or more", n, H, (long long)Np);
+  if (d_x_prev < d_x + Np && d_x < d_x_prev + Np) VQVS_FAIL(VQVS_ERR_ARG, "x_prev must not overlap x");
+  ScratchLease lease;
+  if (flags & VQVS_DDPM_CONSTRAIN)
+    if (int e = scratch_get((size_t)ddpm_scratch_doubles(n, W) * 8, stream, lease)) return e;
+  return run_ddpm_step_windows(d_x, d_eps, d_noise, d_alpha_t, d_alpha_prev, d_x_prev, d_windows, reinterpret_cast<double*>(lease.p), n, W, H,
+                               flags, noise_scale, seed, clip, step_index, reinterpret_cast<hipStream_t>(stream));
+}
+
 int vqvs_ddpm_mean(const float* d_x_t, const float* d_eps, const float* d_alpha_t, const float* d_alpha_prev, float* d_mean, int B, int T,
                    void* stream) {
   if (!d_x_t || !d_eps || !d_alpha_t || !d_alpha_prev || !d_mean) VQVS_FAIL(VQVS_ERR_ARG, "NULL argument");

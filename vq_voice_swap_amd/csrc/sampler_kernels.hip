@@ -45,17 +45,19 @@ __device__ __forceinline__ StepCoef step_coef(float a_t, float a_prev, bool sigm
 
 constexpr int SUM_CHUNK = 4096;
 
-// sum over time of x0 = (x_t - sqrt(1-a_t) eps) rsqrt(a_t), per (clip, chunk); fp64 partials
-__global__ __launch_bounds__(256) void ddpm_x0sum_kernel(const float* x_t, const float* eps, const float* a_t, double* partial, int T, int nchunk) {
+// sum over time of x0 = (x_t - sqrt(1-a_t) eps) rsqrt(a_t), per (clip, chunk); fp64 partials.  Row b of eps is [T] contiguous; row b of
+// x_t starts at b * x_stride and its alpha is a_t[b * a_stride]: (T, 1) for a batch of clips, (hop, 0) for the overlapping windows
+// of one long signal (ddpm_step_windows_kernel), which are then summed exactly as a clip is.
+__global__ __launch_bounds__(256) void ddpm_x0sum_kernel(const float* x_t, const float* eps, const float* a_t, double* partial, int T, int nchunk,
+                                                         int x_stride, int a_stride) {
   __shared__ double red[256];
   const int b = blockIdx.y;
-  const float at = a_t[b];
+  const float at = a_t[b * a_stride];
   const float sq = sqrtf(1.0f - at), rs = 1.0f / sqrtf(at);
   const int beg = blockIdx.x * SUM_CHUNK, end = min(T, beg + SUM_CHUNK);
   double s = 0.0;
   for (int t = beg + threadIdx.x; t < end; t += 256) {
-    const size_t i = (size_t)b * T + t;
-    s += (double)((x_t[i] - sq * eps[i]) * rs);
+    s += (double)((x_t[(size_t)b * x_stride + t] - sq * eps[(size_t)b * T + t]) * rs);
   }
   red[threadIdx.x] = s;
   __syncthreads();
@@ -64,6 +66,37 @@ __global__ __launch_bounds__(256) void ddpm_x0sum_kernel(const float* x_t, const
     __syncthreads();
   }
   if (threadIdx.x == 0) partial[(size_t)b * nchunk + blockIdx.x] = red[0];
+}
+
+// mean of x0 over one clip / window: the chunk partials of ddpm_x0sum_kernel added in chunk order
+__device__ __forceinline__ float x0_mean(const double* partial, int nchunk, int T) {
+  double s = 0.0;
+  for (int i = 0; i < nchunk; ++i) s += partial[i];
+  return (float)(s / (double)T);
+}
+
+// One sample of the reverse step, shared by ddpm_step_kernel and ddpm_step_windows_kernel (diffusion.py:84-90): with `constrain`
+// the prediction is re-derived from x0 clamped about the clip's (window's) own mean; BLEND cross-fades a left and a right window's
+// predictions, each re-derived with its own mean, with weight w on the right one.  Without BLEND the right-hand arguments are unused.
+// Every rounding is spelled out (contraction off, fmaf where the single-clip kernel has always fused), so that the two kernels --
+// and the two sides of BLEND -- round alike whatever surrounds the call: at one window the result is ddpm_step_kernel's to the bit.
+__device__ __forceinline__ float constrained_eps(const StepCoef& k, float x, float e, float mean) {
+#pragma clang fp contract(off)
+  float x0 = fmaf(fmaf(-k.sq1mat, e, x), k.rsat, -mean);
+  x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+  return fmaf(-x0, k.sqat, x) * k.rs1mat;
+}
+
+template <bool BLEND>
+__device__ __forceinline__ float step_sample(const StepCoef& k, bool constrain, float x, float nv, float e, float mean, float e_r = 0.f,
+                                             float mean_r = 0.f, float w = 0.f) {
+#pragma clang fp contract(off)
+  if (constrain) e = constrained_eps(k, x, e, mean);
+  if (BLEND) {
+    if (constrain) e_r = constrained_eps(k, x, e_r, mean_r);
+    e = fmaf(w, e_r - e, e);
+  }
+  return k.c1 * fmaf(-k.c2, e, x) + k.sig * nv;
 }
 
 __global__ __launch_bounds__(256) void ddpm_step_kernel(const float* x_t, const float* eps, const float* noise, const float* a_t,
@@ -75,11 +108,7 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const float* x_t, const 
   if (q * 4 >= T) return;
   const StepCoef k = step_coef(a_t[b], a_prev[b], flags & 1u);
   float mean = 0.f;
-  if (flags & 2u) {
-    double s = 0.0;
-    for (int i = 0; i < nchunk; ++i) s += partial[(size_t)b * nchunk + i];
-    mean = (float)(s / (double)T);
-  }
+  if (flags & 2u) mean = x0_mean(partial + (size_t)b * nchunk, nchunk, T);
   const size_t base = (size_t)b * T + q * 4;
   const int n = min(4, T - q * 4);
   float xv[4], ev[4], nv[4] = {0.f, 0.f, 0.f, 0.f};
@@ -95,14 +124,57 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const float* x_t, const 
       for (int j = 0; j < 4; ++j) nv[j] = z[j] * noise_scale;
     }
   }
-  for (int j = 0; j < n; ++j) {
-    float e = ev[j];
-    if (flags & 2u) {
-      float x0 = (xv[j] - k.sq1mat * e) * k.rsat;
-      x0 = fminf(fmaxf(x0 - mean, -1.0f), 1.0f);
-      e = (xv[j] - x0 * k.sqat) * k.rs1mat;
+  for (int j = 0; j < n; ++j) out[base + j] = step_sample<false>(k, flags & 2u, xv[j], nv[j], ev[j], mean);
+}
+
+// The reverse step of ONE long signal x [Np], Np = (n - 1) * H + W, whose predictions came from n windows of W samples, one every H
+// (eps [n, W]); V = W - H <= H, so a sample lies in one window or in two.  A thread owns the quad at absolute position p = 4 q: W and H
+// are multiples of 4, so the quad lies in the same window(s), and every access is 16 bytes wide.  Window `br` is the last one that
+// starts at or before p; the one before it covers p too while u = p - br * H < V, and the two predictions are then cross-faded with
+// w = (u + 1/2) / V.  The noise is one draw per absolute position -- row 0 of a [1, Np] batch at `clip`, as ddpm_step_kernel draws
+// it -- so the overlapping windows share it, and the result goes to x_prev [Np] and, for the next forward, to both windows' rows of
+// win [n, W] (NULL: not wanted).  partial: n * nchunk chunk sums of ddpm_x0sum_kernel.
+__global__ __launch_bounds__(256) void ddpm_step_windows_kernel(const float* x, const float* eps, const float* noise, const float* a_t,
+                                                                const float* a_prev, const double* partial, int nchunk, float* x_prev,
+                                                                float* win, int n, int W, int H, uint32_t flags, float noise_scale,
+                                                                uint64_t seed, uint64_t clip, uint32_t step_index) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  const int Np = (n - 1) * H + W, V = W - H;
+  if (q >= Np / 4) return;
+  const int p = q * 4;
+  const StepCoef k = step_coef(a_t[0], a_prev[0], flags & 1u);
+  const bool constrain = flags & 2u;
+  const int br = min(p / H, n - 1);
+  const int u = p - br * H;  // offset in window br; in window br - 1 the sample is u + H
+  const bool two = br > 0 && u < V;
+  const size_t at_r = (size_t)br * W + u, at_l = two ? (size_t)(br - 1) * W + u + H : 0;
+  const f32x4 xv = *reinterpret_cast<const f32x4*>(x + p);
+  const f32x4 er = *reinterpret_cast<const f32x4*>(eps + at_r);
+  f32x4 el = er;
+  if (two) el = *reinterpret_cast<const f32x4*>(eps + at_l);
+  float mean_r = 0.f, mean_l = 0.f;
+  if (constrain) {
+    mean_r = x0_mean(partial + (size_t)br * nchunk, nchunk, W);
+    if (two) mean_l = x0_mean(partial + (size_t)(br - 1) * nchunk, nchunk, W);
+  }
+  f32x4 nv = {0.f, 0.f, 0.f, 0.f};
+  if (noise_scale != 0.f) {
+    const f32x4 z = noise ? *reinterpret_cast<const f32x4*>(noise + p) : philox_normal4(seed, (uint32_t)q, clip, step_index, 0u);
+    for (int j = 0; j < 4; ++j) nv[j] = z[j] * noise_scale;
+  }
+  f32x4 o;
+  if (two) {
+    for (int j = 0; j < 4; ++j) {
+      const float w = ((float)(u + j) + 0.5f) / (float)V;
+      o[j] = step_sample<true>(k, constrain, xv[j], nv[j], el[j], mean_l, er[j], mean_r, w);
     }
-    out[base + j] = k.c1 * (xv[j] - k.c2 * e) + k.sig * nv[j];
+  } else {
+    for (int j = 0; j < 4; ++j) o[j] = step_sample<false>(k, constrain, xv[j], nv[j], er[j], mean_r);
+  }
+  *reinterpret_cast<f32x4*>(x_prev + p) = o;
+  if (win) {
+    *reinterpret_cast<f32x4*>(win + at_r) = o;
+    if (two) *reinterpret_cast<f32x4*>(win + at_l) = o;
   }
 }
 
@@ -362,11 +434,26 @@ int run_ddpm_step(const float* x_t, const float* eps, const float* noise, const 
                   uint32_t step_index, hipStream_t st) {
   const int nchunk = (T + SUM_CHUNK - 1) / SUM_CHUNK;
   if (flags & 2u) {
-    hipLaunchKernelGGL(ddpm_x0sum_kernel, dim3(nchunk, B), dim3(256), 0, st, x_t, eps, a_t, scratch, T, nchunk);
+    hipLaunchKernelGGL(ddpm_x0sum_kernel, dim3(nchunk, B), dim3(256), 0, st, x_t, eps, a_t, scratch, T, nchunk, T, 1);
   }
   dim3 grid(((T + 3) / 4 + 255) / 256, B);
   hipLaunchKernelGGL(ddpm_step_kernel, grid, dim3(256), 0, st, x_t, eps, noise, a_t, a_prev, scratch, nchunk, out, T, flags,
                      noise_scale, seed, clip_offset, step_index);
+  VQVS_HIP(hipGetLastError());
+  return 0;
+}
+
+// scratch: ddpm_scratch_doubles(n, W) doubles when flags has CONSTRAIN (not read otherwise)
+int run_ddpm_step_windows(const float* x, const float* eps, const float* noise, const float* a_t, const float* a_prev, float* x_prev,
+                          float* windows, double* scratch, int n, int W, int H, uint32_t flags, float noise_scale, uint64_t seed,
+                          uint64_t clip, uint32_t step_index, hipStream_t st) {
+  const int nchunk = (W + SUM_CHUNK - 1) / SUM_CHUNK;
+  if (flags & 2u) {
+    hipLaunchKernelGGL(ddpm_x0sum_kernel, dim3(nchunk, n), dim3(256), 0, st, x, eps, a_t, scratch, W, nchunk, H, 0);
+  }
+  const int quads = ((n - 1) * H + W) / 4;
+  hipLaunchKernelGGL(ddpm_step_windows_kernel, dim3((quads + 255) / 256), dim3(256), 0, st, x, eps, noise, a_t, a_prev, scratch, nchunk,
+                     x_prev, windows, n, W, H, flags, noise_scale, seed, clip, step_index);
   VQVS_HIP(hipGetLastError());
   return 0;
 }

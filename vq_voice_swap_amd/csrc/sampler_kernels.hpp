@@ -8,6 +8,10 @@ int ddpm_scratch_doubles(int B, int T);
 int run_ddpm_step(const float* x_t, const float* eps, const float* noise, const float* a_t, const float* a_prev, float* out,
                   double* scratch, int B, int T, uint32_t flags, float noise_scale, uint64_t seed, uint64_t clip_offset,
                   uint32_t step_index, hipStream_t st);
+// the step of one long signal [(n - 1) * H + W] from the predictions of its n overlapping windows [n, W]; scratch as run_ddpm_step(n, W)
+int run_ddpm_step_windows(const float* x, const float* eps, const float* noise, const float* a_t, const float* a_prev, float* x_prev,
+                          float* windows, double* scratch, int n, int W, int H, uint32_t flags, float noise_scale, uint64_t seed,
+                          uint64_t clip, uint32_t step_index, hipStream_t st);
 int run_ddpm_mean(const float* x_t, const float* eps, const float* a_t, const float* a_prev, float* out, int B, int T, hipStream_t st);
 int run_ddpm_guided_eps(const float* x_t, const float* mean, const float* grad, const float* a_t, const float* a_prev, float* out,
                         int B, int T, uint32_t flags, hipStream_t st);

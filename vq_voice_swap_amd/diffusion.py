@@ -83,6 +83,36 @@ def _native_modules(fn) -> list:
     return out
 
 
+def few_guided_steps_promotion(what: str, steps: int, predictor, cond_fn):
+    """Few guided steps in a 2-byte mode: the first reverse step multiplies the predictor's rounding error by 1 / sqrt(alpha_bar(1))
+    and a guided run adds the classifier gradient's own; fewer than FEW_GUIDED_STEPS iterations never average that out (measured:
+    config 5 at 3 steps 1.05e-3 in fp16 against the 1e-3 waveform contract, profiles/r05_parity_margins.jsonl).  The call is then
+    promoted to the fp32 mode -- predictor and guidance model -- through precision_override, which keeps each module's own
+    handle; VQVAE.decode_uncond_guidance does the same for its extrapolation.  (VQVS_FEW_STEP_PROMOTE=0: warn only.)
+    Returns None, or an ExitStack holding the overrides: the sampler `what` runs itself again inside it."""
+    if cond_fn is None or steps >= FEW_GUIDED_STEPS:
+        return None
+    promote = [m for m in _native_modules(predictor) + _native_modules(cond_fn) if getattr(m, "precision", "fp32") != "fp32"]
+    if not promote:
+        return None
+    import contextlib
+    import os
+    import warnings
+
+    modes = sorted({m.precision for m in promote})
+    if os.environ.get("VQVS_FEW_STEP_PROMOTE", "1") == "0":
+        warnings.warn(f"{what}: {steps} guided steps in the {modes} mode(s) are outside the 1e-3 waveform contract "
+                      f"(fewer than {FEW_GUIDED_STEPS} steps); VQVS_FEW_STEP_PROMOTE=0 keeps the mode", RuntimeWarning, stacklevel=3)
+        return None
+    warnings.warn(f"{what}: {steps} guided steps (fewer than {FEW_GUIDED_STEPS}): predictor / guidance model run in the fp32 "
+                  f"mode for this call (their {modes} mode(s) do not hold the 1e-3 waveform contract at so few steps)",
+                  RuntimeWarning, stacklevel=3)
+    stack = contextlib.ExitStack()
+    for m in promote:
+        stack.enter_context(m.precision_override("fp32"))
+    return stack
+
+
 class Diffusion:
     def __init__(self, schedule: Schedule):
         self.schedule = schedule
@@ -262,6 +292,45 @@ class Diffusion:
                                            int(step_index), st))
         return out.view_as(x_t)
 
+    def step_tables(self, steps: int, B: int, schedule: Optional[Callable], device):
+        """Per-step scalars of a sampling run, t = steps/steps ... 1/steps: the reference's float32 tensor expressions
+        (diffusion.py:107-118, schedule.py:30-41), evaluated once on the HOST -- the same arithmetic as the CPU reference -- and
+        uploaded as four [steps, B] tables (t, alpha_bar(t), alpha_bar(t - step), t - step), instead of ~20 device micro-kernels per
+        step."""
+        rows = []
+        for t in [(i + 1) / steps for i in range(steps)][::-1]:
+            ts = torch.tensor([t] * B, dtype=torch.float32)
+            t_step = 1 / steps
+            if schedule is not None:
+                t_step = schedule(ts) - schedule(ts - 1 / steps)
+                ts = schedule(ts)
+            step = t_step if torch.is_tensor(t_step) else torch.full_like(ts, float(t_step))
+            rows.append((ts, self.schedule(ts), self.schedule(ts - step), ts - step))
+        return tuple(torch.stack([r[k] for r in rows]).to(torch.float32).contiguous().to(device) for k in range(4))
+
+    @staticmethod
+    def check_sample(predictor, x_t: torch.Tensor, what: str) -> None:
+        """The end of a sampling run: the range guard of a native predictor (once per sample, not per step) and the sample's
+        finiteness."""
+        chk = getattr(predictor, "check_status", None)
+        if chk is None:
+            mods = _native_modules(predictor)
+            chk = mods[0].check_status if mods else None
+        if chk is not None:
+            chk()
+            # The library's guard sees the tensors that feed a GroupNorm.  The network's output and x_t are fp32 in every mode and cannot
+            # overflow a storage type, but a non-finite value can still reach them (an inf / NaN in x_T, in the conditioning or in a
+            # cond_fn's gradient): the finished sample is checked here, on the sync check_status() has just paid for.
+            if not bool(torch.isfinite(x_t).all()):
+                raise _native.NativeError(f"{what}: the sample holds non-finite values (a non-finite x_T, conditioning tensor or "
+                                          "guidance gradient, or an overflow the range guard reported as a warning)")
+
+    def ddpm_sample_windows(self, x_T_long: torch.Tensor, predictor: Callable, steps: int, **kwargs) -> torch.Tensor:
+        """`ddpm_sample` for one long state [1,1,Np] predicted through overlapping windows (longform.ddpm_sample_windows)."""
+        from .longform import ddpm_sample_windows
+
+        return ddpm_sample_windows(self, x_T_long, predictor, steps, **kwargs)
+
     def ddpm_sample(
         self,
         x_T: torch.Tensor,
@@ -282,49 +351,14 @@ class Diffusion:
         _native.require_cuda(x_T)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        # Few guided steps in a 2-byte mode: the first reverse step multiplies the predictor's rounding error by 1 / sqrt(alpha_bar(1))
-        # and a guided run adds the classifier gradient's own; fewer than FEW_GUIDED_STEPS iterations never average that out (measured:
-        # config 5 at 3 steps 1.05e-3 in fp16 against the 1e-3 waveform contract, profiles/r05_parity_margins.jsonl).  The call is then
-        # promoted to the fp32 mode -- predictor and guidance model -- through precision_override, which keeps each module's own
-        # handle; VQVAE.decode_uncond_guidance does the same for its extrapolation.  (VQVS_FEW_STEP_PROMOTE=0: warn only.)
-        promote = []
-        if cond_fn is not None and steps < FEW_GUIDED_STEPS:
-            promote = [m for m in _native_modules(predictor) + _native_modules(cond_fn) if getattr(m, "precision", "fp32") != "fp32"]
-        if promote:
-            import contextlib
-            import os
-            import warnings
-
-            modes = sorted({m.precision for m in promote})
-            if os.environ.get("VQVS_FEW_STEP_PROMOTE", "1") == "0":
-                warnings.warn(f"ddpm_sample: {steps} guided steps in the {modes} mode(s) are outside the 1e-3 waveform contract "
-                              f"(fewer than {FEW_GUIDED_STEPS} steps); VQVS_FEW_STEP_PROMOTE=0 keeps the mode", RuntimeWarning, stacklevel=2)
-            else:
-                warnings.warn(f"ddpm_sample: {steps} guided steps (fewer than {FEW_GUIDED_STEPS}): predictor / guidance model run in the fp32 "
-                              f"mode for this call (their {modes} mode(s) do not hold the 1e-3 waveform contract at so few steps)",
-                              RuntimeWarning, stacklevel=2)
-                with contextlib.ExitStack() as stack:
-                    for m in promote:
-                        stack.enter_context(m.precision_override("fp32"))
-                    return self.ddpm_sample(x_T, predictor, steps, progress=progress, sigma_large=sigma_large, constrain=constrain,
-                                            cond_fn=cond_fn, schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset)
+        stack = few_guided_steps_promotion("ddpm_sample", steps, predictor, cond_fn)
+        if stack is not None:
+            with stack:
+                return self.ddpm_sample(x_T, predictor, steps, progress=progress, sigma_large=sigma_large, constrain=constrain,
+                                        cond_fn=cond_fn, schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset)
         x_t = x_T
         B = x_T.shape[0]
-        t_values = [(i + 1) / steps for i in range(steps)][::-1]
-        # Per-step scalars: the reference's float32 tensor expressions (diffusion.py:107-118, schedule.py:30-41), evaluated once
-        # on the HOST -- the same arithmetic as the CPU reference -- and uploaded as four [steps, B] tables, instead of ~20
-        # device micro-kernels per step.
-        rows = []
-        for t in t_values:
-            ts = torch.tensor([t] * B, dtype=torch.float32)
-            t_step = 1 / steps
-            if schedule is not None:
-                t_step = schedule(ts) - schedule(ts - 1 / steps)
-                ts = schedule(ts)
-            step = t_step if torch.is_tensor(t_step) else torch.full_like(ts, float(t_step))
-            rows.append((ts, self.schedule(ts), self.schedule(ts - step), ts - step))
-        ts_all, a_t_all, a_prev_all, ts_prev_all = (torch.stack([r[k] for r in rows]).to(torch.float32).contiguous().to(x_T.device)
-                                                    for k in range(4))
+        ts_all, a_t_all, a_prev_all, ts_prev_all = self.step_tables(steps, B, schedule, x_T.device)
         its = range(steps)
         if progress:
             from tqdm.auto import tqdm
@@ -344,18 +378,7 @@ class Diffusion:
                 x_t = self._step(x_t, eps, a_t_all[i], a_prev_all[i], ts_prev_all[i], noise=nz, sigma_large=sigma_large,
                                  constrain=constrain, cond_fn=cond_fn, seed=seed, clip_offset=clip_offset, step_index=i,
                                  noise_scale=0.0 if last else 1.0)
-        chk = getattr(predictor, "check_status", None)  # range guard of a native predictor: once per sample, not per step
-        if chk is None:
-            mods = _native_modules(predictor)
-            chk = mods[0].check_status if mods else None
-        if chk is not None:
-            chk()
-            # The library's guard sees the tensors that feed a GroupNorm.  The network's output and x_t are fp32 in every mode and cannot
-            # overflow a storage type, but a non-finite value can still reach them (an inf / NaN in x_T, in the conditioning or in a
-            # cond_fn's gradient): the finished sample is checked here, on the sync check_status() has just paid for.
-            if not bool(torch.isfinite(x_t).all()):
-                raise _native.NativeError("ddpm_sample: the sample holds non-finite values (a non-finite x_T, conditioning tensor or "
-                                          "guidance gradient, or an overflow the range guard reported as a warning)")
+        self.check_sample(predictor, x_t, "ddpm_sample")
         return x_t
 
 

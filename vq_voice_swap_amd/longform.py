@@ -1,0 +1,194 @@
+"""
+Whole recordings: ONE long diffusion state, predicted through overlapping windows of the trained length ("Long-form
+conversion").  The reference converts a single clip and has nothing of the kind.
+
+Every reverse step cuts the long x_t into windows of `window` samples, one every `hop`, runs the predictor on the batch of
+windows, and `vqvs_ddpm_step_windows` does the rest in one pass: each window's `constrain` with its own mean, the predictions of
+the two windows of an overlap cross-faded, ONE noise draw per absolute sample position, the long state and the next forward's
+window batch written together.  Means are blended and the noise is shared, so the windows agree on their common samples at every
+step and the step has the variance a single clip's has.
+
+`Diffusion.ddpm_sample_windows`, `VQVAE.encode_long` and `VQVAE.decode_long` are the functions below.
+"""
+
+from __future__ import annotations
+
+from typing import Callable, Optional, Tuple
+
+import torch
+
+from . import _native
+
+MAX_WINDOWS = 65535  # the limits of vqvs_ddpm_step_windows (include/vqvs.h)
+
+
+def plan_windows(num_samples: int, window: int, hop: int) -> Tuple[int, int]:
+    """(n, padded_len): the number of windows of `window` samples, one every `hop`, that cover `num_samples`, and the length
+    (n - 1) * hop + window of the signal they span.  The overlap window - hop lies in 0..hop: at most two windows cover a sample."""
+    num_samples, window, hop = int(num_samples), int(window), int(hop)
+    if num_samples < 1:
+        raise ValueError(f"num_samples={num_samples} must be at least 1")
+    if window < 4 or hop < 4 or window % 4 or hop % 4:
+        raise ValueError(f"window={window} and hop={hop} must be positive multiples of 4")
+    overlap = window - hop
+    if overlap < 0 or overlap > hop:
+        raise ValueError(f"overlap {overlap} (window {window} - hop {hop}) must lie in 0..hop: at most two windows may cover a sample")
+    n = 1 if num_samples <= window else -(-(num_samples - overlap) // hop)
+    padded_len = (n - 1) * hop + window
+    if n > MAX_WINDOWS or padded_len >= 2 ** 31:
+        raise ValueError(f"{num_samples} samples need {n} windows spanning {padded_len} samples: more than {MAX_WINDOWS} windows or 2^31 samples")
+    return n, padded_len
+
+
+def gather_windows(x: torch.Tensor, window: int, hop: int) -> torch.Tensor:
+    """[1,1,Np] -> the contiguous window batch [n,1,window] (a copy; the step kernel writes the later ones itself)."""
+    return x.reshape(-1).unfold(0, window, hop).unsqueeze(1).contiguous()
+
+
+def ddpm_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, steps: int, *, window: int, hop: int,
+                        window_batch: int = 64, constrain: bool = False, sigma_large: bool = False, cond_fn: Optional[Callable] = None,
+                        schedule: Optional[Callable] = None, noise=None, seed: Optional[int] = None, clip_offset: int = 0,
+                        progress: bool = False) -> torch.Tensor:
+    """`Diffusion.ddpm_sample` for one long state x_T_long [1,1,Np], Np = (n - 1) * hop + window (`plan_windows`): the same
+    host-side tables of t and alpha_bar(t), the same step numbering, zero noise on the last step.
+
+    `predictor(windows [m,1,window], ts [m], first=b0)` is called on slices of at most `window_batch` windows; `first` is the
+    index of the slice's first window, for a callee that slices its conditioning.  `cond_fn(mean [m,1,window], ts_prev [m],
+    first=b0)` guides each slice through `vqvs_ddpm_mean` / `vqvs_ddpm_guided_eps`, as in the single-clip step, before the
+    windows' predictions meet in `vqvs_ddpm_step_windows`.  `noise` is a list or callable giving [1,1,Np] per step; None draws in the
+    kernel from (seed, clip_offset, step): the draws of row `clip_offset` of a batch of clips of length Np."""
+    from .diffusion import few_guided_steps_promotion
+
+    _native.require_cuda(x_T_long)
+    if x_T_long.dim() != 3 or x_T_long.shape[0] != 1 or x_T_long.shape[1] != 1:
+        raise ValueError(f"x_T_long must be [1, 1, Np], got {tuple(x_T_long.shape)}")
+    Np = x_T_long.shape[2]
+    n, padded = plan_windows(Np, window, hop)
+    if padded != Np:
+        raise ValueError(f"x_T_long has {Np} samples: {n} windows of {window} every {hop} span {padded} (see plan_windows)")
+    if window_batch < 1:
+        raise ValueError(f"window_batch={window_batch} must be at least 1")
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    stack = few_guided_steps_promotion("ddpm_sample_windows", steps, predictor, cond_fn)
+    if stack is not None:
+        with stack:
+            return ddpm_sample_windows(diffusion, x_T_long, predictor, steps, window=window, hop=hop, window_batch=window_batch,
+                                       constrain=constrain, sigma_large=sigma_large, cond_fn=cond_fn, schedule=schedule, noise=noise,
+                                       seed=seed, clip_offset=clip_offset, progress=progress)
+    dev = x_T_long.device
+    mb = min(n, int(window_batch))
+    ts_all, a_t_all, a_prev_all, ts_prev_all = diffusion.step_tables(steps, mb, schedule, dev)
+    flags = (_native.DDPM_SIGMA_LARGE if sigma_large else 0) | (_native.DDPM_CONSTRAIN if constrain else 0)
+    L = _native.lib()
+    x = x_T_long.detach().to(torch.float32).contiguous()
+    windows = gather_windows(x, window, hop)
+    eps = torch.empty_like(windows)
+    its = range(steps)
+    if progress:
+        from tqdm.auto import tqdm
+
+        its = tqdm(its, total=steps)
+    with torch.no_grad(), torch.cuda.device(dev):
+        for i in its:
+            st = _native._stream_ptr()
+            for b0 in range(0, n, mb):
+                m = min(mb, n - b0)
+                xw = windows[b0:b0 + m]
+                e = predictor(xw, ts_all[i, :m], first=b0)
+                _native.require_cuda(e)
+                if tuple(e.shape) != tuple(xw.shape):
+                    raise ValueError(f"the predictor returned shape {tuple(e.shape)} for windows of shape {tuple(xw.shape)}")
+                e = e.detach().to(torch.float32).contiguous()
+                if cond_fn is not None:  # the two half-steps of Diffusion._step around cond_fn, on this slice of windows
+                    a_t, a_prev = a_t_all[i, :m], a_prev_all[i, :m]
+                    mean = torch.empty_like(xw)
+                    _native.check(L.vqvs_ddpm_mean(xw.data_ptr(), e.data_ptr(), a_t.data_ptr(), a_prev.data_ptr(), mean.data_ptr(), m, window, st))
+                    grad = cond_fn(mean, ts_prev_all[i, :m], first=b0).detach().to(torch.float32).contiguous()
+                    _native.check(L.vqvs_ddpm_guided_eps(xw.data_ptr(), mean.data_ptr(), grad.data_ptr(), a_t.data_ptr(), a_prev.data_ptr(),
+                                                         eps[b0:b0 + m].data_ptr(), m, window, flags, st))
+                else:
+                    eps[b0:b0 + m].copy_(e)
+            last = i + 1 == steps
+            nz = None
+            if not last and noise is not None:
+                nz = noise(i) if callable(noise) else noise[i]
+                _native.require_cuda(nz)
+                nz = nz.detach().to(torch.float32).contiguous()
+                if nz.numel() != Np:
+                    raise ValueError(f"noise of step {i} has {nz.numel()} values: expected [1, 1, {Np}]")
+            x_prev, next_windows = torch.empty_like(x), torch.empty_like(windows)
+            _native.check(L.vqvs_ddpm_step_windows(x.data_ptr(), eps.data_ptr(), _native._ptr(nz), a_t_all[i].data_ptr(), a_prev_all[i].data_ptr(),
+                                                   x_prev.data_ptr(), next_windows.data_ptr(), n, window, hop, flags, 0.0 if last else 1.0,
+                                                   int(seed), int(clip_offset), i, st))
+            x, windows = x_prev, next_windows
+    diffusion.check_sample(predictor, x, "ddpm_sample_windows")
+    return x.view_as(x_T_long)
+
+
+def encode_long(model, wave: torch.Tensor, window: int, hop: int, window_batch: int = 64) -> torch.Tensor:
+    """[1,1,N] waveform -> codes [n, window / rate] of its n windows (`plan_windows`), the tail zero-padded.  Windows are encoded in
+    slices of `window_batch`; behind the version-2 (dB) MFCC front end, which floors at the maximum over the BATCH, one at a time, so
+    that the codes do not depend on `window_batch`."""
+    if wave.dim() != 3 or wave.shape[0] != 1 or wave.shape[1] != 1:
+        raise ValueError(f"wave must be [1, 1, N], got {tuple(wave.shape)}")
+    check_rate(model, window, hop)
+    n, padded = plan_windows(wave.shape[2], window, hop)
+    windows = gather_windows(torch.nn.functional.pad(wave, (0, padded - wave.shape[2])), window, hop)
+    mb = 1 if getattr(model.encoder, "version", 1) == 2 else max(1, int(window_batch))
+    return torch.cat([model.encode(windows[b0:b0 + mb]) for b0 in range(0, n, mb)])
+
+
+def check_rate(model, window: int, hop: int) -> None:
+    rate = model.downsample_rate
+    if window % rate or hop % rate:
+        raise ValueError(f"window={window} and hop={hop} must be multiples of the model's downsample rate {rate}")
+
+
+def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, *, num_samples: int, window: int, hop: int,
+                steps: int = 100, progress: bool = False, constrain: bool = False, enc_pred=None, enc_pred_scale: float = 1.0,
+                seed: Optional[int] = None, clip_offset: int = 0, window_batch: int = 64, **kwargs) -> torch.Tensor:
+    """Window codes [n,T1] int or [n,C,T1] float (`encode_long`) -> [1,1,num_samples] waveform: `VQVAE.decode` on one long state.
+    x_T is ONE row of (n - 1) * hop + window samples keyed by `clip_offset`; `labels` is one label for every window, or [n].
+    With one window the result is `decode`'s, bit for bit, at the same seed and clip_offset."""
+    from .diffusion import randn_clips
+
+    if codes.dim() == 2:
+        cond_seq = model.vq.embed(codes)
+    elif codes.dim() == 3:
+        cond_seq = codes
+    else:
+        raise ValueError(f"unsupported codes shape: {codes.shape}")
+    check_rate(model, window, hop)
+    n, padded = plan_windows(num_samples, window, hop)
+    if cond_seq.shape[0] != n:
+        raise ValueError(f"{num_samples} samples in windows of {window} every {hop} are {n} windows; codes hold {cond_seq.shape[0]}")
+    if codes.shape[-1] * model.encoder.downsample_rate != window:
+        raise ValueError(f"codes of length {codes.shape[-1]} describe {codes.shape[-1] * model.encoder.downsample_rate} samples, not window={window}")
+    if labels is not None:
+        labels = labels.reshape(-1)
+        if labels.numel() == 1:
+            labels = labels.expand(n)
+        if labels.shape != (n,):
+            raise ValueError(f"labels must hold one label or one per window ({n}), got {labels.numel()}")
+        labels = labels.contiguous()
+    cond_fn = None
+    if enc_pred is not None:  # guidance towards each window's own codes (VQVAE.decode)
+        targets = model.vq.encode(cond_seq)
+
+        def cond_fn(x, ts, first):
+            return enc_pred.guidance_grad(x, ts, targets[first:first + x.shape[0]], enc_pred_scale)
+
+        cond_fn.native_modules = (enc_pred,)
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+
+    def predictor(xs, ts, first):
+        sl = slice(first, first + xs.shape[0])
+        return model.predictor(xs, ts, cond=cond_seq[sl], labels=None if labels is None else labels[sl])
+
+    x_T = randn_clips(1, padded, codes.device, seed, clip_offset)
+    out = ddpm_sample_windows(model.diffusion, x_T, predictor, steps, window=window, hop=hop, window_batch=window_batch, constrain=constrain,
+                              cond_fn=cond_fn, seed=seed, clip_offset=clip_offset, progress=progress, **kwargs)
+    model.predictor.check_status()  # range guard of the decoder's mode (once per sample)
+    return out[..., :num_samples]

@@ -116,6 +116,19 @@ class VQVAE(DiffusionModel):
         self.predictor.check_status()  # range guard of the decoder's mode (once per sample)
         return out
 
+    def encode_long(self, wave: torch.Tensor, window: int, hop: int, window_batch: int = 64) -> torch.Tensor:
+        """[1,1,N] waveform of any length -> codes [n, window / rate] of its overlapping windows (longform.encode_long)."""
+        from .longform import encode_long
+
+        return encode_long(self, wave, window, hop, window_batch)
+
+    def decode_long(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
+        """Window codes [n,T1] or [n,C,T1] -> [1,1,num_samples] waveform: `decode` on one long state whose windows are blended at
+        every step (longform.decode_long; keywords num_samples, window, hop, steps, constrain, enc_pred, seed, window_batch ...)."""
+        from .longform import decode_long
+
+        return decode_long(self, codes, labels, **kwargs)
+
     def decode_uncond_guidance(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, steps: int = 100,
                                progress: bool = False, constrain: bool = False, label_scale: float = 0.0, vq_scale: float = 0.0,
                                x_T: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
