@@ -249,6 +249,49 @@ int vqvs_ddpm_mean(const float* d_x_t, const float* d_eps, const float* d_alpha_
                    float* d_mean, int B, int T, void* stream);
 int vqvs_ddpm_guided_eps(const float* d_x_t, const float* d_mean, const float* d_grad, const float* d_alpha_t,
                          const float* d_alpha_prev, float* d_eps_out, int B, int T, uint32_t flags, void* stream);
+/* ---- DDIM step (handle-less; Song, Meng, Ermon: "Denoising diffusion implicit models", 2020 -- the reference has no counterpart) ----
+ * One step from the time the state is at, alpha_bar = a_t, to the time stepped TO, alpha_bar = a_to, of B rows of T samples:
+ *   e    = eps                       or, with d_grad, e = fmaf(-sqrt(1-a_t), grad, eps): a cond_fn's gradient at (x_t, t) enters the
+ *                                    prediction, so a guided step is this ONE call (vqvs_ddpm_mean / _guided_eps are not involved)
+ *   x0   = fmaf(-sqrt(1-a_t), e, x) * (1/sqrt(a_t)),  e' = e
+ *          with CONSTRAIN: x0 = clamp(fmaf(fmaf(-sqrt(1-a_t), e, x), 1/sqrt(a_t), -mean), -1, 1), e' = fmaf(-x0, sqrt(a_t), x) * (1/sqrt(1-a_t))
+ *          -- the two halves of vqvs_ddpm_step's CONSTRAIN -- about the row's mean of x0 OF THE GUIDED PREDICTION (summed in fp64 from
+ *          the fp32 inputs per 4096 samples, the chunk sums added in chunk order, rounded to fp32 once: B * ceil(T / 4096) doubles of the
+ *          per-(device, stream) scratch buffer)
+ *   sig  = eta * sqrt(max((1-a_to)/(1-a_t), 0)) * sqrt(max(1 - a_t/a_to, 0));  0 under INVERT or when 1 - a_t == 0
+ *   x_to = fmaf(sqrt(a_to), x0, fmaf(sqrt(max(1 - a_to - sig^2, 0)), e', sig * (noise_scale * z)))
+ * Coefficients: there is no reference operation order to follow here, so every per-row scalar above is computed IN FP64 from the fp32
+ * alphas and rounded to fp32 ONCE -- no cancellation in 1 - a_to - sig^2, one rounding per coefficient; the per-sample operations are
+ * fp32 with the fmaf's where they are written (contraction off elsewhere).
+ * Direction: a_to is alpha_bar of the time stepped TO.  Sampling steps towards t = 0, a_to > a_t; under VQVS_DDIM_INVERT the same
+ * step runs towards LARGER t, a_to < a_t, with sig = 0: for a fixed prediction it is the exact inverse of the eta = 0 step back.
+ * eta = 0 is deterministic; at eta = 1, sig^2 = (1 - a_t/a_to)(1-a_to)/(1-a_t) and the step is algebraically vqvs_ddpm_step's with the
+ * small sigma (flags 0 / CONSTRAIN) on the same eps -- not under guidance, which the DDPM path applies to the mean at t - step.
+ *   d_x_t, d_eps [B,T] f32; d_grad [B,T] f32 or NULL; d_alpha_t, d_alpha_to [B] f32; d_x_to [B,T] f32 out
+ *   d_noise [B,T] f32, or NULL to draw z = philox_normal4(seed, quad, clip_offset + row, step_index, stream 0): the words
+ *     vqvs_ddpm_step draws, so a run at eta = 1 with its seed sees its noise.  Nothing is drawn, and d_noise is not read, when sig == 0
+ *     (eta = 0, INVERT, a_to = 1) or noise_scale == 0.
+ * VQVS_ERR_ARG before the device is touched: NULL d_x_t, d_eps, d_alpha_t, d_alpha_to or d_x_to; B outside 1..65535, T outside
+ * 1..2^30; eta negative or not finite; flag bit 1 (SIGMA_LARGE has no meaning here) or any undefined bit; INVERT with CONSTRAIN;
+ * INVERT with eta != 0; d_x_to overlapping an input. */
+#define VQVS_DDIM_CONSTRAIN 2u /* same bit as VQVS_DDPM_CONSTRAIN */
+#define VQVS_DDIM_INVERT 4u
+int vqvs_ddim_step(const float* d_x_t, const float* d_eps, const float* d_grad, const float* d_noise, const float* d_alpha_t,
+                   const float* d_alpha_to, float* d_x_to, int B, int T, uint32_t flags, float eta, float noise_scale,
+                   uint64_t seed, uint64_t clip_offset, uint32_t step_index, void* stream);
+/* The DDIM step of ONE long signal predicted through overlapping windows: the geometry, limits, 16-byte accesses, per-window means,
+ * shared noise per absolute position and d_windows side output of vqvs_ddpm_step_windows, the arithmetic of vqvs_ddim_step.
+ *   d_x [Np], d_eps [n,W], d_grad [n,W] or NULL (guidance enters per window, before the blend), d_noise [Np] or NULL,
+ *   ONE d_alpha_t / d_alpha_to, d_x_to [Np] out, d_windows [n,W] out or NULL
+ * A window b that covers p contributes its own (x0_b, e'_b), guided by its own gradient and constrained about its own mean.  One
+ * window: they are used as they are.  Two, left and right, w = (u + 1/2) / V as there: x0 = fmaf(w, x0_r - x0_l, x0_l) and
+ * e' = fmaf(w, e'_r - e'_l, e'_l), then the last line above.  At n = 1 the result equals vqvs_ddim_step(B = 1, T = W,
+ * clip_offset = clip) bit for bit; at V = 0 without CONSTRAIN it equals one row of n * W samples.
+ * VQVS_ERR_ARG before the device is touched: every limit of vqvs_ddpm_step_windows, the eta and flag rules of vqvs_ddim_step, and
+ * d_x_to or d_windows overlapping an input or each other. */
+int vqvs_ddim_step_windows(const float* d_x, const float* d_eps, const float* d_grad, const float* d_noise, const float* d_alpha_t,
+                           const float* d_alpha_to, float* d_x_to, float* d_windows, int n, int W, int H, uint32_t flags, float eta,
+                           float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index, void* stream);
 /* x_T ~ N(0,1) from the same counter-based generator (replaces torch.randn, sample_diffusion.py:86) */
 int vqvs_randn(float* d_out, int B, int T, uint64_t seed, uint64_t clip_offset, uint32_t stream_id, void* stream);
 

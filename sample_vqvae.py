@@ -4,6 +4,8 @@ Encode a clip with a VQ-VAE and decode it as another speaker, on MI355X.  Counte
 sample_vqvae.py (same flags and positionals; reference sample_vqvae.py:76-92): read 4 s of 16 kHz audio,
 `encode`, `decode(labels, constrain=True)`, clamp, write WAV; `--check-vq` re-encodes the result.
 `--whole-file` (not in the reference) converts the whole input instead: `encode_long` / `decode_long` on overlapping windows.
+`--sampler ddim` (with `--eta`, default 0: deterministic) samples with the DDIM step instead of the ancestral DDPM loop; with
+`--source-label L` it starts from `VQVAE.invert` of the input under its own codes and label L instead of from a fresh draw.
 Differences: WAV in/out directly (no ffmpeg); the model is put in eval mode (the reference's train-mode VQ
 bookkeeping crashes on current numpy; outputs are identical).  `--enc-pred-path` loads an
 EncoderPredictor whose guidance gradient comes from the library's explicit backward schedule (no autograd).
@@ -22,8 +24,15 @@ from vq_voice_swap_amd import VQVAE, EncoderPredictor  # noqa: E402
 from vq_voice_swap_amd.audio import ChunkReader, ChunkWriter  # noqa: E402
 
 
-def arg_parser():
+def arg_parser(sampler_flags: bool = False):
+    """The command line.  `sampler_flags` adds --sampler / --eta / --source-label, which `main` parses (`parse_args`); without it
+    the parser is the one of the DDPM-only script, flag for flag."""
     p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    if sampler_flags:
+        p.add_argument("--sampler", default="ddpm", choices=["ddpm", "ddim"])
+        p.add_argument("--eta", type=float, default=0.0, help="DDIM noise level: 0 deterministic, 1 the DDPM step's variance (--sampler ddim)")
+        p.add_argument("--source-label", type=int, default=None,
+                       help="with --sampler ddim: start from the DDIM inversion of the input under this label (the speaker it was spoken by)")
     p.add_argument("--sample-rate", type=int, default=16000)
     p.add_argument("--sample-steps", type=int, default=100)
     p.add_argument("--seconds", type=int, default=4)
@@ -46,11 +55,29 @@ def arg_parser():
     return p
 
 
+def parse_args(argv=None):
+    parser = arg_parser(sampler_flags=True)
+    args = parser.parse_args(argv)
+    if args.sampler == "ddpm" and args.eta:
+        parser.error("--eta belongs to --sampler ddim")
+    if args.eta < 0:
+        parser.error("--eta must not be negative")
+    if args.source_label is not None:
+        if args.sampler != "ddim":
+            parser.error("--source-label needs --sampler ddim (the inversion is the DDIM step run backwards)")
+        if args.whole_file:
+            parser.error("--source-label is not available with --whole-file")
+        if args.no_vq:
+            parser.error("--source-label is not available with --no-vq")
+    return args
+
+
 def main(argv=None):
-    args = arg_parser().parse_args(argv)
+    args = parse_args(argv)
     print("loading model from checkpoint...")
     model = VQVAE.load(args.checkpoint_path)
     assert args.label < model.num_labels
+    assert args.source_label is None or 0 <= args.source_label < model.num_labels
     if not torch.cuda.is_available():
         raise SystemExit("no ROCm device visible: the sampler has no CPU path")
     device = torch.device("cuda")
@@ -82,8 +109,12 @@ def main(argv=None):
 
     print("decoding audio samples...")
     labels = torch.tensor([args.label]).long().to(device)
+    x_T = None
+    if args.source_label is not None:
+        print("inverting the input to its latent...")
+        x_T = model.invert(in_seq, torch.tensor([args.source_label]).long().to(device), steps=args.sample_steps, codes=encoded)
     sample = model.decode(encoded, labels, steps=args.sample_steps, progress=True, constrain=True, seed=args.seed,
-                          enc_pred=enc_pred, enc_pred_scale=args.enc_pred_scale)
+                          enc_pred=enc_pred, enc_pred_scale=args.enc_pred_scale, x_T=x_T, sampler=args.sampler, eta=args.eta)
 
     if args.check_vq:
         assert not args.no_vq
@@ -124,7 +155,7 @@ def convert_whole_file(args, model, enc_pred, device):
     labels = torch.tensor([args.label]).long().to(device)
     sample = model.decode_long(encoded, labels, num_samples=num_samples, window=window, hop=hop, steps=args.sample_steps, progress=True,
                                constrain=True, seed=args.seed, enc_pred=enc_pred, enc_pred_scale=args.enc_pred_scale,
-                               window_batch=args.window_batch)
+                               window_batch=args.window_batch, sampler=args.sampler, eta=args.eta)
 
     if args.check_vq:
         count = (encoded == model.encode_long(sample, window, hop, args.window_batch)).float().mean()

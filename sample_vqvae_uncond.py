@@ -4,7 +4,7 @@ Encode a clip with a VQ-VAE and decode it with unconditional ("classifier-free"-
 the speaker label, on MI355X.  Counterpart of the reference's sample_vqvae_uncond.py (same flags and positionals; reference
 sample_vqvae_uncond.py:14-92): the model is one fine-tuned by train_vqvae_uncond.py, whose label 0 is the unconditional label
 (hence `--label + 1 < num_labels`).  Differences: WAV in / out directly (no ffmpeg); `--schedule` is parsed, not eval()ed;
-eval mode; `--seed`, `--precision` are new; any combination of the two guidance scales works (the reference's always-tripled
+eval mode; `--seed`, `--precision`, `--sampler {ddpm,ddim}` and `--eta` are new; any combination of the two guidance scales works (the reference's always-tripled
 batch only lines up when both are non-zero, vq_vae.py:188-203).
 """
 import argparse
@@ -35,13 +35,25 @@ def arg_parser():
     p.add_argument("--check-vq", action="store_true")
     p.add_argument("--seed", default=None, type=int)
     p.add_argument("--precision", default="fp32", choices=["fp32", "fp16", "bf16"])
+    p.add_argument("--sampler", default="ddpm", choices=["ddpm", "ddim"])
+    p.add_argument("--eta", type=float, default=0.0, help="DDIM noise level: 0 deterministic, 1 the DDPM step's variance (--sampler ddim)")
     p.add_argument("checkpoint_path", type=str)
     p.add_argument("output_file", type=str)
     return p
 
 
+def parse_args(argv=None):
+    parser = arg_parser()
+    args = parser.parse_args(argv)
+    if args.sampler == "ddpm" and args.eta:
+        parser.error("--eta belongs to --sampler ddim")
+    if args.eta < 0:
+        parser.error("--eta must not be negative")
+    return args
+
+
 def main(argv=None):
-    args = arg_parser().parse_args(argv)
+    args = parse_args(argv)
     schedule = parse_time_schedule(args.schedule)
     print("loading model from checkpoint...")
     model = VQVAE.load(args.checkpoint_path)
@@ -69,7 +81,7 @@ def main(argv=None):
     labels = torch.tensor([args.label]).long().to(device)
     sample = model.decode_uncond_guidance(encoded, labels, steps=args.sample_steps, progress=True, constrain=True,
                                           label_scale=args.guide_label_scale, vq_scale=args.guide_vq_scale, schedule=schedule,
-                                          seed=args.seed)
+                                          seed=args.seed, sampler=args.sampler, eta=args.eta)
 
     if args.check_vq:
         assert not args.no_vq

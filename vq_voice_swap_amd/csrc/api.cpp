@@ -1,4 +1,5 @@
 // extern "C" surface of libvqvs_hip.so (declared and documented in include/vqvs.h).
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -363,6 +364,60 @@ int vqvs_ddpm_step_windows(const float* d_x, const float* d_eps, const float* d_
     if (int e = scratch_get((size_t)ddpm_scratch_doubles(n, W) * 8, stream, lease)) return e;
   return run_ddpm_step_windows(d_x, d_eps, d_noise, d_alpha_t, d_alpha_prev, d_x_prev, d_windows, reinterpret_cast<double*>(lease.p), n, W, H,
                                flags, noise_scale, seed, clip, step_index, reinterpret_cast<hipStream_t>(stream));
+}
+
+// shared argument rules of the two DDIM entry points
+static int check_ddim_args(uint32_t flags, float eta) {
+  if (!std::isfinite(eta) || eta < 0.f) VQVS_FAIL(VQVS_ERR_ARG, "eta %g must be finite and not negative", (double)eta);
+  if (flags & ~(VQVS_DDIM_CONSTRAIN | VQVS_DDIM_INVERT))
+    VQVS_FAIL(VQVS_ERR_ARG, "flags %#x: only VQVS_DDIM_CONSTRAIN and VQVS_DDIM_INVERT are defined for the DDIM step", flags);
+  if ((flags & VQVS_DDIM_INVERT) && (flags & VQVS_DDIM_CONSTRAIN)) VQVS_FAIL(VQVS_ERR_ARG, "INVERT cannot be combined with CONSTRAIN");
+  if ((flags & VQVS_DDIM_INVERT) && eta != 0.f) VQVS_FAIL(VQVS_ERR_ARG, "INVERT needs eta = 0 (got %g)", (double)eta);
+  return 0;
+}
+// [out, out + n_out) against an input of n_in floats (NULL: absent)
+static bool floats_overlap(const float* out, int64_t n_out, const float* in, int64_t n_in) {
+  return out && in && out < in + n_in && in < out + n_out;
+}
+
+int vqvs_ddim_step(const float* d_x_t, const float* d_eps, const float* d_grad, const float* d_noise, const float* d_alpha_t,
+                   const float* d_alpha_to, float* d_x_to, int B, int T, uint32_t flags, float eta, float noise_scale, uint64_t seed,
+                   uint64_t clip_offset, uint32_t step_index, void* stream) {
+  if (!d_x_t || !d_eps || !d_alpha_t || !d_alpha_to || !d_x_to) VQVS_FAIL(VQVS_ERR_ARG, "x_t, eps, alpha_t, alpha_to and x_to must be non-NULL");
+  if (B < 1 || B > 65535) VQVS_FAIL(VQVS_ERR_ARG, "batch %d outside 1..65535", B);
+  if (T < 1 || T > (1 << 30)) VQVS_FAIL(VQVS_ERR_ARG, "row length %d outside 1..2^30", T);
+  if (int e = check_ddim_args(flags, eta)) return e;
+  const int64_t N = (int64_t)B * T;
+  for (const float* in : {d_x_t, d_eps, d_grad, d_noise})
+    if (floats_overlap(d_x_to, N, in, N)) VQVS_FAIL(VQVS_ERR_ARG, "x_to must not overlap x_t, eps, grad or noise");
+  if (floats_overlap(d_x_to, N, d_alpha_t, B) || floats_overlap(d_x_to, N, d_alpha_to, B)) VQVS_FAIL(VQVS_ERR_ARG, "x_to must not overlap the alphas");
+  ScratchLease lease;
+  if (flags & VQVS_DDIM_CONSTRAIN)
+    if (int e = scratch_get((size_t)ddpm_scratch_doubles(B, T) * 8, stream, lease)) return e;
+  return run_ddim_step(d_x_t, d_eps, d_grad, d_noise, d_alpha_t, d_alpha_to, d_x_to, reinterpret_cast<double*>(lease.p), B, T, flags, eta,
+                       noise_scale, seed, clip_offset, step_index, reinterpret_cast<hipStream_t>(stream));
+}
+
+int vqvs_ddim_step_windows(const float* d_x, const float* d_eps, const float* d_grad, const float* d_noise, const float* d_alpha_t,
+                           const float* d_alpha_to, float* d_x_to, float* d_windows, int n, int W, int H, uint32_t flags, float eta,
+                           float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index, void* stream) {
+  if (!d_x || !d_eps || !d_alpha_t || !d_alpha_to || !d_x_to) VQVS_FAIL(VQVS_ERR_ARG, "x, eps, alpha_t, alpha_to and x_to must be non-NULL");
+  if (n < 1 || n > 65535) VQVS_FAIL(VQVS_ERR_ARG, "window count %d outside 1..65535", n);
+  if (W < 4 || H < 4 || W % 4 || H % 4) VQVS_FAIL(VQVS_ERR_ARG, "window %d and hop %d must be positive multiples of 4", W, H);
+  if (W < H || W - H > H) VQVS_FAIL(VQVS_ERR_ARG, "overlap %d (window %d - hop %d) outside 0..hop: at most two windows may cover a sample", W - H, W, H);
+  const int64_t Np = (int64_t)(n - 1) * H + W, NW = (int64_t)n * W;
+  if (Np >= ((int64_t)1 << 31)) VQVS_FAIL(VQVS_ERR_ARG, "%d windows every %d samples span %lld samples: 2^31 or more", n, H, (long long)Np);
+  if (int e = check_ddim_args(flags, eta)) return e;
+  const struct { const float* p; int64_t len; } ins[] = {{d_x, Np}, {d_eps, NW}, {d_grad, NW}, {d_noise, Np}, {d_alpha_t, 1}, {d_alpha_to, 1}};
+  for (const auto& in : ins)
+    if (floats_overlap(d_x_to, Np, in.p, in.len) || floats_overlap(d_windows, NW, in.p, in.len))
+      VQVS_FAIL(VQVS_ERR_ARG, "x_to and windows must not overlap x, eps, grad, noise or the alphas");
+  if (floats_overlap(d_x_to, Np, d_windows, NW)) VQVS_FAIL(VQVS_ERR_ARG, "x_to must not overlap windows");
+  ScratchLease lease;
+  if (flags & VQVS_DDIM_CONSTRAIN)
+    if (int e = scratch_get((size_t)ddpm_scratch_doubles(n, W) * 8, stream, lease)) return e;
+  return run_ddim_step_windows(d_x, d_eps, d_grad, d_noise, d_alpha_t, d_alpha_to, d_x_to, d_windows, reinterpret_cast<double*>(lease.p), n, W, H,
+                               flags, eta, noise_scale, seed, clip, step_index, reinterpret_cast<hipStream_t>(stream));
 }
 
 int vqvs_ddpm_mean(const float* d_x_t, const float* d_eps, const float* d_alpha_t, const float* d_alpha_prev, float* d_mean, int B, int T,

@@ -204,6 +204,183 @@ __global__ __launch_bounds__(256) void ddpm_guided_eps_kernel(const float* x_t, 
 }
 
 // ---------------------------------------------------------------------------------
+// DDIM step (Song et al. 2020; the reference has none), include/vqvs.h "DDIM step".  From alpha_bar a_t of the time the state is at
+// to alpha_bar a_to of the time stepped TO:
+//   x0 = (x - sqrt(1 - a_t) e) / sqrt(a_t),   x_to = sqrt(a_to) x0 + sqrt(1 - a_to - sig^2) e' + sig z
+// with e the prediction less sqrt(1 - a_t) * grad under guidance, and e' = e or, with CONSTRAIN, e re-derived from x0 clamped about
+// the clip's mean (constrained_eps' two halves).  There is no reference operation order to follow, so the per-row scalars are formed
+// in fp64 from the fp32 alphas and rounded to fp32 ONCE: no cancellation in 1 - a_to - sig^2, and every coefficient carries a single
+// rounding (tests/ddim_ref.py counts them).
+// ---------------------------------------------------------------------------------
+struct DdimCoef {
+  float sq1mat, rsat, sqat, rs1mat, sqto, sig, ce;
+};
+
+// the fp64 scalars of the x0 prediction: shared by the coefficients below and by ddim_x0sum_kernel
+struct DdimX0Coef {
+  double sq1mat, rsat;
+};
+__device__ __forceinline__ DdimX0Coef ddim_x0_coef(float a_t) {
+  const double at = (double)a_t;
+  return {sqrt(1.0 - at), 1.0 / sqrt(at)};
+}
+
+__device__ __forceinline__ DdimCoef ddim_coef(float a_t, float a_to, float eta, bool invert) {
+  const double at = (double)a_t, ato = (double)a_to, om = 1.0 - at;
+  const DdimX0Coef x = ddim_x0_coef(a_t);
+  double sig = 0.0;
+  if (!invert && om != 0.0) sig = (double)eta * sqrt(fmax((1.0 - ato) / om, 0.0)) * sqrt(fmax(1.0 - at / ato, 0.0));
+  DdimCoef k;
+  k.sq1mat = (float)x.sq1mat;
+  k.rsat = (float)x.rsat;
+  k.sqat = (float)sqrt(at);
+  k.rs1mat = (float)(1.0 / x.sq1mat);
+  k.sqto = (float)sqrt(ato);
+  k.sig = (float)sig;
+  k.ce = (float)sqrt(fmax(1.0 - ato - sig * sig, 0.0));
+  return k;
+}
+
+// ddpm_x0sum_kernel for the DDIM step: the clip's (window's) sum of x0 OF THE GUIDED PREDICTION, e = eps - sqrt(1 - a_t) grad (grad
+// NULL: e = eps).  Same rows, strides, chunks and partial layout; the summand is formed in fp64 from the fp32 inputs and the fp64
+// scalars, so the mean that x0_mean rounds to fp32 carries that one rounding.
+__global__ __launch_bounds__(256) void ddim_x0sum_kernel(const float* x_t, const float* eps, const float* grad, const float* a_t,
+                                                         double* partial, int T, int nchunk, int x_stride, int a_stride) {
+  __shared__ double red[256];
+  const int b = blockIdx.y;
+  const DdimX0Coef k = ddim_x0_coef(a_t[b * a_stride]);
+  const int beg = blockIdx.x * SUM_CHUNK, end = min(T, beg + SUM_CHUNK);
+  double s = 0.0;
+  for (int t = beg + threadIdx.x; t < end; t += 256) {
+    double e = (double)eps[(size_t)b * T + t];
+    if (grad) e -= k.sq1mat * (double)grad[(size_t)b * T + t];
+    s += ((double)x_t[(size_t)b * x_stride + t] - k.sq1mat * e) * k.rsat;
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int m = 128; m >= 1; m >>= 1) {
+    if (threadIdx.x < m) red[threadIdx.x] += red[threadIdx.x + m];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[(size_t)b * nchunk + blockIdx.x] = red[0];
+}
+
+// (x0, e') of one sample under one clip's / window's prediction e and gradient g (guided: e <- e - sqrt(1 - a_t) g)
+template <bool GUIDED>
+__device__ __forceinline__ void ddim_x0_eps(const DdimCoef& k, bool constrain, float x, float e, float g, float mean, float& x0, float& ep) {
+#pragma clang fp contract(off)
+  if (GUIDED) e = fmaf(-k.sq1mat, g, e);
+  if (constrain) {
+    x0 = fmaf(fmaf(-k.sq1mat, e, x), k.rsat, -mean);
+    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    ep = fmaf(-x0, k.sqat, x) * k.rs1mat;
+  } else {
+    x0 = fmaf(-k.sq1mat, e, x) * k.rsat;
+    ep = e;
+  }
+}
+
+// One sample of the step, shared by ddim_step_kernel and ddim_step_windows_kernel.  BLEND cross-fades the (x0, e') of a left and a
+// right window, each guided and constrained on its own, with weight w on the right one; without BLEND the right-hand arguments are
+// unused.  Every rounding is spelled out, as in step_sample: at one window the result is ddim_step_kernel's to the bit.
+template <bool BLEND, bool GUIDED>
+__device__ __forceinline__ float ddim_sample(const DdimCoef& k, bool constrain, float x, float nv, float e, float g, float mean,
+                                             float e_r = 0.f, float g_r = 0.f, float mean_r = 0.f, float w = 0.f) {
+#pragma clang fp contract(off)
+  float x0, ep;
+  ddim_x0_eps<GUIDED>(k, constrain, x, e, g, mean, x0, ep);
+  if (BLEND) {
+    float x0_r, ep_r;
+    ddim_x0_eps<GUIDED>(k, constrain, x, e_r, g_r, mean_r, x0_r, ep_r);
+    x0 = fmaf(w, x0_r - x0, x0);
+    ep = fmaf(w, ep_r - ep, ep);
+  }
+  return fmaf(k.sqto, x0, fmaf(k.ce, ep, k.sig * nv));
+}
+
+template <bool GUIDED>
+__global__ __launch_bounds__(256) void ddim_step_kernel(const float* x_t, const float* eps, const float* grad, const float* noise,
+                                                        const float* a_t, const float* a_to, const double* partial, int nchunk,
+                                                        float* out, int T, uint32_t flags, float eta, float noise_scale, uint64_t seed,
+                                                        uint64_t clip_offset, uint32_t step_index) {
+  const int b = blockIdx.y;
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q * 4 >= T) return;
+  const DdimCoef k = ddim_coef(a_t[b], a_to[b], eta, flags & 4u);
+  float mean = 0.f;
+  if (flags & 2u) mean = x0_mean(partial + (size_t)b * nchunk, nchunk, T);
+  const size_t base = (size_t)b * T + q * 4;
+  const int n = min(4, T - q * 4);
+  float xv[4], ev[4], gv[4] = {0.f, 0.f, 0.f, 0.f}, nv[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int j = 0; j < n; ++j) {
+    xv[j] = x_t[base + j];
+    ev[j] = eps[base + j];
+    if (GUIDED) gv[j] = grad[base + j];
+  }
+  if (noise_scale != 0.f && k.sig != 0.f) {  // (eta = 0, INVERT, a_to = 1: nothing is drawn or read)
+    if (noise) {
+      for (int j = 0; j < n; ++j) nv[j] = noise[base + j] * noise_scale;
+    } else {
+      const f32x4 z = philox_normal4(seed, (uint32_t)q, clip_offset + b, step_index, 0u);
+      for (int j = 0; j < 4; ++j) nv[j] = z[j] * noise_scale;
+    }
+  }
+  for (int j = 0; j < n; ++j) out[base + j] = ddim_sample<false, GUIDED>(k, flags & 2u, xv[j], nv[j], ev[j], gv[j], mean);
+}
+
+// ddpm_step_windows_kernel's geometry, limits, 16-byte accesses, per-window means, shared noise and `win` output, for the DDIM step;
+// grad [n, W] enters per window, before the blend.
+template <bool GUIDED>
+__global__ __launch_bounds__(256) void ddim_step_windows_kernel(const float* x, const float* eps, const float* grad, const float* noise,
+                                                                const float* a_t, const float* a_to, const double* partial, int nchunk,
+                                                                float* x_to, float* win, int n, int W, int H, uint32_t flags, float eta,
+                                                                float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  const int Np = (n - 1) * H + W, V = W - H;
+  if (q >= Np / 4) return;
+  const int p = q * 4;
+  const DdimCoef k = ddim_coef(a_t[0], a_to[0], eta, flags & 4u);
+  const bool constrain = flags & 2u;
+  const int br = min(p / H, n - 1);
+  const int u = p - br * H;  // offset in window br; in window br - 1 the sample is u + H
+  const bool two = br > 0 && u < V;
+  const size_t at_r = (size_t)br * W + u, at_l = two ? (size_t)(br - 1) * W + u + H : 0;
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  const f32x4 xv = *reinterpret_cast<const f32x4*>(x + p);
+  const f32x4 er = *reinterpret_cast<const f32x4*>(eps + at_r);
+  f32x4 el = er, gr = zero, gl = zero;
+  if (two) el = *reinterpret_cast<const f32x4*>(eps + at_l);
+  if (GUIDED) {
+    gr = *reinterpret_cast<const f32x4*>(grad + at_r);
+    if (two) gl = *reinterpret_cast<const f32x4*>(grad + at_l);
+  }
+  float mean_r = 0.f, mean_l = 0.f;
+  if (constrain) {
+    mean_r = x0_mean(partial + (size_t)br * nchunk, nchunk, W);
+    if (two) mean_l = x0_mean(partial + (size_t)(br - 1) * nchunk, nchunk, W);
+  }
+  f32x4 nv = zero;
+  if (noise_scale != 0.f && k.sig != 0.f) {
+    const f32x4 z = noise ? *reinterpret_cast<const f32x4*>(noise + p) : philox_normal4(seed, (uint32_t)q, clip, step_index, 0u);
+    for (int j = 0; j < 4; ++j) nv[j] = z[j] * noise_scale;
+  }
+  f32x4 o;
+  if (two) {
+    for (int j = 0; j < 4; ++j) {
+      const float w = ((float)(u + j) + 0.5f) / (float)V;
+      o[j] = ddim_sample<true, GUIDED>(k, constrain, xv[j], nv[j], el[j], gl[j], mean_l, er[j], gr[j], mean_r, w);
+    }
+  } else {
+    for (int j = 0; j < 4; ++j) o[j] = ddim_sample<false, GUIDED>(k, constrain, xv[j], nv[j], er[j], gr[j], mean_r);
+  }
+  *reinterpret_cast<f32x4*>(x_to + p) = o;
+  if (win) {
+    *reinterpret_cast<f32x4*>(win + at_r) = o;
+    if (two) *reinterpret_cast<f32x4*>(win + at_l) = o;
+  }
+}
+
+// ---------------------------------------------------------------------------------
 // VQ nearest codeword (reference vq.py:127-131, 199-221).
 //   dist[k] = ((-2 * <x, e_k>) + |e_k|^2) + |x|^2   in fp32, dot as an fmaf chain in channel
 //   order; argmin with the FIRST minimal index (torch.argmin semantics).
@@ -454,6 +631,38 @@ int run_ddpm_step_windows(const float* x, const float* eps, const float* noise, 
   const int quads = ((n - 1) * H + W) / 4;
   hipLaunchKernelGGL(ddpm_step_windows_kernel, dim3((quads + 255) / 256), dim3(256), 0, st, x, eps, noise, a_t, a_prev, scratch, nchunk,
                      x_prev, windows, n, W, H, flags, noise_scale, seed, clip, step_index);
+  VQVS_HIP(hipGetLastError());
+  return 0;
+}
+
+// scratch: ddpm_scratch_doubles(B, T) doubles when flags has CONSTRAIN (not read otherwise)
+int run_ddim_step(const float* x_t, const float* eps, const float* grad, const float* noise, const float* a_t, const float* a_to, float* out,
+                  double* scratch, int B, int T, uint32_t flags, float eta, float noise_scale, uint64_t seed, uint64_t clip_offset,
+                  uint32_t step_index, hipStream_t st) {
+  const int nchunk = (T + SUM_CHUNK - 1) / SUM_CHUNK;
+  if (flags & 2u) {
+    hipLaunchKernelGGL(ddim_x0sum_kernel, dim3(nchunk, B), dim3(256), 0, st, x_t, eps, grad, a_t, scratch, T, nchunk, T, 1);
+  }
+  dim3 grid(((T + 3) / 4 + 255) / 256, B);
+  auto kernel = grad ? ddim_step_kernel<true> : ddim_step_kernel<false>;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, x_t, eps, grad, noise, a_t, a_to, scratch, nchunk, out, T, flags, eta, noise_scale, seed,
+                     clip_offset, step_index);
+  VQVS_HIP(hipGetLastError());
+  return 0;
+}
+
+// scratch: ddpm_scratch_doubles(n, W) doubles when flags has CONSTRAIN (not read otherwise)
+int run_ddim_step_windows(const float* x, const float* eps, const float* grad, const float* noise, const float* a_t, const float* a_to,
+                          float* x_to, float* windows, double* scratch, int n, int W, int H, uint32_t flags, float eta, float noise_scale,
+                          uint64_t seed, uint64_t clip, uint32_t step_index, hipStream_t st) {
+  const int nchunk = (W + SUM_CHUNK - 1) / SUM_CHUNK;
+  if (flags & 2u) {
+    hipLaunchKernelGGL(ddim_x0sum_kernel, dim3(nchunk, n), dim3(256), 0, st, x, eps, grad, a_t, scratch, W, nchunk, H, 0);
+  }
+  const int quads = ((n - 1) * H + W) / 4;
+  auto kernel = grad ? ddim_step_windows_kernel<true> : ddim_step_windows_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((quads + 255) / 256), dim3(256), 0, st, x, eps, grad, noise, a_t, a_to, scratch, nchunk, x_to, windows, n, W,
+                     H, flags, eta, noise_scale, seed, clip, step_index);
   VQVS_HIP(hipGetLastError());
   return 0;
 }

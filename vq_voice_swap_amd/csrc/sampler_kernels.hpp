@@ -12,6 +12,13 @@ int run_ddpm_step(const float* x_t, const float* eps, const float* noise, const 
 int run_ddpm_step_windows(const float* x, const float* eps, const float* noise, const float* a_t, const float* a_prev, float* x_prev,
                           float* windows, double* scratch, int n, int W, int H, uint32_t flags, float noise_scale, uint64_t seed,
                           uint64_t clip, uint32_t step_index, hipStream_t st);
+// DDIM step from alpha_bar a_t to a_to, single clips and the windows of one long signal; grad NULL: unguided; scratch as the DDPM steps'
+int run_ddim_step(const float* x_t, const float* eps, const float* grad, const float* noise, const float* a_t, const float* a_to, float* out,
+                  double* scratch, int B, int T, uint32_t flags, float eta, float noise_scale, uint64_t seed, uint64_t clip_offset,
+                  uint32_t step_index, hipStream_t st);
+int run_ddim_step_windows(const float* x, const float* eps, const float* grad, const float* noise, const float* a_t, const float* a_to,
+                          float* x_to, float* windows, double* scratch, int n, int W, int H, uint32_t flags, float eta, float noise_scale,
+                          uint64_t seed, uint64_t clip, uint32_t step_index, hipStream_t st);
 int run_ddpm_mean(const float* x_t, const float* eps, const float* a_t, const float* a_prev, float* out, int B, int T, hipStream_t st);
 int run_ddpm_guided_eps(const float* x_t, const float* mean, const float* grad, const float* a_t, const float* a_prev, float* out,
                         int B, int T, uint32_t flags, hipStream_t st);

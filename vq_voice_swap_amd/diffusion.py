@@ -113,6 +113,32 @@ def few_guided_steps_promotion(what: str, steps: int, predictor, cond_fn):
     return stack
 
 
+SAMPLERS = ("ddpm", "ddim")
+
+
+def check_sampler(sampler: str, eta: float = 0.0) -> str:
+    """The `sampler=` / `eta=` pair of the sampling entry points: eta belongs to the DDIM sampler alone."""
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler={sampler!r}: expected one of {SAMPLERS}")
+    if sampler == "ddpm" and eta:
+        raise ValueError(f"eta={eta!r} has no meaning for sampler='ddpm' (the DDIM sampler at eta = 1 is its small-sigma step)")
+    return sampler
+
+
+def warn_few_unguided_steps(what: str, steps: int, predictor, cond_fn) -> None:
+    """An UN-guided DDIM run of fewer than FEW_GUIDED_STEPS steps in a 2-byte mode: the first step's 1 / sqrt(alpha_bar(1)) acts on
+    the predictor's rounding error just the same, but nothing has been measured for it, so the run keeps its mode and only warns.
+    (Guided runs are promoted by few_guided_steps_promotion; the DDPM samplers are not touched.)"""
+    if cond_fn is not None or steps >= FEW_GUIDED_STEPS:
+        return
+    modes = sorted({m.precision for m in _native_modules(predictor) if getattr(m, "precision", "fp32") != "fp32"})
+    if modes:
+        import warnings
+
+        warnings.warn(f"{what}: {steps} steps (fewer than {FEW_GUIDED_STEPS}) in the {modes} mode(s): the 1e-3 waveform contract is not "
+                      "established for so few steps; the mode is kept", RuntimeWarning, stacklevel=3)
+
+
 class Diffusion:
     def __init__(self, schedule: Schedule):
         self.schedule = schedule
@@ -380,6 +406,138 @@ class Diffusion:
                                  noise_scale=0.0 if last else 1.0)
         self.check_sample(predictor, x_t, "ddpm_sample")
         return x_t
+
+    # ---- DDIM (Song et al. 2020; not in the reference): DESIGN.md section 3.10 -----------------------
+    def ddim_previous(
+        self,
+        x_t: torch.Tensor,
+        ts: torch.Tensor,
+        step,
+        epsilon_prediction: torch.Tensor,
+        noise: Optional[torch.Tensor] = None,
+        eta: float = 0.0,
+        constrain: bool = False,
+        cond_fn: Optional[Callable] = None,
+        *,
+        seed: int = 0,
+        clip_offset: int = 0,
+        step_index: int = 0,
+        noise_scale: float = 1.0,
+    ) -> torch.Tensor:
+        """The DDIM step from ts to ts - step (`vqvs_ddim_step`): deterministic at eta = 0, the small-sigma `ddpm_previous` at
+        eta = 1.  `cond_fn(x_t, ts)` -- the callable the DDPM path takes -- is evaluated AT (x_t, ts) and its result handed to the
+        kernel, which subtracts sqrt(1 - alpha_bar(ts)) times it from the prediction.  `noise=None` draws from the in-kernel
+        generator keyed by (seed, clip_offset + row, step_index), the words `ddpm_previous` draws."""
+        _native.require_cuda(x_t, epsilon_prediction, noise)
+        ts = ts.detach().to(device=x_t.device, dtype=torch.float32)
+        if not torch.is_tensor(step):
+            step = torch.full_like(ts, float(step))
+        step = step.to(ts)
+        return self._ddim_step(x_t, epsilon_prediction, self.schedule(ts).contiguous(), self.schedule(ts - step).contiguous(), ts,
+                               noise=noise, eta=eta, constrain=constrain, cond_fn=cond_fn, seed=seed, clip_offset=clip_offset,
+                               step_index=step_index, noise_scale=noise_scale)
+
+    def _ddim_step(self, x_t, epsilon_prediction, a_t, a_to, ts, *, noise=None, eta=0.0, constrain=False, cond_fn=None, invert=False,
+                   seed=0, clip_offset=0, step_index=0, noise_scale=1.0) -> torch.Tensor:
+        """One `vqvs_ddim_step` given alpha_bar of the time the state is at and of the time stepped to, as [B] device tensors."""
+        if x_t.dim() < 2:
+            raise ValueError("x_t must be [N, ..., T]")
+        B = x_t.shape[0]
+        T = x_t[0].numel()
+        x = x_t.detach().to(torch.float32).contiguous()
+        eps = epsilon_prediction.detach().to(torch.float32).contiguous()
+        flags = (_native.DDIM_CONSTRAIN if constrain else 0) | (_native.DDIM_INVERT if invert else 0)
+        with torch.cuda.device(x.device):
+            grad = None
+            if cond_fn is not None:
+                grad = cond_fn(x.view_as(x_t), ts).detach().to(torch.float32).contiguous()
+                _native.require_cuda(grad)
+                if grad.numel() != x.numel():
+                    raise ValueError(f"cond_fn returned shape {tuple(grad.shape)} for a state of shape {tuple(x_t.shape)}")
+            if noise is not None:
+                noise = noise.detach().to(torch.float32).contiguous()
+            out = torch.empty_like(x)
+            _native.check(_native.lib().vqvs_ddim_step(x.data_ptr(), eps.data_ptr(), _native._ptr(grad), _native._ptr(noise), a_t.data_ptr(),
+                                                       a_to.data_ptr(), out.data_ptr(), B, T, flags, float(eta), float(noise_scale),
+                                                       int(seed), int(clip_offset), int(step_index), _native._stream_ptr()))
+        return out.view_as(x_t)
+
+    def ddim_sample(
+        self,
+        x_T: torch.Tensor,
+        predictor: Callable[[torch.Tensor, torch.Tensor], torch.Tensor],
+        steps: int,
+        eta: float = 0.0,
+        progress: bool = False,
+        constrain: bool = False,
+        cond_fn: Optional[Callable] = None,
+        schedule: Optional[Callable] = None,
+        *,
+        noise: NoiseSource = None,
+        seed: Optional[int] = None,
+        clip_offset: int = 0,
+    ) -> torch.Tensor:
+        """`ddpm_sample` with the DDIM step: the same tables of t and alpha_bar(t) (`step_tables`), the same step numbering and noise
+        words, zero noise on the last iteration -- which, stepping to alpha_bar(0) = 1, returns x0 itself.  At eta = 0 the result
+        depends on x_T alone."""
+        _native.require_cuda(x_T)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        stack = few_guided_steps_promotion("ddim_sample", steps, predictor, cond_fn)
+        if stack is not None:
+            with stack:
+                return self.ddim_sample(x_T, predictor, steps, eta=eta, progress=progress, constrain=constrain, cond_fn=cond_fn,
+                                        schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset)
+        warn_few_unguided_steps("ddim_sample", steps, predictor, cond_fn)
+        x_t = x_T
+        ts_all, a_t_all, a_to_all, _ = self.step_tables(steps, x_T.shape[0], schedule, x_T.device)
+        its = range(steps)
+        if progress:
+            from tqdm.auto import tqdm
+
+            its = tqdm(its, total=steps)
+        for i in its:
+            with torch.no_grad():
+                eps = predictor(x_t, ts_all[i])
+                last = i + 1 == steps
+                if last or noise is None or not eta:
+                    nz = None
+                elif callable(noise):
+                    nz = noise(i)
+                else:
+                    nz = noise[i]
+                _native.require_cuda(eps, nz)
+                x_t = self._ddim_step(x_t, eps, a_t_all[i], a_to_all[i], ts_all[i], noise=nz, eta=eta, constrain=constrain, cond_fn=cond_fn,
+                                      seed=seed, clip_offset=clip_offset, step_index=i, noise_scale=0.0 if last else 1.0)
+        self.check_sample(predictor, x_t, "ddim_sample")
+        return x_t
+
+    def ddim_invert(self, x_0: torch.Tensor, predictor: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], steps: int,
+                    schedule: Optional[Callable] = None, progress: bool = False) -> torch.Tensor:
+        """x_0 -> the x_T that `ddim_sample(x_T, predictor, steps, eta=0)` maps back towards it: the rows of `step_tables` walked
+        BACKWARDS.  Iteration j takes the row of t = (j + 1) / steps, evaluates the predictor at the row's t - step -- where the state
+        is -- and steps from alpha_bar(t - step) to alpha_bar(t) with VQVS_DDIM_INVERT.  Each step inverts the forward one exactly for a
+        FIXED prediction; the forward run predicts at t, not at t - step, so a round trip returns x_0 only up to that discretisation
+        error."""
+        x_t = x_0
+        _, a_t_all, a_prev_all, ts_prev_all = self.step_tables(steps, x_0.shape[0], schedule, x_0.device)
+        its = range(steps - 1, -1, -1)
+        if progress:
+            from tqdm.auto import tqdm
+
+            its = tqdm(its, total=steps)
+        for i in its:
+            with torch.no_grad():
+                eps = predictor(x_t, ts_prev_all[i])
+                x_t = self._ddim_step(x_t, eps, a_prev_all[i], a_t_all[i], ts_prev_all[i], invert=True)
+        self.check_sample(predictor, x_t, "ddim_invert")
+        return x_t
+
+    def ddim_sample_windows(self, x_T_long: torch.Tensor, predictor: Callable, steps: int, **kwargs) -> torch.Tensor:
+        """`ddim_sample` for one long state [1,1,Np] predicted through overlapping windows (longform.ddim_sample_windows)."""
+        from .longform import ddim_sample_windows
+
+        return ddim_sample_windows(self, x_T_long, predictor, steps, **kwargs)
 
 
 def randn_clips(n: int, T: int, device, seed: int, clip_offset: int = 0, stream_id: int = 1) -> torch.Tensor:

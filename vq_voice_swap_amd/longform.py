@@ -8,7 +8,8 @@ the two windows of an overlap cross-faded, ONE noise draw per absolute sample po
 window batch written together.  Means are blended and the noise is shared, so the windows agree on their common samples at every
 step and the step has the variance a single clip's has.
 
-`Diffusion.ddpm_sample_windows`, `VQVAE.encode_long` and `VQVAE.decode_long` are the functions below.
+`Diffusion.ddpm_sample_windows`, `VQVAE.encode_long` and `VQVAE.decode_long` are the functions below; `Diffusion.ddim_sample_windows`
+is the same walk with the DDIM step `vqvs_ddim_step_windows`.
 """
 
 from __future__ import annotations
@@ -126,6 +127,82 @@ def ddpm_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, 
     return x.view_as(x_T_long)
 
 
+def ddim_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, steps: int, *, window: int, hop: int,
+                        window_batch: int = 64, eta: float = 0.0, constrain: bool = False, cond_fn: Optional[Callable] = None,
+                        schedule: Optional[Callable] = None, noise=None, seed: Optional[int] = None, clip_offset: int = 0,
+                        progress: bool = False) -> torch.Tensor:
+    """`Diffusion.ddim_sample` for one long state x_T_long [1,1,Np]: `ddpm_sample_windows` with `vqvs_ddim_step_windows` as the step.
+    `predictor` and `noise` are as there.  `cond_fn(x [m,1,window], ts [m], first=b0)` is evaluated on each slice of windows AT the
+    windows the predictor saw and at their t; its gradients fill a [n, window] batch that the step kernel applies per window, before
+    the windows' predictions are blended -- one kernel after the forwards, no half-steps."""
+    from .diffusion import few_guided_steps_promotion, warn_few_unguided_steps
+
+    _native.require_cuda(x_T_long)
+    if x_T_long.dim() != 3 or x_T_long.shape[0] != 1 or x_T_long.shape[1] != 1:
+        raise ValueError(f"x_T_long must be [1, 1, Np], got {tuple(x_T_long.shape)}")
+    Np = x_T_long.shape[2]
+    n, padded = plan_windows(Np, window, hop)
+    if padded != Np:
+        raise ValueError(f"x_T_long has {Np} samples: {n} windows of {window} every {hop} span {padded} (see plan_windows)")
+    if window_batch < 1:
+        raise ValueError(f"window_batch={window_batch} must be at least 1")
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    stack = few_guided_steps_promotion("ddim_sample_windows", steps, predictor, cond_fn)
+    if stack is not None:
+        with stack:
+            return ddim_sample_windows(diffusion, x_T_long, predictor, steps, window=window, hop=hop, window_batch=window_batch, eta=eta,
+                                       constrain=constrain, cond_fn=cond_fn, schedule=schedule, noise=noise, seed=seed,
+                                       clip_offset=clip_offset, progress=progress)
+    warn_few_unguided_steps("ddim_sample_windows", steps, predictor, cond_fn)
+    dev = x_T_long.device
+    mb = min(n, int(window_batch))
+    ts_all, a_t_all, a_to_all, _ = diffusion.step_tables(steps, mb, schedule, dev)
+    flags = _native.DDIM_CONSTRAIN if constrain else 0
+    L = _native.lib()
+    x = x_T_long.detach().to(torch.float32).contiguous()
+    windows = gather_windows(x, window, hop)
+    eps = torch.empty_like(windows)
+    grad = torch.empty_like(windows) if cond_fn is not None else None
+    its = range(steps)
+    if progress:
+        from tqdm.auto import tqdm
+
+        its = tqdm(its, total=steps)
+    with torch.no_grad(), torch.cuda.device(dev):
+        for i in its:
+            st = _native._stream_ptr()
+            for b0 in range(0, n, mb):
+                m = min(mb, n - b0)
+                xw = windows[b0:b0 + m]
+                e = predictor(xw, ts_all[i, :m], first=b0)
+                _native.require_cuda(e)
+                if tuple(e.shape) != tuple(xw.shape):
+                    raise ValueError(f"the predictor returned shape {tuple(e.shape)} for windows of shape {tuple(xw.shape)}")
+                eps[b0:b0 + m].copy_(e.detach())
+                if cond_fn is not None:
+                    g = cond_fn(xw, ts_all[i, :m], first=b0)
+                    _native.require_cuda(g)
+                    if tuple(g.shape) != tuple(xw.shape):
+                        raise ValueError(f"cond_fn returned shape {tuple(g.shape)} for windows of shape {tuple(xw.shape)}")
+                    grad[b0:b0 + m].copy_(g.detach())
+            last = i + 1 == steps
+            nz = None
+            if not last and noise is not None and eta:
+                nz = noise(i) if callable(noise) else noise[i]
+                _native.require_cuda(nz)
+                nz = nz.detach().to(torch.float32).contiguous()
+                if nz.numel() != Np:
+                    raise ValueError(f"noise of step {i} has {nz.numel()} values: expected [1, 1, {Np}]")
+            x_to, next_windows = torch.empty_like(x), torch.empty_like(windows)
+            _native.check(L.vqvs_ddim_step_windows(x.data_ptr(), eps.data_ptr(), _native._ptr(grad), _native._ptr(nz), a_t_all[i].data_ptr(),
+                                                   a_to_all[i].data_ptr(), x_to.data_ptr(), next_windows.data_ptr(), n, window, hop, flags,
+                                                   float(eta), 0.0 if last else 1.0, int(seed), int(clip_offset), i, st))
+            x, windows = x_to, next_windows
+    diffusion.check_sample(predictor, x, "ddim_sample_windows")
+    return x.view_as(x_T_long)
+
+
 def encode_long(model, wave: torch.Tensor, window: int, hop: int, window_batch: int = 64) -> torch.Tensor:
     """[1,1,N] waveform -> codes [n, window / rate] of its n windows (`plan_windows`), the tail zero-padded.  Windows are encoded in
     slices of `window_batch`; behind the version-2 (dB) MFCC front end, which floors at the maximum over the BATCH, one at a time, so
@@ -147,11 +224,13 @@ def check_rate(model, window: int, hop: int) -> None:
 
 def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, *, num_samples: int, window: int, hop: int,
                 steps: int = 100, progress: bool = False, constrain: bool = False, enc_pred=None, enc_pred_scale: float = 1.0,
-                seed: Optional[int] = None, clip_offset: int = 0, window_batch: int = 64, **kwargs) -> torch.Tensor:
+                seed: Optional[int] = None, clip_offset: int = 0, window_batch: int = 64, sampler: str = "ddpm", eta: float = 0.0,
+                **kwargs) -> torch.Tensor:
     """Window codes [n,T1] int or [n,C,T1] float (`encode_long`) -> [1,1,num_samples] waveform: `VQVAE.decode` on one long state.
     x_T is ONE row of (n - 1) * hop + window samples keyed by `clip_offset`; `labels` is one label for every window, or [n].
-    With one window the result is `decode`'s, bit for bit, at the same seed and clip_offset."""
-    from .diffusion import randn_clips
+    With one window the result is `decode`'s, bit for bit, at the same seed and clip_offset.  `sampler` "ddim" runs
+    `ddim_sample_windows` with `eta` instead of `ddpm_sample_windows`."""
+    from .diffusion import check_sampler, randn_clips
 
     if codes.dim() == 2:
         cond_seq = model.vq.embed(codes)
@@ -188,7 +267,11 @@ def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = Non
         return model.predictor(xs, ts, cond=cond_seq[sl], labels=None if labels is None else labels[sl])
 
     x_T = randn_clips(1, padded, codes.device, seed, clip_offset)
-    out = ddpm_sample_windows(model.diffusion, x_T, predictor, steps, window=window, hop=hop, window_batch=window_batch, constrain=constrain,
-                              cond_fn=cond_fn, seed=seed, clip_offset=clip_offset, progress=progress, **kwargs)
+    if check_sampler(sampler, eta) == "ddim":
+        out = ddim_sample_windows(model.diffusion, x_T, predictor, steps, window=window, hop=hop, window_batch=window_batch, eta=eta,
+                                  constrain=constrain, cond_fn=cond_fn, seed=seed, clip_offset=clip_offset, progress=progress, **kwargs)
+    else:
+        out = ddpm_sample_windows(model.diffusion, x_T, predictor, steps, window=window, hop=hop, window_batch=window_batch,
+                                  constrain=constrain, cond_fn=cond_fn, seed=seed, clip_offset=clip_offset, progress=progress, **kwargs)
     model.predictor.check_status()  # range guard of the decoder's mode (once per sample)
     return out[..., :num_samples]

@@ -86,18 +86,23 @@ def sample_clips(
     labels: Optional[torch.Tensor] = None,
     gather: bool = True,
     sample_fn: Optional[Callable[[int, int, int], torch.Tensor]] = None,
+    sampler: str = "ddpm",
+    eta: float = 0.0,
 ) -> Optional[torch.Tensor]:
     """Sample `n_total` clips over all ranks.  `labels` (global, [n_total]) selects per-clip classes for a
     class-conditional model (the counterpart of sample_diffusion.py:108-122).  `sample_fn(begin, end, seed)`
-    replaces the HIP sampler (used by the CPU gloo tests of the sharding logic)."""
+    replaces the HIP sampler (used by the CPU gloo tests of the sharding logic).  `sampler` "ddim" samples with
+    `Diffusion.ddim_sample` at `eta` (`sigma_large` belongs to the DDPM sampler alone)."""
     rank, world = _dist_info()
     begin, end = shard_range(n_total, rank, world)
     n_local = end - begin
     if sample_fn is not None:
         local = sample_fn(begin, end, seed)
     else:
-        from .diffusion import randn_clips
+        from .diffusion import check_sampler, randn_clips
 
+        if check_sampler(sampler, eta) == "ddim" and sigma_large:
+            raise ValueError("sigma_large has no meaning for sampler='ddim'")
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device())
         if n_local == 0:
@@ -108,8 +113,12 @@ def sample_clips(
             if labels is not None:
                 lab = labels[begin:end].to(device)
                 pred = lambda xs, ts, _p=model.predictor, _l=lab: _p(xs, ts, labels=_l)  # noqa: E731
-            local = model.diffusion.ddpm_sample(x_T, pred, steps, constrain=constrain, sigma_large=sigma_large,
-                                                schedule=schedule, seed=seed, clip_offset=begin)
+            if sampler == "ddim":
+                local = model.diffusion.ddim_sample(x_T, pred, steps, eta=eta, constrain=constrain, schedule=schedule, seed=seed,
+                                                    clip_offset=begin)
+            else:
+                local = model.diffusion.ddpm_sample(x_T, pred, steps, constrain=constrain, sigma_large=sigma_large,
+                                                    schedule=schedule, seed=seed, clip_offset=begin)
     if not gather:
         return local
     return gather_clips(local, n_total, T)

@@ -10,7 +10,7 @@ from typing import Any, Dict, Optional
 
 import torch
 
-from .diffusion import randn_clips
+from .diffusion import check_sampler, randn_clips
 from .diffusion_model import DiffusionModel
 from .conv_encoder import ConvMFCCEncoder
 from .unet import UNetEncoder
@@ -91,8 +91,9 @@ class VQVAE(DiffusionModel):
 
     def decode(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, steps: int = 100, progress: bool = False,
                constrain: bool = False, enc_pred=None, enc_pred_scale: float = 1.0, x_T: Optional[torch.Tensor] = None,
-               **kwargs) -> torch.Tensor:
-        """codes [N,T1] int or [N,C,T1] float -> [N,1,T1*256] waveform (vq_vae.py:92-145)."""
+               sampler: str = "ddpm", eta: float = 0.0, **kwargs) -> torch.Tensor:
+        """codes [N,T1] int or [N,C,T1] float -> [N,1,T1*256] waveform (vq_vae.py:92-145).  `sampler` "ddim" runs
+        `Diffusion.ddim_sample` with `eta` (0: the result depends on x_T alone) instead of `ddpm_sample`."""
         if codes.dim() == 2:
             cond_seq = self.vq.embed(codes)
         elif codes.dim() == 3:
@@ -110,10 +111,34 @@ class VQVAE(DiffusionModel):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         if x_T is None:
             x_T = randn_clips(codes.shape[0], T, codes.device, seed, kwargs.get("clip_offset", 0))
-        out = self.diffusion.ddpm_sample(
+        if check_sampler(sampler, eta) == "ddim":
+            kwargs["eta"] = eta
+        sample = self.diffusion.ddim_sample if sampler == "ddim" else self.diffusion.ddpm_sample
+        out = sample(
             x_T, lambda xs, ts, **kw: self.predictor(xs, ts, cond=cond_seq, labels=labels, **kw),
             steps=steps, progress=progress, constrain=constrain, cond_fn=cond_fn, seed=seed, **kwargs)
         self.predictor.check_status()  # range guard of the decoder's mode (once per sample)
+        return out
+
+    def invert(self, inputs: torch.Tensor, labels: Optional[torch.Tensor] = None, steps: int = 100, codes: Optional[torch.Tensor] = None,
+               **kwargs) -> torch.Tensor:
+        """[N,1,T] waveform -> the x_T [N,1,T] that the DDIM sampler at eta = 0 maps back towards it under ITS OWN codes (encoded here
+        unless `codes`, [N,T1] int or [N,C,T1] float, is given) and its own `labels`: `Diffusion.ddim_invert` with the decoder's
+        predictor.  `decode(codes, other_labels, steps=steps, sampler="ddim", x_T=...)` then converts the voice from the source's
+        latent instead of a fresh draw."""
+        if codes is None:
+            codes = self.encode(inputs)
+        if codes.dim() == 2:
+            cond_seq = self.vq.embed(codes)
+        elif codes.dim() == 3:
+            cond_seq = codes
+        else:
+            raise ValueError(f"unsupported codes shape: {codes.shape}")
+        T = codes.shape[-1] * self.encoder.downsample_rate
+        if inputs.dim() != 3 or inputs.shape[0] != cond_seq.shape[0] or inputs.shape[-1] != T:
+            raise ValueError(f"inputs of shape {tuple(inputs.shape)} do not match codes for {cond_seq.shape[0]} clips of {T} samples")
+        out = self.diffusion.ddim_invert(inputs, lambda xs, ts: self.predictor(xs, ts, cond=cond_seq, labels=labels), steps, **kwargs)
+        self.predictor.check_status()
         return out
 
     def encode_long(self, wave: torch.Tensor, window: int, hop: int, window_batch: int = 64) -> torch.Tensor:
@@ -124,14 +149,15 @@ class VQVAE(DiffusionModel):
 
     def decode_long(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
         """Window codes [n,T1] or [n,C,T1] -> [1,1,num_samples] waveform: `decode` on one long state whose windows are blended at
-        every step (longform.decode_long; keywords num_samples, window, hop, steps, constrain, enc_pred, seed, window_batch ...)."""
+        every step (longform.decode_long; keywords num_samples, window, hop, steps, constrain, enc_pred, seed, window_batch, sampler,
+        eta ...)."""
         from .longform import decode_long
 
         return decode_long(self, codes, labels, **kwargs)
 
     def decode_uncond_guidance(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, steps: int = 100,
                                progress: bool = False, constrain: bool = False, label_scale: float = 0.0, vq_scale: float = 0.0,
-                               x_T: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
+                               x_T: Optional[torch.Tensor] = None, sampler: str = "ddpm", eta: float = 0.0, **kwargs) -> torch.Tensor:
         """Decode with classifier-free-style guidance towards the VQ codes and/or the label (reference
         vq_vae.py:147-220): the predictor runs on a 1x-3x batch [conditional | codes dropped | label dropped] and the
         prediction is base + scale * (base - dropped).  Labels are NOT offset by the caller: label 0 is the
@@ -186,8 +212,11 @@ class VQVAE(DiffusionModel):
             warnings.warn(f"decode_uncond_guidance: the predictor runs in the fp32 mode for this call (decoder mode {prev!r} does not "
                           "meet the 1e-3 waveform contract under guidance extrapolation)", stacklevel=2)
         # (precision_override keeps the decoder's own handle and arena; the fp32 handle is cached beside it for the next call)
+        if check_sampler(sampler, eta) == "ddim":
+            kwargs["eta"] = eta
+        sample = self.diffusion.ddim_sample if sampler == "ddim" else self.diffusion.ddpm_sample
         with self.predictor.precision_override("fp32" if promote else prev):
-            out = self.diffusion.ddpm_sample(x_T, pred_fn, steps=steps, progress=progress, constrain=constrain, seed=seed, **kwargs)
+            out = sample(x_T, pred_fn, steps=steps, progress=progress, constrain=constrain, seed=seed, **kwargs)
             self.predictor.check_status()
         return out
 
