@@ -453,7 +453,8 @@ def vqvae_decode_uncond_guidance(
 # `torchaudio.transforms.MFCC` (conv_encoder.py:42-58), and torchaudio is not installed in the build container (SURVEY.md
 # 8c), so the front end below restates torchaudio's published algorithm -- transforms.MFCC / MelSpectrogram / Spectrogram /
 # MelScale / AmplitudeToDB and functional.create_dct / melscale_fbanks / amplitude_to_DB (torchaudio 0.8 ... 2.x, same
-# arithmetic throughout) -- and cannot be checked against the reference's own output here.  The three constant tensors of
+# arithmetic throughout) -- and cannot be checked against the reference's own output here; it is held to a float64 reference
+# of the whole front end instead (tests/mfcc_ref.py, tests/test_mfcc_front_end.py).  The three constant tensors of
 # the transform (Hann window, mel filter bank, DCT matrix) are persistent buffers of the reference module, so a reference
 # checkpoint carries them ("encoder.mfcc.*"); both this oracle and the HIP path read them from the state dict.  The
 # convolution stack after the front end, `deltas` and `invert_ulaw` ARE the reference's own code and are restated 1:1.

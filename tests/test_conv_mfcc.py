@@ -1,12 +1,15 @@
 """ConvMFCCEncoder (reference models/conv_encoder.py:14-133, scope row 8f.4).
 
-PARITY UNPINNED for the MFCC front end: the reference builds it from torchaudio, which is not installed where the golden
-vectors are generated, so there is no fixture from the reference itself.  What is checked instead:
-  * CPU: the oracle's front end (oracle/ref_cpu.py, torch.stft based) against an independent numpy restatement of the
-    published algorithm (explicit reflect padding, framing, rfft, filter bank, log / dB, DCT) -- pins the framing,
-    normalisation and dB conventions against a second derivation; the state-dict layout of the parameter container;
-  * GPU: the HIP path (through the C ABI) against the oracle: feature rows, encoder output, VQ codes, and the conditional
-    predictor forward with T/320 conditioning rows (nearest up-sampling as F.interpolate, unet.py:139)."""
+The reference builds the MFCC front end from torchaudio, which is not installed where the golden vectors are generated, so there
+is no fixture from the reference itself.  The front end is pinned to a float64 reference of the published algorithm instead
+(tests/mfcc_ref.py; tests/test_mfcc_front_end.py holds the oracle and the HIP kernels to it over a grid of inputs and lengths, with
+a gate derived per case from the oracle's own error).  What is checked here:
+  * CPU: the oracle's front end (oracle/ref_cpu.py, torch.stft based) against a second, independent numpy derivation that builds
+    its own window, filter bank and DCT matrix (mfcc_ref.numpy_mfcc) -- pins the construction of those constants along with the
+    framing, normalisation and dB conventions; the state-dict layout of the parameter container;
+  * GPU: the HIP path (through the C ABI) against the oracle: feature rows (at the per-case gate of mfcc_ref.Case), encoder
+    output, VQ codes, and the conditional predictor forward with T/320 conditioning rows (nearest up-sampling as F.interpolate,
+    unet.py:139)."""
 import math
 
 import numpy as np
@@ -17,40 +20,10 @@ from oracle import ref_cpu
 from vq_voice_swap_amd import ConvMFCCEncoder, VQVAE
 from vq_voice_swap_amd.det_init import det_init_
 
+from mfcc_ref import Case, numpy_mfcc
 from util import rel_rms, seeded
 
 torch.set_num_threads(8)
-
-
-def numpy_mfcc(wave: np.ndarray, cfg: dict) -> np.ndarray:
-    """Independent restatement of torchaudio.transforms.MFCC for one [T] waveform (float64 throughout)."""
-    n_fft, hop, n_mels, sr = cfg["n_fft"], cfg["hop"], cfg["n_mels"], cfg["sample_rate"]
-    x = np.pad(wave.astype(np.float64), n_fft // 2, mode="reflect")
-    frames = 1 + (len(x) - n_fft) // hop
-    win = 0.5 - 0.5 * np.cos(2 * np.pi * np.arange(n_fft) / n_fft)  # periodic Hann
-    spec = np.stack([np.fft.rfft(x[f * hop:f * hop + n_fft] * win) for f in range(frames)], axis=1)  # [freq, frames]
-    if cfg["normalized"]:
-        spec = spec / np.sqrt((win ** 2).sum())
-    power = np.abs(spec) ** 2
-    # HTK mel filter bank, norm=None
-    hz2mel = lambda f: 2595.0 * np.log10(1.0 + f / 700.0)  # noqa: E731
-    mel2hz = lambda m: 700.0 * (10 ** (m / 2595.0) - 1.0)  # noqa: E731
-    freqs = np.linspace(0, sr // 2, n_fft // 2 + 1)
-    pts = mel2hz(np.linspace(hz2mel(0.0), hz2mel(sr // 2), n_mels + 2))
-    fb = np.zeros((len(freqs), n_mels))
-    for m in range(n_mels):
-        lo, ce, hi = pts[m], pts[m + 1], pts[m + 2]
-        fb[:, m] = np.maximum(0.0, np.minimum((freqs - lo) / (ce - lo), (hi - freqs) / (hi - ce)))
-    mel = fb.T @ power
-    if cfg["log_mels"]:
-        mel = np.log(mel + 1e-6)
-    else:
-        mel = 10.0 * np.log10(np.maximum(mel, 1e-10))
-        mel = np.maximum(mel, mel.max() - 80.0)
-    k = np.arange(cfg["n_mfcc"])[:, None]
-    dct = np.cos(np.pi / n_mels * (np.arange(n_mels)[None] + 0.5) * k) * np.sqrt(2.0 / n_mels)
-    dct[0] *= 1.0 / np.sqrt(2.0)
-    return dct @ mel
 
 
 @pytest.mark.parametrize("version", [1, 2])
@@ -112,16 +85,22 @@ def test_hip_encoder_vs_oracle(enc_name, version, ulaw):
         h = enc._handle
         names = [n for n, _, _ in h.taps()]
         f = h.read_tap(names.index("features"), B, T)[:, :39]
-        # log / dB features of noise-floor bins amplify the fp32 FFT's rounding: compare in absolute terms against their range
-        assert (f - feats["features"]).abs().max().item() <= 5e-3 * feats["features"].abs().max().item(), (enc_name, T)
+        # log / dB features of noise-floor bins amplify the fp32 FFT's rounding: compare in absolute terms.  Against the float64
+        # reference the HIP rows owe the case's gate, 8 * max(E_oracle, E_model); against the oracle, that plus the oracle's own
+        # error -- in no case more than the 5e-3 of the feature range asked before
+        c = Case(x[:, 0], version, ulaw)
+        e_ref, where = c.error(f)
+        assert e_ref <= c.gate <= c.cap, (enc_name, T, e_ref, c.gate, where)
+        bound = min(c.gate + c.e_oracle, 5e-3 * feats["features"].abs().max().item())
+        assert (f - feats["features"]).abs().max().item() <= bound, (enc_name, T, bound)
         assert rel_rms(got, want) < 2e-3, (enc_name, B, T, rel_rms(got, want))
     # Codes through the VQ layer.  (a) The VQ layer itself is BIT-EXACT: the codes of the HIP path are the reference argmin
     # (vq.py:199-221 order, first index on ties) of the HIP encoder's own z.  (b) Against the oracle's codes the only admissible
     # difference is a PROVEN near-tie: with delta = z_hip - z_oracle at a position, replacing z by z + delta moves the difference
     # of two squared distances by exactly 2 delta . (e2 - e1), so the argmin can only move from e1 to e2 where the oracle's top
     # gap d(z, e2) - d(z, e1) is at most 2 |delta| |e2 - e1| (+ the fp32 rounding of the distances themselves, 1e-5 relative).
-    # The front end is where delta comes from (fp64 DFT here, fp32 FFT in torchaudio / the oracle: "parity unpinned" for the MFCC
-    # transform); everything else is asserted exactly.
+    # The front end is where delta comes from (fp64 DFT here, fp32 FFT in torchaudio / the oracle; both are held to a float64 reference,
+    # DESIGN.md section 4); everything else is asserted exactly.
     x = (0.4 * seeded((2, 1, 64000), 9)).clamp(-1, 1)
     z = ref_cpu.conv_mfcc_encoder(sd, x, version=version, input_ulaw=ulaw)
     dic = sd["vq.dictionary"]

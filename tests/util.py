@@ -13,6 +13,25 @@ def rms(a):
     return a.pow(2).mean().sqrt().item()
 
 
+def record_margin(file_name, rec):
+    """Print one measured margin and, when the environment names a directory in VQVS_MARGINS_DIR, append it to <file_name>
+    there (the print-and-append half of `gate`, for gates that are not an RMS of a waveform; a GPU run's records are kept under
+    profiles/)."""
+    import json
+    import os
+
+    print("[margin] " + json.dumps(rec))
+    out = os.environ.get("VQVS_MARGINS_DIR")
+    if not out:
+        return
+    try:
+        os.makedirs(out, exist_ok=True)
+        with open(os.path.join(out, file_name), "a") as f:
+            f.write(json.dumps(rec) + "\n")
+    except OSError:
+        pass
+
+
 def gate(name, got, want, bound, relative=False):
     """Waveform gate: assert RMS(got - want) < bound (relative to RMS(want) when `relative`; bound None = record the value without
     gating it, only a gross-error check at 1e-2 stays), print the measured value and

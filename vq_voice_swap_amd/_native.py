@@ -82,6 +82,11 @@ class NativeError(RuntimeError):
     pass
 
 
+class NativeArgumentError(NativeError, ValueError):
+    """VQVS_ERR_ARG: the library refused the arguments on the host, before it touched the device.  A ValueError, as the
+    reference raises for shape problems, and a NativeError like every other error the library reports."""
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile every HIP source for gfx950 into libvqvs_hip.so (in-tree)."""
     cmd = ["make", "-C", CSRC, "-j", str(min(8, os.cpu_count() or 1))]
@@ -171,14 +176,14 @@ def last_error() -> str:
 def check(rc: int) -> None:
     """Map the ABI's error codes to the exception types the reference raises
     (AssertionError for the forward-argument asserts of unet.py:126-131, ValueError for
-    shape problems, RuntimeError for HIP failures)."""
+    shape problems -- NativeArgumentError, which is a NativeError too --, RuntimeError for HIP failures)."""
     if rc == 0:
         return
     msg = last_error()
     if rc == -1:
         if msg.startswith("must provide"):
             raise AssertionError(msg)
-        raise ValueError(msg)
+        raise NativeArgumentError(msg)
     raise NativeError(f"libvqvs_hip error {rc}: {msg}")
 
 

@@ -106,8 +106,10 @@ __global__ __launch_bounds__(256) void mfcc_batch_max_kernel(const float* wgmax,
   if (threadIdx.x == 0) out[0] = red[0];
 }
 
-// DCT + deltas + delta-deltas -> feat[b][row][64]: channels 0..12 MFCC, 13..25 deltas, 26..38 delta-deltas, 39..63 zero;
-// rows frames .. rows_alloc-1 are zero (the padding row read by the stride-2 convolution).
+// DCT + deltas + delta-deltas -> feat[b][row][64]: channels 0..12 MFCC, 13..25 deltas, 26..38 delta-deltas, 39..63 zero.
+// The host passes rows_alloc = frames: the feature tensor has no padding row (rows frames .. rows_alloc-1 would be written as
+// zeros if it had).  The padding row the stride-2 convolution's pair view reads for an odd frame count belongs to the output
+// of blocks.1 and is zeroed there (net.cpp, "pad_row").
 constexpr int FT_OUT = 60, FT_WIN = 64, FT_C = 13;
 __global__ __launch_bounds__(256) void mfcc_features_kernel(const MfccFeatArgs a) {
   __shared__ float m[FT_WIN][FT_C + 1], d[FT_WIN][FT_C + 1];
