@@ -292,6 +292,34 @@ int vqvs_ddim_step(const float* d_x_t, const float* d_eps, const float* d_grad, 
 int vqvs_ddim_step_windows(const float* d_x, const float* d_eps, const float* d_grad, const float* d_noise, const float* d_alpha_t,
                            const float* d_alpha_to, float* d_x_to, float* d_windows, int n, int W, int H, uint32_t flags, float eta,
                            float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index, void* stream);
+/* ---- Keep region (handle-less; the "replacement" method of Song et al., "Score-based generative modeling through stochastic
+ * differential equations", 2021, as in RePaint and SDEdit -- the reference has no counterpart) ----
+ * IN PLACE on the state d_x [B,T]: every sample with d_keep[row,p] != 0 -- every sample when d_keep is NULL -- is put back on the
+ * forward process q(x_t | x0) of a source at alpha_bar = d_alpha[row]:
+ *   x[p] = fmaf(ca, x0[p], cn * (noise_scale * z)),   ca = sqrt(alpha), cn = sqrt(max(1 - alpha, 0))
+ * ca and cn are computed in fp64 from the fp32 alpha and rounded to fp32 once, the rule of vqvs_ddim_step's coefficients.  A sample
+ * that is not kept is not written, and the state is never read.
+ *   d_x0 [B,T] f32 the source; d_keep [B,T] uint8 or NULL; d_alpha [B] f32
+ *   d_noise [B,T] f32, or NULL to draw z = philox_normal4(seed, quad = p / 4, clip_offset + row, index, stream 3): a stream of its own,
+ *     independent of the step noise (0), of x_T (1) and of the loss noise (2).  A sampler passes as `index` the number of the step
+ *     that will consume the state.
+ * Nothing is drawn, and d_noise is not read, when cn == 0 or noise_scale == 0: then x[p] = ca * x0[p], at alpha = 1 the source bit for
+ * bit.  Any T: 16-byte accesses when T % 4 == 0 and the buffers are 16-byte aligned (d_keep: 4-byte), one sample at a time otherwise,
+ * and a quad that the mask cuts through stores its kept samples one by one; the values do not depend on which.
+ * VQVS_ERR_ARG before the device is touched: NULL d_x, d_x0 or d_alpha; B outside 1..65535, T outside 1..2^30; noise_scale not finite;
+ * d_x overlapping d_x0, d_keep, d_noise or d_alpha. */
+int vqvs_keep_region(float* d_x, const float* d_x0, const uint8_t* d_keep, const float* d_noise, const float* d_alpha, int B, int T,
+                     float noise_scale, uint64_t seed, uint64_t clip_offset, uint32_t index, void* stream);
+/* The same on ONE long state in the geometry of vqvs_ddpm_step_windows: d_x [Np], d_x0 [Np], d_keep [Np] or NULL and d_noise [Np] or NULL
+ * are indexed by absolute position, Np = (n - 1) * H + W, and there is ONE d_alpha.  A kept sample is written to d_x and, with the same
+ * value, to its copy d_windows[b,j] in every window that covers it (d_windows [n,W] in/out, or NULL).  Drawn noise is
+ * philox_normal4(seed, p / 4, clip, index, stream 3): what vqvs_keep_region draws for one row of Np samples at clip_offset = clip.  At
+ * n = 1 the result equals vqvs_keep_region(B = 1, T = W, clip_offset = clip) bit for bit.
+ * VQVS_ERR_ARG before the device is touched: the rules above; every limit of vqvs_ddpm_step_windows on (n, W, H); d_windows overlapping
+ * an input or d_x. */
+int vqvs_keep_region_windows(float* d_x, float* d_windows, const float* d_x0, const uint8_t* d_keep, const float* d_noise,
+                             const float* d_alpha, int n, int W, int H, float noise_scale, uint64_t seed, uint64_t clip, uint32_t index,
+                             void* stream);
 /* x_T ~ N(0,1) from the same counter-based generator (replaces torch.randn, sample_diffusion.py:86) */
 int vqvs_randn(float* d_out, int B, int T, uint64_t seed, uint64_t clip_offset, uint32_t stream_id, void* stream);
 

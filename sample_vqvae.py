@@ -6,6 +6,8 @@ sample_vqvae.py (same flags and positionals; reference sample_vqvae.py:76-92): r
 `--whole-file` (not in the reference) converts the whole input instead: `encode_long` / `decode_long` on overlapping windows.
 `--sampler ddim` (with `--eta`, default 0: deterministic) samples with the DDIM step instead of the ancestral DDPM loop; with
 `--source-label L` it starts from `VQVAE.invert` of the input under its own codes and label L instead of from a fresh draw.
+`--keep START:END` (seconds, repeatable) leaves those ranges of the input as they are and converts the rest around them;
+`--strength S` below 1 starts from the noised input instead of from pure noise.  Both work with either sampler and with `--whole-file`.
 Differences: WAV in/out directly (no ffmpeg); the model is put in eval mode (the reference's train-mode VQ
 bookkeeping crashes on current numpy; outputs are identical).  `--enc-pred-path` loads an
 EncoderPredictor whose guidance gradient comes from the library's explicit backward schedule (no autograd).
@@ -21,18 +23,23 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from vq_voice_swap_amd import VQVAE, EncoderPredictor  # noqa: E402
-from vq_voice_swap_amd.audio import ChunkReader, ChunkWriter  # noqa: E402
+from vq_voice_swap_amd.audio import ChunkReader, ChunkWriter, keep_mask, parse_keep_range  # noqa: E402
 
 
-def arg_parser(sampler_flags: bool = False):
-    """The command line.  `sampler_flags` adds --sampler / --eta / --source-label, which `main` parses (`parse_args`); without it
-    the parser is the one of the DDPM-only script, flag for flag."""
+def arg_parser(sampler_flags: bool = False, keep_flags: bool = False):
+    """The command line.  `sampler_flags` adds --sampler / --eta / --source-label and `keep_flags` adds --keep / --strength, all of
+    which `main` parses (`parse_args`); without them the parser is the one of the DDPM-only script, flag for flag."""
     p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     if sampler_flags:
         p.add_argument("--sampler", default="ddpm", choices=["ddpm", "ddim"])
         p.add_argument("--eta", type=float, default=0.0, help="DDIM noise level: 0 deterministic, 1 the DDPM step's variance (--sampler ddim)")
         p.add_argument("--source-label", type=int, default=None,
                        help="with --sampler ddim: start from the DDIM inversion of the input under this label (the speaker it was spoken by)")
+    if keep_flags:
+        p.add_argument("--keep", action="append", default=[], metavar="START:END",
+                       help="seconds of the input to leave as they are (repeatable; an empty side is the start / end of the file)")
+        p.add_argument("--strength", type=float, default=1.0,
+                       help="in (0, 1]: below 1 the conversion starts from the noised input and runs the last ceil(S * steps) steps")
     p.add_argument("--sample-rate", type=int, default=16000)
     p.add_argument("--sample-steps", type=int, default=100)
     p.add_argument("--seconds", type=int, default=4)
@@ -56,12 +63,20 @@ def arg_parser(sampler_flags: bool = False):
 
 
 def parse_args(argv=None):
-    parser = arg_parser(sampler_flags=True)
+    parser = arg_parser(sampler_flags=True, keep_flags=True)
     args = parser.parse_args(argv)
     if args.sampler == "ddpm" and args.eta:
         parser.error("--eta belongs to --sampler ddim")
     if args.eta < 0:
         parser.error("--eta must not be negative")
+    try:
+        args.keep = [parse_keep_range(text) for text in args.keep]
+    except ValueError as e:
+        parser.error(str(e))
+    if not 0.0 < args.strength <= 1.0:
+        parser.error("--strength must lie in (0, 1]")
+    if args.source_label is not None and (args.keep or args.strength < 1):
+        parser.error("--source-label starts from the inverted input: it cannot be combined with --keep or --strength")
     if args.source_label is not None:
         if args.sampler != "ddim":
             parser.error("--source-label needs --sampler ddim (the inversion is the DDIM step run backwards)")
@@ -70,6 +85,18 @@ def parse_args(argv=None):
         if args.no_vq:
             parser.error("--source-label is not available with --no-vq")
     return args
+
+
+def source_kwargs(args, wave: torch.Tensor):
+    """decode's source / keep / strength keywords for the input `wave` [1,1,N]: nothing unless --keep or --strength asks."""
+    if not args.keep and args.strength == 1.0:
+        return {}
+    kw = dict(source=wave, strength=args.strength)
+    if args.keep:
+        mask = keep_mask(args.keep, wave.shape[-1], args.sample_rate)
+        print(f"keeping {mask.mean():.1%} of the input ({int(mask.sum())} of {mask.size} samples)")
+        kw["keep"] = torch.from_numpy(mask[None, None]).to(wave.device)
+    return kw
 
 
 def main(argv=None):
@@ -114,7 +141,8 @@ def main(argv=None):
         print("inverting the input to its latent...")
         x_T = model.invert(in_seq, torch.tensor([args.source_label]).long().to(device), steps=args.sample_steps, codes=encoded)
     sample = model.decode(encoded, labels, steps=args.sample_steps, progress=True, constrain=True, seed=args.seed,
-                          enc_pred=enc_pred, enc_pred_scale=args.enc_pred_scale, x_T=x_T, sampler=args.sampler, eta=args.eta)
+                          enc_pred=enc_pred, enc_pred_scale=args.enc_pred_scale, x_T=x_T, sampler=args.sampler, eta=args.eta,
+                          **source_kwargs(args, in_seq))
 
     if args.check_vq:
         assert not args.no_vq
@@ -155,7 +183,7 @@ def convert_whole_file(args, model, enc_pred, device):
     labels = torch.tensor([args.label]).long().to(device)
     sample = model.decode_long(encoded, labels, num_samples=num_samples, window=window, hop=hop, steps=args.sample_steps, progress=True,
                                constrain=True, seed=args.seed, enc_pred=enc_pred, enc_pred_scale=args.enc_pred_scale,
-                               window_batch=args.window_batch, sampler=args.sampler, eta=args.eta)
+                               window_batch=args.window_batch, sampler=args.sampler, eta=args.eta, **source_kwargs(args, wave))
 
     if args.check_vq:
         count = (encoded == model.encode_long(sample, window, hop, args.window_batch)).float().mean()

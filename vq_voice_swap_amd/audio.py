@@ -186,3 +186,47 @@ def parse_time_schedule(text: str):
         p = float(s[3:])
         return lambda t, _p=p: t ** _p
     raise ValueError(f"unsupported sample-time schedule {text!r}; use 'lambda t: t' or 'lambda t: t**P'")
+
+
+def parse_keep_range(text: str):
+    """One `--keep START:END` in seconds -> (start, end) floats; an empty side is None, the start or the end of the file.
+    "1.5:2", ":0.5", "3:".  A negative, non-finite, reversed or empty range is refused."""
+    parts = text.strip().split(":")
+    if len(parts) != 2:
+        raise ValueError(f"keep range {text!r}: expected START:END in seconds (either side may be empty)")
+    try:
+        start, end = (float(p) if p.strip() else None for p in parts)
+    except ValueError:
+        raise ValueError(f"keep range {text!r}: START and END must be numbers of seconds") from None
+    for v in (start, end):
+        if v is not None and not (0.0 <= v < float("inf")):
+            raise ValueError(f"keep range {text!r}: times must be finite and not negative")
+    if start is not None and end is not None and end <= start:
+        raise ValueError(f"keep range {text!r}: END must lie after START")
+    return start, end
+
+
+def keep_sample_ranges(ranges, num_samples: int, sample_rate: int):
+    """(start, end) ranges in seconds (`parse_keep_range`) -> sorted, disjoint [a, b) sample ranges of a file of `num_samples`:
+    indices are round(seconds * sample_rate) clipped to the file, overlapping or touching ranges are merged, empty ones dropped."""
+    spans = []
+    for start, end in ranges:
+        a = 0 if start is None else min(max(round(start * sample_rate), 0), num_samples)
+        b = num_samples if end is None else min(max(round(end * sample_rate), 0), num_samples)
+        if b > a:
+            spans.append((a, b))
+    merged = []
+    for a, b in sorted(spans):
+        if merged and a <= merged[-1][1]:
+            merged[-1] = (merged[-1][0], max(merged[-1][1], b))
+        else:
+            merged.append((a, b))
+    return merged
+
+
+def keep_mask(ranges, num_samples: int, sample_rate: int) -> np.ndarray:
+    """The bool mask [num_samples] of the samples inside any of the ranges (`keep_sample_ranges`)."""
+    mask = np.zeros(num_samples, dtype=bool)
+    for a, b in keep_sample_ranges(ranges, num_samples, sample_rate):
+        mask[a:b] = True
+    return mask

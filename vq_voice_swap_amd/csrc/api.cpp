@@ -420,6 +420,53 @@ int vqvs_ddim_step_windows(const float* d_x, const float* d_eps, const float* d_
                                flags, eta, noise_scale, seed, clip, step_index, reinterpret_cast<hipStream_t>(stream));
 }
 
+// [a, a + na) against [b, b + nb) in bytes (NULL: absent)
+static bool bytes_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
+  const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
+  return pa && pb && pa < pb + nb && pb < pa + na;
+}
+// Shared argument rules of the two keep-region entry points.  N: samples of the state (and of x0, keep, noise); n_alpha: entries of
+// d_alpha; NW: samples of d_windows (0 when the entry point has none).
+static int check_keep_args(const float* d_x, const float* d_windows, const float* d_x0, const uint8_t* d_keep, const float* d_noise,
+                           const float* d_alpha, int64_t N, int64_t n_alpha, int64_t NW, float noise_scale) {
+  if (!std::isfinite(noise_scale)) VQVS_FAIL(VQVS_ERR_ARG, "noise_scale %g must be finite", (double)noise_scale);
+  const struct { const char* name; const void* p; int64_t bytes; } ins[] = {
+      {"d_x0", d_x0, N * 4}, {"d_keep", d_keep, N}, {"d_noise", d_noise, N * 4}, {"d_alpha", d_alpha, n_alpha * 4}};
+  for (const auto& in : ins) {
+    if (bytes_overlap(d_x, N * 4, in.p, in.bytes)) VQVS_FAIL(VQVS_ERR_ARG, "d_x must not overlap %s", in.name);
+    if (bytes_overlap(d_windows, NW * 4, in.p, in.bytes)) VQVS_FAIL(VQVS_ERR_ARG, "d_windows must not overlap %s", in.name);
+  }
+  if (bytes_overlap(d_windows, NW * 4, d_x, N * 4)) VQVS_FAIL(VQVS_ERR_ARG, "d_windows must not overlap d_x");
+  return 0;
+}
+
+int vqvs_keep_region(float* d_x, const float* d_x0, const uint8_t* d_keep, const float* d_noise, const float* d_alpha, int B, int T,
+                     float noise_scale, uint64_t seed, uint64_t clip_offset, uint32_t index, void* stream) {
+  if (!d_x) VQVS_FAIL(VQVS_ERR_ARG, "d_x must be non-NULL");
+  if (!d_x0) VQVS_FAIL(VQVS_ERR_ARG, "d_x0 must be non-NULL");
+  if (!d_alpha) VQVS_FAIL(VQVS_ERR_ARG, "d_alpha must be non-NULL");
+  if (B < 1 || B > 65535) VQVS_FAIL(VQVS_ERR_ARG, "batch B=%d outside 1..65535", B);
+  if (T < 1 || T > (1 << 30)) VQVS_FAIL(VQVS_ERR_ARG, "row length T=%d outside 1..2^30", T);
+  if (int e = check_keep_args(d_x, nullptr, d_x0, d_keep, d_noise, d_alpha, (int64_t)B * T, B, 0, noise_scale)) return e;
+  return run_keep_region(d_x, d_x0, d_keep, d_noise, d_alpha, B, T, noise_scale, seed, clip_offset, index, reinterpret_cast<hipStream_t>(stream));
+}
+
+int vqvs_keep_region_windows(float* d_x, float* d_windows, const float* d_x0, const uint8_t* d_keep, const float* d_noise,
+                             const float* d_alpha, int n, int W, int H, float noise_scale, uint64_t seed, uint64_t clip, uint32_t index,
+                             void* stream) {
+  if (!d_x) VQVS_FAIL(VQVS_ERR_ARG, "d_x must be non-NULL");
+  if (!d_x0) VQVS_FAIL(VQVS_ERR_ARG, "d_x0 must be non-NULL");
+  if (!d_alpha) VQVS_FAIL(VQVS_ERR_ARG, "d_alpha must be non-NULL");
+  if (n < 1 || n > 65535) VQVS_FAIL(VQVS_ERR_ARG, "window count n=%d outside 1..65535", n);
+  if (W < 4 || H < 4 || W % 4 || H % 4) VQVS_FAIL(VQVS_ERR_ARG, "window W=%d and hop H=%d must be positive multiples of 4", W, H);
+  if (W < H || W - H > H) VQVS_FAIL(VQVS_ERR_ARG, "overlap %d (window W=%d - hop H=%d) outside 0..hop: at most two windows may cover a sample", W - H, W, H);
+  const int64_t Np = (int64_t)(n - 1) * H + W;
+  if (Np >= ((int64_t)1 << 31)) VQVS_FAIL(VQVS_ERR_ARG, "n=%d windows every H=%d samples span %lld samples: 2^31 or more", n, H, (long long)Np);
+  if (int e = check_keep_args(d_x, d_windows, d_x0, d_keep, d_noise, d_alpha, Np, 1, (int64_t)n * W, noise_scale)) return e;
+  return run_keep_region_windows(d_x, d_windows, d_x0, d_keep, d_noise, d_alpha, n, W, H, noise_scale, seed, clip, index,
+                                 reinterpret_cast<hipStream_t>(stream));
+}
+
 int vqvs_ddpm_mean(const float* d_x_t, const float* d_eps, const float* d_alpha_t, const float* d_alpha_prev, float* d_mean, int B, int T,
                    void* stream) {
   if (!d_x_t || !d_eps || !d_alpha_t || !d_alpha_prev || !d_mean) VQVS_FAIL(VQVS_ERR_ARG, "NULL argument");

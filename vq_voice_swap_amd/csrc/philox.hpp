@@ -5,8 +5,8 @@
 namespace vqvs {
 
 // stream ids in use (the last counter word): 0 = the reverse step's noise, 1 = x_T, 2 = the forward process' epsilon
-// (vqvs_ddpm_noise / vqvs_ddpm_sqerr)
-constexpr uint32_t PHILOX_STREAM_STEP = 0u, PHILOX_STREAM_XT = 1u, PHILOX_STREAM_LOSS = 2u;
+// (vqvs_ddpm_noise / vqvs_ddpm_sqerr), 3 = the noise that puts a kept region back on the source's forward process (vqvs_keep_region)
+constexpr uint32_t PHILOX_STREAM_STEP = 0u, PHILOX_STREAM_XT = 1u, PHILOX_STREAM_LOSS = 2u, PHILOX_STREAM_KEEP = 3u;
 
 // ---------------------------------------------------------------------------------
 // Philox4x32-10 (Salmon et al. 2011), keyed by the sampler seed; the counter carries

@@ -381,6 +381,113 @@ __global__ __launch_bounds__(256) void ddim_step_windows_kernel(const float* x, 
 }
 
 // ---------------------------------------------------------------------------------
+// Keep region (the "replacement" method of Song et al. 2021; the reference has none), include/vqvs.h "Keep region".  Kept samples of a
+// state are put back on the forward process of a source at alpha_bar = alpha:
+//   x[p] = fmaf(ca, x0[p], cn * (noise_scale * z)),   ca = sqrt(alpha), cn = sqrt(max(1 - alpha, 0))
+// with the coefficients formed in fp64 from the fp32 alpha and rounded to fp32 once, as ddim_coef forms its own.  The state itself is
+// never read: a quad without a kept sample costs its four mask bytes, a quad that is kept whole is one 16-byte store, and a quad the
+// mask cuts through stores its kept samples one by one, so that a sample outside the mask is not written at all.
+// ---------------------------------------------------------------------------------
+struct KeepCoef {
+  float ca, cn;
+};
+
+__device__ __forceinline__ KeepCoef keep_coef(float alpha) {
+  const double a = (double)alpha;
+  return {(float)sqrt(a), (float)sqrt(fmax(1.0 - a, 0.0))};
+}
+
+// The values of the quad at element offset `at` of x0 / keep / noise (`live` of its four samples exist: the tail of a row has fewer)
+// and the mask of its kept samples; o is set only where the mask is, and nothing but the mask bytes is read when it is empty.  `vec`:
+// the quad is whole and 16-byte aligned in every array, so each array is read with one access.  The noise of quad `quad` of clip
+// `clip` is drawn when `noise` is NULL; with cn == 0 or noise_scale == 0 none is drawn or read and the value is ca * x0 -- at
+// alpha = 1 the source itself, sign of zero included.
+__device__ __forceinline__ uint32_t keep_quad(const float* x0, const uint8_t* keep, const float* noise, size_t at, int live, bool vec,
+                                              const KeepCoef& k, float noise_scale, uint64_t seed, uint32_t quad, uint64_t clip,
+                                              uint32_t index, f32x4& o) {
+#pragma clang fp contract(off)
+  uint32_t mask = (1u << live) - 1u;
+  if (keep) {
+    uint32_t m = 0u;
+    if (vec) {
+      const uint32_t w = *reinterpret_cast<const uint32_t*>(keep + at);
+      for (int j = 0; j < 4; ++j) m |= ((w >> (8 * j)) & 0xffu) ? 1u << j : 0u;
+    } else {
+      for (int j = 0; j < live; ++j) m |= keep[at + j] ? 1u << j : 0u;
+    }
+    mask &= m;
+  }
+  if (!mask) return 0u;
+  f32x4 sv = {0.f, 0.f, 0.f, 0.f}, zv = {0.f, 0.f, 0.f, 0.f};
+  if (vec) {
+    sv = *reinterpret_cast<const f32x4*>(x0 + at);
+  } else {
+    for (int j = 0; j < live; ++j) sv[j] = x0[at + j];
+  }
+  const bool noisy = k.cn != 0.f && noise_scale != 0.f;
+  if (noisy) {
+    if (!noise) {
+      zv = philox_normal4(seed, quad, clip, index, PHILOX_STREAM_KEEP);
+    } else if (vec) {
+      zv = *reinterpret_cast<const f32x4*>(noise + at);
+    } else {
+      for (int j = 0; j < live; ++j) zv[j] = noise[at + j];
+    }
+  }
+  for (int j = 0; j < 4; ++j) o[j] = noisy ? fmaf(k.ca, sv[j], k.cn * (noise_scale * zv[j])) : k.ca * sv[j];
+  return mask;
+}
+
+// the kept samples of a quad to dst: one 16-byte store when all four are kept and the quad is aligned, else the kept ones alone
+__device__ __forceinline__ void keep_store(float* dst, const f32x4& o, uint32_t mask, bool vec) {
+  if (vec && mask == 0xfu) {
+    *reinterpret_cast<f32x4*>(dst) = o;
+  } else {
+    for (int j = 0; j < 4; ++j)
+      if (mask & (1u << j)) dst[j] = o[j];
+  }
+}
+
+// x [B, T] in place; row b is clip clip_offset + b and has its own alpha.  aligned: T % 4 == 0 and every base pointer is 16-byte
+// aligned (keep: 4-byte), so every quad of every row is; otherwise the samples are accessed one by one.
+__global__ __launch_bounds__(256) void keep_region_kernel(float* x, const float* x0, const uint8_t* keep, const float* noise,
+                                                          const float* alpha, int T, bool aligned, float noise_scale, uint64_t seed,
+                                                          uint64_t clip_offset, uint32_t index) {
+  const int b = blockIdx.y;
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q * 4 >= T) return;
+  const KeepCoef k = keep_coef(alpha[b]);
+  const size_t at = (size_t)b * T + q * 4;
+  const int live = min(4, T - q * 4);
+  f32x4 o;
+  const uint32_t mask = keep_quad(x0, keep, noise, at, live, aligned, k, noise_scale, seed, (uint32_t)q, clip_offset + b, index, o);
+  if (mask) keep_store(x + at, o, mask, aligned);
+}
+
+// ddpm_step_windows_kernel's geometry for the same operation on ONE long state x [Np]: x0, keep and noise are indexed by absolute
+// position, there is one alpha, the drawn noise is that of one row of Np samples at `clip`, and a kept sample goes to x and to its
+// copy in every window that covers it (win [n, W]; NULL: not wanted).  W and H are multiples of 4: every quad is whole.
+__global__ __launch_bounds__(256) void keep_region_windows_kernel(float* x, float* win, const float* x0, const uint8_t* keep,
+                                                                  const float* noise, const float* alpha, int n, int W, int H, bool aligned,
+                                                                  float noise_scale, uint64_t seed, uint64_t clip, uint32_t index) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  const int Np = (n - 1) * H + W, V = W - H;
+  if (q >= Np / 4) return;
+  const int p = q * 4;
+  const KeepCoef k = keep_coef(alpha[0]);
+  f32x4 o;
+  const uint32_t mask = keep_quad(x0, keep, noise, (size_t)p, 4, aligned, k, noise_scale, seed, (uint32_t)q, clip, index, o);
+  if (!mask) return;
+  keep_store(x + p, o, mask, aligned);
+  if (win) {
+    const int br = min(p / H, n - 1);
+    const int u = p - br * H;  // offset in window br; in window br - 1 the sample is u + H
+    keep_store(win + (size_t)br * W + u, o, mask, aligned);
+    if (br > 0 && u < V) keep_store(win + (size_t)(br - 1) * W + u + H, o, mask, aligned);
+  }
+}
+
+// ---------------------------------------------------------------------------------
 // VQ nearest codeword (reference vq.py:127-131, 199-221).
 //   dist[k] = ((-2 * <x, e_k>) + |e_k|^2) + |x|^2   in fp32, dot as an fmaf chain in channel
 //   order; argmin with the FIRST minimal index (torch.argmin semantics).
@@ -663,6 +770,32 @@ int run_ddim_step_windows(const float* x, const float* eps, const float* grad, c
   auto kernel = grad ? ddim_step_windows_kernel<true> : ddim_step_windows_kernel<false>;
   hipLaunchKernelGGL(kernel, dim3((quads + 255) / 256), dim3(256), 0, st, x, eps, grad, noise, a_t, a_to, scratch, nchunk, x_to, windows, n, W,
                      H, flags, eta, noise_scale, seed, clip, step_index);
+  VQVS_HIP(hipGetLastError());
+  return 0;
+}
+
+// 16-byte accesses need every array to start on a 16-byte boundary (the mask, read 4 bytes at a time, on a 4-byte one)
+static bool keep_aligned(const float* x, const float* win, const float* x0, const uint8_t* keep, const float* noise) {
+  const uintptr_t floats = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(win) | reinterpret_cast<uintptr_t>(x0) |
+                           reinterpret_cast<uintptr_t>(noise);
+  return floats % 16 == 0 && reinterpret_cast<uintptr_t>(keep) % 4 == 0;
+}
+
+int run_keep_region(float* x, const float* x0, const uint8_t* keep, const float* noise, const float* alpha, int B, int T, float noise_scale,
+                    uint64_t seed, uint64_t clip_offset, uint32_t index, hipStream_t st) {
+  const bool aligned = T % 4 == 0 && keep_aligned(x, nullptr, x0, keep, noise);
+  dim3 grid(((T + 3) / 4 + 255) / 256, B);
+  hipLaunchKernelGGL(keep_region_kernel, grid, dim3(256), 0, st, x, x0, keep, noise, alpha, T, aligned, noise_scale, seed, clip_offset, index);
+  VQVS_HIP(hipGetLastError());
+  return 0;
+}
+
+int run_keep_region_windows(float* x, float* windows, const float* x0, const uint8_t* keep, const float* noise, const float* alpha, int n,
+                            int W, int H, float noise_scale, uint64_t seed, uint64_t clip, uint32_t index, hipStream_t st) {
+  const bool aligned = keep_aligned(x, windows, x0, keep, noise);
+  const int quads = ((n - 1) * H + W) / 4;
+  hipLaunchKernelGGL(keep_region_windows_kernel, dim3((quads + 255) / 256), dim3(256), 0, st, x, windows, x0, keep, noise, alpha, n, W, H,
+                     aligned, noise_scale, seed, clip, index);
   VQVS_HIP(hipGetLastError());
   return 0;
 }

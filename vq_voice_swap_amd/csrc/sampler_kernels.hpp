@@ -19,6 +19,12 @@ int run_ddim_step(const float* x_t, const float* eps, const float* grad, const f
 int run_ddim_step_windows(const float* x, const float* eps, const float* grad, const float* noise, const float* a_t, const float* a_to,
                           float* x_to, float* windows, double* scratch, int n, int W, int H, uint32_t flags, float eta, float noise_scale,
                           uint64_t seed, uint64_t clip, uint32_t step_index, hipStream_t st);
+// kept samples of x (NULL keep: all) put back on the forward process of x0 at alpha, in place: B rows of T, and one long state with
+// its window copies
+int run_keep_region(float* x, const float* x0, const uint8_t* keep, const float* noise, const float* alpha, int B, int T, float noise_scale,
+                    uint64_t seed, uint64_t clip_offset, uint32_t index, hipStream_t st);
+int run_keep_region_windows(float* x, float* windows, const float* x0, const uint8_t* keep, const float* noise, const float* alpha, int n,
+                            int W, int H, float noise_scale, uint64_t seed, uint64_t clip, uint32_t index, hipStream_t st);
 int run_ddpm_mean(const float* x_t, const float* eps, const float* a_t, const float* a_prev, float* out, int B, int T, hipStream_t st);
 int run_ddpm_guided_eps(const float* x_t, const float* mean, const float* grad, const float* a_t, const float* a_prev, float* out,
                         int B, int T, uint32_t flags, hipStream_t st);

@@ -16,6 +16,7 @@ Additions over the reference (it has no seeding):
 from __future__ import annotations
 
 import math
+import operator
 from typing import Callable, List, Optional, Sequence, Union
 
 import torch
@@ -137,6 +138,44 @@ def warn_few_unguided_steps(what: str, steps: int, predictor, cond_fn) -> None:
 
         warnings.warn(f"{what}: {steps} steps (fewer than {FEW_GUIDED_STEPS}) in the {modes} mode(s): the 1e-3 waveform contract is not "
                       "established for so few steps; the mode is kept", RuntimeWarning, stacklevel=3)
+
+
+def strength_to_start_step(strength: float, steps: int) -> int:
+    """The first step of a partial-noise start: a conversion of `strength` in (0, 1] runs the last ceil(strength * steps) of the
+    `steps` steps, from the source noised to that step's alpha_bar.  1 is the whole run, from x_T."""
+    strength, steps = float(strength), int(steps)
+    if not 0.0 < strength <= 1.0:
+        raise ValueError(f"strength={strength!r} must lie in (0, 1]")
+    if steps < 1:
+        raise ValueError(f"steps={steps} must be at least 1")
+    return min(max(steps - math.ceil(strength * steps), 0), steps - 1)
+
+
+def check_keep_args(state: torch.Tensor, source: Optional[torch.Tensor], keep: Optional[torch.Tensor], start_step: int, steps: int):
+    """The `source=` / `keep=` / `start_step=` keywords of the four sampling loops, checked before anything touches the device:
+    (source, mask) as contiguous float32 / uint8 tensors, or (None, None) when the loop runs as it always has.  `keep` is a bool or
+    uint8 tensor shaped like the state (nonzero: kept); without one no sample is kept and `source` only serves a `start_step` > 0."""
+    try:
+        start_step = operator.index(start_step)
+    except TypeError:
+        raise ValueError(f"start_step={start_step!r} must be an integer") from None
+    if not 0 <= start_step < max(int(steps), 1):
+        raise ValueError(f"start_step={start_step} outside 0..{int(steps) - 1} (steps={steps})")
+    if source is None:
+        if keep is not None:
+            raise ValueError("keep= needs source=: the kept samples are taken from it")
+        if start_step:
+            raise ValueError("start_step > 0 needs source=: the run starts from the noised source")
+        return None, None
+    if tuple(source.shape) != tuple(state.shape):
+        raise ValueError(f"source of shape {tuple(source.shape)} does not match the state's {tuple(state.shape)}")
+    if keep is not None:
+        if keep.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"keep must be a bool or uint8 tensor, got {keep.dtype}")
+        if tuple(keep.shape) != tuple(state.shape):
+            raise ValueError(f"keep of shape {tuple(keep.shape)} does not match the state's {tuple(state.shape)}")
+        keep = keep.detach().to(torch.uint8).contiguous()
+    return source.detach().to(torch.float32).contiguous(), keep
 
 
 class Diffusion:
@@ -351,6 +390,54 @@ class Diffusion:
                 raise _native.NativeError(f"{what}: the sample holds non-finite values (a non-finite x_T, conditioning tensor or "
                                           "guidance gradient, or an overflow the range guard reported as a warning)")
 
+    # ---- keep region (the replacement method; not in the reference): DESIGN.md section 3.11 -------------
+    def keep_region(self, x: torch.Tensor, source: torch.Tensor, alpha, keep: Optional[torch.Tensor] = None, *,
+                    noise: Optional[torch.Tensor] = None, noise_scale: float = 1.0, seed: int, clip_offset: int = 0,
+                    index: int) -> torch.Tensor:
+        """A copy of the state `x` [N, ..., T] whose kept samples (`keep` nonzero, bool or uint8 shaped like x; None: every sample)
+        lie on the forward process of `source` at alpha_bar = `alpha` ([N] or one value): sqrt(alpha) source + sqrt(1 - alpha) z
+        (`vqvs_keep_region`).  `noise=None` draws z from the generator's stream 3 keyed by (seed, clip_offset + row, index); a sampler
+        passes the number of the step that will consume the state as `index`.  At alpha = 1 the kept samples are the source."""
+        if x.dim() < 2:
+            raise ValueError("x must be [N, ..., T]")
+        source, keep = check_keep_args(x, source, keep, 0, 1)
+        _native.require_cuda(x, source, keep, noise)
+        if noise is not None:
+            if tuple(noise.shape) != tuple(x.shape):
+                raise ValueError(f"noise of shape {tuple(noise.shape)} does not match the state's {tuple(x.shape)}")
+            noise = noise.detach().to(torch.float32).contiguous()
+        if not torch.is_tensor(alpha):
+            alpha = torch.full((x.shape[0],), float(alpha), dtype=torch.float32)
+        alpha = alpha.detach().to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
+        if alpha.numel() == 1:
+            alpha = alpha.expand(x.shape[0]).contiguous()
+        if alpha.shape != (x.shape[0],):
+            raise ValueError(f"alpha must hold one value or one per row ({x.shape[0]}), got {alpha.numel()}")
+        out = x.detach().to(torch.float32).contiguous().clone()
+        self._keep_(out, source, keep, alpha, noise=noise, noise_scale=noise_scale, seed=seed, clip_offset=clip_offset, index=index)
+        return out.view_as(x)
+
+    @staticmethod
+    def _keep_(x, source, keep, alpha, *, noise=None, noise_scale=1.0, seed, clip_offset, index) -> None:
+        """`vqvs_keep_region` IN PLACE on a contiguous float32 state the caller owns; alpha is a [B] device tensor."""
+        B, T = x.shape[0], x[0].numel()
+        with torch.cuda.device(x.device):
+            _native.check(_native.lib().vqvs_keep_region(x.data_ptr(), source.data_ptr(), _native._ptr(keep), _native._ptr(noise),
+                                                         alpha.data_ptr(), B, T, float(noise_scale), int(seed), int(clip_offset), int(index),
+                                                         _native._stream_ptr()))
+
+    def _keep_start(self, x_T, source, keep, alpha, *, start_step, seed, clip_offset) -> torch.Tensor:
+        """The state a run with `source` starts from: the source noised to the first step's alpha_bar (start_step > 0; x_T is not
+        used), or x_T with its kept samples replaced."""
+        if start_step > 0:
+            x, keep = torch.empty_like(source), None
+        elif keep is None:
+            return x_T
+        else:
+            x = x_T.detach().to(torch.float32).contiguous().clone()
+        self._keep_(x, source, keep, alpha, seed=seed, clip_offset=clip_offset, index=start_step)
+        return x.view_as(x_T)
+
     def ddpm_sample_windows(self, x_T_long: torch.Tensor, predictor: Callable, steps: int, **kwargs) -> torch.Tensor:
         """`ddpm_sample` for one long state [1,1,Np] predicted through overlapping windows (longform.ddpm_sample_windows)."""
         from .longform import ddpm_sample_windows
@@ -371,25 +458,38 @@ class Diffusion:
         noise: NoiseSource = None,
         seed: Optional[int] = None,
         clip_offset: int = 0,
+        source: Optional[torch.Tensor] = None,
+        keep: Optional[torch.Tensor] = None,
+        start_step: int = 0,
     ) -> torch.Tensor:
         """Reverse diffusion from x_T (reference diffusion.py:92-133): t runs steps/steps ... 1/steps,
-        optional sample-time remap `schedule`, zero noise on the last iteration."""
-        _native.require_cuda(x_T)
+        optional sample-time remap `schedule`, zero noise on the last iteration.
+
+        `source` (shaped like x_T) with `keep` (bool / uint8, shaped like x_T) keeps the masked samples of the source: before the
+        first step and after every step they are put back on the source's forward process at the alpha_bar the state has just
+        reached (`keep_region`, indexed by the step that consumes the state), so the result holds the source there, bit for bit.
+        `start_step` > 0 runs steps start_step .. steps - 1 of the same tables from the source noised to a_t[start_step], instead
+        of from x_T.  Step numbers, and with them the step noise, are unchanged."""
+        source, keep = check_keep_args(x_T, source, keep, start_step, steps)
+        _native.require_cuda(x_T, source, keep)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         stack = few_guided_steps_promotion("ddpm_sample", steps, predictor, cond_fn)
         if stack is not None:
             with stack:
                 return self.ddpm_sample(x_T, predictor, steps, progress=progress, sigma_large=sigma_large, constrain=constrain,
-                                        cond_fn=cond_fn, schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset)
+                                        cond_fn=cond_fn, schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset,
+                                        source=source, keep=keep, start_step=start_step)
         x_t = x_T
         B = x_T.shape[0]
         ts_all, a_t_all, a_prev_all, ts_prev_all = self.step_tables(steps, B, schedule, x_T.device)
-        its = range(steps)
+        if source is not None:
+            x_t = self._keep_start(x_T, source, keep, a_t_all[start_step], start_step=start_step, seed=seed, clip_offset=clip_offset)
+        its = range(start_step, steps)
         if progress:
             from tqdm.auto import tqdm
 
-            its = tqdm(its, total=steps)
+            its = tqdm(its, total=steps - start_step)
         for i in its:
             with torch.no_grad():
                 eps = predictor(x_t, ts_all[i])
@@ -404,6 +504,8 @@ class Diffusion:
                 x_t = self._step(x_t, eps, a_t_all[i], a_prev_all[i], ts_prev_all[i], noise=nz, sigma_large=sigma_large,
                                  constrain=constrain, cond_fn=cond_fn, seed=seed, clip_offset=clip_offset, step_index=i,
                                  noise_scale=0.0 if last else 1.0)
+                if keep is not None:  # (the step's output is a fresh float32 tensor of this loop's)
+                    self._keep_(x_t, source, keep, a_prev_all[i], seed=seed, clip_offset=clip_offset, index=i + 1)
         self.check_sample(predictor, x_t, "ddpm_sample")
         return x_t
 
@@ -476,26 +578,34 @@ class Diffusion:
         noise: NoiseSource = None,
         seed: Optional[int] = None,
         clip_offset: int = 0,
+        source: Optional[torch.Tensor] = None,
+        keep: Optional[torch.Tensor] = None,
+        start_step: int = 0,
     ) -> torch.Tensor:
         """`ddpm_sample` with the DDIM step: the same tables of t and alpha_bar(t) (`step_tables`), the same step numbering and noise
         words, zero noise on the last iteration -- which, stepping to alpha_bar(0) = 1, returns x0 itself.  At eta = 0 the result
-        depends on x_T alone."""
-        _native.require_cuda(x_T)
+        depends on x_T alone -- and, with `source` / `keep` / `start_step` (as in `ddpm_sample`; the kept samples are replaced at the
+        alpha_bar stepped TO), on the seed of the replacement noise."""
+        source, keep = check_keep_args(x_T, source, keep, start_step, steps)
+        _native.require_cuda(x_T, source, keep)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         stack = few_guided_steps_promotion("ddim_sample", steps, predictor, cond_fn)
         if stack is not None:
             with stack:
                 return self.ddim_sample(x_T, predictor, steps, eta=eta, progress=progress, constrain=constrain, cond_fn=cond_fn,
-                                        schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset)
+                                        schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset, source=source, keep=keep,
+                                        start_step=start_step)
         warn_few_unguided_steps("ddim_sample", steps, predictor, cond_fn)
         x_t = x_T
         ts_all, a_t_all, a_to_all, _ = self.step_tables(steps, x_T.shape[0], schedule, x_T.device)
-        its = range(steps)
+        if source is not None:
+            x_t = self._keep_start(x_T, source, keep, a_t_all[start_step], start_step=start_step, seed=seed, clip_offset=clip_offset)
+        its = range(start_step, steps)
         if progress:
             from tqdm.auto import tqdm
 
-            its = tqdm(its, total=steps)
+            its = tqdm(its, total=steps - start_step)
         for i in its:
             with torch.no_grad():
                 eps = predictor(x_t, ts_all[i])
@@ -509,6 +619,8 @@ class Diffusion:
                 _native.require_cuda(eps, nz)
                 x_t = self._ddim_step(x_t, eps, a_t_all[i], a_to_all[i], ts_all[i], noise=nz, eta=eta, constrain=constrain, cond_fn=cond_fn,
                                       seed=seed, clip_offset=clip_offset, step_index=i, noise_scale=0.0 if last else 1.0)
+                if keep is not None:
+                    self._keep_(x_t, source, keep, a_to_all[i], seed=seed, clip_offset=clip_offset, index=i + 1)
         self.check_sample(predictor, x_t, "ddim_sample")
         return x_t
 

@@ -46,10 +46,48 @@ def gather_windows(x: torch.Tensor, window: int, hop: int) -> torch.Tensor:
     return x.reshape(-1).unfold(0, window, hop).unsqueeze(1).contiguous()
 
 
+def keep_windows_(x: torch.Tensor, windows: Optional[torch.Tensor], source: torch.Tensor, keep: Optional[torch.Tensor], alpha: torch.Tensor, *,
+                  n: int, window: int, hop: int, seed: int, clip_offset: int, index: int) -> None:
+    """`vqvs_keep_region_windows` IN PLACE on the long state x [Np] and (unless None) on the window batch [n,1,window] gathered from
+    it: the kept samples (keep None: all) are put back on the source's forward process at alpha[0]."""
+    _native.check(_native.lib().vqvs_keep_region_windows(x.data_ptr(), _native._ptr(windows), source.data_ptr(), _native._ptr(keep), None,
+                                                         alpha.data_ptr(), n, window, hop, 1.0, int(seed), int(clip_offset), int(index),
+                                                         _native._stream_ptr()))
+
+
+def start_windows(x_T_long: torch.Tensor, source, keep, alpha, *, start_step: int, n: int, window: int, hop: int, seed: int, clip_offset: int):
+    """(long state, window batch) a windowed run starts from: x_T as it is, x_T with the kept samples replaced, or -- `start_step` > 0
+    -- the source noised to that step's alpha_bar (Diffusion._keep_start, on the long state)."""
+    x = x_T_long.detach().to(torch.float32).contiguous()
+    if source is not None and (start_step > 0 or keep is not None):
+        x = torch.empty_like(x) if start_step > 0 else x.clone()
+        with torch.cuda.device(x.device):
+            keep_windows_(x, None, source, None if start_step > 0 else keep, alpha, n=n, window=window, hop=hop, seed=seed,
+                          clip_offset=clip_offset, index=start_step)
+    return x, gather_windows(x, window, hop)
+
+
+def pad_source_keep(source: Optional[torch.Tensor], keep: Optional[torch.Tensor], num_samples: int, padded_len: int):
+    """`decode_long`'s `source` / `keep` [1,1,num_samples] at the length of the long state: the source zero-padded as `encode_long`
+    pads the encoder's input, the mask padded with zeros (the padding is cut off the result and never kept)."""
+    for name, t in (("source", source), ("keep", keep)):
+        if t is not None and tuple(t.shape) != (1, 1, num_samples):
+            raise ValueError(f"{name} must be [1, 1, {num_samples}], got {tuple(t.shape)}")
+    pad = (0, padded_len - num_samples)
+    if source is not None:
+        source = torch.nn.functional.pad(source, pad)
+    if keep is not None:
+        if keep.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"keep must be a bool or uint8 tensor, got {keep.dtype}")
+        keep = torch.nn.functional.pad(keep.to(torch.uint8), pad)
+    return source, keep
+
+
 def ddpm_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, steps: int, *, window: int, hop: int,
                         window_batch: int = 64, constrain: bool = False, sigma_large: bool = False, cond_fn: Optional[Callable] = None,
                         schedule: Optional[Callable] = None, noise=None, seed: Optional[int] = None, clip_offset: int = 0,
-                        progress: bool = False) -> torch.Tensor:
+                        progress: bool = False, source: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
+                        start_step: int = 0) -> torch.Tensor:
     """`Diffusion.ddpm_sample` for one long state x_T_long [1,1,Np], Np = (n - 1) * hop + window (`plan_windows`): the same
     host-side tables of t and alpha_bar(t), the same step numbering, zero noise on the last step.
 
@@ -57,10 +95,13 @@ def ddpm_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, 
     index of the slice's first window, for a callee that slices its conditioning.  `cond_fn(mean [m,1,window], ts_prev [m],
     first=b0)` guides each slice through `vqvs_ddpm_mean` / `vqvs_ddpm_guided_eps`, as in the single-clip step, before the
     windows' predictions meet in `vqvs_ddpm_step_windows`.  `noise` is a list or callable giving [1,1,Np] per step; None draws in the
-    kernel from (seed, clip_offset, step): the draws of row `clip_offset` of a batch of clips of length Np."""
-    from .diffusion import few_guided_steps_promotion
+    kernel from (seed, clip_offset, step): the draws of row `clip_offset` of a batch of clips of length Np.
+    `source`, `keep` ([1,1,Np]) and `start_step` are `ddpm_sample`'s, applied by `vqvs_keep_region_windows` to the long state and to
+    both window copies of an overlap sample."""
+    from .diffusion import check_keep_args, few_guided_steps_promotion
 
-    _native.require_cuda(x_T_long)
+    source, keep = check_keep_args(x_T_long, source, keep, start_step, steps)
+    _native.require_cuda(x_T_long, source, keep)
     if x_T_long.dim() != 3 or x_T_long.shape[0] != 1 or x_T_long.shape[1] != 1:
         raise ValueError(f"x_T_long must be [1, 1, Np], got {tuple(x_T_long.shape)}")
     Np = x_T_long.shape[2]
@@ -76,20 +117,21 @@ def ddpm_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, 
         with stack:
             return ddpm_sample_windows(diffusion, x_T_long, predictor, steps, window=window, hop=hop, window_batch=window_batch,
                                        constrain=constrain, sigma_large=sigma_large, cond_fn=cond_fn, schedule=schedule, noise=noise,
-                                       seed=seed, clip_offset=clip_offset, progress=progress)
+                                       seed=seed, clip_offset=clip_offset, progress=progress, source=source, keep=keep,
+                                       start_step=start_step)
     dev = x_T_long.device
     mb = min(n, int(window_batch))
     ts_all, a_t_all, a_prev_all, ts_prev_all = diffusion.step_tables(steps, mb, schedule, dev)
     flags = (_native.DDPM_SIGMA_LARGE if sigma_large else 0) | (_native.DDPM_CONSTRAIN if constrain else 0)
     L = _native.lib()
-    x = x_T_long.detach().to(torch.float32).contiguous()
-    windows = gather_windows(x, window, hop)
+    x, windows = start_windows(x_T_long, source, keep, a_t_all[start_step], start_step=start_step, n=n, window=window, hop=hop, seed=seed,
+                               clip_offset=clip_offset)
     eps = torch.empty_like(windows)
-    its = range(steps)
+    its = range(start_step, steps)
     if progress:
         from tqdm.auto import tqdm
 
-        its = tqdm(its, total=steps)
+        its = tqdm(its, total=steps - start_step)
     with torch.no_grad(), torch.cuda.device(dev):
         for i in its:
             st = _native._stream_ptr()
@@ -122,6 +164,9 @@ def ddpm_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, 
             _native.check(L.vqvs_ddpm_step_windows(x.data_ptr(), eps.data_ptr(), _native._ptr(nz), a_t_all[i].data_ptr(), a_prev_all[i].data_ptr(),
                                                    x_prev.data_ptr(), next_windows.data_ptr(), n, window, hop, flags, 0.0 if last else 1.0,
                                                    int(seed), int(clip_offset), i, st))
+            if keep is not None:
+                keep_windows_(x_prev, next_windows, source, keep, a_prev_all[i], n=n, window=window, hop=hop, seed=seed,
+                              clip_offset=clip_offset, index=i + 1)
             x, windows = x_prev, next_windows
     diffusion.check_sample(predictor, x, "ddpm_sample_windows")
     return x.view_as(x_T_long)
@@ -130,14 +175,17 @@ def ddpm_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, 
 def ddim_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, steps: int, *, window: int, hop: int,
                         window_batch: int = 64, eta: float = 0.0, constrain: bool = False, cond_fn: Optional[Callable] = None,
                         schedule: Optional[Callable] = None, noise=None, seed: Optional[int] = None, clip_offset: int = 0,
-                        progress: bool = False) -> torch.Tensor:
+                        progress: bool = False, source: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
+                        start_step: int = 0) -> torch.Tensor:
     """`Diffusion.ddim_sample` for one long state x_T_long [1,1,Np]: `ddpm_sample_windows` with `vqvs_ddim_step_windows` as the step.
     `predictor` and `noise` are as there.  `cond_fn(x [m,1,window], ts [m], first=b0)` is evaluated on each slice of windows AT the
     windows the predictor saw and at their t; its gradients fill a [n, window] batch that the step kernel applies per window, before
-    the windows' predictions are blended -- one kernel after the forwards, no half-steps."""
-    from .diffusion import few_guided_steps_promotion, warn_few_unguided_steps
+    the windows' predictions are blended -- one kernel after the forwards, no half-steps.  `source`, `keep` and `start_step` are as
+    there, the kept samples replaced at the alpha_bar stepped TO."""
+    from .diffusion import check_keep_args, few_guided_steps_promotion, warn_few_unguided_steps
 
-    _native.require_cuda(x_T_long)
+    source, keep = check_keep_args(x_T_long, source, keep, start_step, steps)
+    _native.require_cuda(x_T_long, source, keep)
     if x_T_long.dim() != 3 or x_T_long.shape[0] != 1 or x_T_long.shape[1] != 1:
         raise ValueError(f"x_T_long must be [1, 1, Np], got {tuple(x_T_long.shape)}")
     Np = x_T_long.shape[2]
@@ -153,22 +201,22 @@ def ddim_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, 
         with stack:
             return ddim_sample_windows(diffusion, x_T_long, predictor, steps, window=window, hop=hop, window_batch=window_batch, eta=eta,
                                        constrain=constrain, cond_fn=cond_fn, schedule=schedule, noise=noise, seed=seed,
-                                       clip_offset=clip_offset, progress=progress)
+                                       clip_offset=clip_offset, progress=progress, source=source, keep=keep, start_step=start_step)
     warn_few_unguided_steps("ddim_sample_windows", steps, predictor, cond_fn)
     dev = x_T_long.device
     mb = min(n, int(window_batch))
     ts_all, a_t_all, a_to_all, _ = diffusion.step_tables(steps, mb, schedule, dev)
     flags = _native.DDIM_CONSTRAIN if constrain else 0
     L = _native.lib()
-    x = x_T_long.detach().to(torch.float32).contiguous()
-    windows = gather_windows(x, window, hop)
+    x, windows = start_windows(x_T_long, source, keep, a_t_all[start_step], start_step=start_step, n=n, window=window, hop=hop, seed=seed,
+                               clip_offset=clip_offset)
     eps = torch.empty_like(windows)
     grad = torch.empty_like(windows) if cond_fn is not None else None
-    its = range(steps)
+    its = range(start_step, steps)
     if progress:
         from tqdm.auto import tqdm
 
-        its = tqdm(its, total=steps)
+        its = tqdm(its, total=steps - start_step)
     with torch.no_grad(), torch.cuda.device(dev):
         for i in its:
             st = _native._stream_ptr()
@@ -198,6 +246,9 @@ def ddim_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, 
             _native.check(L.vqvs_ddim_step_windows(x.data_ptr(), eps.data_ptr(), _native._ptr(grad), _native._ptr(nz), a_t_all[i].data_ptr(),
                                                    a_to_all[i].data_ptr(), x_to.data_ptr(), next_windows.data_ptr(), n, window, hop, flags,
                                                    float(eta), 0.0 if last else 1.0, int(seed), int(clip_offset), i, st))
+            if keep is not None:
+                keep_windows_(x_to, next_windows, source, keep, a_to_all[i], n=n, window=window, hop=hop, seed=seed,
+                              clip_offset=clip_offset, index=i + 1)
             x, windows = x_to, next_windows
     diffusion.check_sample(predictor, x, "ddim_sample_windows")
     return x.view_as(x_T_long)
@@ -225,12 +276,19 @@ def check_rate(model, window: int, hop: int) -> None:
 def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, *, num_samples: int, window: int, hop: int,
                 steps: int = 100, progress: bool = False, constrain: bool = False, enc_pred=None, enc_pred_scale: float = 1.0,
                 seed: Optional[int] = None, clip_offset: int = 0, window_batch: int = 64, sampler: str = "ddpm", eta: float = 0.0,
+                source: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None, strength: float = 1.0,
                 **kwargs) -> torch.Tensor:
     """Window codes [n,T1] int or [n,C,T1] float (`encode_long`) -> [1,1,num_samples] waveform: `VQVAE.decode` on one long state.
     x_T is ONE row of (n - 1) * hop + window samples keyed by `clip_offset`; `labels` is one label for every window, or [n].
     With one window the result is `decode`'s, bit for bit, at the same seed and clip_offset.  `sampler` "ddim" runs
-    `ddim_sample_windows` with `eta` instead of `ddpm_sample_windows`."""
-    from .diffusion import check_sampler, randn_clips
+    `ddim_sample_windows` with `eta` instead of `ddpm_sample_windows`.  `source` [1,1,num_samples] (the recording itself), `keep`
+    (bool / uint8, [1,1,num_samples]: samples that stay the source's) and `strength` in (0, 1] (below 1: start from the noised
+    source, `strength_to_start_step`) are `VQVAE.decode`'s."""
+    from .diffusion import check_sampler, randn_clips, strength_to_start_step
+
+    start_step = strength_to_start_step(strength, steps)
+    if source is None and (keep is not None or start_step):
+        raise ValueError("keep= and strength < 1 need source=, the waveform whose samples are kept or noised")
 
     if codes.dim() == 2:
         cond_seq = model.vq.embed(codes)
@@ -266,6 +324,9 @@ def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = Non
         sl = slice(first, first + xs.shape[0])
         return model.predictor(xs, ts, cond=cond_seq[sl], labels=None if labels is None else labels[sl])
 
+    if source is not None:
+        source, keep = pad_source_keep(source, keep, num_samples, padded)
+        kwargs.update(source=source, keep=keep, start_step=start_step)
     x_T = randn_clips(1, padded, codes.device, seed, clip_offset)
     if check_sampler(sampler, eta) == "ddim":
         out = ddim_sample_windows(model.diffusion, x_T, predictor, steps, window=window, hop=hop, window_batch=window_batch, eta=eta,

@@ -10,7 +10,7 @@ from typing import Any, Dict, Optional
 
 import torch
 
-from .diffusion import check_sampler, randn_clips
+from .diffusion import check_sampler, randn_clips, strength_to_start_step
 from .diffusion_model import DiffusionModel
 from .conv_encoder import ConvMFCCEncoder
 from .unet import UNetEncoder
@@ -91,9 +91,18 @@ class VQVAE(DiffusionModel):
 
     def decode(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, steps: int = 100, progress: bool = False,
                constrain: bool = False, enc_pred=None, enc_pred_scale: float = 1.0, x_T: Optional[torch.Tensor] = None,
-               sampler: str = "ddpm", eta: float = 0.0, **kwargs) -> torch.Tensor:
+               sampler: str = "ddpm", eta: float = 0.0, source: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
+               strength: float = 1.0, **kwargs) -> torch.Tensor:
         """codes [N,T1] int or [N,C,T1] float -> [N,1,T1*256] waveform (vq_vae.py:92-145).  `sampler` "ddim" runs
-        `Diffusion.ddim_sample` with `eta` (0: the result depends on x_T alone) instead of `ddpm_sample`."""
+        `Diffusion.ddim_sample` with `eta` (0: the result depends on x_T alone) instead of `ddpm_sample`.
+        `source` [N,1,T] is the waveform being converted: the samples `keep` marks (bool / uint8, [N,1,T]) stay the source's, bit for
+        bit, and are shown to the predictor at every noise level; `strength` in (0, 1] below 1 starts from the source noised to step
+        `strength_to_start_step(strength, steps)` instead of from x_T."""
+        start_step = strength_to_start_step(strength, steps)
+        if source is None and (keep is not None or start_step):
+            raise ValueError("keep= and strength < 1 need source=, the waveform whose samples are kept or noised")
+        if source is not None:
+            kwargs.update(source=source, keep=keep, start_step=start_step)
         if codes.dim() == 2:
             cond_seq = self.vq.embed(codes)
         elif codes.dim() == 3:
@@ -150,7 +159,7 @@ class VQVAE(DiffusionModel):
     def decode_long(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
         """Window codes [n,T1] or [n,C,T1] -> [1,1,num_samples] waveform: `decode` on one long state whose windows are blended at
         every step (longform.decode_long; keywords num_samples, window, hop, steps, constrain, enc_pred, seed, window_batch, sampler,
-        eta ...)."""
+        eta, source, keep, strength ...)."""
         from .longform import decode_long
 
         return decode_long(self, codes, labels, **kwargs)
