@@ -347,7 +347,11 @@ int vqvs_ddpm_sqerr(const float* d_pred, const float* d_eps, int eps_rows, const
 
 /* ---- vector quantisation -------------------------------------------------------
  * idx = argmin_k ((-2 z.e_k) + |e_k|^2) + |z|^2, first index on ties
- * reference vq.py:112-143, 199-243.   d_z [B,Cd,T1] f32 NCT, d_dict [K,Cd] f32 -> d_idx [B,T1] int64 */
+ * reference vq.py:112-143, 199-243.   d_z [B,Cd,T1] f32 NCT, d_dict [K,Cd] f32 -> d_idx [B,T1] int64
+ * B in 1..65535 (a grid dimension), Cd a positive multiple of 4, T1 and K positive: anything else, or a NULL pointer, returns
+ * VQVS_ERR_ARG with a message before the device is touched.  A position of z that holds a NaN gets code 0 (no distance
+ * compares below the running best), which is what torch.argmin returns for an all-NaN row.  tests/vq_ref.py states the bound
+ * the fp32 distance is held to against a float64 nearest-code reference. */
 int vqvs_vq_argmin(const float* d_z, const float* d_dict, int64_t* d_idx, int B, int Cd, int T1, int K, void* stream);
 /* Quantise and score in one pass (handle-less): what VQ.forward and StandardVQLoss need of z (reference vq.py:45-51, 112-143),
  * plus the code counts of an evaluation pass.
@@ -366,7 +370,10 @@ int vqvs_vq_argmin(const float* d_z, const float* d_dict, int64_t* d_idx, int B,
  * `stream`; NULL d_z / d_dict / d_idx or non-positive sizes return VQVS_ERR_ARG before the device is touched. */
 int vqvs_vq_quantize(const float* d_z, const float* d_dict, int64_t* d_idx, float* d_embedded, double* d_sqerr, int64_t* d_hist,
                      int B, int Cd, int T1, int K, void* stream);
-/* out[b,:,t] = dict[idx[b,t],:]   reference vq.py:98-110 */
+/* out[b,:,t] = dict[idx[b,t],:]   reference vq.py:98-110
+ *   d_idx [B,T1] int64 (values outside 0..K-1 are clamped into it), d_dict [K,Cd] f32 -> d_out [B,Cd,T1] f32 NCT, an exact copy.
+ * B and Cd in 1..65535 (grid dimensions z and y; any Cd, not only multiples of 4), T1 and K positive: a NULL pointer, a
+ * non-positive size, or B or Cd above 65535 returns VQVS_ERR_ARG with a message before anything is launched. */
 int vqvs_vq_embed(const int64_t* d_idx, const float* d_dict, float* d_out, int B, int Cd, int T1, int K, void* stream);
 
 /* ---- guidance-model scores (handle-less) -------------------------------------------------

@@ -515,7 +515,8 @@ int vqvs_ddpm_sqerr(const float* d_pred, const float* d_eps, int eps_rows, const
 
 int vqvs_vq_argmin(const float* d_z, const float* d_dict, int64_t* d_idx, int B, int Cd, int T1, int K, void* stream) {
   if (!d_z || !d_dict || !d_idx) VQVS_FAIL(VQVS_ERR_ARG, "NULL argument");
-  if (B < 1 || Cd < 1 || T1 < 1 || K < 1) VQVS_FAIL(VQVS_ERR_ARG, "bad shape");
+  if (B < 1 || Cd < 1 || T1 < 1 || K < 1) VQVS_FAIL(VQVS_ERR_ARG, "bad shape B=%d Cd=%d T1=%d K=%d", B, Cd, T1, K);
+  if (B > 65535) VQVS_FAIL(VQVS_ERR_ARG, "batch %d outside 1..65535", B);
   if (Cd % 4) VQVS_FAIL(VQVS_ERR_ARG, "Cd must be a multiple of 4 (got %d)", Cd);
   ScratchLease lease;
   if (int e = scratch_get((size_t)K * 4, stream, lease)) return e;
@@ -548,7 +549,10 @@ int vqvs_xent_score(const float* d_logits, const int64_t* d_targets, double* d_n
 }
 
 int vqvs_vq_embed(const int64_t* d_idx, const float* d_dict, float* d_out, int B, int Cd, int T1, int K, void* stream) {
-  if (!d_idx || !d_dict || !d_out) VQVS_FAIL(VQVS_ERR_ARG, "NULL argument");
+  if (!d_idx || !d_dict || !d_out) VQVS_FAIL(VQVS_ERR_ARG, "idx, dict and out must be non-NULL");
+  if (B < 1 || Cd < 1 || T1 < 1 || K < 1) VQVS_FAIL(VQVS_ERR_ARG, "bad shape B=%d Cd=%d T1=%d K=%d", B, Cd, T1, K);
+  if (B > 65535) VQVS_FAIL(VQVS_ERR_ARG, "batch %d outside 1..65535", B);           // grid dimension z
+  if (Cd > 65535) VQVS_FAIL(VQVS_ERR_ARG, "channels %d outside 1..65535", Cd);      // grid dimension y
   return run_vq_embed(d_idx, d_dict, d_out, B, Cd, T1, K, reinterpret_cast<hipStream_t>(stream));
 }
 
