@@ -315,3 +315,136 @@ def test_few_step_promotion_finds_the_native_modules():
     assert _native_modules(clf.guidance_fn(torch.zeros(1, dtype=torch.long), 2.0)) == [clf]
     assert _native_modules(ep.guidance_fn(torch.zeros(1, 4, dtype=torch.long), 1.0)) == [ep]
     assert _native_modules(lambda x, ts: x) == []
+
+
+def test_the_four_sampling_loops_walk_one_sequence(monkeypatch):
+    """`ddpm_sample`, `ddim_sample` and their window forms on CPU tensors, with the device check and the kernel seams (`_step`,
+    `_ddim_step`, `_keep_`, `longform._*_step_windows`, `longform.keep_windows_`) replaced by recording stubs: every loop walks steps
+    start_step .. steps - 1, shows the predictor row i of the t table, passes no noise on the last step (and none at eta = 0) and
+    noise_scale 0 there alone, re-applies the keep region with index i + 1 at the alpha_bar stepped to, and checks `source` / `keep`
+    once.  A guided run of 3 steps in a 2-byte mode enters the fp32 override once and runs its 3 steps once, inside it."""
+    import contextlib
+    import warnings
+
+    from vq_voice_swap_amd import diffusion as dmod, longform
+    from vq_voice_swap_amd.diffusion import Diffusion, make_schedule
+
+    steps, n, W, H = 5, 3, 8, 4
+    Np = (n - 1) * H + W
+    d = Diffusion(make_schedule("exp"))
+    log = []
+    monkeypatch.delenv("VQVS_FEW_STEP_PROMOTE", raising=False)
+    monkeypatch.setattr(_native, "require_cuda", lambda *tensors: None)
+    monkeypatch.setattr(_native, "_stream_ptr", lambda: 0)
+    monkeypatch.setattr(torch.cuda, "device", lambda device: contextlib.nullcontext())
+    real_check = dmod.check_keep_args
+    monkeypatch.setattr(dmod, "check_keep_args", lambda *a: (log.append(("check",)), real_check(*a))[1])
+
+    def clip_step(x_t, eps, a_t, a_to, ts, **kw):
+        assert torch.equal(eps, 0.5 * x_t)
+        log.append(("step", kw["step_index"], a_t, a_to, kw["noise"], kw["noise_scale"], kw["cond_fn"]))
+        return x_t + 1
+
+    def windows_step(rule, x, eps, grad, nz, a_t, a_to, x_to, next_windows, n_, window, hop, noise_scale, seed, clip_offset, step_index, st):
+        assert (n_, window, hop, seed, clip_offset) == (n, W, H, 7, 3) and torch.equal(eps, 0.5 * longform.gather_windows(x, W, H))
+        log.append(("step", step_index, a_t, a_to, nz, noise_scale, None))
+        x_to.copy_(x + 1)
+        next_windows.copy_(longform.gather_windows(x_to, W, H))
+
+    def guided_fill(rule, xw, e, tables, i, b0, cond_fn, eps, grad, st):
+        eps[b0:b0 + xw.shape[0]].copy_(e)
+        cond_fn(xw, tables[3][i, :xw.shape[0]], first=b0)
+
+    def keep_stub(*args, **kw):
+        assert (kw["seed"], kw["clip_offset"]) == (7, 3)
+        log.append(("keep", kw["index"], args[-1]))
+
+    monkeypatch.setattr(d, "_step", clip_step)
+    monkeypatch.setattr(d, "_ddim_step", clip_step)
+    monkeypatch.setattr(d, "_keep_", keep_stub)
+    monkeypatch.setattr(longform, "_ddpm_step_windows", windows_step)
+    monkeypatch.setattr(longform, "_ddim_step_windows", windows_step)
+    monkeypatch.setattr(longform, "keep_windows_", keep_stub)
+
+    def predictor(x, ts, first=0):
+        log.append(("pred", ts.clone(), first))
+        return 0.5 * x
+
+    clips, long = dict(x=torch.zeros(2, 1, 8), firsts=[0]), dict(x=torch.zeros(1, 1, Np), firsts=[0, 2], window=W, hop=H, window_batch=2)
+    loops = [("ddpm_sample", d.ddpm_sample, clips, {}, True), ("ddim_sample", d.ddim_sample, clips, dict(eta=0.0), False),
+             ("ddim_sample", d.ddim_sample, clips, dict(eta=0.5), True),
+             ("ddpm_sample_windows", lambda *a, **kw: longform.ddpm_sample_windows(d, *a, **kw), long, {}, True),
+             ("ddim_sample_windows", lambda *a, **kw: longform.ddim_sample_windows(d, *a, **kw), long, dict(eta=0.0), False),
+             ("ddim_sample_windows", lambda *a, **kw: longform.ddim_sample_windows(d, *a, **kw), long, dict(eta=0.5), True)]
+    ts_all, a_t_all, a_to_all, _ = d.step_tables(steps, 2, None, torch.device("cpu"))  # two rows: the clips, or the windows of a slice
+    for name, call, group, rule_kw, noisy in loops:
+        x_T = group["x"]
+        layout_kw = {k: v for k, v in group.items() if k not in ("x", "firsts")}
+        noise = [torch.full_like(x_T, float(i)) for i in range(steps)]
+        source, keep = torch.ones_like(x_T), torch.zeros_like(x_T, dtype=torch.bool)
+        keep[..., 3:6] = True
+        for start in (0, 2):
+            del log[:]
+            out = call(x_T, predictor, steps, noise=noise, seed=7, clip_offset=3, source=source, keep=keep, start_step=start,
+                       **layout_kw, **rule_kw)
+            assert out.shape == x_T.shape, name
+            assert log[0] == ("check",) and [e[0] for e in log].count("check") == 1, name
+            assert log[1][:2] == ("keep", start) and torch.equal(log[1][2], a_t_all[start]), name  # the start state, at a_t[start]
+            per_step = len(group["firsts"]) + 2
+            assert len(log) == 2 + per_step * (steps - start), (name, len(log))
+            for k, i in enumerate(range(start, steps)):
+                entries = log[2 + per_step * k:2 + per_step * (k + 1)]
+                preds, step, kept = entries[:-2], entries[-2], entries[-1]
+                for first, p in zip(group["firsts"], preds):
+                    assert p[0] == "pred" and p[2] == first and torch.equal(p[1], ts_all[i, :p[1].numel()]), (name, i)
+                last = i + 1 == steps
+                assert step[:2] == ("step", i) and torch.equal(step[2], a_t_all[i]) and torch.equal(step[3], a_to_all[i]), (name, i)
+                assert step[5] == (0.0 if last else 1.0), (name, i)
+                if last or not noisy:
+                    assert step[4] is None, (name, i)
+                else:
+                    assert torch.equal(step[4].reshape(-1), noise[i].reshape(-1)), (name, i)
+                assert kept[:2] == ("keep", i + 1) and torch.equal(kept[2], a_to_all[i]), (name, i)
+
+    # a guided run of 3 steps in a 2-byte mode: one entry into the fp32 override, the loop run once, inside it
+    class HalfPredictor:
+        precision, entered, inside = "fp16", 0, False
+
+        @contextlib.contextmanager
+        def precision_override(self, mode):
+            assert mode == "fp32"
+            self.entered, self.inside = self.entered + 1, True
+            try:
+                yield
+            finally:
+                self.inside = False
+
+        def check_status(self):
+            log.append(("status", self.inside))
+
+        def __call__(self, x, ts, first=0):
+            assert self.inside
+            return predictor(x, ts, first)
+
+    def cond_fn(x, ts, first=0):
+        log.append(("cond", first))
+        return 0.1 * x
+
+    monkeypatch.setattr(longform, "_ddpm_fill", guided_fill)
+    for name, call, group, rule_kw, _ in loops:
+        half = HalfPredictor()
+        layout_kw = {k: v for k, v in group.items() if k not in ("x", "firsts")}
+        del log[:]
+        with warnings.catch_warnings(record=True) as rec:
+            warnings.simplefilter("always")
+            call(group["x"], half, 3, cond_fn=cond_fn, seed=7, clip_offset=3, **layout_kw, **rule_kw)
+        promoted = [w for w in rec if "run in the fp32" in str(w.message)]
+        assert len(promoted) == 1 and promoted[0].category is RuntimeWarning and name + ":" in str(promoted[0].message), name
+        assert promoted[0].filename == __file__, (name, promoted[0].filename)  # the warning points at the caller of the entry point
+        assert half.entered == 1 and not half.inside, name
+        assert [e[1] for e in log if e[0] == "step"] == [0, 1, 2] and [e[0] for e in log].count("check") == 1, name
+        assert log[-1] == ("status", True), name  # the final guard runs on the promoted handle
+        if group is long:
+            assert [e for e in log if e[0] == "cond"] == [("cond", 0), ("cond", 2)] * 3, name
+        else:
+            assert all(e[6] is cond_fn for e in log if e[0] == "step"), name

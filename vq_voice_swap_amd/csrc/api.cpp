@@ -337,14 +337,32 @@ int vqvs_encpred_guidance(vqvs_model* m, const float* d_x, const float* d_ts, co
   return run_model(m, c);
 }
 
+// the x0-sum partials of a CONSTRAIN step over `rows` clips / windows of `len` samples; nothing is leased without the flag
+static int lease_x0sum(bool constrain, int rows, int len, void* stream, ScratchLease& lease) {
+  return constrain ? scratch_get((size_t)ddpm_scratch_doubles(rows, len) * 8, stream, lease) : 0;
+}
+// [a, a + na) against [b, b + nb) in bytes (NULL: absent)
+static bool bytes_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
+  const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
+  return pa && pb && pa < pb + nb && pb < pa + na;
+}
+// The window geometry of the three ..._windows entry points: n windows of W samples, one every H, span *Np = (n - 1) * H + W.
+static int check_window_geometry(int n, int W, int H, int64_t* Np) {
+  if (n < 1 || n > 65535) VQVS_FAIL(VQVS_ERR_ARG, "window count n=%d outside 1..65535", n);
+  if (W < 4 || H < 4 || W % 4 || H % 4) VQVS_FAIL(VQVS_ERR_ARG, "window W=%d and hop H=%d must be positive multiples of 4", W, H);
+  if (W < H || W - H > H) VQVS_FAIL(VQVS_ERR_ARG, "overlap %d (window W=%d - hop H=%d) outside 0..hop: at most two windows may cover a sample", W - H, W, H);
+  *Np = (int64_t)(n - 1) * H + W;
+  if (*Np >= ((int64_t)1 << 31)) VQVS_FAIL(VQVS_ERR_ARG, "n=%d windows every H=%d samples span %lld samples: 2^31 or more", n, H, (long long)*Np);
+  return 0;
+}
+
 int vqvs_ddpm_step(const float* d_x_t, const float* d_eps, const float* d_noise, const float* d_alpha_t, const float* d_alpha_prev,
                    float* d_x_prev, int B, int T, uint32_t flags, float noise_scale, uint64_t seed, uint64_t clip_offset,
                    uint32_t step_index, void* stream) {
   if (!d_x_t || !d_eps || !d_alpha_t || !d_alpha_prev || !d_x_prev) VQVS_FAIL(VQVS_ERR_ARG, "NULL argument");
   if (B < 1 || T < 1) VQVS_FAIL(VQVS_ERR_ARG, "bad shape B=%d T=%d", B, T);
   ScratchLease lease;
-  if (flags & VQVS_DDPM_CONSTRAIN)
-    if (int e = scratch_get((size_t)ddpm_scratch_doubles(B, T) * 8, stream, lease)) return e;
+  if (int e = lease_x0sum(flags & VQVS_DDPM_CONSTRAIN, B, T, stream, lease)) return e;
   return run_ddpm_step(d_x_t, d_eps, d_noise, d_alpha_t, d_alpha_prev, d_x_prev, reinterpret_cast<double*>(lease.p), B, T, flags,
                        noise_scale, seed, clip_offset, step_index, reinterpret_cast<hipStream_t>(stream));
 }
@@ -353,15 +371,11 @@ int vqvs_ddpm_step_windows(const float* d_x, const float* d_eps, const float* d_
                            float* d_x_prev, float* d_windows, int n, int W, int H, uint32_t flags, float noise_scale, uint64_t seed,
                            uint64_t clip, uint32_t step_index, void* stream) {
   if (!d_x || !d_eps || !d_alpha_t || !d_alpha_prev || !d_x_prev) VQVS_FAIL(VQVS_ERR_ARG, "x, eps, alpha_t, alpha_prev and x_prev must be non-NULL");
-  if (n < 1 || n > 65535) VQVS_FAIL(VQVS_ERR_ARG, "window count %d outside 1..65535", n);
-  if (W < 4 || H < 4 || W % 4 || H % 4) VQVS_FAIL(VQVS_ERR_ARG, "window %d and hop %d must be positive multiples of 4", W, H);
-  if (W < H || W - H > H) VQVS_FAIL(VQVS_ERR_ARG, "overlap %d (window %d - hop %d) outside 0..hop: at most two windows may cover a sample", W - H, W, H);
-  const int64_t Np = (int64_t)(n - 1) * H + W;
-  if (Np >= ((int64_t)1 << 31)) VQVS_FAIL(VQVS_ERR_ARG, "%d windows every %d samples span %lld samples: 2^31 or more", n, H, (long long)Np);
-  if (d_x_prev < d_x + Np && d_x < d_x_prev + Np) VQVS_FAIL(VQVS_ERR_ARG, "x_prev must not overlap x");
+  int64_t Np;
+  if (int e = check_window_geometry(n, W, H, &Np)) return e;
+  if (bytes_overlap(d_x_prev, Np * 4, d_x, Np * 4)) VQVS_FAIL(VQVS_ERR_ARG, "x_prev must not overlap x");
   ScratchLease lease;
-  if (flags & VQVS_DDPM_CONSTRAIN)
-    if (int e = scratch_get((size_t)ddpm_scratch_doubles(n, W) * 8, stream, lease)) return e;
+  if (int e = lease_x0sum(flags & VQVS_DDPM_CONSTRAIN, n, W, stream, lease)) return e;
   return run_ddpm_step_windows(d_x, d_eps, d_noise, d_alpha_t, d_alpha_prev, d_x_prev, d_windows, reinterpret_cast<double*>(lease.p), n, W, H,
                                flags, noise_scale, seed, clip, step_index, reinterpret_cast<hipStream_t>(stream));
 }
@@ -375,10 +389,6 @@ static int check_ddim_args(uint32_t flags, float eta) {
   if ((flags & VQVS_DDIM_INVERT) && eta != 0.f) VQVS_FAIL(VQVS_ERR_ARG, "INVERT needs eta = 0 (got %g)", (double)eta);
   return 0;
 }
-// [out, out + n_out) against an input of n_in floats (NULL: absent)
-static bool floats_overlap(const float* out, int64_t n_out, const float* in, int64_t n_in) {
-  return out && in && out < in + n_in && in < out + n_out;
-}
 
 int vqvs_ddim_step(const float* d_x_t, const float* d_eps, const float* d_grad, const float* d_noise, const float* d_alpha_t,
                    const float* d_alpha_to, float* d_x_to, int B, int T, uint32_t flags, float eta, float noise_scale, uint64_t seed,
@@ -389,11 +399,11 @@ int vqvs_ddim_step(const float* d_x_t, const float* d_eps, const float* d_grad, 
   if (int e = check_ddim_args(flags, eta)) return e;
   const int64_t N = (int64_t)B * T;
   for (const float* in : {d_x_t, d_eps, d_grad, d_noise})
-    if (floats_overlap(d_x_to, N, in, N)) VQVS_FAIL(VQVS_ERR_ARG, "x_to must not overlap x_t, eps, grad or noise");
-  if (floats_overlap(d_x_to, N, d_alpha_t, B) || floats_overlap(d_x_to, N, d_alpha_to, B)) VQVS_FAIL(VQVS_ERR_ARG, "x_to must not overlap the alphas");
+    if (bytes_overlap(d_x_to, N * 4, in, N * 4)) VQVS_FAIL(VQVS_ERR_ARG, "x_to must not overlap x_t, eps, grad or noise");
+  if (bytes_overlap(d_x_to, N * 4, d_alpha_t, B * 4) || bytes_overlap(d_x_to, N * 4, d_alpha_to, B * 4))
+    VQVS_FAIL(VQVS_ERR_ARG, "x_to must not overlap the alphas");
   ScratchLease lease;
-  if (flags & VQVS_DDIM_CONSTRAIN)
-    if (int e = scratch_get((size_t)ddpm_scratch_doubles(B, T) * 8, stream, lease)) return e;
+  if (int e = lease_x0sum(flags & VQVS_DDIM_CONSTRAIN, B, T, stream, lease)) return e;
   return run_ddim_step(d_x_t, d_eps, d_grad, d_noise, d_alpha_t, d_alpha_to, d_x_to, reinterpret_cast<double*>(lease.p), B, T, flags, eta,
                        noise_scale, seed, clip_offset, step_index, reinterpret_cast<hipStream_t>(stream));
 }
@@ -402,29 +412,21 @@ int vqvs_ddim_step_windows(const float* d_x, const float* d_eps, const float* d_
                            const float* d_alpha_to, float* d_x_to, float* d_windows, int n, int W, int H, uint32_t flags, float eta,
                            float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index, void* stream) {
   if (!d_x || !d_eps || !d_alpha_t || !d_alpha_to || !d_x_to) VQVS_FAIL(VQVS_ERR_ARG, "x, eps, alpha_t, alpha_to and x_to must be non-NULL");
-  if (n < 1 || n > 65535) VQVS_FAIL(VQVS_ERR_ARG, "window count %d outside 1..65535", n);
-  if (W < 4 || H < 4 || W % 4 || H % 4) VQVS_FAIL(VQVS_ERR_ARG, "window %d and hop %d must be positive multiples of 4", W, H);
-  if (W < H || W - H > H) VQVS_FAIL(VQVS_ERR_ARG, "overlap %d (window %d - hop %d) outside 0..hop: at most two windows may cover a sample", W - H, W, H);
-  const int64_t Np = (int64_t)(n - 1) * H + W, NW = (int64_t)n * W;
-  if (Np >= ((int64_t)1 << 31)) VQVS_FAIL(VQVS_ERR_ARG, "%d windows every %d samples span %lld samples: 2^31 or more", n, H, (long long)Np);
+  int64_t Np;
+  if (int e = check_window_geometry(n, W, H, &Np)) return e;
   if (int e = check_ddim_args(flags, eta)) return e;
+  const int64_t NW = (int64_t)n * W;
   const struct { const float* p; int64_t len; } ins[] = {{d_x, Np}, {d_eps, NW}, {d_grad, NW}, {d_noise, Np}, {d_alpha_t, 1}, {d_alpha_to, 1}};
   for (const auto& in : ins)
-    if (floats_overlap(d_x_to, Np, in.p, in.len) || floats_overlap(d_windows, NW, in.p, in.len))
+    if (bytes_overlap(d_x_to, Np * 4, in.p, in.len * 4) || bytes_overlap(d_windows, NW * 4, in.p, in.len * 4))
       VQVS_FAIL(VQVS_ERR_ARG, "x_to and windows must not overlap x, eps, grad, noise or the alphas");
-  if (floats_overlap(d_x_to, Np, d_windows, NW)) VQVS_FAIL(VQVS_ERR_ARG, "x_to must not overlap windows");
+  if (bytes_overlap(d_x_to, Np * 4, d_windows, NW * 4)) VQVS_FAIL(VQVS_ERR_ARG, "x_to must not overlap windows");
   ScratchLease lease;
-  if (flags & VQVS_DDIM_CONSTRAIN)
-    if (int e = scratch_get((size_t)ddpm_scratch_doubles(n, W) * 8, stream, lease)) return e;
+  if (int e = lease_x0sum(flags & VQVS_DDIM_CONSTRAIN, n, W, stream, lease)) return e;
   return run_ddim_step_windows(d_x, d_eps, d_grad, d_noise, d_alpha_t, d_alpha_to, d_x_to, d_windows, reinterpret_cast<double*>(lease.p), n, W, H,
                                flags, eta, noise_scale, seed, clip, step_index, reinterpret_cast<hipStream_t>(stream));
 }
 
-// [a, a + na) against [b, b + nb) in bytes (NULL: absent)
-static bool bytes_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
-  const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
-  return pa && pb && pa < pb + nb && pb < pa + na;
-}
 // Shared argument rules of the two keep-region entry points.  N: samples of the state (and of x0, keep, noise); n_alpha: entries of
 // d_alpha; NW: samples of d_windows (0 when the entry point has none).
 static int check_keep_args(const float* d_x, const float* d_windows, const float* d_x0, const uint8_t* d_keep, const float* d_noise,
@@ -457,11 +459,8 @@ int vqvs_keep_region_windows(float* d_x, float* d_windows, const float* d_x0, co
   if (!d_x) VQVS_FAIL(VQVS_ERR_ARG, "d_x must be non-NULL");
   if (!d_x0) VQVS_FAIL(VQVS_ERR_ARG, "d_x0 must be non-NULL");
   if (!d_alpha) VQVS_FAIL(VQVS_ERR_ARG, "d_alpha must be non-NULL");
-  if (n < 1 || n > 65535) VQVS_FAIL(VQVS_ERR_ARG, "window count n=%d outside 1..65535", n);
-  if (W < 4 || H < 4 || W % 4 || H % 4) VQVS_FAIL(VQVS_ERR_ARG, "window W=%d and hop H=%d must be positive multiples of 4", W, H);
-  if (W < H || W - H > H) VQVS_FAIL(VQVS_ERR_ARG, "overlap %d (window W=%d - hop H=%d) outside 0..hop: at most two windows may cover a sample", W - H, W, H);
-  const int64_t Np = (int64_t)(n - 1) * H + W;
-  if (Np >= ((int64_t)1 << 31)) VQVS_FAIL(VQVS_ERR_ARG, "n=%d windows every H=%d samples span %lld samples: 2^31 or more", n, H, (long long)Np);
+  int64_t Np;
+  if (int e = check_window_geometry(n, W, H, &Np)) return e;
   if (int e = check_keep_args(d_x, d_windows, d_x0, d_keep, d_noise, d_alpha, Np, 1, (int64_t)n * W, noise_scale)) return e;
   return run_keep_region_windows(d_x, d_windows, d_x0, d_keep, d_noise, d_alpha, n, W, H, noise_scale, seed, clip, index,
                                  reinterpret_cast<hipStream_t>(stream));

@@ -1,5 +1,6 @@
-// DDPM reverse-step kernels, the counter-based normal generator, and the VQ codebook search.
-// All of these are HBM-bound elementwise / small-reduction kernels.
+// DDPM and DDIM reverse-step kernels, the keep region, the counter-based normal generator, and the VQ codebook search.
+// All of these are HBM-bound elementwise / small-reduction kernels.  The step and keep kernels come as a batch of clips [B, T] and as
+// ONE long row seen through overlapping windows; the forms share block_sum_256, step_noise_tail / _quad, quad_windows and store_quad.
 #include "kernels.hpp"
 #include "philox.hpp"
 #include "sampler_kernels.hpp"
@@ -45,12 +46,72 @@ __device__ __forceinline__ StepCoef step_coef(float a_t, float a_prev, bool sigm
 
 constexpr int SUM_CHUNK = 4096;
 
+// *out = the sum of `s` over the 256 threads of the workgroup, in fp64: the fixed tree whose stride halves from 128 to 1, thread 0 writes
+__device__ __forceinline__ void block_sum_256(double s, double* out) {
+  __shared__ double red[256];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int m = 128; m >= 1; m >>= 1) {
+    if (threadIdx.x < m) red[threadIdx.x] += red[threadIdx.x + m];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *out = red[0];
+}
+
+// The step noise of one quad (quad `quad` of clip `clip` at `step_index`, stream 0) times noise_scale: read from `noise` -- `live`
+// samples at element `base` --, or drawn when it is NULL.
+__device__ __forceinline__ void step_noise_tail(float* nv, const float* noise, size_t base, int live, float noise_scale, uint64_t seed,
+                                                uint32_t quad, uint64_t clip, uint32_t step_index) {
+  if (noise) {
+    for (int j = 0; j < live; ++j) nv[j] = noise[base + j] * noise_scale;
+  } else {
+    const f32x4 z = philox_normal4(seed, quad, clip, step_index, 0u);
+    for (int j = 0; j < 4; ++j) nv[j] = z[j] * noise_scale;
+  }
+}
+// ... of a whole, 16-byte aligned quad at element p
+__device__ __forceinline__ f32x4 step_noise_quad(const float* noise, int p, float noise_scale, uint64_t seed, uint32_t quad, uint64_t clip,
+                                                 uint32_t step_index) {
+  const f32x4 z = noise ? *reinterpret_cast<const f32x4*>(noise + p) : philox_normal4(seed, quad, clip, step_index, 0u);
+  f32x4 nv;
+  for (int j = 0; j < 4; ++j) nv[j] = z[j] * noise_scale;
+  return nv;
+}
+
+// ONE long signal x [Np], Np = (n - 1) * H + W, seen through n windows of W samples, one every H ([n, W] arrays); V = W - H <= H, so a
+// sample lies in one window or in two.  A thread owns the quad at absolute position p = 4 q: W and H are multiples of 4, so the quad
+// lies in the same window(s), and every access is 16 bytes wide.  Window `br` is the last one that starts at or before p, and the
+// quad is at offset u = p - br * H in it; the window before covers it too (`two`) while u < V, at offset u + H.  at_r / at_l are the
+// quad's elements in an [n, W] array: window br's copy, and window br - 1's (0 without one).
+struct QuadWindows {
+  int br, u;
+  bool two;
+  size_t at_r, at_l;
+};
+__device__ __forceinline__ QuadWindows quad_windows(int p, int n, int W, int H) {
+  QuadWindows g;
+  g.br = min(p / H, n - 1);
+  g.u = p - g.br * H;
+  g.two = g.br > 0 && g.u < W - H;
+  g.at_r = (size_t)g.br * W + g.u;
+  g.at_l = g.two ? (size_t)(g.br - 1) * W + g.u + H : 0;
+  return g;
+}
+// a finished quad goes to the long row and, for the next forward, to its copy in every window that covers it (win NULL: not wanted)
+template <typename Store>
+__device__ __forceinline__ void store_quad(float* x, float* win, int p, const QuadWindows& g, Store store) {
+  store(x + p);
+  if (win) {
+    store(win + g.at_r);
+    if (g.two) store(win + g.at_l);
+  }
+}
+
 // sum over time of x0 = (x_t - sqrt(1-a_t) eps) rsqrt(a_t), per (clip, chunk); fp64 partials.  Row b of eps is [T] contiguous; row b of
 // x_t starts at b * x_stride and its alpha is a_t[b * a_stride]: (T, 1) for a batch of clips, (hop, 0) for the overlapping windows
 // of one long signal (ddpm_step_windows_kernel), which are then summed exactly as a clip is.
 __global__ __launch_bounds__(256) void ddpm_x0sum_kernel(const float* x_t, const float* eps, const float* a_t, double* partial, int T, int nchunk,
                                                          int x_stride, int a_stride) {
-  __shared__ double red[256];
   const int b = blockIdx.y;
   const float at = a_t[b * a_stride];
   const float sq = sqrtf(1.0f - at), rs = 1.0f / sqrtf(at);
@@ -59,13 +120,7 @@ __global__ __launch_bounds__(256) void ddpm_x0sum_kernel(const float* x_t, const
   for (int t = beg + threadIdx.x; t < end; t += 256) {
     s += (double)((x_t[(size_t)b * x_stride + t] - sq * eps[(size_t)b * T + t]) * rs);
   }
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int m = 128; m >= 1; m >>= 1) {
-    if (threadIdx.x < m) red[threadIdx.x] += red[threadIdx.x + m];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[(size_t)b * nchunk + blockIdx.x] = red[0];
+  block_sum_256(s, partial + (size_t)b * nchunk + blockIdx.x);
 }
 
 // mean of x0 over one clip / window: the chunk partials of ddpm_x0sum_kernel added in chunk order
@@ -116,24 +171,14 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const float* x_t, const 
     xv[j] = x_t[base + j];
     ev[j] = eps[base + j];
   }
-  if (noise_scale != 0.f) {
-    if (noise) {
-      for (int j = 0; j < n; ++j) nv[j] = noise[base + j] * noise_scale;
-    } else {
-      const f32x4 z = philox_normal4(seed, (uint32_t)q, clip_offset + b, step_index, 0u);
-      for (int j = 0; j < 4; ++j) nv[j] = z[j] * noise_scale;
-    }
-  }
+  if (noise_scale != 0.f) step_noise_tail(nv, noise, base, n, noise_scale, seed, (uint32_t)q, clip_offset + b, step_index);
   for (int j = 0; j < n; ++j) out[base + j] = step_sample<false>(k, flags & 2u, xv[j], nv[j], ev[j], mean);
 }
 
-// The reverse step of ONE long signal x [Np], Np = (n - 1) * H + W, whose predictions came from n windows of W samples, one every H
-// (eps [n, W]); V = W - H <= H, so a sample lies in one window or in two.  A thread owns the quad at absolute position p = 4 q: W and H
-// are multiples of 4, so the quad lies in the same window(s), and every access is 16 bytes wide.  Window `br` is the last one that
-// starts at or before p; the one before it covers p too while u = p - br * H < V, and the two predictions are then cross-faded with
-// w = (u + 1/2) / V.  The noise is one draw per absolute position -- row 0 of a [1, Np] batch at `clip`, as ddpm_step_kernel draws
-// it -- so the overlapping windows share it, and the result goes to x_prev [Np] and, for the next forward, to both windows' rows of
-// win [n, W] (NULL: not wanted).  partial: n * nchunk chunk sums of ddpm_x0sum_kernel.
+// The reverse step of one long signal x [Np] whose predictions came from its n windows (eps [n, W]; quad_windows).  Where two windows
+// cover a quad their predictions are cross-faded with w = (u + 1/2) / V.  The noise is one draw per absolute position -- row 0 of a
+// [1, Np] batch at `clip`, as ddpm_step_kernel draws it -- so the overlapping windows share it, and the result goes to x_prev [Np]
+// and to win [n, W] (store_quad).  partial: n * nchunk chunk sums of ddpm_x0sum_kernel.
 __global__ __launch_bounds__(256) void ddpm_step_windows_kernel(const float* x, const float* eps, const float* noise, const float* a_t,
                                                                 const float* a_prev, const double* partial, int nchunk, float* x_prev,
                                                                 float* win, int n, int W, int H, uint32_t flags, float noise_scale,
@@ -144,38 +189,28 @@ __global__ __launch_bounds__(256) void ddpm_step_windows_kernel(const float* x, 
   const int p = q * 4;
   const StepCoef k = step_coef(a_t[0], a_prev[0], flags & 1u);
   const bool constrain = flags & 2u;
-  const int br = min(p / H, n - 1);
-  const int u = p - br * H;  // offset in window br; in window br - 1 the sample is u + H
-  const bool two = br > 0 && u < V;
-  const size_t at_r = (size_t)br * W + u, at_l = two ? (size_t)(br - 1) * W + u + H : 0;
+  const QuadWindows g = quad_windows(p, n, W, H);
   const f32x4 xv = *reinterpret_cast<const f32x4*>(x + p);
-  const f32x4 er = *reinterpret_cast<const f32x4*>(eps + at_r);
+  const f32x4 er = *reinterpret_cast<const f32x4*>(eps + g.at_r);
   f32x4 el = er;
-  if (two) el = *reinterpret_cast<const f32x4*>(eps + at_l);
+  if (g.two) el = *reinterpret_cast<const f32x4*>(eps + g.at_l);
   float mean_r = 0.f, mean_l = 0.f;
   if (constrain) {
-    mean_r = x0_mean(partial + (size_t)br * nchunk, nchunk, W);
-    if (two) mean_l = x0_mean(partial + (size_t)(br - 1) * nchunk, nchunk, W);
+    mean_r = x0_mean(partial + (size_t)g.br * nchunk, nchunk, W);
+    if (g.two) mean_l = x0_mean(partial + (size_t)(g.br - 1) * nchunk, nchunk, W);
   }
   f32x4 nv = {0.f, 0.f, 0.f, 0.f};
-  if (noise_scale != 0.f) {
-    const f32x4 z = noise ? *reinterpret_cast<const f32x4*>(noise + p) : philox_normal4(seed, (uint32_t)q, clip, step_index, 0u);
-    for (int j = 0; j < 4; ++j) nv[j] = z[j] * noise_scale;
-  }
+  if (noise_scale != 0.f) nv = step_noise_quad(noise, p, noise_scale, seed, (uint32_t)q, clip, step_index);
   f32x4 o;
-  if (two) {
+  if (g.two) {
     for (int j = 0; j < 4; ++j) {
-      const float w = ((float)(u + j) + 0.5f) / (float)V;
+      const float w = ((float)(g.u + j) + 0.5f) / (float)V;
       o[j] = step_sample<true>(k, constrain, xv[j], nv[j], el[j], mean_l, er[j], mean_r, w);
     }
   } else {
     for (int j = 0; j < 4; ++j) o[j] = step_sample<false>(k, constrain, xv[j], nv[j], er[j], mean_r);
   }
-  *reinterpret_cast<f32x4*>(x_prev + p) = o;
-  if (win) {
-    *reinterpret_cast<f32x4*>(win + at_r) = o;
-    if (two) *reinterpret_cast<f32x4*>(win + at_l) = o;
-  }
+  store_quad(x_prev, win, p, g, [&](float* dst) { *reinterpret_cast<f32x4*>(dst) = o; });
 }
 
 // mean = eps_to_prev(eps)
@@ -246,7 +281,6 @@ __device__ __forceinline__ DdimCoef ddim_coef(float a_t, float a_to, float eta, 
 // scalars, so the mean that x0_mean rounds to fp32 carries that one rounding.
 __global__ __launch_bounds__(256) void ddim_x0sum_kernel(const float* x_t, const float* eps, const float* grad, const float* a_t,
                                                          double* partial, int T, int nchunk, int x_stride, int a_stride) {
-  __shared__ double red[256];
   const int b = blockIdx.y;
   const DdimX0Coef k = ddim_x0_coef(a_t[b * a_stride]);
   const int beg = blockIdx.x * SUM_CHUNK, end = min(T, beg + SUM_CHUNK);
@@ -256,13 +290,7 @@ __global__ __launch_bounds__(256) void ddim_x0sum_kernel(const float* x_t, const
     if (grad) e -= k.sq1mat * (double)grad[(size_t)b * T + t];
     s += ((double)x_t[(size_t)b * x_stride + t] - k.sq1mat * e) * k.rsat;
   }
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int m = 128; m >= 1; m >>= 1) {
-    if (threadIdx.x < m) red[threadIdx.x] += red[threadIdx.x + m];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[(size_t)b * nchunk + blockIdx.x] = red[0];
+  block_sum_256(s, partial + (size_t)b * nchunk + blockIdx.x);
 }
 
 // (x0, e') of one sample under one clip's / window's prediction e and gradient g (guided: e <- e - sqrt(1 - a_t) g)
@@ -317,19 +345,13 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const float* x_t, const 
     ev[j] = eps[base + j];
     if (GUIDED) gv[j] = grad[base + j];
   }
-  if (noise_scale != 0.f && k.sig != 0.f) {  // (eta = 0, INVERT, a_to = 1: nothing is drawn or read)
-    if (noise) {
-      for (int j = 0; j < n; ++j) nv[j] = noise[base + j] * noise_scale;
-    } else {
-      const f32x4 z = philox_normal4(seed, (uint32_t)q, clip_offset + b, step_index, 0u);
-      for (int j = 0; j < 4; ++j) nv[j] = z[j] * noise_scale;
-    }
-  }
+  if (noise_scale != 0.f && k.sig != 0.f)  // (eta = 0, INVERT, a_to = 1: nothing is drawn or read)
+    step_noise_tail(nv, noise, base, n, noise_scale, seed, (uint32_t)q, clip_offset + b, step_index);
   for (int j = 0; j < n; ++j) out[base + j] = ddim_sample<false, GUIDED>(k, flags & 2u, xv[j], nv[j], ev[j], gv[j], mean);
 }
 
-// ddpm_step_windows_kernel's geometry, limits, 16-byte accesses, per-window means, shared noise and `win` output, for the DDIM step;
-// grad [n, W] enters per window, before the blend.
+// ddpm_step_windows_kernel's per-window means, shared noise and outputs, for the DDIM step; grad [n, W] enters per window, before
+// the blend.
 template <bool GUIDED>
 __global__ __launch_bounds__(256) void ddim_step_windows_kernel(const float* x, const float* eps, const float* grad, const float* noise,
                                                                 const float* a_t, const float* a_to, const double* partial, int nchunk,
@@ -341,43 +363,33 @@ __global__ __launch_bounds__(256) void ddim_step_windows_kernel(const float* x, 
   const int p = q * 4;
   const DdimCoef k = ddim_coef(a_t[0], a_to[0], eta, flags & 4u);
   const bool constrain = flags & 2u;
-  const int br = min(p / H, n - 1);
-  const int u = p - br * H;  // offset in window br; in window br - 1 the sample is u + H
-  const bool two = br > 0 && u < V;
-  const size_t at_r = (size_t)br * W + u, at_l = two ? (size_t)(br - 1) * W + u + H : 0;
+  const QuadWindows g = quad_windows(p, n, W, H);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
   const f32x4 xv = *reinterpret_cast<const f32x4*>(x + p);
-  const f32x4 er = *reinterpret_cast<const f32x4*>(eps + at_r);
+  const f32x4 er = *reinterpret_cast<const f32x4*>(eps + g.at_r);
   f32x4 el = er, gr = zero, gl = zero;
-  if (two) el = *reinterpret_cast<const f32x4*>(eps + at_l);
+  if (g.two) el = *reinterpret_cast<const f32x4*>(eps + g.at_l);
   if (GUIDED) {
-    gr = *reinterpret_cast<const f32x4*>(grad + at_r);
-    if (two) gl = *reinterpret_cast<const f32x4*>(grad + at_l);
+    gr = *reinterpret_cast<const f32x4*>(grad + g.at_r);
+    if (g.two) gl = *reinterpret_cast<const f32x4*>(grad + g.at_l);
   }
   float mean_r = 0.f, mean_l = 0.f;
   if (constrain) {
-    mean_r = x0_mean(partial + (size_t)br * nchunk, nchunk, W);
-    if (two) mean_l = x0_mean(partial + (size_t)(br - 1) * nchunk, nchunk, W);
+    mean_r = x0_mean(partial + (size_t)g.br * nchunk, nchunk, W);
+    if (g.two) mean_l = x0_mean(partial + (size_t)(g.br - 1) * nchunk, nchunk, W);
   }
   f32x4 nv = zero;
-  if (noise_scale != 0.f && k.sig != 0.f) {
-    const f32x4 z = noise ? *reinterpret_cast<const f32x4*>(noise + p) : philox_normal4(seed, (uint32_t)q, clip, step_index, 0u);
-    for (int j = 0; j < 4; ++j) nv[j] = z[j] * noise_scale;
-  }
+  if (noise_scale != 0.f && k.sig != 0.f) nv = step_noise_quad(noise, p, noise_scale, seed, (uint32_t)q, clip, step_index);
   f32x4 o;
-  if (two) {
+  if (g.two) {
     for (int j = 0; j < 4; ++j) {
-      const float w = ((float)(u + j) + 0.5f) / (float)V;
+      const float w = ((float)(g.u + j) + 0.5f) / (float)V;
       o[j] = ddim_sample<true, GUIDED>(k, constrain, xv[j], nv[j], el[j], gl[j], mean_l, er[j], gr[j], mean_r, w);
     }
   } else {
     for (int j = 0; j < 4; ++j) o[j] = ddim_sample<false, GUIDED>(k, constrain, xv[j], nv[j], er[j], gr[j], mean_r);
   }
-  *reinterpret_cast<f32x4*>(x_to + p) = o;
-  if (win) {
-    *reinterpret_cast<f32x4*>(win + at_r) = o;
-    if (two) *reinterpret_cast<f32x4*>(win + at_l) = o;
-  }
+  store_quad(x_to, win, p, g, [&](float* dst) { *reinterpret_cast<f32x4*>(dst) = o; });
 }
 
 // ---------------------------------------------------------------------------------
@@ -464,27 +476,20 @@ __global__ __launch_bounds__(256) void keep_region_kernel(float* x, const float*
   if (mask) keep_store(x + at, o, mask, aligned);
 }
 
-// ddpm_step_windows_kernel's geometry for the same operation on ONE long state x [Np]: x0, keep and noise are indexed by absolute
-// position, there is one alpha, the drawn noise is that of one row of Np samples at `clip`, and a kept sample goes to x and to its
-// copy in every window that covers it (win [n, W]; NULL: not wanted).  W and H are multiples of 4: every quad is whole.
+// The same operation on ONE long state x [Np] (quad_windows): x0, keep and noise are indexed by absolute position, there is one
+// alpha, the drawn noise is that of one row of Np samples at `clip`, and a kept sample goes to x and to win [n, W] (store_quad).
 __global__ __launch_bounds__(256) void keep_region_windows_kernel(float* x, float* win, const float* x0, const uint8_t* keep,
                                                                   const float* noise, const float* alpha, int n, int W, int H, bool aligned,
                                                                   float noise_scale, uint64_t seed, uint64_t clip, uint32_t index) {
   const int q = blockIdx.x * 256 + threadIdx.x;
-  const int Np = (n - 1) * H + W, V = W - H;
+  const int Np = (n - 1) * H + W;
   if (q >= Np / 4) return;
   const int p = q * 4;
   const KeepCoef k = keep_coef(alpha[0]);
   f32x4 o;
   const uint32_t mask = keep_quad(x0, keep, noise, (size_t)p, 4, aligned, k, noise_scale, seed, (uint32_t)q, clip, index, o);
   if (!mask) return;
-  keep_store(x + p, o, mask, aligned);
-  if (win) {
-    const int br = min(p / H, n - 1);
-    const int u = p - br * H;  // offset in window br; in window br - 1 the sample is u + H
-    keep_store(win + (size_t)br * W + u, o, mask, aligned);
-    if (br > 0 && u < V) keep_store(win + (size_t)(br - 1) * W + u + H, o, mask, aligned);
-  }
+  store_quad(x, win, p, quad_windows(p, n, W, H), [&](float* dst) { keep_store(dst, o, mask, aligned); });
 }
 
 // ---------------------------------------------------------------------------------

@@ -15,6 +15,7 @@ Additions over the reference (it has no seeding):
 
 from __future__ import annotations
 
+import contextlib
 import math
 import operator
 from typing import Callable, List, Optional, Sequence, Union
@@ -84,30 +85,54 @@ def _native_modules(fn) -> list:
     return out
 
 
-def few_guided_steps_promotion(what: str, steps: int, predictor, cond_fn):
+def predictor_check_status(predictor):
+    """The range guard of a native predictor -- its own `check_status`, or that of the first native module behind the callable --
+    or None for a plain Python function."""
+    chk = getattr(predictor, "check_status", None)
+    if chk is None:
+        mods = _native_modules(predictor)
+        chk = mods[0].check_status if mods else None
+    return chk
+
+
+def fresh_seed() -> int:
+    """The seed of a call that was given none: one draw from torch's global generator."""
+    return int(torch.randint(0, 2 ** 62, (1,)).item())
+
+
+def _progress(its: range, progress: bool):
+    """`its`, under tqdm when asked."""
+    if not progress:
+        return its
+    from tqdm.auto import tqdm
+
+    return tqdm(its, total=len(its))
+
+
+def few_guided_steps_promotion(what: str, steps: int, predictor, cond_fn, stacklevel: int = 3):
     """Few guided steps in a 2-byte mode: the first reverse step multiplies the predictor's rounding error by 1 / sqrt(alpha_bar(1))
     and a guided run adds the classifier gradient's own; fewer than FEW_GUIDED_STEPS iterations never average that out (measured:
     config 5 at 3 steps 1.05e-3 in fp16 against the 1e-3 waveform contract, profiles/r05_parity_margins.jsonl).  The call is then
     promoted to the fp32 mode -- predictor and guidance model -- through precision_override, which keeps each module's own
     handle; VQVAE.decode_uncond_guidance does the same for its extrapolation.  (VQVS_FEW_STEP_PROMOTE=0: warn only.)
-    Returns None, or an ExitStack holding the overrides: the sampler `what` runs itself again inside it."""
+    Returns None, or an ExitStack holding the overrides: the sampler `what` runs its loop inside it.  `stacklevel` is the warnings'
+    (3: the caller of the function that called this one)."""
     if cond_fn is None or steps >= FEW_GUIDED_STEPS:
         return None
     promote = [m for m in _native_modules(predictor) + _native_modules(cond_fn) if getattr(m, "precision", "fp32") != "fp32"]
     if not promote:
         return None
-    import contextlib
     import os
     import warnings
 
     modes = sorted({m.precision for m in promote})
     if os.environ.get("VQVS_FEW_STEP_PROMOTE", "1") == "0":
         warnings.warn(f"{what}: {steps} guided steps in the {modes} mode(s) are outside the 1e-3 waveform contract "
-                      f"(fewer than {FEW_GUIDED_STEPS} steps); VQVS_FEW_STEP_PROMOTE=0 keeps the mode", RuntimeWarning, stacklevel=3)
+                      f"(fewer than {FEW_GUIDED_STEPS} steps); VQVS_FEW_STEP_PROMOTE=0 keeps the mode", RuntimeWarning, stacklevel=stacklevel)
         return None
     warnings.warn(f"{what}: {steps} guided steps (fewer than {FEW_GUIDED_STEPS}): predictor / guidance model run in the fp32 "
                   f"mode for this call (their {modes} mode(s) do not hold the 1e-3 waveform contract at so few steps)",
-                  RuntimeWarning, stacklevel=3)
+                  RuntimeWarning, stacklevel=stacklevel)
     stack = contextlib.ExitStack()
     for m in promote:
         stack.enter_context(m.precision_override("fp32"))
@@ -126,7 +151,16 @@ def check_sampler(sampler: str, eta: float = 0.0) -> str:
     return sampler
 
 
-def warn_few_unguided_steps(what: str, steps: int, predictor, cond_fn) -> None:
+def pick_sampler(diffusion, sampler: str, eta: float = 0.0, *, sigma_large: Optional[bool] = None, windows: bool = False):
+    """(sampling method of `diffusion`, its keywords) for a `sampler=` / `eta=` pair: `eta` goes to the DDIM sampler alone and
+    `sigma_large` (None: not the caller's to pass) to the DDPM sampler alone.  `windows`: the `..._sample_windows` forms."""
+    fn = getattr(diffusion, check_sampler(sampler, eta) + ("_sample_windows" if windows else "_sample"))
+    if sampler == "ddim":
+        return fn, dict(eta=eta)
+    return fn, {} if sigma_large is None else dict(sigma_large=sigma_large)
+
+
+def warn_few_unguided_steps(what: str, steps: int, predictor, cond_fn, stacklevel: int = 3) -> None:
     """An UN-guided DDIM run of fewer than FEW_GUIDED_STEPS steps in a 2-byte mode: the first step's 1 / sqrt(alpha_bar(1)) acts on
     the predictor's rounding error just the same, but nothing has been measured for it, so the run keeps its mode and only warns.
     (Guided runs are promoted by few_guided_steps_promotion; the DDPM samplers are not touched.)"""
@@ -137,7 +171,7 @@ def warn_few_unguided_steps(what: str, steps: int, predictor, cond_fn) -> None:
         import warnings
 
         warnings.warn(f"{what}: {steps} steps (fewer than {FEW_GUIDED_STEPS}) in the {modes} mode(s): the 1e-3 waveform contract is not "
-                      "established for so few steps; the mode is kept", RuntimeWarning, stacklevel=3)
+                      "established for so few steps; the mode is kept", RuntimeWarning, stacklevel=stacklevel)
 
 
 def strength_to_start_step(strength: float, steps: int) -> int:
@@ -149,6 +183,14 @@ def strength_to_start_step(strength: float, steps: int) -> int:
     if steps < 1:
         raise ValueError(f"steps={steps} must be at least 1")
     return min(max(steps - math.ceil(strength * steps), 0), steps - 1)
+
+
+def source_start_step(source, keep, strength: float, steps: int) -> int:
+    """The `source=` / `keep=` / `strength=` keywords of `VQVAE.decode` and `decode_long`: the step the run starts at."""
+    start_step = strength_to_start_step(strength, steps)
+    if source is None and (keep is not None or start_step):
+        raise ValueError("keep= and strength < 1 need source=, the waveform whose samples are kept or noised")
+    return start_step
 
 
 def check_keep_args(state: torch.Tensor, source: Optional[torch.Tensor], keep: Optional[torch.Tensor], start_step: int, steps: int):
@@ -250,7 +292,7 @@ class Diffusion:
         if x_0.dim() < 2:
             raise ValueError("x_0 must be [N, ..., T]")
         if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            seed = fresh_seed()
         x0 = x_0.detach().to(torch.float32).contiguous()
         if ts is None:
             ts = self.draw_ts(x0.shape[0], seed, clip_offset)
@@ -291,13 +333,9 @@ class Diffusion:
             pred = pred.detach().to(torch.float32).contiguous()
             _native.check(L.vqvs_ddpm_sqerr(pred.data_ptr(), _native._ptr(eps), eps_rows, _native._ptr(idx), loss.data_ptr(), B, T,
                                             int(seed), int(clip_offset), _native._stream_ptr()))
-        if check:
-            chk = getattr(predictor, "check_status", None)  # range guard of a native predictor, as in ddpm_sample
-            if chk is None:
-                mods = _native_modules(predictor)
-                chk = mods[0].check_status if mods else None
-            if chk is not None:
-                chk()
+        chk = predictor_check_status(predictor) if check else None  # range guard of a native predictor, as in check_sample
+        if chk is not None:
+            chk()
         return loss
 
     # ---- hot path -------------------------------------------------------------------------
@@ -377,10 +415,7 @@ class Diffusion:
     def check_sample(predictor, x_t: torch.Tensor, what: str) -> None:
         """The end of a sampling run: the range guard of a native predictor (once per sample, not per step) and the sample's
         finiteness."""
-        chk = getattr(predictor, "check_status", None)
-        if chk is None:
-            mods = _native_modules(predictor)
-            chk = mods[0].check_status if mods else None
+        chk = predictor_check_status(predictor)
         if chk is not None:
             chk()
             # The library's guard sees the tensors that feed a GroupNorm.  The network's output and x_t are fp32 in every mode and cannot
@@ -438,6 +473,40 @@ class Diffusion:
         self._keep_(x, source, keep, alpha, seed=seed, clip_offset=clip_offset, index=start_step)
         return x.view_as(x_T)
 
+    # ---- the sampling loop of ddpm_sample, ddim_sample and their window forms (longform.py) --------------
+    def _sample(self, what: str, layout, x_T: torch.Tensor, steps: int, *, schedule, noise: NoiseSource, seed, clip_offset, progress, source,
+                keep, start_step) -> torch.Tensor:
+        """The one reverse loop.  `layout` (`_Clips` here, `longform._Windows`) holds the state, calls the predictor and cond_fn and
+        launches its form of the kernels of `layout.rule` (`_Ddpm` / `_Ddim`); everything the four entry points share is here: the
+        `source` / `keep` / `start_step` checks, the default seed, the few-steps promotion and warning, the tables, steps
+        start_step .. steps - 1 with no noise on the last one, the keep region at the alpha_bar stepped to, the final guard."""
+        source, keep = check_keep_args(x_T, source, keep, start_step, steps)
+        _native.require_cuda(x_T, source, keep)
+        rows = layout.rows(x_T)
+        if seed is None:
+            seed = fresh_seed()
+        key = dict(seed=seed, clip_offset=clip_offset)
+        rule, predictor, cond_fn = layout.rule, layout.predictor, layout.cond_fn
+        stack = few_guided_steps_promotion(what, steps, predictor, cond_fn, stacklevel=4)  # (4: the caller of the entry point)
+        with stack if stack is not None else contextlib.nullcontext():
+            if rule.name == "ddim":
+                warn_few_unguided_steps(what, steps, predictor, cond_fn, stacklevel=4)
+            tables = self.step_tables(steps, rows, schedule, x_T.device)  # t, alpha_bar(t), alpha_bar(t - step), t - step
+            x_t = layout.start(x_T, source, keep, tables[1][start_step], start_step=start_step, **key)
+            with torch.no_grad(), torch.cuda.device(x_T.device):
+                for i in _progress(range(start_step, steps), progress):
+                    last = i + 1 == steps
+                    eps = layout.predict(x_t, tables, i)
+                    nz = None
+                    if not last and noise is not None and rule.draws_noise:
+                        nz = noise(i) if callable(noise) else noise[i]
+                    x_t = layout.step(x_t, eps, nz, tables, i, noise_scale=0.0 if last else 1.0, **key)
+                    if keep is not None:  # (the step's output is a fresh float32 tensor of this loop's)
+                        layout.keep(x_t, source, keep, tables[2][i], index=i + 1, **key)
+            x_t = x_t.view_as(x_T)
+            self.check_sample(predictor, x_t, what)
+        return x_t
+
     def ddpm_sample_windows(self, x_T_long: torch.Tensor, predictor: Callable, steps: int, **kwargs) -> torch.Tensor:
         """`ddpm_sample` for one long state [1,1,Np] predicted through overlapping windows (longform.ddpm_sample_windows)."""
         from .longform import ddpm_sample_windows
@@ -470,44 +539,9 @@ class Diffusion:
         reached (`keep_region`, indexed by the step that consumes the state), so the result holds the source there, bit for bit.
         `start_step` > 0 runs steps start_step .. steps - 1 of the same tables from the source noised to a_t[start_step], instead
         of from x_T.  Step numbers, and with them the step noise, are unchanged."""
-        source, keep = check_keep_args(x_T, source, keep, start_step, steps)
-        _native.require_cuda(x_T, source, keep)
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        stack = few_guided_steps_promotion("ddpm_sample", steps, predictor, cond_fn)
-        if stack is not None:
-            with stack:
-                return self.ddpm_sample(x_T, predictor, steps, progress=progress, sigma_large=sigma_large, constrain=constrain,
-                                        cond_fn=cond_fn, schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset,
-                                        source=source, keep=keep, start_step=start_step)
-        x_t = x_T
-        B = x_T.shape[0]
-        ts_all, a_t_all, a_prev_all, ts_prev_all = self.step_tables(steps, B, schedule, x_T.device)
-        if source is not None:
-            x_t = self._keep_start(x_T, source, keep, a_t_all[start_step], start_step=start_step, seed=seed, clip_offset=clip_offset)
-        its = range(start_step, steps)
-        if progress:
-            from tqdm.auto import tqdm
-
-            its = tqdm(its, total=steps - start_step)
-        for i in its:
-            with torch.no_grad():
-                eps = predictor(x_t, ts_all[i])
-                last = i + 1 == steps
-                if last or noise is None:
-                    nz = None
-                elif callable(noise):
-                    nz = noise(i)
-                else:
-                    nz = noise[i]
-                _native.require_cuda(eps, nz)
-                x_t = self._step(x_t, eps, a_t_all[i], a_prev_all[i], ts_prev_all[i], noise=nz, sigma_large=sigma_large,
-                                 constrain=constrain, cond_fn=cond_fn, seed=seed, clip_offset=clip_offset, step_index=i,
-                                 noise_scale=0.0 if last else 1.0)
-                if keep is not None:  # (the step's output is a fresh float32 tensor of this loop's)
-                    self._keep_(x_t, source, keep, a_prev_all[i], seed=seed, clip_offset=clip_offset, index=i + 1)
-        self.check_sample(predictor, x_t, "ddpm_sample")
-        return x_t
+        return self._sample("ddpm_sample", _Clips(self, _Ddpm(sigma_large, constrain), predictor, cond_fn), x_T, steps, schedule=schedule,
+                            noise=noise, seed=seed, clip_offset=clip_offset, progress=progress, source=source, keep=keep,
+                            start_step=start_step)
 
     # ---- DDIM (Song et al. 2020; not in the reference): DESIGN.md section 3.10 -----------------------
     def ddim_previous(
@@ -586,43 +620,9 @@ class Diffusion:
         words, zero noise on the last iteration -- which, stepping to alpha_bar(0) = 1, returns x0 itself.  At eta = 0 the result
         depends on x_T alone -- and, with `source` / `keep` / `start_step` (as in `ddpm_sample`; the kept samples are replaced at the
         alpha_bar stepped TO), on the seed of the replacement noise."""
-        source, keep = check_keep_args(x_T, source, keep, start_step, steps)
-        _native.require_cuda(x_T, source, keep)
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        stack = few_guided_steps_promotion("ddim_sample", steps, predictor, cond_fn)
-        if stack is not None:
-            with stack:
-                return self.ddim_sample(x_T, predictor, steps, eta=eta, progress=progress, constrain=constrain, cond_fn=cond_fn,
-                                        schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset, source=source, keep=keep,
-                                        start_step=start_step)
-        warn_few_unguided_steps("ddim_sample", steps, predictor, cond_fn)
-        x_t = x_T
-        ts_all, a_t_all, a_to_all, _ = self.step_tables(steps, x_T.shape[0], schedule, x_T.device)
-        if source is not None:
-            x_t = self._keep_start(x_T, source, keep, a_t_all[start_step], start_step=start_step, seed=seed, clip_offset=clip_offset)
-        its = range(start_step, steps)
-        if progress:
-            from tqdm.auto import tqdm
-
-            its = tqdm(its, total=steps - start_step)
-        for i in its:
-            with torch.no_grad():
-                eps = predictor(x_t, ts_all[i])
-                last = i + 1 == steps
-                if last or noise is None or not eta:
-                    nz = None
-                elif callable(noise):
-                    nz = noise(i)
-                else:
-                    nz = noise[i]
-                _native.require_cuda(eps, nz)
-                x_t = self._ddim_step(x_t, eps, a_t_all[i], a_to_all[i], ts_all[i], noise=nz, eta=eta, constrain=constrain, cond_fn=cond_fn,
-                                      seed=seed, clip_offset=clip_offset, step_index=i, noise_scale=0.0 if last else 1.0)
-                if keep is not None:
-                    self._keep_(x_t, source, keep, a_to_all[i], seed=seed, clip_offset=clip_offset, index=i + 1)
-        self.check_sample(predictor, x_t, "ddim_sample")
-        return x_t
+        return self._sample("ddim_sample", _Clips(self, _Ddim(eta, constrain), predictor, cond_fn), x_T, steps, schedule=schedule,
+                            noise=noise, seed=seed, clip_offset=clip_offset, progress=progress, source=source, keep=keep,
+                            start_step=start_step)
 
     def ddim_invert(self, x_0: torch.Tensor, predictor: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], steps: int,
                     schedule: Optional[Callable] = None, progress: bool = False) -> torch.Tensor:
@@ -633,12 +633,7 @@ class Diffusion:
         error."""
         x_t = x_0
         _, a_t_all, a_prev_all, ts_prev_all = self.step_tables(steps, x_0.shape[0], schedule, x_0.device)
-        its = range(steps - 1, -1, -1)
-        if progress:
-            from tqdm.auto import tqdm
-
-            its = tqdm(its, total=steps)
-        for i in its:
+        for i in _progress(range(steps - 1, -1, -1), progress):
             with torch.no_grad():
                 eps = predictor(x_t, ts_prev_all[i])
                 x_t = self._ddim_step(x_t, eps, a_prev_all[i], a_t_all[i], ts_prev_all[i], invert=True)
@@ -650,6 +645,57 @@ class Diffusion:
         from .longform import ddim_sample_windows
 
         return ddim_sample_windows(self, x_T_long, predictor, steps, **kwargs)
+
+
+class _Ddpm:
+    """The DDPM step rule of `Diffusion._sample`: `vqvs_ddpm_step`, guided -- inside `Diffusion._step` -- by `cond_fn(mean, t - step)`
+    between `vqvs_ddpm_mean` and `vqvs_ddpm_guided_eps`."""
+    name, draws_noise = "ddpm", True
+
+    def __init__(self, sigma_large: bool, constrain: bool):
+        self.sigma_large, self.constrain = sigma_large, constrain
+        self.flags = (_native.DDPM_SIGMA_LARGE if sigma_large else 0) | (_native.DDPM_CONSTRAIN if constrain else 0)
+
+    def step(self, diffusion, x_t, eps, tables, i, **kw):
+        _, a_t, a_prev, ts_prev = tables
+        return diffusion._step(x_t, eps, a_t[i], a_prev[i], ts_prev[i], sigma_large=self.sigma_large, constrain=self.constrain, **kw)
+
+
+class _Ddim:
+    """The DDIM step rule: `vqvs_ddim_step` at `eta` (0: no noise is drawn or asked for), guided by `cond_fn(x_t, t)` handed to the
+    kernel."""
+    name = "ddim"
+
+    def __init__(self, eta: float, constrain: bool):
+        self.eta, self.constrain, self.draws_noise = eta, constrain, bool(eta)
+        self.flags = _native.DDIM_CONSTRAIN if constrain else 0
+
+    def step(self, diffusion, x_t, eps, tables, i, **kw):
+        ts, a_t, a_to, _ = tables
+        return diffusion._ddim_step(x_t, eps, a_t[i], a_to[i], ts[i], eta=self.eta, constrain=self.constrain, **kw)
+
+
+class _Clips:
+    """The state layout of `ddpm_sample` / `ddim_sample`: a batch of clips [B, ..., T], predicted and stepped whole."""
+
+    def __init__(self, diffusion: Diffusion, rule, predictor: Callable, cond_fn: Optional[Callable]):
+        self.diffusion, self.rule, self.predictor, self.cond_fn = diffusion, rule, predictor, cond_fn
+
+    def rows(self, x_T) -> int:
+        return x_T.shape[0]
+
+    def start(self, x_T, source, keep, alpha, **kw):
+        return x_T if source is None else self.diffusion._keep_start(x_T, source, keep, alpha, **kw)
+
+    def predict(self, x_t, tables, i):
+        return self.predictor(x_t, tables[0][i])
+
+    def step(self, x_t, eps, nz, tables, i, **kw):
+        _native.require_cuda(eps, nz)
+        return self.rule.step(self.diffusion, x_t, eps, tables, i, noise=nz, cond_fn=self.cond_fn, step_index=i, **kw)
+
+    def keep(self, x_t, source, keep, alpha, **kw) -> None:
+        self.diffusion._keep_(x_t, source, keep, alpha, **kw)
 
 
 def randn_clips(n: int, T: int, device, seed: int, clip_offset: int = 0, stream_id: int = 1) -> torch.Tensor:

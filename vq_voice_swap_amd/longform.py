@@ -83,6 +83,103 @@ def pad_source_keep(source: Optional[torch.Tensor], keep: Optional[torch.Tensor]
     return source, keep
 
 
+def _ddpm_fill(rule, xw, e, tables, i, b0, cond_fn, eps, grad, st) -> None:
+    """The DDPM rule on one slice of windows: the prediction `e`, or -- guided -- the two half-steps of `Diffusion._step` around
+    cond_fn, written straight into the slice's rows of `eps`."""
+    m, window = xw.shape[0], xw.shape[-1]
+    e = e.detach().to(torch.float32).contiguous()
+    if cond_fn is None:
+        eps[b0:b0 + m].copy_(e)
+        return
+    L = _native.lib()
+    a_t, a_prev = tables[1][i, :m], tables[2][i, :m]
+    mean = torch.empty_like(xw)
+    _native.check(L.vqvs_ddpm_mean(xw.data_ptr(), e.data_ptr(), a_t.data_ptr(), a_prev.data_ptr(), mean.data_ptr(), m, window, st))
+    g = cond_fn(mean, tables[3][i, :m], first=b0).detach().to(torch.float32).contiguous()
+    _native.check(L.vqvs_ddpm_guided_eps(xw.data_ptr(), mean.data_ptr(), g.data_ptr(), a_t.data_ptr(), a_prev.data_ptr(),
+                                         eps[b0:b0 + m].data_ptr(), m, window, rule.flags, st))
+
+
+def _ddim_fill(rule, xw, e, tables, i, b0, cond_fn, eps, grad, st) -> None:
+    """The DDIM rule on one slice of windows: the prediction into `eps` and cond_fn's gradient AT the windows the predictor saw
+    into `grad`, which the step kernel applies per window."""
+    m = xw.shape[0]
+    eps[b0:b0 + m].copy_(e.detach())
+    if cond_fn is not None:
+        g = cond_fn(xw, tables[0][i, :m], first=b0)
+        _native.require_cuda(g)
+        if tuple(g.shape) != tuple(xw.shape):
+            raise ValueError(f"cond_fn returned shape {tuple(g.shape)} for windows of shape {tuple(xw.shape)}")
+        grad[b0:b0 + m].copy_(g.detach())
+
+
+def _ddpm_step_windows(rule, x, eps, grad, nz, a_t, a_to, x_to, next_windows, n, window, hop, noise_scale, seed, clip_offset, step_index, st) -> None:
+    _native.check(_native.lib().vqvs_ddpm_step_windows(x.data_ptr(), eps.data_ptr(), _native._ptr(nz), a_t.data_ptr(), a_to.data_ptr(),
+                                                       x_to.data_ptr(), next_windows.data_ptr(), n, window, hop, rule.flags, noise_scale,
+                                                       int(seed), int(clip_offset), step_index, st))
+
+
+def _ddim_step_windows(rule, x, eps, grad, nz, a_t, a_to, x_to, next_windows, n, window, hop, noise_scale, seed, clip_offset, step_index, st) -> None:
+    _native.check(_native.lib().vqvs_ddim_step_windows(x.data_ptr(), eps.data_ptr(), _native._ptr(grad), _native._ptr(nz), a_t.data_ptr(),
+                                                       a_to.data_ptr(), x_to.data_ptr(), next_windows.data_ptr(), n, window, hop,
+                                                       rule.flags, float(rule.eta), noise_scale, int(seed), int(clip_offset), step_index, st))
+
+
+class _Windows:
+    """The state layout of the two window loops for `Diffusion._sample`: the long row [Np], with its window batch [n,1,window] kept
+    beside it.  The predictor and cond_fn see slices of at most `window_batch` windows, with `first=`; `fill` and `step` are the
+    rule's window forms above."""
+
+    def __init__(self, rule, predictor: Callable, cond_fn: Optional[Callable], window: int, hop: int, window_batch: int, fill, step):
+        self.rule, self.predictor, self.cond_fn, self.fill, self.step_windows = rule, predictor, cond_fn, fill, step
+        self.window, self.hop, self.window_batch = window, hop, window_batch
+
+    def rows(self, x_T_long) -> int:
+        """The input checks; the tables hold one row per window of a slice."""
+        if x_T_long.dim() != 3 or x_T_long.shape[0] != 1 or x_T_long.shape[1] != 1:
+            raise ValueError(f"x_T_long must be [1, 1, Np], got {tuple(x_T_long.shape)}")
+        self.Np = x_T_long.shape[2]
+        self.n, padded = plan_windows(self.Np, self.window, self.hop)
+        if padded != self.Np:
+            raise ValueError(f"x_T_long has {self.Np} samples: {self.n} windows of {self.window} every {self.hop} span {padded} (see plan_windows)")
+        if self.window_batch < 1:
+            raise ValueError(f"window_batch={self.window_batch} must be at least 1")
+        self.mb = min(self.n, int(self.window_batch))
+        return self.mb
+
+    def start(self, x_T_long, source, keep, alpha, **kw):
+        x, self.windows = start_windows(x_T_long, source, keep, alpha, n=self.n, window=self.window, hop=self.hop, **kw)
+        self.eps = torch.empty_like(self.windows)
+        self.grad = torch.empty_like(self.windows) if self.cond_fn is not None and self.rule.name == "ddim" else None
+        return x
+
+    def predict(self, x, tables, i) -> None:
+        self.st = _native._stream_ptr()  # (of this step: the slices' kernels and the step kernel)
+        for b0 in range(0, self.n, self.mb):
+            m = min(self.mb, self.n - b0)
+            xw = self.windows[b0:b0 + m]
+            e = self.predictor(xw, tables[0][i, :m], first=b0)
+            _native.require_cuda(e)
+            if tuple(e.shape) != tuple(xw.shape):
+                raise ValueError(f"the predictor returned shape {tuple(e.shape)} for windows of shape {tuple(xw.shape)}")
+            self.fill(self.rule, xw, e, tables, i, b0, self.cond_fn, self.eps, self.grad, self.st)
+
+    def step(self, x, _, nz, tables, i, *, noise_scale, seed, clip_offset):
+        if nz is not None:
+            _native.require_cuda(nz)
+            nz = nz.detach().to(torch.float32).contiguous()
+            if nz.numel() != self.Np:
+                raise ValueError(f"noise of step {i} has {nz.numel()} values: expected [1, 1, {self.Np}]")
+        x_to, next_windows = torch.empty_like(x), torch.empty_like(self.windows)
+        self.step_windows(self.rule, x, self.eps, self.grad, nz, tables[1][i], tables[2][i], x_to, next_windows, self.n, self.window, self.hop,
+                          noise_scale, seed, clip_offset, i, self.st)
+        self.windows = next_windows
+        return x_to
+
+    def keep(self, x, source, keep, alpha, **kw) -> None:
+        keep_windows_(x, self.windows, source, keep, alpha, n=self.n, window=self.window, hop=self.hop, **kw)
+
+
 def ddpm_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, steps: int, *, window: int, hop: int,
                         window_batch: int = 64, constrain: bool = False, sigma_large: bool = False, cond_fn: Optional[Callable] = None,
                         schedule: Optional[Callable] = None, noise=None, seed: Optional[int] = None, clip_offset: int = 0,
@@ -98,78 +195,11 @@ def ddpm_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, 
     kernel from (seed, clip_offset, step): the draws of row `clip_offset` of a batch of clips of length Np.
     `source`, `keep` ([1,1,Np]) and `start_step` are `ddpm_sample`'s, applied by `vqvs_keep_region_windows` to the long state and to
     both window copies of an overlap sample."""
-    from .diffusion import check_keep_args, few_guided_steps_promotion
+    from .diffusion import _Ddpm
 
-    source, keep = check_keep_args(x_T_long, source, keep, start_step, steps)
-    _native.require_cuda(x_T_long, source, keep)
-    if x_T_long.dim() != 3 or x_T_long.shape[0] != 1 or x_T_long.shape[1] != 1:
-        raise ValueError(f"x_T_long must be [1, 1, Np], got {tuple(x_T_long.shape)}")
-    Np = x_T_long.shape[2]
-    n, padded = plan_windows(Np, window, hop)
-    if padded != Np:
-        raise ValueError(f"x_T_long has {Np} samples: {n} windows of {window} every {hop} span {padded} (see plan_windows)")
-    if window_batch < 1:
-        raise ValueError(f"window_batch={window_batch} must be at least 1")
-    if seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-    stack = few_guided_steps_promotion("ddpm_sample_windows", steps, predictor, cond_fn)
-    if stack is not None:
-        with stack:
-            return ddpm_sample_windows(diffusion, x_T_long, predictor, steps, window=window, hop=hop, window_batch=window_batch,
-                                       constrain=constrain, sigma_large=sigma_large, cond_fn=cond_fn, schedule=schedule, noise=noise,
-                                       seed=seed, clip_offset=clip_offset, progress=progress, source=source, keep=keep,
-                                       start_step=start_step)
-    dev = x_T_long.device
-    mb = min(n, int(window_batch))
-    ts_all, a_t_all, a_prev_all, ts_prev_all = diffusion.step_tables(steps, mb, schedule, dev)
-    flags = (_native.DDPM_SIGMA_LARGE if sigma_large else 0) | (_native.DDPM_CONSTRAIN if constrain else 0)
-    L = _native.lib()
-    x, windows = start_windows(x_T_long, source, keep, a_t_all[start_step], start_step=start_step, n=n, window=window, hop=hop, seed=seed,
-                               clip_offset=clip_offset)
-    eps = torch.empty_like(windows)
-    its = range(start_step, steps)
-    if progress:
-        from tqdm.auto import tqdm
-
-        its = tqdm(its, total=steps - start_step)
-    with torch.no_grad(), torch.cuda.device(dev):
-        for i in its:
-            st = _native._stream_ptr()
-            for b0 in range(0, n, mb):
-                m = min(mb, n - b0)
-                xw = windows[b0:b0 + m]
-                e = predictor(xw, ts_all[i, :m], first=b0)
-                _native.require_cuda(e)
-                if tuple(e.shape) != tuple(xw.shape):
-                    raise ValueError(f"the predictor returned shape {tuple(e.shape)} for windows of shape {tuple(xw.shape)}")
-                e = e.detach().to(torch.float32).contiguous()
-                if cond_fn is not None:  # the two half-steps of Diffusion._step around cond_fn, on this slice of windows
-                    a_t, a_prev = a_t_all[i, :m], a_prev_all[i, :m]
-                    mean = torch.empty_like(xw)
-                    _native.check(L.vqvs_ddpm_mean(xw.data_ptr(), e.data_ptr(), a_t.data_ptr(), a_prev.data_ptr(), mean.data_ptr(), m, window, st))
-                    grad = cond_fn(mean, ts_prev_all[i, :m], first=b0).detach().to(torch.float32).contiguous()
-                    _native.check(L.vqvs_ddpm_guided_eps(xw.data_ptr(), mean.data_ptr(), grad.data_ptr(), a_t.data_ptr(), a_prev.data_ptr(),
-                                                         eps[b0:b0 + m].data_ptr(), m, window, flags, st))
-                else:
-                    eps[b0:b0 + m].copy_(e)
-            last = i + 1 == steps
-            nz = None
-            if not last and noise is not None:
-                nz = noise(i) if callable(noise) else noise[i]
-                _native.require_cuda(nz)
-                nz = nz.detach().to(torch.float32).contiguous()
-                if nz.numel() != Np:
-                    raise ValueError(f"noise of step {i} has {nz.numel()} values: expected [1, 1, {Np}]")
-            x_prev, next_windows = torch.empty_like(x), torch.empty_like(windows)
-            _native.check(L.vqvs_ddpm_step_windows(x.data_ptr(), eps.data_ptr(), _native._ptr(nz), a_t_all[i].data_ptr(), a_prev_all[i].data_ptr(),
-                                                   x_prev.data_ptr(), next_windows.data_ptr(), n, window, hop, flags, 0.0 if last else 1.0,
-                                                   int(seed), int(clip_offset), i, st))
-            if keep is not None:
-                keep_windows_(x_prev, next_windows, source, keep, a_prev_all[i], n=n, window=window, hop=hop, seed=seed,
-                              clip_offset=clip_offset, index=i + 1)
-            x, windows = x_prev, next_windows
-    diffusion.check_sample(predictor, x, "ddpm_sample_windows")
-    return x.view_as(x_T_long)
+    layout = _Windows(_Ddpm(sigma_large, constrain), predictor, cond_fn, window, hop, window_batch, _ddpm_fill, _ddpm_step_windows)
+    return diffusion._sample("ddpm_sample_windows", layout, x_T_long, steps, schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset,
+                             progress=progress, source=source, keep=keep, start_step=start_step)
 
 
 def ddim_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, steps: int, *, window: int, hop: int,
@@ -182,76 +212,11 @@ def ddim_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, 
     windows the predictor saw and at their t; its gradients fill a [n, window] batch that the step kernel applies per window, before
     the windows' predictions are blended -- one kernel after the forwards, no half-steps.  `source`, `keep` and `start_step` are as
     there, the kept samples replaced at the alpha_bar stepped TO."""
-    from .diffusion import check_keep_args, few_guided_steps_promotion, warn_few_unguided_steps
+    from .diffusion import _Ddim
 
-    source, keep = check_keep_args(x_T_long, source, keep, start_step, steps)
-    _native.require_cuda(x_T_long, source, keep)
-    if x_T_long.dim() != 3 or x_T_long.shape[0] != 1 or x_T_long.shape[1] != 1:
-        raise ValueError(f"x_T_long must be [1, 1, Np], got {tuple(x_T_long.shape)}")
-    Np = x_T_long.shape[2]
-    n, padded = plan_windows(Np, window, hop)
-    if padded != Np:
-        raise ValueError(f"x_T_long has {Np} samples: {n} windows of {window} every {hop} span {padded} (see plan_windows)")
-    if window_batch < 1:
-        raise ValueError(f"window_batch={window_batch} must be at least 1")
-    if seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-    stack = few_guided_steps_promotion("ddim_sample_windows", steps, predictor, cond_fn)
-    if stack is not None:
-        with stack:
-            return ddim_sample_windows(diffusion, x_T_long, predictor, steps, window=window, hop=hop, window_batch=window_batch, eta=eta,
-                                       constrain=constrain, cond_fn=cond_fn, schedule=schedule, noise=noise, seed=seed,
-                                       clip_offset=clip_offset, progress=progress, source=source, keep=keep, start_step=start_step)
-    warn_few_unguided_steps("ddim_sample_windows", steps, predictor, cond_fn)
-    dev = x_T_long.device
-    mb = min(n, int(window_batch))
-    ts_all, a_t_all, a_to_all, _ = diffusion.step_tables(steps, mb, schedule, dev)
-    flags = _native.DDIM_CONSTRAIN if constrain else 0
-    L = _native.lib()
-    x, windows = start_windows(x_T_long, source, keep, a_t_all[start_step], start_step=start_step, n=n, window=window, hop=hop, seed=seed,
-                               clip_offset=clip_offset)
-    eps = torch.empty_like(windows)
-    grad = torch.empty_like(windows) if cond_fn is not None else None
-    its = range(start_step, steps)
-    if progress:
-        from tqdm.auto import tqdm
-
-        its = tqdm(its, total=steps - start_step)
-    with torch.no_grad(), torch.cuda.device(dev):
-        for i in its:
-            st = _native._stream_ptr()
-            for b0 in range(0, n, mb):
-                m = min(mb, n - b0)
-                xw = windows[b0:b0 + m]
-                e = predictor(xw, ts_all[i, :m], first=b0)
-                _native.require_cuda(e)
-                if tuple(e.shape) != tuple(xw.shape):
-                    raise ValueError(f"the predictor returned shape {tuple(e.shape)} for windows of shape {tuple(xw.shape)}")
-                eps[b0:b0 + m].copy_(e.detach())
-                if cond_fn is not None:
-                    g = cond_fn(xw, ts_all[i, :m], first=b0)
-                    _native.require_cuda(g)
-                    if tuple(g.shape) != tuple(xw.shape):
-                        raise ValueError(f"cond_fn returned shape {tuple(g.shape)} for windows of shape {tuple(xw.shape)}")
-                    grad[b0:b0 + m].copy_(g.detach())
-            last = i + 1 == steps
-            nz = None
-            if not last and noise is not None and eta:
-                nz = noise(i) if callable(noise) else noise[i]
-                _native.require_cuda(nz)
-                nz = nz.detach().to(torch.float32).contiguous()
-                if nz.numel() != Np:
-                    raise ValueError(f"noise of step {i} has {nz.numel()} values: expected [1, 1, {Np}]")
-            x_to, next_windows = torch.empty_like(x), torch.empty_like(windows)
-            _native.check(L.vqvs_ddim_step_windows(x.data_ptr(), eps.data_ptr(), _native._ptr(grad), _native._ptr(nz), a_t_all[i].data_ptr(),
-                                                   a_to_all[i].data_ptr(), x_to.data_ptr(), next_windows.data_ptr(), n, window, hop, flags,
-                                                   float(eta), 0.0 if last else 1.0, int(seed), int(clip_offset), i, st))
-            if keep is not None:
-                keep_windows_(x_to, next_windows, source, keep, a_to_all[i], n=n, window=window, hop=hop, seed=seed,
-                              clip_offset=clip_offset, index=i + 1)
-            x, windows = x_to, next_windows
-    diffusion.check_sample(predictor, x, "ddim_sample_windows")
-    return x.view_as(x_T_long)
+    layout = _Windows(_Ddim(eta, constrain), predictor, cond_fn, window, hop, window_batch, _ddim_fill, _ddim_step_windows)
+    return diffusion._sample("ddim_sample_windows", layout, x_T_long, steps, schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset,
+                             progress=progress, source=source, keep=keep, start_step=start_step)
 
 
 def encode_long(model, wave: torch.Tensor, window: int, hop: int, window_batch: int = 64) -> torch.Tensor:
@@ -284,18 +249,10 @@ def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = Non
     `ddim_sample_windows` with `eta` instead of `ddpm_sample_windows`.  `source` [1,1,num_samples] (the recording itself), `keep`
     (bool / uint8, [1,1,num_samples]: samples that stay the source's) and `strength` in (0, 1] (below 1: start from the noised
     source, `strength_to_start_step`) are `VQVAE.decode`'s."""
-    from .diffusion import check_sampler, randn_clips, strength_to_start_step
+    from .diffusion import fresh_seed, pick_sampler, randn_clips, source_start_step
 
-    start_step = strength_to_start_step(strength, steps)
-    if source is None and (keep is not None or start_step):
-        raise ValueError("keep= and strength < 1 need source=, the waveform whose samples are kept or noised")
-
-    if codes.dim() == 2:
-        cond_seq = model.vq.embed(codes)
-    elif codes.dim() == 3:
-        cond_seq = codes
-    else:
-        raise ValueError(f"unsupported codes shape: {codes.shape}")
+    start_step = source_start_step(source, keep, strength, steps)
+    cond_seq = model.cond_sequence(codes)
     check_rate(model, window, hop)
     n, padded = plan_windows(num_samples, window, hop)
     if cond_seq.shape[0] != n:
@@ -318,7 +275,7 @@ def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = Non
 
         cond_fn.native_modules = (enc_pred,)
     if seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        seed = fresh_seed()
 
     def predictor(xs, ts, first):
         sl = slice(first, first + xs.shape[0])
@@ -328,11 +285,8 @@ def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = Non
         source, keep = pad_source_keep(source, keep, num_samples, padded)
         kwargs.update(source=source, keep=keep, start_step=start_step)
     x_T = randn_clips(1, padded, codes.device, seed, clip_offset)
-    if check_sampler(sampler, eta) == "ddim":
-        out = ddim_sample_windows(model.diffusion, x_T, predictor, steps, window=window, hop=hop, window_batch=window_batch, eta=eta,
-                                  constrain=constrain, cond_fn=cond_fn, seed=seed, clip_offset=clip_offset, progress=progress, **kwargs)
-    else:
-        out = ddpm_sample_windows(model.diffusion, x_T, predictor, steps, window=window, hop=hop, window_batch=window_batch,
-                                  constrain=constrain, cond_fn=cond_fn, seed=seed, clip_offset=clip_offset, progress=progress, **kwargs)
+    sample, sampler_kw = pick_sampler(model.diffusion, sampler, eta, windows=True)
+    out = sample(x_T, predictor, steps, window=window, hop=hop, window_batch=window_batch, constrain=constrain, cond_fn=cond_fn, seed=seed,
+                 clip_offset=clip_offset, progress=progress, **sampler_kw, **kwargs)
     model.predictor.check_status()  # range guard of the decoder's mode (once per sample)
     return out[..., :num_samples]

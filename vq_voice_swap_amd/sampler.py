@@ -99,9 +99,10 @@ def sample_clips(
     if sample_fn is not None:
         local = sample_fn(begin, end, seed)
     else:
-        from .diffusion import check_sampler, randn_clips
+        from .diffusion import pick_sampler, randn_clips
 
-        if check_sampler(sampler, eta) == "ddim" and sigma_large:
+        sample, sampler_kw = pick_sampler(model.diffusion, sampler, eta, sigma_large=sigma_large)
+        if sampler == "ddim" and sigma_large:
             raise ValueError("sigma_large has no meaning for sampler='ddim'")
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device())
@@ -113,12 +114,7 @@ def sample_clips(
             if labels is not None:
                 lab = labels[begin:end].to(device)
                 pred = lambda xs, ts, _p=model.predictor, _l=lab: _p(xs, ts, labels=_l)  # noqa: E731
-            if sampler == "ddim":
-                local = model.diffusion.ddim_sample(x_T, pred, steps, eta=eta, constrain=constrain, schedule=schedule, seed=seed,
-                                                    clip_offset=begin)
-            else:
-                local = model.diffusion.ddpm_sample(x_T, pred, steps, constrain=constrain, sigma_large=sigma_large,
-                                                    schedule=schedule, seed=seed, clip_offset=begin)
+            local = sample(x_T, pred, steps, constrain=constrain, schedule=schedule, seed=seed, clip_offset=begin, **sampler_kw)
     if not gather:
         return local
     return gather_clips(local, n_total, T)

@@ -10,7 +10,7 @@ from typing import Any, Dict, Optional
 
 import torch
 
-from .diffusion import check_sampler, randn_clips, strength_to_start_step
+from .diffusion import fresh_seed, pick_sampler, randn_clips, source_start_step
 from .diffusion_model import DiffusionModel
 from .conv_encoder import ConvMFCCEncoder
 from .unet import UNetEncoder
@@ -49,6 +49,24 @@ class VQVAE(DiffusionModel):
         self.encoder.set_precision(encoder_precision)  # (ConvMFCCEncoder accepts fp32 only)
         return self
 
+    def cond_sequence(self, codes: torch.Tensor) -> torch.Tensor:
+        """codes [N,T1] int (embedded here) or [N,C,T1] float (taken as they are) -> the decoder's conditioning sequence [N,C,T1]."""
+        if codes.dim() == 2:
+            return self.vq.embed(codes)
+        if codes.dim() == 3:
+            return codes
+        raise ValueError(f"unsupported codes shape: {codes.shape}")
+
+    def _seed_and_x_T(self, codes: torch.Tensor, x_T: Optional[torch.Tensor], kwargs: dict):
+        """(seed, x_T) of a decode: `seed` taken out of the sampler's keywords or drawn, x_T drawn from it at their `clip_offset`."""
+        seed = kwargs.pop("seed", None)
+        if seed is None:
+            seed = fresh_seed()
+        if x_T is None:
+            T = codes.shape[-1] * self.encoder.downsample_rate
+            x_T = randn_clips(codes.shape[0], T, codes.device, seed, kwargs.get("clip_offset", 0))
+        return seed, x_T
+
     def encode(self, inputs: torch.Tensor) -> torch.Tensor:
         """[N,1,T] waveform -> [N,T/256] int64 codes (vq_vae.py:82-90)."""
         with torch.no_grad():
@@ -74,7 +92,7 @@ class VQVAE(DiffusionModel):
 
         _native.require_cuda(inputs, labels, noise, hist)
         if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            seed = fresh_seed()
         if ts is None:
             ts = self.diffusion.draw_ts(inputs.shape[0], seed, clip_offset)
         with torch.no_grad():
@@ -98,34 +116,20 @@ class VQVAE(DiffusionModel):
         `source` [N,1,T] is the waveform being converted: the samples `keep` marks (bool / uint8, [N,1,T]) stay the source's, bit for
         bit, and are shown to the predictor at every noise level; `strength` in (0, 1] below 1 starts from the source noised to step
         `strength_to_start_step(strength, steps)` instead of from x_T."""
-        start_step = strength_to_start_step(strength, steps)
-        if source is None and (keep is not None or start_step):
-            raise ValueError("keep= and strength < 1 need source=, the waveform whose samples are kept or noised")
+        start_step = source_start_step(source, keep, strength, steps)
         if source is not None:
             kwargs.update(source=source, keep=keep, start_step=start_step)
-        if codes.dim() == 2:
-            cond_seq = self.vq.embed(codes)
-        elif codes.dim() == 3:
-            cond_seq = codes
-        else:
-            raise ValueError(f"unsupported codes shape: {codes.shape}")
+        cond_seq = self.cond_sequence(codes)
         cond_fn = None
         if enc_pred is not None:  # vq_vae.py:123-130: guidance towards the codes, gradient from the native backward schedule
             targets = self.vq.encode(cond_seq)
             cond_fn = enc_pred.guidance_fn(targets, enc_pred_scale)
 
-        T = codes.shape[-1] * self.encoder.downsample_rate
-        seed = kwargs.pop("seed", None)
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        if x_T is None:
-            x_T = randn_clips(codes.shape[0], T, codes.device, seed, kwargs.get("clip_offset", 0))
-        if check_sampler(sampler, eta) == "ddim":
-            kwargs["eta"] = eta
-        sample = self.diffusion.ddim_sample if sampler == "ddim" else self.diffusion.ddpm_sample
+        seed, x_T = self._seed_and_x_T(codes, x_T, kwargs)
+        sample, sampler_kw = pick_sampler(self.diffusion, sampler, eta)
         out = sample(
             x_T, lambda xs, ts, **kw: self.predictor(xs, ts, cond=cond_seq, labels=labels, **kw),
-            steps=steps, progress=progress, constrain=constrain, cond_fn=cond_fn, seed=seed, **kwargs)
+            steps=steps, progress=progress, constrain=constrain, cond_fn=cond_fn, seed=seed, **sampler_kw, **kwargs)
         self.predictor.check_status()  # range guard of the decoder's mode (once per sample)
         return out
 
@@ -137,12 +141,7 @@ class VQVAE(DiffusionModel):
         latent instead of a fresh draw."""
         if codes is None:
             codes = self.encode(inputs)
-        if codes.dim() == 2:
-            cond_seq = self.vq.embed(codes)
-        elif codes.dim() == 3:
-            cond_seq = codes
-        else:
-            raise ValueError(f"unsupported codes shape: {codes.shape}")
+        cond_seq = self.cond_sequence(codes)
         T = codes.shape[-1] * self.encoder.downsample_rate
         if inputs.dim() != 3 or inputs.shape[0] != cond_seq.shape[0] or inputs.shape[-1] != T:
             raise ValueError(f"inputs of shape {tuple(inputs.shape)} do not match codes for {cond_seq.shape[0]} clips of {T} samples")
@@ -171,19 +170,9 @@ class VQVAE(DiffusionModel):
         vq_vae.py:147-220): the predictor runs on a 1x-3x batch [conditional | codes dropped | label dropped] and the
         prediction is base + scale * (base - dropped).  Labels are NOT offset by the caller: label 0 is the
         unconditional label of such a model, so `labels + 1` is used as in the reference."""
-        if codes.dim() == 2:
-            cond_seq = self.vq.embed(codes)
-        elif codes.dim() == 3:
-            cond_seq = codes
-        else:
-            raise ValueError(f"unsupported codes shape: {codes.shape}")
+        cond_seq = self.cond_sequence(codes)
         n = cond_seq.shape[0]
-        T = codes.shape[-1] * self.encoder.downsample_rate
-        seed = kwargs.pop("seed", None)
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        if x_T is None:
-            x_T = randn_clips(n, T, codes.device, seed, kwargs.get("clip_offset", 0))
+        seed, x_T = self._seed_and_x_T(codes, x_T, kwargs)
 
         use_vq = bool(vq_scale)
         use_label = labels is not None and bool(label_scale)
@@ -221,11 +210,9 @@ class VQVAE(DiffusionModel):
             warnings.warn(f"decode_uncond_guidance: the predictor runs in the fp32 mode for this call (decoder mode {prev!r} does not "
                           "meet the 1e-3 waveform contract under guidance extrapolation)", stacklevel=2)
         # (precision_override keeps the decoder's own handle and arena; the fp32 handle is cached beside it for the next call)
-        if check_sampler(sampler, eta) == "ddim":
-            kwargs["eta"] = eta
-        sample = self.diffusion.ddim_sample if sampler == "ddim" else self.diffusion.ddpm_sample
+        sample, sampler_kw = pick_sampler(self.diffusion, sampler, eta)
         with self.predictor.precision_override("fp32" if promote else prev):
-            out = sample(x_T, pred_fn, steps=steps, progress=progress, constrain=constrain, seed=seed, **kwargs)
+            out = sample(x_T, pred_fn, steps=steps, progress=progress, constrain=constrain, seed=seed, **sampler_kw, **kwargs)
             self.predictor.check_status()
         return out
 
