@@ -292,6 +292,48 @@ int vqvs_ddim_step(const float* d_x_t, const float* d_eps, const float* d_grad, 
 int vqvs_ddim_step_windows(const float* d_x, const float* d_eps, const float* d_grad, const float* d_noise, const float* d_alpha_t,
                            const float* d_alpha_to, float* d_x_to, float* d_windows, int n, int W, int H, uint32_t flags, float eta,
                            float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index, void* stream);
+/* ---- DPM-Solver++(2M) step (handle-less; Lu, Zhou, Bao, Chen, Li, Zhu: "DPM-Solver++: fast solver for guided sampling of diffusion
+ * probabilistic models", 2022, Algorithm 2 -- the reference has no counterpart) ----
+ * The second-order multistep solver of the probability-flow ODE in data-prediction form: one step of B rows of T samples from
+ * alpha_bar = a_t to a_to, with the x0 prediction and the alpha_bar (a_from) of the step before as history.  With alpha = sqrt(a),
+ * sigma = sqrt(1 - a) and lambda(a) = (log a - log1p(-a)) / 2:
+ *   x0   = exactly what vqvs_ddim_step forms: e = eps or, with d_grad, fmaf(-sigma_t, grad, eps); x0 = fmaf(-sigma_t, e, x) * (1/alpha_t)
+ *          or, with VQVS_DDIM_CONSTRAIN (bit 2, the only defined flag), clamp(fmaf(fmaf(-sigma_t, e, x), 1/alpha_t, -mean), -1, 1) about
+ *          the row's mean of x0 of the guided prediction (fp64 sums per 4096 samples, as there: B * ceil(T / 4096) doubles of the
+ *          per-(device, stream) scratch buffer)
+ *   h    = lambda(a_to) - lambda(a_t),  h_prev = lambda(a_t) - lambda(a_from),  q = h / (2 h_prev)
+ *   c_x  = sigma_to / sigma_t,  phi = alpha_to - sigma_to alpha_t / sigma_t   ( = alpha_to (1 - exp(-h)), without forming h)
+ *   c0   = phi (1 + q),  c1 = -phi q
+ *   x_to = fmaf(c_x, x, fmaf(c0, x0, c1 * x0_prev));  d_x0_out = x0, the history of the next call
+ * Order: the step is FIRST order -- q = 0, x_to = fmaf(c_x, x, c0 * x0), d_x0_prev is not read -- when d_x0_prev is NULL, d_alpha_from
+ * is NULL, 1 - a_to == 0, h_prev is not > 0 (a_from == a_t, or a history from a smaller t), or q is not finite; otherwise second
+ * order.  At first order the step is algebraically vqvs_ddim_step's at eta = 0; at 1 - a_to == 0, c_x = 0 and phi = 1: the result
+ * is x0.  No noise is drawn: the step is deterministic.
+ * Coefficients: every per-row scalar (sigma_t, 1/alpha_t, c_x, c0, c1, the mean) is computed IN FP64 from the fp32 alphas and rounded
+ * to fp32 ONCE, the rule of vqvs_ddim_step; the per-sample operations are fp32 with the fmaf's where they are written (contraction off
+ * elsewhere).  Alphas outside (0, 1) give whatever the formulas give, as there.
+ *   d_x_t, d_eps [B,T] f32; d_grad [B,T] f32 or NULL; d_x0_prev [B,T] f32 or NULL; d_alpha_from [B] f32 or NULL;
+ *   d_alpha_t, d_alpha_to [B] f32; d_x_to [B,T] f32 out; d_x0_out [B,T] f32 out or NULL
+ * Aliasing: d_x0_out may be the SAME pointer as d_x0_prev (each element is read, then written, by one thread).  Any T: 16-byte
+ * accesses when T % 4 == 0 and the buffers are 16-byte aligned, one sample at a time otherwise; the values do not depend on which.
+ * VQVS_ERR_ARG before the device is touched: NULL d_x_t, d_eps, d_alpha_t, d_alpha_to or d_x_to; B outside 1..65535, T outside
+ * 1..2^30; any flag bit but VQVS_DDIM_CONSTRAIN; d_x_to or d_x0_out overlapping an input (but for d_x0_out == d_x0_prev) or each other. */
+int vqvs_dpmpp_step(const float* d_x_t, const float* d_eps, const float* d_grad, const float* d_x0_prev, const float* d_alpha_from,
+                    const float* d_alpha_t, const float* d_alpha_to, float* d_x_to, float* d_x0_out, int B, int T, uint32_t flags,
+                    void* stream);
+/* The DPM-Solver++(2M) step of ONE long signal predicted through overlapping windows: the geometry, limits, 16-byte accesses,
+ * per-window means and d_windows side output of vqvs_ddim_step_windows, the arithmetic of vqvs_dpmpp_step.
+ *   d_x [Np], d_eps [n,W], d_grad [n,W] or NULL, d_x0_prev [Np] or NULL, ONE d_alpha_from (or NULL) / d_alpha_t / d_alpha_to,
+ *   d_x_to [Np] out, d_x0_out [Np] out or NULL, d_windows [n,W] out or NULL: d_windows[b,j] = d_x_to[b * H + j]
+ * A window b that covers p contributes its own x0_b, guided by its own gradient and constrained about its own mean.  One window: it is
+ * used as it is.  Two, left and right, w = (u + 1/2) / V as there: x0 = fmaf(w, x0_r - x0_l, x0_l).  The history d_x0_prev / d_x0_out
+ * is this BLENDED x0 in the long layout, one value per absolute position; then the x_to line above.  d_x0_out may be d_x0_prev itself.
+ * At n = 1 the result equals vqvs_dpmpp_step(B = 1, T = W) bit for bit; at V = 0 without CONSTRAIN it equals one row of n * W samples.
+ * VQVS_ERR_ARG before the device is touched: every limit of vqvs_ddpm_step_windows, the flag rule of vqvs_dpmpp_step, and d_x_to,
+ * d_x0_out or d_windows overlapping an input (but for d_x0_out == d_x0_prev) or each other. */
+int vqvs_dpmpp_step_windows(const float* d_x, const float* d_eps, const float* d_grad, const float* d_x0_prev, const float* d_alpha_from,
+                            const float* d_alpha_t, const float* d_alpha_to, float* d_x_to, float* d_x0_out, float* d_windows, int n, int W,
+                            int H, uint32_t flags, void* stream);
 /* ---- Keep region (handle-less; the "replacement" method of Song et al., "Score-based generative modeling through stochastic
  * differential equations", 2021, as in RePaint and SDEdit -- the reference has no counterpart) ----
  * IN PLACE on the state d_x [B,T]: every sample with d_keep[row,p] != 0 -- every sample when d_keep is NULL -- is put back on the

@@ -4,7 +4,7 @@ Sample waveforms from a diffusion model on MI355X.  Counterpart of the reference
 (same flags; reference sample_diffusion.py:125-141), running on the gfx950 library: x_T ~ N(0,1), optional
 class labels (uniform or --target-class), `ddpm_sample`, one 16 kHz mono s16 WAV per clip.
 Differences: WAV files are written directly (no ffmpeg); `--schedule` accepts "lambda t: t" / "lambda t: t**P"
-without eval; `--seed`, `--precision`, `--sampler {ddpm,ddim}` and `--eta` (the DDIM step, deterministic at eta 0) are new; so are `--stats-classifier`, `--stats-path`, `--stats-precision`, which score the run in
+without eval; `--seed`, `--precision`, `--sampler {ddpm,ddim,dpmpp}` and `--eta` (the DDIM step, deterministic at eta 0) are new; so are `--stats-classifier`, `--stats-path`, `--stats-precision`, which score the run in
 line: every written clip, as the WAV file holds it, goes through the classifier's stem at t = 0 and into the feature
 statistics that stat_generate.py computes from the files (same npz).  Classifier guidance (`--classifier-path`, reference
 sample_diffusion.py:30-42) runs on the same library: the classifier forward and the gradient of log p(y | x_t)
@@ -40,7 +40,7 @@ def arg_parser():
     p.add_argument("--encoding", default="linear", type=str)
     p.add_argument("--seed", default=None, type=int)
     p.add_argument("--precision", default="fp32", choices=["fp32", "fp16", "bf16"])
-    p.add_argument("--sampler", default="ddpm", choices=["ddpm", "ddim"])
+    p.add_argument("--sampler", default="ddpm", choices=["ddpm", "ddim", "dpmpp"])
     p.add_argument("--eta", type=float, default=0.0, help="DDIM noise level: 0 deterministic, 1 the DDPM step's variance (--sampler ddim)")
     p.add_argument("--stats-classifier", default=None, type=str, help="classifier checkpoint for in-line feature statistics")
     p.add_argument("--stats-path", default=None, type=str, help="npz of the in-line statistics (stat_generate.py's format)")
@@ -55,8 +55,8 @@ def parse_args(argv=None):
         parser.error("--stats-classifier and --stats-path must be given together")
     if args.stats_path is not None and (args.num_samples is None or args.num_samples < 2):
         parser.error("--stats-path needs --num-samples of at least 2 (a covariance needs two clips)")
-    if args.sampler == "ddpm" and args.eta:
-        parser.error("--eta belongs to --sampler ddim")
+    if args.sampler != "ddim" and args.eta:
+        parser.error("--eta belongs to --sampler ddim (ddpm has its own variance, dpmpp is deterministic)")
     if args.eta < 0:
         parser.error("--eta must not be negative")
     return args
@@ -89,6 +89,9 @@ def sample_batch(args, model, classifier, device, n, seed, clip_offset, schedule
     if args.sampler == "ddim":
         return model.diffusion.ddim_sample(x_T, pred, args.sample_steps, eta=args.eta, progress=n == 1, constrain=args.constrain,
                                            cond_fn=cond_fn, schedule=schedule, seed=seed, clip_offset=clip_offset)
+    if args.sampler == "dpmpp":
+        return model.diffusion.dpmpp_sample(x_T, pred, args.sample_steps, progress=n == 1, constrain=args.constrain,
+                                            cond_fn=cond_fn, schedule=schedule, seed=seed, clip_offset=clip_offset)
     return model.diffusion.ddpm_sample(x_T, pred, args.sample_steps, progress=n == 1, constrain=args.constrain,
                                        cond_fn=cond_fn, schedule=schedule, seed=seed, clip_offset=clip_offset)
 

@@ -31,7 +31,7 @@ def arg_parser(sampler_flags: bool = False, keep_flags: bool = False):
     which `main` parses (`parse_args`); without them the parser is the one of the DDPM-only script, flag for flag."""
     p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     if sampler_flags:
-        p.add_argument("--sampler", default="ddpm", choices=["ddpm", "ddim"])
+        p.add_argument("--sampler", default="ddpm", choices=["ddpm", "ddim", "dpmpp"])
         p.add_argument("--eta", type=float, default=0.0, help="DDIM noise level: 0 deterministic, 1 the DDPM step's variance (--sampler ddim)")
         p.add_argument("--source-label", type=int, default=None,
                        help="with --sampler ddim: start from the DDIM inversion of the input under this label (the speaker it was spoken by)")
@@ -65,8 +65,8 @@ def arg_parser(sampler_flags: bool = False, keep_flags: bool = False):
 def parse_args(argv=None):
     parser = arg_parser(sampler_flags=True, keep_flags=True)
     args = parser.parse_args(argv)
-    if args.sampler == "ddpm" and args.eta:
-        parser.error("--eta belongs to --sampler ddim")
+    if args.sampler != "ddim" and args.eta:
+        parser.error("--eta belongs to --sampler ddim (ddpm has its own variance, dpmpp is deterministic)")
     if args.eta < 0:
         parser.error("--eta must not be negative")
     try:

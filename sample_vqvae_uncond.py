@@ -4,7 +4,7 @@ Encode a clip with a VQ-VAE and decode it with unconditional ("classifier-free"-
 the speaker label, on MI355X.  Counterpart of the reference's sample_vqvae_uncond.py (same flags and positionals; reference
 sample_vqvae_uncond.py:14-92): the model is one fine-tuned by train_vqvae_uncond.py, whose label 0 is the unconditional label
 (hence `--label + 1 < num_labels`).  Differences: WAV in / out directly (no ffmpeg); `--schedule` is parsed, not eval()ed;
-eval mode; `--seed`, `--precision`, `--sampler {ddpm,ddim}` and `--eta` are new; any combination of the two guidance scales works (the reference's always-tripled
+eval mode; `--seed`, `--precision`, `--sampler {ddpm,ddim,dpmpp}` and `--eta` are new; any combination of the two guidance scales works (the reference's always-tripled
 batch only lines up when both are non-zero, vq_vae.py:188-203).
 """
 import argparse
@@ -35,7 +35,7 @@ def arg_parser():
     p.add_argument("--check-vq", action="store_true")
     p.add_argument("--seed", default=None, type=int)
     p.add_argument("--precision", default="fp32", choices=["fp32", "fp16", "bf16"])
-    p.add_argument("--sampler", default="ddpm", choices=["ddpm", "ddim"])
+    p.add_argument("--sampler", default="ddpm", choices=["ddpm", "ddim", "dpmpp"])
     p.add_argument("--eta", type=float, default=0.0, help="DDIM noise level: 0 deterministic, 1 the DDPM step's variance (--sampler ddim)")
     p.add_argument("checkpoint_path", type=str)
     p.add_argument("output_file", type=str)
@@ -45,8 +45,8 @@ def arg_parser():
 def parse_args(argv=None):
     parser = arg_parser()
     args = parser.parse_args(argv)
-    if args.sampler == "ddpm" and args.eta:
-        parser.error("--eta belongs to --sampler ddim")
+    if args.sampler != "ddim" and args.eta:
+        parser.error("--eta belongs to --sampler ddim (ddpm has its own variance, dpmpp is deterministic)")
     if args.eta < 0:
         parser.error("--eta must not be negative")
     return args

@@ -1,6 +1,7 @@
 // extern "C" surface of libvqvs_hip.so (declared and documented in include/vqvs.h).
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -425,6 +426,61 @@ int vqvs_ddim_step_windows(const float* d_x, const float* d_eps, const float* d_
   if (int e = lease_x0sum(flags & VQVS_DDIM_CONSTRAIN, n, W, stream, lease)) return e;
   return run_ddim_step_windows(d_x, d_eps, d_grad, d_noise, d_alpha_t, d_alpha_to, d_x_to, d_windows, reinterpret_cast<double*>(lease.p), n, W, H,
                                flags, eta, noise_scale, seed, clip, step_index, reinterpret_cast<hipStream_t>(stream));
+}
+
+// Shared argument rules of the two DPM-Solver++ entry points.  ins: every input but the history, with its length in floats (NULL:
+// absent); hist: x0_prev; outs: x_to, x0_out (FIRST) and -- the windows form -- windows.  An output may not overlap an input or another
+// output, except that x0_out may BE x0_prev.
+struct FloatSpan {
+  const float* p;
+  int64_t len;
+};
+static int check_dpmpp_args(uint32_t flags, FloatSpan hist, std::initializer_list<FloatSpan> ins, std::initializer_list<FloatSpan> outs) {
+  if (flags & ~VQVS_DDIM_CONSTRAIN) VQVS_FAIL(VQVS_ERR_ARG, "flags %#x: only VQVS_DDIM_CONSTRAIN is defined for the DPM-Solver++ step", flags);
+  for (const auto& out : outs) {
+    const bool in_place = &out == outs.begin() && out.p == hist.p;  // the history updated in place
+    if (!in_place && bytes_overlap(out.p, out.len * 4, hist.p, hist.len * 4))
+      VQVS_FAIL(VQVS_ERR_ARG, "x_to and windows must not overlap x0_prev, and x0_out may be x0_prev itself but not a part of it");
+    for (const auto& in : ins)
+      if (bytes_overlap(out.p, out.len * 4, in.p, in.len * 4))
+        VQVS_FAIL(VQVS_ERR_ARG, "x_to, x0_out and windows must not overlap x, eps, grad or the alphas");
+    for (const auto& other : outs)
+      if (&other != &out && bytes_overlap(out.p, out.len * 4, other.p, other.len * 4))
+        VQVS_FAIL(VQVS_ERR_ARG, "x_to, x0_out and windows must not overlap each other");
+  }
+  return 0;
+}
+
+int vqvs_dpmpp_step(const float* d_x_t, const float* d_eps, const float* d_grad, const float* d_x0_prev, const float* d_alpha_from,
+                    const float* d_alpha_t, const float* d_alpha_to, float* d_x_to, float* d_x0_out, int B, int T, uint32_t flags,
+                    void* stream) {
+  if (!d_x_t || !d_eps || !d_alpha_t || !d_alpha_to || !d_x_to) VQVS_FAIL(VQVS_ERR_ARG, "x_t, eps, alpha_t, alpha_to and x_to must be non-NULL");
+  if (B < 1 || B > 65535) VQVS_FAIL(VQVS_ERR_ARG, "batch %d outside 1..65535", B);
+  if (T < 1 || T > (1 << 30)) VQVS_FAIL(VQVS_ERR_ARG, "row length %d outside 1..2^30", T);
+  const int64_t N = (int64_t)B * T;
+  if (int e = check_dpmpp_args(flags, {d_x0_prev, N}, {{d_x_t, N}, {d_eps, N}, {d_grad, N}, {d_alpha_from, B}, {d_alpha_t, B}, {d_alpha_to, B}},
+                               {{d_x0_out, N}, {d_x_to, N}}))
+    return e;
+  ScratchLease lease;
+  if (int e = lease_x0sum(flags & VQVS_DDIM_CONSTRAIN, B, T, stream, lease)) return e;
+  return run_dpmpp_step(d_x_t, d_eps, d_grad, d_x0_prev, d_alpha_from, d_alpha_t, d_alpha_to, d_x_to, d_x0_out,
+                        reinterpret_cast<double*>(lease.p), B, T, flags, reinterpret_cast<hipStream_t>(stream));
+}
+
+int vqvs_dpmpp_step_windows(const float* d_x, const float* d_eps, const float* d_grad, const float* d_x0_prev, const float* d_alpha_from,
+                            const float* d_alpha_t, const float* d_alpha_to, float* d_x_to, float* d_x0_out, float* d_windows, int n, int W,
+                            int H, uint32_t flags, void* stream) {
+  if (!d_x || !d_eps || !d_alpha_t || !d_alpha_to || !d_x_to) VQVS_FAIL(VQVS_ERR_ARG, "x, eps, alpha_t, alpha_to and x_to must be non-NULL");
+  int64_t Np;
+  if (int e = check_window_geometry(n, W, H, &Np)) return e;
+  const int64_t NW = (int64_t)n * W;
+  if (int e = check_dpmpp_args(flags, {d_x0_prev, Np}, {{d_x, Np}, {d_eps, NW}, {d_grad, NW}, {d_alpha_from, 1}, {d_alpha_t, 1}, {d_alpha_to, 1}},
+                               {{d_x0_out, Np}, {d_x_to, Np}, {d_windows, NW}}))
+    return e;
+  ScratchLease lease;
+  if (int e = lease_x0sum(flags & VQVS_DDIM_CONSTRAIN, n, W, stream, lease)) return e;
+  return run_dpmpp_step_windows(d_x, d_eps, d_grad, d_x0_prev, d_alpha_from, d_alpha_t, d_alpha_to, d_x_to, d_x0_out, d_windows,
+                                reinterpret_cast<double*>(lease.p), n, W, H, flags, reinterpret_cast<hipStream_t>(stream));
 }
 
 // Shared argument rules of the two keep-region entry points.  N: samples of the state (and of x0, keep, noise); n_alpha: entries of

@@ -1,4 +1,4 @@
-// DDPM and DDIM reverse-step kernels, the keep region, the counter-based normal generator, and the VQ codebook search.
+// DDPM, DDIM and DPM-Solver++(2M) reverse-step kernels, the keep region, the counter-based normal generator, and the VQ codebook search.
 // All of these are HBM-bound elementwise / small-reduction kernels.  The step and keep kernels come as a batch of clips [B, T] and as
 // ONE long row seen through overlapping windows; the forms share block_sum_256, step_noise_tail / _quad, quad_windows and store_quad.
 #include "kernels.hpp"
@@ -393,6 +393,161 @@ __global__ __launch_bounds__(256) void ddim_step_windows_kernel(const float* x, 
 }
 
 // ---------------------------------------------------------------------------------
+// DPM-Solver++(2M) step (Lu et al. 2022, "DPM-Solver++", Algorithm 2; the reference has none), include/vqvs.h "DPM-Solver++(2M)
+// step".  The second-order multistep solver of the probability-flow ODE in data-prediction form: from alpha_bar a_t to a_to, with
+// alpha = sqrt(a), sigma = sqrt(1 - a), lambda(a) = (log a - log1p(-a)) / 2,
+//   x_to = (sigma_to / sigma_t) x + phi ((1 + q) x0 - q x0_prev),   phi = alpha_to - sigma_to alpha_t / sigma_t,   q = h / (2 h_prev)
+// h = lambda(a_to) - lambda(a_t), h_prev = lambda(a_t) - lambda(a_from); x0 is the DDIM step's guided, constrained prediction
+// (ddim_x0_coef, ddim_x0_eps, ddim_x0sum_kernel) and x0_prev the one the step before formed.  Without a usable history q = 0, and the
+// step is the eta = 0 DDIM step written in x0.  The scalars are formed in fp64 and rounded to fp32 once, as ddim_coef's are; the two
+// logarithms and log1p's cost a few hundred fp64 instructions, so ONE thread of a workgroup forms them and the rest read them from
+// LDS, instead of every wave repeating them in front of sixteen bytes of traffic per array.
+// ---------------------------------------------------------------------------------
+struct DpmppCoef {
+  DdimCoef x0;  // sq1mat and rsat alone are set: the x0 half of ddim_x0_eps reads no other
+  float cx, c0, c1;
+  bool second;  // c1 != 0 is not the test: the history is not read at first order, whatever it holds
+};
+
+__device__ __forceinline__ double dpmpp_lambda(double a) { return 0.5 * (log(a) - log1p(-a)); }
+
+// a_from NULL, or no x0_prev (`history` false): first order
+__device__ __forceinline__ DpmppCoef dpmpp_coef(const float* a_from, bool history, float a_t, float a_to) {
+  const double at = (double)a_t, ato = (double)a_to;
+  const DdimX0Coef x = ddim_x0_coef(a_t);
+  const double sig_to = sqrt(1.0 - ato);
+  const double phi = sqrt(ato) - sig_to * sqrt(at) / x.sq1mat;
+  double q = 0.0;
+  bool second = false;
+  if (history && a_from && 1.0 - ato != 0.0) {
+    const double lt = dpmpp_lambda(at);
+    const double h = dpmpp_lambda(ato) - lt, h_prev = lt - dpmpp_lambda((double)a_from[0]);
+    q = h / (2.0 * h_prev);
+    second = h_prev > 0.0 && isfinite(q);
+  }
+  if (!second) q = 0.0;
+  DpmppCoef k;
+  k.x0 = DdimCoef{(float)x.sq1mat, (float)x.rsat, 0.f, 0.f, 0.f, 0.f, 0.f};
+  k.cx = (float)(sig_to / x.sq1mat);
+  k.c0 = (float)(phi * (1.0 + q));
+  k.c1 = (float)(-phi * q);
+  k.second = second;
+  return k;
+}
+
+// x0 of one sample under one clip's / window's prediction: the x0 half of ddim_x0_eps (its e' is not formed once inlined)
+template <bool GUIDED>
+__device__ __forceinline__ float dpmpp_x0(const DpmppCoef& k, bool constrain, float x, float e, float g, float mean) {
+  float x0, ep;
+  ddim_x0_eps<GUIDED>(k.x0, constrain, x, e, g, mean, x0, ep);
+  return x0;
+}
+
+// the output line: every rounding spelled out, so that the clip and the windows kernel round alike
+__device__ __forceinline__ float dpmpp_out(const DpmppCoef& k, float x, float x0, float x0_prev) {
+#pragma clang fp contract(off)
+  return fmaf(k.cx, x, k.second ? fmaf(k.c0, x0, k.c1 * x0_prev) : k.c0 * x0);
+}
+
+// `live` samples at p: one 16-byte access when `vec` (the quad is whole and aligned in every array), one by one otherwise
+__device__ __forceinline__ f32x4 load_quad(const float* p, int live, bool vec) {
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (vec) {
+    v = *reinterpret_cast<const f32x4*>(p);
+  } else {
+    for (int j = 0; j < live; ++j) v[j] = p[j];
+  }
+  return v;
+}
+__device__ __forceinline__ void store_quad_at(float* p, const f32x4& v, int live, bool vec) {
+  if (vec) {
+    *reinterpret_cast<f32x4*>(p) = v;
+  } else {
+    for (int j = 0; j < live; ++j) p[j] = v[j];
+  }
+}
+
+// B rows of T; row b has its own alphas.  aligned: T % 4 == 0 and every base pointer is 16-byte aligned.  x0_out may be x0_prev
+// itself: a thread reads its quad of the history before it writes it.
+template <bool GUIDED>
+__global__ __launch_bounds__(256) void dpmpp_step_kernel(const float* x_t, const float* eps, const float* grad, const float* x0_prev,
+                                                         const float* a_from, const float* a_t, const float* a_to, const double* partial,
+                                                         int nchunk, float* x_to, float* x0_out, int T, uint32_t flags, bool aligned) {
+  __shared__ DpmppCoef ks;
+  __shared__ float means;
+  const int b = blockIdx.y;
+  if (threadIdx.x == 0) {
+    ks = dpmpp_coef(a_from ? a_from + b : nullptr, x0_prev != nullptr, a_t[b], a_to[b]);
+    means = (flags & 2u) ? x0_mean(partial + (size_t)b * nchunk, nchunk, T) : 0.f;
+  }
+  __syncthreads();
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q * 4 >= T) return;
+  const DpmppCoef k = ks;
+  const float mean = means;
+  const size_t base = (size_t)b * T + q * 4;
+  const int n = min(4, T - q * 4);
+  const f32x4 xv = load_quad(x_t + base, n, aligned), ev = load_quad(eps + base, n, aligned);
+  f32x4 gv = {0.f, 0.f, 0.f, 0.f}, pv = gv;
+  if (GUIDED) gv = load_quad(grad + base, n, aligned);
+  if (k.second) pv = load_quad(x0_prev + base, n, aligned);
+  f32x4 x0, o;
+  for (int j = 0; j < 4; ++j) {
+    x0[j] = dpmpp_x0<GUIDED>(k, flags & 2u, xv[j], ev[j], gv[j], mean);
+    o[j] = dpmpp_out(k, xv[j], x0[j], pv[j]);
+  }
+  store_quad_at(x_to + base, o, n, aligned);
+  if (x0_out) store_quad_at(x0_out + base, x0, n, aligned);
+}
+
+// ddim_step_windows_kernel's geometry, per-window gradients and means and outputs, for the 2M step: the windows' x0 are blended, and
+// the history x0_prev / x0_out [Np] holds the BLENDED x0 per absolute position (x0_out may be x0_prev itself, as above).
+template <bool GUIDED>
+__global__ __launch_bounds__(256) void dpmpp_step_windows_kernel(const float* x, const float* eps, const float* grad, const float* x0_prev,
+                                                                 const float* a_from, const float* a_t, const float* a_to,
+                                                                 const double* partial, int nchunk, float* x_to, float* x0_out, float* win,
+                                                                 int n, int W, int H, uint32_t flags) {
+#pragma clang fp contract(off)
+  __shared__ DpmppCoef ks;
+  if (threadIdx.x == 0) ks = dpmpp_coef(a_from, x0_prev != nullptr, a_t[0], a_to[0]);
+  __syncthreads();
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  const int Np = (n - 1) * H + W, V = W - H;
+  if (q >= Np / 4) return;
+  const int p = q * 4;
+  const DpmppCoef k = ks;
+  const bool constrain = flags & 2u;
+  const QuadWindows g = quad_windows(p, n, W, H);
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  const f32x4 xv = *reinterpret_cast<const f32x4*>(x + p);
+  const f32x4 er = *reinterpret_cast<const f32x4*>(eps + g.at_r);
+  f32x4 el = er, gr = zero, gl = zero, pv = zero;
+  if (g.two) el = *reinterpret_cast<const f32x4*>(eps + g.at_l);
+  if (GUIDED) {
+    gr = *reinterpret_cast<const f32x4*>(grad + g.at_r);
+    if (g.two) gl = *reinterpret_cast<const f32x4*>(grad + g.at_l);
+  }
+  if (k.second) pv = *reinterpret_cast<const f32x4*>(x0_prev + p);
+  float mean_r = 0.f, mean_l = 0.f;
+  if (constrain) {
+    mean_r = x0_mean(partial + (size_t)g.br * nchunk, nchunk, W);
+    if (g.two) mean_l = x0_mean(partial + (size_t)(g.br - 1) * nchunk, nchunk, W);
+  }
+  f32x4 x0, o;
+  for (int j = 0; j < 4; ++j) {
+    x0[j] = dpmpp_x0<GUIDED>(k, constrain, xv[j], er[j], gr[j], mean_r);
+    if (g.two) {
+      const float w = ((float)(g.u + j) + 0.5f) / (float)V;
+      const float x0_l = dpmpp_x0<GUIDED>(k, constrain, xv[j], el[j], gl[j], mean_l);
+      x0[j] = fmaf(w, x0[j] - x0_l, x0_l);
+    }
+    o[j] = dpmpp_out(k, xv[j], x0[j], pv[j]);
+  }
+  store_quad(x_to, win, p, g, [&](float* dst) { *reinterpret_cast<f32x4*>(dst) = o; });
+  if (x0_out) *reinterpret_cast<f32x4*>(x0_out + p) = x0;
+}
+
+// ---------------------------------------------------------------------------------
 // Keep region (the "replacement" method of Song et al. 2021; the reference has none), include/vqvs.h "Keep region".  Kept samples of a
 // state are put back on the forward process of a source at alpha_bar = alpha:
 //   x[p] = fmaf(ca, x0[p], cn * (noise_scale * z)),   ca = sqrt(alpha), cn = sqrt(max(1 - alpha, 0))
@@ -775,6 +930,39 @@ int run_ddim_step_windows(const float* x, const float* eps, const float* grad, c
   auto kernel = grad ? ddim_step_windows_kernel<true> : ddim_step_windows_kernel<false>;
   hipLaunchKernelGGL(kernel, dim3((quads + 255) / 256), dim3(256), 0, st, x, eps, grad, noise, a_t, a_to, scratch, nchunk, x_to, windows, n, W,
                      H, flags, eta, noise_scale, seed, clip, step_index);
+  VQVS_HIP(hipGetLastError());
+  return 0;
+}
+
+// scratch: ddpm_scratch_doubles(B, T) doubles when flags has CONSTRAIN (not read otherwise)
+int run_dpmpp_step(const float* x_t, const float* eps, const float* grad, const float* x0_prev, const float* a_from, const float* a_t,
+                   const float* a_to, float* x_to, float* x0_out, double* scratch, int B, int T, uint32_t flags, hipStream_t st) {
+  const int nchunk = (T + SUM_CHUNK - 1) / SUM_CHUNK;
+  if (flags & 2u) {
+    hipLaunchKernelGGL(ddim_x0sum_kernel, dim3(nchunk, B), dim3(256), 0, st, x_t, eps, grad, a_t, scratch, T, nchunk, T, 1);
+  }
+  uintptr_t bits = 0;
+  for (const float* p : {x_t, eps, grad, x0_prev, (const float*)x_to, (const float*)x0_out}) bits |= reinterpret_cast<uintptr_t>(p);
+  const bool aligned = T % 4 == 0 && bits % 16 == 0;
+  dim3 grid(((T + 3) / 4 + 255) / 256, B);
+  auto kernel = grad ? dpmpp_step_kernel<true> : dpmpp_step_kernel<false>;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, x_t, eps, grad, x0_prev, a_from, a_t, a_to, scratch, nchunk, x_to, x0_out, T, flags, aligned);
+  VQVS_HIP(hipGetLastError());
+  return 0;
+}
+
+// scratch: ddpm_scratch_doubles(n, W) doubles when flags has CONSTRAIN (not read otherwise)
+int run_dpmpp_step_windows(const float* x, const float* eps, const float* grad, const float* x0_prev, const float* a_from, const float* a_t,
+                           const float* a_to, float* x_to, float* x0_out, float* windows, double* scratch, int n, int W, int H, uint32_t flags,
+                           hipStream_t st) {
+  const int nchunk = (W + SUM_CHUNK - 1) / SUM_CHUNK;
+  if (flags & 2u) {
+    hipLaunchKernelGGL(ddim_x0sum_kernel, dim3(nchunk, n), dim3(256), 0, st, x, eps, grad, a_t, scratch, W, nchunk, H, 0);
+  }
+  const int quads = ((n - 1) * H + W) / 4;
+  auto kernel = grad ? dpmpp_step_windows_kernel<true> : dpmpp_step_windows_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((quads + 255) / 256), dim3(256), 0, st, x, eps, grad, x0_prev, a_from, a_t, a_to, scratch, nchunk, x_to,
+                     x0_out, windows, n, W, H, flags);
   VQVS_HIP(hipGetLastError());
   return 0;
 }

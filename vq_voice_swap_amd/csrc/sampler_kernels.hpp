@@ -19,6 +19,13 @@ int run_ddim_step(const float* x_t, const float* eps, const float* grad, const f
 int run_ddim_step_windows(const float* x, const float* eps, const float* grad, const float* noise, const float* a_t, const float* a_to,
                           float* x_to, float* windows, double* scratch, int n, int W, int H, uint32_t flags, float eta, float noise_scale,
                           uint64_t seed, uint64_t clip, uint32_t step_index, hipStream_t st);
+// DPM-Solver++(2M) step from alpha_bar a_t to a_to with the previous step's x0 and alpha_bar (x0_prev / a_from NULL: first order),
+// single clips and the windows of one long signal; x0_out NULL: not wanted; scratch as the DDPM steps'
+int run_dpmpp_step(const float* x_t, const float* eps, const float* grad, const float* x0_prev, const float* a_from, const float* a_t,
+                   const float* a_to, float* x_to, float* x0_out, double* scratch, int B, int T, uint32_t flags, hipStream_t st);
+int run_dpmpp_step_windows(const float* x, const float* eps, const float* grad, const float* x0_prev, const float* a_from, const float* a_t,
+                           const float* a_to, float* x_to, float* x0_out, float* windows, double* scratch, int n, int W, int H, uint32_t flags,
+                           hipStream_t st);
 // kept samples of x (NULL keep: all) put back on the forward process of x0 at alpha, in place: B rows of T, and one long state with
 // its window copies
 int run_keep_region(float* x, const float* x0, const uint8_t* keep, const float* noise, const float* alpha, int B, int T, float noise_scale,

@@ -139,7 +139,7 @@ def few_guided_steps_promotion(what: str, steps: int, predictor, cond_fn, stackl
     return stack
 
 
-SAMPLERS = ("ddpm", "ddim")
+SAMPLERS = ("ddpm", "ddim", "dpmpp")
 
 
 def check_sampler(sampler: str, eta: float = 0.0) -> str:
@@ -148,20 +148,25 @@ def check_sampler(sampler: str, eta: float = 0.0) -> str:
         raise ValueError(f"sampler={sampler!r}: expected one of {SAMPLERS}")
     if sampler == "ddpm" and eta:
         raise ValueError(f"eta={eta!r} has no meaning for sampler='ddpm' (the DDIM sampler at eta = 1 is its small-sigma step)")
+    if sampler == "dpmpp" and eta:
+        raise ValueError(f"eta={eta!r} has no meaning for sampler='dpmpp': the DPM-Solver++(2M) sampler is deterministic")
     return sampler
 
 
 def pick_sampler(diffusion, sampler: str, eta: float = 0.0, *, sigma_large: Optional[bool] = None, windows: bool = False):
     """(sampling method of `diffusion`, its keywords) for a `sampler=` / `eta=` pair: `eta` goes to the DDIM sampler alone and
-    `sigma_large` (None: not the caller's to pass) to the DDPM sampler alone.  `windows`: the `..._sample_windows` forms."""
+    `sigma_large` (None: not the caller's to pass) to the DDPM sampler alone; the DPM-Solver++ sampler takes neither.  `windows`: the
+    `..._sample_windows` forms."""
     fn = getattr(diffusion, check_sampler(sampler, eta) + ("_sample_windows" if windows else "_sample"))
     if sampler == "ddim":
         return fn, dict(eta=eta)
+    if sampler == "dpmpp":
+        return fn, {}
     return fn, {} if sigma_large is None else dict(sigma_large=sigma_large)
 
 
 def warn_few_unguided_steps(what: str, steps: int, predictor, cond_fn, stacklevel: int = 3) -> None:
-    """An UN-guided DDIM run of fewer than FEW_GUIDED_STEPS steps in a 2-byte mode: the first step's 1 / sqrt(alpha_bar(1)) acts on
+    """An UN-guided DDIM or DPM-Solver++ run of fewer than FEW_GUIDED_STEPS steps in a 2-byte mode: the first step's 1 / sqrt(alpha_bar(1)) acts on
     the predictor's rounding error just the same, but nothing has been measured for it, so the run keeps its mode and only warns.
     (Guided runs are promoted by few_guided_steps_promotion; the DDPM samplers are not touched.)"""
     if cond_fn is not None or steps >= FEW_GUIDED_STEPS:
@@ -473,11 +478,11 @@ class Diffusion:
         self._keep_(x, source, keep, alpha, seed=seed, clip_offset=clip_offset, index=start_step)
         return x.view_as(x_T)
 
-    # ---- the sampling loop of ddpm_sample, ddim_sample and their window forms (longform.py) --------------
+    # ---- the sampling loop of ddpm_sample, ddim_sample, dpmpp_sample and their window forms (longform.py) --------------
     def _sample(self, what: str, layout, x_T: torch.Tensor, steps: int, *, schedule, noise: NoiseSource, seed, clip_offset, progress, source,
                 keep, start_step) -> torch.Tensor:
         """The one reverse loop.  `layout` (`_Clips` here, `longform._Windows`) holds the state, calls the predictor and cond_fn and
-        launches its form of the kernels of `layout.rule` (`_Ddpm` / `_Ddim`); everything the four entry points share is here: the
+        launches its form of the kernels of `layout.rule` (`_Ddpm` / `_Ddim` / `_Dpmpp`); everything the entry points share is here: the
         `source` / `keep` / `start_step` checks, the default seed, the few-steps promotion and warning, the tables, steps
         start_step .. steps - 1 with no noise on the last one, the keep region at the alpha_bar stepped to, the final guard."""
         source, keep = check_keep_args(x_T, source, keep, start_step, steps)
@@ -489,7 +494,7 @@ class Diffusion:
         rule, predictor, cond_fn = layout.rule, layout.predictor, layout.cond_fn
         stack = few_guided_steps_promotion(what, steps, predictor, cond_fn, stacklevel=4)  # (4: the caller of the entry point)
         with stack if stack is not None else contextlib.nullcontext():
-            if rule.name == "ddim":
+            if rule.name != "ddpm":
                 warn_few_unguided_steps(what, steps, predictor, cond_fn, stacklevel=4)
             tables = self.step_tables(steps, rows, schedule, x_T.device)  # t, alpha_bar(t), alpha_bar(t - step), t - step
             x_t = layout.start(x_T, source, keep, tables[1][start_step], start_step=start_step, **key)
@@ -647,6 +652,103 @@ class Diffusion:
         return ddim_sample_windows(self, x_T_long, predictor, steps, **kwargs)
 
 
+    # ---- DPM-Solver++(2M) (Lu et al. 2022; not in the reference): DESIGN.md section 3.12 -----------------------
+    def dpmpp_previous(
+        self,
+        x_t: torch.Tensor,
+        ts: torch.Tensor,
+        step,
+        epsilon_prediction: torch.Tensor,
+        x0_prev: Optional[torch.Tensor] = None,
+        ts_from: Optional[torch.Tensor] = None,
+        constrain: bool = False,
+        cond_fn: Optional[Callable] = None,
+    ):
+        """The DPM-Solver++(2M) step from ts to ts - step (`vqvs_dpmpp_step`): returns (x_to, x0), x0 being the guided, constrained
+        data prediction the step formed -- the `x0_prev` of the next call, with this call's `ts` as its `ts_from`.  Without both the
+        step is first order: the eta = 0 `ddim_previous`.  `cond_fn(x_t, ts)` is evaluated AT (x_t, ts), as there.  No noise is
+        drawn.  alpha_bar is evaluated on the HOST, as `step_tables` evaluates it, so the calls of a run chained by hand reproduce
+        `dpmpp_sample` bit for bit (a `ts` on the device costs one copy back)."""
+        _native.require_cuda(x_t, epsilon_prediction, x0_prev)
+        ts_host = ts.detach().to(device="cpu", dtype=torch.float32)
+        if not torch.is_tensor(step):
+            step = torch.full_like(ts_host, float(step))
+        step = step.detach().to(ts_host)
+
+        def alpha(t):
+            return self.schedule(t).to(device=x_t.device, dtype=torch.float32).contiguous()
+
+        a_from = None
+        if x0_prev is not None and ts_from is not None:
+            if not torch.is_tensor(ts_from):
+                ts_from = torch.full_like(ts_host, float(ts_from))
+            a_from = alpha(ts_from.detach().to(ts_host))
+        return self._dpmpp_step(x_t, epsilon_prediction, a_from, alpha(ts_host), alpha(ts_host - step), ts_host.to(x_t.device),
+                                x0_prev=x0_prev if a_from is not None else None, constrain=constrain, cond_fn=cond_fn)
+
+    def _dpmpp_step(self, x_t, epsilon_prediction, a_from, a_t, a_to, ts, *, x0_prev=None, constrain=False, cond_fn=None):
+        """One `vqvs_dpmpp_step` given alpha_bar of the step before (None: no history), of the time the state is at and of the time
+        stepped to, as [B] device tensors: (x_to, x0), both fresh tensors shaped like x_t."""
+        if x_t.dim() < 2:
+            raise ValueError("x_t must be [N, ..., T]")
+        B = x_t.shape[0]
+        T = x_t[0].numel()
+        x = x_t.detach().to(torch.float32).contiguous()
+        eps = epsilon_prediction.detach().to(torch.float32).contiguous()
+        if eps.numel() != x.numel():
+            raise ValueError(f"the prediction has shape {tuple(epsilon_prediction.shape)} for a state of shape {tuple(x_t.shape)}")
+        if a_from is None or x0_prev is None:
+            a_from = x0_prev = None
+        else:
+            x0_prev = x0_prev.detach().to(torch.float32).contiguous()
+            if x0_prev.numel() != x.numel():
+                raise ValueError(f"x0_prev of shape {tuple(x0_prev.shape)} does not match the state's {tuple(x_t.shape)}")
+        with torch.cuda.device(x.device):
+            grad = None
+            if cond_fn is not None:
+                grad = cond_fn(x.view_as(x_t), ts).detach().to(torch.float32).contiguous()
+                _native.require_cuda(grad)
+                if grad.numel() != x.numel():
+                    raise ValueError(f"cond_fn returned shape {tuple(grad.shape)} for a state of shape {tuple(x_t.shape)}")
+            out, x0 = torch.empty_like(x), torch.empty_like(x)
+            _native.check(_native.lib().vqvs_dpmpp_step(x.data_ptr(), eps.data_ptr(), _native._ptr(grad), _native._ptr(x0_prev),
+                                                        _native._ptr(a_from), a_t.data_ptr(), a_to.data_ptr(), out.data_ptr(), x0.data_ptr(),
+                                                        B, T, _native.DDIM_CONSTRAIN if constrain else 0, _native._stream_ptr()))
+        return out.view_as(x_t), x0.view_as(x_t)
+
+    def dpmpp_sample(
+        self,
+        x_T: torch.Tensor,
+        predictor: Callable[[torch.Tensor, torch.Tensor], torch.Tensor],
+        steps: int,
+        progress: bool = False,
+        constrain: bool = False,
+        cond_fn: Optional[Callable] = None,
+        schedule: Optional[Callable] = None,
+        *,
+        noise: NoiseSource = None,
+        seed: Optional[int] = None,
+        clip_offset: int = 0,
+        source: Optional[torch.Tensor] = None,
+        keep: Optional[torch.Tensor] = None,
+        start_step: int = 0,
+    ) -> torch.Tensor:
+        """`ddim_sample` at eta = 0 with the DPM-Solver++(2M) step: the same tables, one forward per step, and the previous step's x0
+        prediction as the only extra state.  The first executed step (step `start_step`) has no history and is first order -- the DDIM
+        step --, and so is the last one, which steps to alpha_bar(0) = 1 and returns x0.  The result depends on x_T alone: `noise` is
+        accepted and never asked for anything, and `seed` only feeds the replacement noise of `source` / `keep` / `start_step` (as in
+        `ddpm_sample`; the history holds x0 predictions and is not touched by the replacement)."""
+        return self._sample("dpmpp_sample", _Clips(self, _Dpmpp(constrain), predictor, cond_fn), x_T, steps, schedule=schedule,
+                            noise=noise, seed=seed, clip_offset=clip_offset, progress=progress, source=source, keep=keep,
+                            start_step=start_step)
+
+    def dpmpp_sample_windows(self, x_T_long: torch.Tensor, predictor: Callable, steps: int, **kwargs) -> torch.Tensor:
+        """`dpmpp_sample` for one long state [1,1,Np] predicted through overlapping windows (longform.dpmpp_sample_windows)."""
+        from .longform import dpmpp_sample_windows
+
+        return dpmpp_sample_windows(self, x_T_long, predictor, steps, **kwargs)
+
+
 class _Ddpm:
     """The DDPM step rule of `Diffusion._sample`: `vqvs_ddpm_step`, guided -- inside `Diffusion._step` -- by `cond_fn(mean, t - step)`
     between `vqvs_ddpm_mean` and `vqvs_ddpm_guided_eps`."""
@@ -675,8 +777,27 @@ class _Ddim:
         return diffusion._ddim_step(x_t, eps, a_t[i], a_to[i], ts[i], eta=self.eta, constrain=self.constrain, **kw)
 
 
+class _Dpmpp:
+    """The DPM-Solver++(2M) step rule: `vqvs_dpmpp_step`, guided as the DDIM rule is.  It owns the multistep history -- the x0 the
+    previous step wrote (clips: shaped like the state; windows: the blended x0 of the long row) and that step's alpha_bar(t).  Every
+    entry point builds a rule of its own, so a run starts with none: its first step, whatever `start_step`, is first order."""
+    name, draws_noise = "dpmpp", False
+
+    def __init__(self, constrain: bool):
+        self.constrain = constrain
+        self.flags = _native.DDIM_CONSTRAIN if constrain else 0
+        self.x0_prev = self.a_from = None
+
+    def step(self, diffusion, x_t, eps, tables, i, *, cond_fn=None, **noise_keys):
+        ts, a_t, a_to, _ = tables  # (noise, seed, clip_offset, step_index and noise_scale belong to drawn noise: there is none)
+        x_to, self.x0_prev = diffusion._dpmpp_step(x_t, eps, self.a_from, a_t[i], a_to[i], ts[i], x0_prev=self.x0_prev,
+                                                   constrain=self.constrain, cond_fn=cond_fn)
+        self.a_from = a_t[i]
+        return x_to
+
+
 class _Clips:
-    """The state layout of `ddpm_sample` / `ddim_sample`: a batch of clips [B, ..., T], predicted and stepped whole."""
+    """The state layout of `ddpm_sample` / `ddim_sample` / `dpmpp_sample`: a batch of clips [B, ..., T], predicted and stepped whole."""
 
     def __init__(self, diffusion: Diffusion, rule, predictor: Callable, cond_fn: Optional[Callable]):
         self.diffusion, self.rule, self.predictor, self.cond_fn = diffusion, rule, predictor, cond_fn

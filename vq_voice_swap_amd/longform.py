@@ -9,7 +9,8 @@ window batch written together.  Means are blended and the noise is shared, so th
 step and the step has the variance a single clip's has.
 
 `Diffusion.ddpm_sample_windows`, `VQVAE.encode_long` and `VQVAE.decode_long` are the functions below; `Diffusion.ddim_sample_windows`
-is the same walk with the DDIM step `vqvs_ddim_step_windows`.
+is the same walk with the DDIM step `vqvs_ddim_step_windows`, `Diffusion.dpmpp_sample_windows` with the
+DPM-Solver++(2M) step `vqvs_dpmpp_step_windows` (section 3.12).
 """
 
 from __future__ import annotations
@@ -125,8 +126,24 @@ def _ddim_step_windows(rule, x, eps, grad, nz, a_t, a_to, x_to, next_windows, n,
                                                        rule.flags, float(rule.eta), noise_scale, int(seed), int(clip_offset), step_index, st))
 
 
+def dpmpp_step_windows_(x, eps, grad, x0_prev, a_from, a_t, a_to, x_to, x0_out, next_windows, n, window, hop, flags, st) -> None:
+    """`vqvs_dpmpp_step_windows` on the long state x [Np] and the window batches eps / grad [n,1,window]: x_to and x0_out [Np] and the
+    next forward's windows are written; x0_prev / a_from None: no history."""
+    _native.check(_native.lib().vqvs_dpmpp_step_windows(x.data_ptr(), eps.data_ptr(), _native._ptr(grad), _native._ptr(x0_prev), _native._ptr(a_from),
+                                                        a_t.data_ptr(), a_to.data_ptr(), x_to.data_ptr(), x0_out.data_ptr(),
+                                                        next_windows.data_ptr(), n, window, hop, flags, st))
+
+
+def _dpmpp_step_windows(rule, x, eps, grad, nz, a_t, a_to, x_to, next_windows, n, window, hop, noise_scale, seed, clip_offset, step_index, st) -> None:
+    """The 2M rule's window step.  The history is the rule's: the blended x0 of the long row that the step before wrote, and that step's
+    alpha_bar (`a_t` is the table row of a slice, one value per window, all equal: the kernel reads the first)."""
+    x0 = torch.empty_like(x)
+    dpmpp_step_windows_(x, eps, grad, rule.x0_prev, rule.a_from, a_t, a_to, x_to, x0, next_windows, n, window, hop, rule.flags, st)
+    rule.x0_prev, rule.a_from = x0, a_t
+
+
 class _Windows:
-    """The state layout of the two window loops for `Diffusion._sample`: the long row [Np], with its window batch [n,1,window] kept
+    """The state layout of the window loops for `Diffusion._sample`: the long row [Np], with its window batch [n,1,window] kept
     beside it.  The predictor and cond_fn see slices of at most `window_batch` windows, with `first=`; `fill` and `step` are the
     rule's window forms above."""
 
@@ -150,7 +167,7 @@ class _Windows:
     def start(self, x_T_long, source, keep, alpha, **kw):
         x, self.windows = start_windows(x_T_long, source, keep, alpha, n=self.n, window=self.window, hop=self.hop, **kw)
         self.eps = torch.empty_like(self.windows)
-        self.grad = torch.empty_like(self.windows) if self.cond_fn is not None and self.rule.name == "ddim" else None
+        self.grad = torch.empty_like(self.windows) if self.cond_fn is not None and self.rule.name != "ddpm" else None
         return x
 
     def predict(self, x, tables, i) -> None:
@@ -219,6 +236,22 @@ def ddim_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, 
                              progress=progress, source=source, keep=keep, start_step=start_step)
 
 
+def dpmpp_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, steps: int, *, window: int, hop: int,
+                         window_batch: int = 64, constrain: bool = False, cond_fn: Optional[Callable] = None,
+                         schedule: Optional[Callable] = None, noise=None, seed: Optional[int] = None, clip_offset: int = 0,
+                         progress: bool = False, source: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
+                         start_step: int = 0) -> torch.Tensor:
+    """`Diffusion.dpmpp_sample` for one long state x_T_long [1,1,Np]: `ddim_sample_windows` at eta = 0 with `vqvs_dpmpp_step_windows` as
+    the step.  `predictor` and `cond_fn` are as there (the gradient is taken at the windows the predictor saw and applied per window,
+    before the blend); the history is the BLENDED x0 of the long row, one value per absolute position, kept by the rule.  `noise` is
+    accepted and never asked for anything; `source`, `keep` and `start_step` are as there and leave the history alone."""
+    from .diffusion import _Dpmpp
+
+    layout = _Windows(_Dpmpp(constrain), predictor, cond_fn, window, hop, window_batch, _ddim_fill, _dpmpp_step_windows)
+    return diffusion._sample("dpmpp_sample_windows", layout, x_T_long, steps, schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset,
+                             progress=progress, source=source, keep=keep, start_step=start_step)
+
+
 def encode_long(model, wave: torch.Tensor, window: int, hop: int, window_batch: int = 64) -> torch.Tensor:
     """[1,1,N] waveform -> codes [n, window / rate] of its n windows (`plan_windows`), the tail zero-padded.  Windows are encoded in
     slices of `window_batch`; behind the version-2 (dB) MFCC front end, which floors at the maximum over the BATCH, one at a time, so
@@ -246,7 +279,7 @@ def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = Non
     """Window codes [n,T1] int or [n,C,T1] float (`encode_long`) -> [1,1,num_samples] waveform: `VQVAE.decode` on one long state.
     x_T is ONE row of (n - 1) * hop + window samples keyed by `clip_offset`; `labels` is one label for every window, or [n].
     With one window the result is `decode`'s, bit for bit, at the same seed and clip_offset.  `sampler` "ddim" runs
-    `ddim_sample_windows` with `eta` instead of `ddpm_sample_windows`.  `source` [1,1,num_samples] (the recording itself), `keep`
+    `ddim_sample_windows` with `eta` instead of `ddpm_sample_windows`, "dpmpp" `dpmpp_sample_windows`.  `source` [1,1,num_samples] (the recording itself), `keep`
     (bool / uint8, [1,1,num_samples]: samples that stay the source's) and `strength` in (0, 1] (below 1: start from the noised
     source, `strength_to_start_step`) are `VQVAE.decode`'s."""
     from .diffusion import fresh_seed, pick_sampler, randn_clips, source_start_step

@@ -92,7 +92,7 @@ def sample_clips(
     """Sample `n_total` clips over all ranks.  `labels` (global, [n_total]) selects per-clip classes for a
     class-conditional model (the counterpart of sample_diffusion.py:108-122).  `sample_fn(begin, end, seed)`
     replaces the HIP sampler (used by the CPU gloo tests of the sharding logic).  `sampler` "ddim" samples with
-    `Diffusion.ddim_sample` at `eta` (`sigma_large` belongs to the DDPM sampler alone)."""
+    `Diffusion.ddim_sample` at `eta`, "dpmpp" with `Diffusion.dpmpp_sample` (`sigma_large` belongs to the DDPM sampler alone)."""
     rank, world = _dist_info()
     begin, end = shard_range(n_total, rank, world)
     n_local = end - begin
@@ -102,8 +102,8 @@ def sample_clips(
         from .diffusion import pick_sampler, randn_clips
 
         sample, sampler_kw = pick_sampler(model.diffusion, sampler, eta, sigma_large=sigma_large)
-        if sampler == "ddim" and sigma_large:
-            raise ValueError("sigma_large has no meaning for sampler='ddim'")
+        if sampler != "ddpm" and sigma_large:
+            raise ValueError(f"sigma_large has no meaning for sampler={sampler!r}")
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device())
         if n_local == 0:

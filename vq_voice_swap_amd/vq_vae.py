@@ -112,7 +112,8 @@ class VQVAE(DiffusionModel):
                sampler: str = "ddpm", eta: float = 0.0, source: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
                strength: float = 1.0, **kwargs) -> torch.Tensor:
         """codes [N,T1] int or [N,C,T1] float -> [N,1,T1*256] waveform (vq_vae.py:92-145).  `sampler` "ddim" runs
-        `Diffusion.ddim_sample` with `eta` (0: the result depends on x_T alone) instead of `ddpm_sample`.
+        `Diffusion.ddim_sample` with `eta` (0: the result depends on x_T alone) instead of `ddpm_sample`, "dpmpp" the deterministic
+        second-order `Diffusion.dpmpp_sample`.
         `source` [N,1,T] is the waveform being converted: the samples `keep` marks (bool / uint8, [N,1,T]) stay the source's, bit for
         bit, and are shown to the predictor at every noise level; `strength` in (0, 1] below 1 starts from the source noised to step
         `strength_to_start_step(strength, steps)` instead of from x_T."""
