@@ -442,6 +442,30 @@ int vqvs_vq_embed(const int64_t* d_idx, const float* d_dict, float* d_out, int B
 int vqvs_xent_score(const float* d_logits, const int64_t* d_targets, double* d_nll, int64_t* d_top1, int64_t* d_topk, int k,
                     int64_t* d_confusion, int B, int K, int L, void* stream);
 
+/* ---- conversion-quality scores (handle-less) ---------------------------------------------
+ * Two frame-synchronous spectral distances between waveform batches a and b, per clip the SUM over frames, in one kernel
+ * (spectral_kernels.hip; no spectrum, mel value or cepstrum goes to memory).  Frames F = T / hop + 1, centred, reflect padding of
+ * n_fft / 2 on both sides.  Per frame, with the rounding points of the MFCC front end:
+ *   xw[n] = f32(x[s] * window[n]);  P[k] = |sum_n xw[n] e^{-2 pi i k n / n_fft}|^2, a direct DFT accumulated in f64 against
+ *   d_twiddle, rounded to f32;  mel[m] = sum_k P[k] fb[k,m] in f64 -> f32;  L[m] = log(mel[m] + eps), the sum in f32, the logarithm
+ *   in f64 rounded to f32 once;  c[j] = sum_m L[m] dct[m,j] in f64 -> f32;  then in f64
+ *   mcd = (10 / ln 10) sqrt(2 sum_{j=1}^{n_ceps-1} (c_a[j] - c_b[j])^2)      (coefficient 0 is left out)
+ *   lsd = (10 / ln 10) sqrt((1 / n_mels) sum_m (L_a[m] - L_b[m])^2)
+ *   d_a, d_b  [B,T] f32;  d_window [n_fft] f32;  d_twiddle [n_fft][2] f64: cos and sin of 2 pi i / n_fft
+ *   d_fb [n_fft/2+1, n_mels] f32;  d_dct [n_mels, n_ceps] f32  (caller-owned device constants)
+ *   d_mcd, d_lsd  [B] f64 out: either may be NULL, not both
+ * Both signals of a frame run through the same instruction sequence, a workgroup adds its four frames in frame order, and one
+ * thread adds a clip's workgroup partials (16 bytes per (clip, workgroup) in the per-(device, stream) scratch buffer) in order and
+ * is the clip's only writer -- no floating-point atomics.  So d(a, a) is exactly 0, d(a, b) == d(b, a) bitwise, and a clip's value
+ * is bitwise the same from run to run and whatever B and its row are.
+ * Limits: B in 1..65535; n_fft even, in 16..512; n_fft / 2 < T <= 2^30 with at most 2^25 frames; hop in 1..n_fft; n_mels in
+ * 1..128; n_ceps in 2..min(n_mels, 64); eps finite and positive; an output may not overlap an input or the other output.
+ * Asynchronous on `stream`; a NULL required pointer, both outputs NULL or anything outside the limits returns VQVS_ERR_ARG with
+ * a message before the device is touched. */
+int vqvs_spectral_distance(const float* d_a, const float* d_b, const float* d_window, const double* d_twiddle,
+                           const float* d_fb, const float* d_dct, double* d_mcd, double* d_lsd,
+                           int B, int T, int n_fft, int hop, int n_mels, int n_ceps, float eps, void* stream);
+
 /* ---- test / profiling hooks ------------------------------------------------------ */
 int vqvs_debug_tap_count(const vqvs_model* m);
 int vqvs_debug_tap_info(const vqvs_model* m, int i, char* name_out, int name_cap, int* channels, int* length_shift);

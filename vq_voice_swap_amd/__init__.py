@@ -16,6 +16,7 @@ from .diffusion_model import DiffusionModel
 from .encoder_predictor import EncoderPredictor
 from .longform import plan_windows
 from .losses import LossTracker, classification_scores, speaker_search_losses
+from .spectral import SpectralDistance, spectral_constants
 from .stats import FeatureStats, class_score, frechet_distance, wav_roundtrip
 from .unet import ResBlockModule, UNetEncoder, UNetPredictor
 from .vq import VQ, StandardVQLoss, VQLoss, code_usage
@@ -26,4 +27,5 @@ __all__ = [
     "DiffusionModel", "Classifier", "ConvMFCCEncoder", "EncoderPredictor", "ResBlockModule", "UNetEncoder", "UNetPredictor", "VQ", "VQVAE",
     "FeatureStats", "class_score", "frechet_distance", "wav_roundtrip", "LossTracker", "speaker_search_losses", "create_data_loader",
     "StandardVQLoss", "VQLoss", "code_usage", "classification_scores", "plan_windows",
+    "SpectralDistance", "spectral_constants",
 ]

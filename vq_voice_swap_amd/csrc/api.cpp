@@ -603,6 +603,35 @@ int vqvs_xent_score(const float* d_logits, const int64_t* d_targets, double* d_n
                         reinterpret_cast<hipStream_t>(stream));
 }
 
+int vqvs_spectral_distance(const float* d_a, const float* d_b, const float* d_window, const double* d_twiddle, const float* d_fb,
+                           const float* d_dct, double* d_mcd, double* d_lsd, int B, int T, int n_fft, int hop, int n_mels, int n_ceps,
+                           float eps, void* stream) {
+  if (!d_a || !d_b || !d_window || !d_twiddle || !d_fb || !d_dct) VQVS_FAIL(VQVS_ERR_ARG, "a, b, window, twiddle, fb and dct must be non-NULL");
+  if (!d_mcd && !d_lsd) VQVS_FAIL(VQVS_ERR_ARG, "mcd and lsd are both NULL: nothing to compute");
+  if (B < 1 || B > 65535) VQVS_FAIL(VQVS_ERR_ARG, "batch %d outside 1..65535", B);
+  if (n_fft < 16 || n_fft > 512 || n_fft % 2) VQVS_FAIL(VQVS_ERR_ARG, "n_fft=%d must be even and in 16..512", n_fft);
+  if (T <= n_fft / 2) VQVS_FAIL(VQVS_ERR_ARG, "clip of %d samples is no longer than the reflect padding (%d)", T, n_fft / 2);
+  if (T > (1 << 30)) VQVS_FAIL(VQVS_ERR_ARG, "clip of %d samples: more than 2^30", T);
+  if (hop < 1 || hop > n_fft) VQVS_FAIL(VQVS_ERR_ARG, "hop=%d outside 1..n_fft=%d", hop, n_fft);
+  if (T / hop + 1 > (1 << 25)) VQVS_FAIL(VQVS_ERR_ARG, "T=%d at hop=%d is more than 2^25 frames per clip", T, hop);
+  if (n_mels < 1 || n_mels > 128) VQVS_FAIL(VQVS_ERR_ARG, "n_mels=%d outside 1..128", n_mels);
+  if (n_ceps < 2 || n_ceps > (n_mels < 64 ? n_mels : 64)) VQVS_FAIL(VQVS_ERR_ARG, "n_ceps=%d outside 2..min(n_mels=%d, 64)", n_ceps, n_mels);
+  if (!std::isfinite(eps) || !(eps > 0.f)) VQVS_FAIL(VQVS_ERR_ARG, "eps=%g must be finite and positive", (double)eps);
+  const int64_t N = (int64_t)B * T;
+  const struct { const void* p; int64_t bytes; const char* name; } ins[] = {
+      {d_a, N * 4, "a"}, {d_b, N * 4, "b"}, {d_window, (int64_t)n_fft * 4, "window"}, {d_twiddle, (int64_t)n_fft * 16, "twiddle"},
+      {d_fb, (int64_t)(n_fft / 2 + 1) * n_mels * 4, "fb"}, {d_dct, (int64_t)n_mels * n_ceps * 4, "dct"}};
+  for (const auto& in : ins) {
+    if (bytes_overlap(d_mcd, (int64_t)B * 8, in.p, in.bytes)) VQVS_FAIL(VQVS_ERR_ARG, "d_mcd must not overlap %s", in.name);
+    if (bytes_overlap(d_lsd, (int64_t)B * 8, in.p, in.bytes)) VQVS_FAIL(VQVS_ERR_ARG, "d_lsd must not overlap %s", in.name);
+  }
+  if (bytes_overlap(d_mcd, (int64_t)B * 8, d_lsd, (int64_t)B * 8)) VQVS_FAIL(VQVS_ERR_ARG, "d_mcd must not overlap d_lsd");
+  ScratchLease lease;
+  if (int e = scratch_get(spectral_distance_scratch_bytes(B, T, hop), stream, lease)) return e;
+  return run_spectral_distance(d_a, d_b, d_window, d_twiddle, d_fb, d_dct, lease.p, d_mcd, d_lsd, B, T, n_fft, hop, n_mels, n_ceps, eps,
+                               reinterpret_cast<hipStream_t>(stream));
+}
+
 int vqvs_vq_embed(const int64_t* d_idx, const float* d_dict, float* d_out, int B, int Cd, int T1, int K, void* stream) {
   if (!d_idx || !d_dict || !d_out) VQVS_FAIL(VQVS_ERR_ARG, "idx, dict and out must be non-NULL");
   if (B < 1 || Cd < 1 || T1 < 1 || K < 1) VQVS_FAIL(VQVS_ERR_ARG, "bad shape B=%d Cd=%d T1=%d K=%d", B, Cd, T1, K);

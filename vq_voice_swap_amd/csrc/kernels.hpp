@@ -307,6 +307,15 @@ struct MfccFeatArgs {
 };
 int launch_mfcc_features(const MfccFeatArgs& a, int B, hipStream_t st);
 
+// ----------------------------------------------------------------------------------
+// Conversion-quality scores (spectral_kernels.hip): per-clip sums over frames of the mel-cepstral distortion and the log-mel
+// spectral distance of two waveform batches; scratch holds spectral_distance_scratch_bytes(B, T, hop) bytes of tile partials
+// ----------------------------------------------------------------------------------
+size_t spectral_distance_scratch_bytes(int B, int T, int hop);
+int run_spectral_distance(const float* a, const float* b, const float* window, const double* twiddle, const float* fb, const float* dct,
+                          void* scratch, double* mcd, double* lsd, int B, int T, int n_fft, int hop, int n_mels, int n_ceps, float eps,
+                          hipStream_t st);
+
 // layout changes at the library boundary (reference tensors are NCT float32)
 int launch_nct_to_ntc(const float* in, void* out, float* stats, int B, int C, int L, int ntiles, int precision, hipStream_t st);
 int launch_ntc_to_nct(const void* in, float* out, int B, int C, int L, int in_precision, hipStream_t st);

@@ -72,6 +72,14 @@ class VQVAE(DiffusionModel):
         with torch.no_grad():
             return self.vq.encode(self.encoder(inputs))
 
+    def code_agreement(self, codes: torch.Tensor, audio: torch.Tensor) -> torch.Tensor:
+        """codes [N,T1] int64 against `encode(audio)` of a [N,1,T] waveform (say, a conversion decoded from them): the int64 [N]
+        count of positions whose code survived the round trip."""
+        again = self.encode(audio)
+        if again.shape != codes.shape:
+            raise ValueError(f"codes of shape {tuple(codes.shape)} against audio that encodes to {tuple(again.shape)}")
+        return (again == codes.to(again.device)).sum(dim=1)
+
     def losses(self, vq_loss, inputs: torch.Tensor, labels: Optional[torch.Tensor] = None, jitter: float = 0.0, no_vq_prob: float = 0.0,
                *, ts: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, seed: Optional[int] = None,
                clip_offset: int = 0, hist: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
