@@ -17,10 +17,10 @@ nll_q* / acc_q* / top5_q* are the per-quartile-of-t averages of the clips' NLL, 
 so the line does not depend on the batch size or the rank count.  `--confusion-path` writes the [num_labels, num_labels] matrix
 of (label, prediction) counts as .npy.
 
-`data_dir`, `--precision`, `--seed`, `--max-samples` and `--dist-backend` are those of eval_vqvae.py.  Under torchrun
-(WORLD_SIZE > 1) batches are dealt round-robin, rank 0 merges the states and prints the one final line.
+`data_dir`, `--precision`, `--seed`, `--max-samples` and `--dist-backend` are the common parser's and the pass is the shared one
+(vq_voice_swap_amd/eval_pass.py).  Under torchrun (WORLD_SIZE > 1) batches are dealt round-robin, rank 0 merges the states and
+prints the one final line.
 """
-import argparse
 import os
 import sys
 from fractions import Fraction
@@ -30,22 +30,16 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from vq_voice_swap_amd import Classifier, Diffusion, LossTracker, create_data_loader, make_schedule  # noqa: E402
+from vq_voice_swap_amd import Classifier, Diffusion, LossTracker, make_schedule  # noqa: E402
+from vq_voice_swap_amd.eval_pass import common_parser, format_line, run_pass  # noqa: E402,F401
 
 
 def arg_parser():
-    p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
-    p.add_argument("--batch-size", type=int, default=4)
-    p.add_argument("--precision", default="fp32", choices=["fp32", "fp16", "bf16"])
-    p.add_argument("--seed", default=0, type=int)
-    p.add_argument("--max-samples", default=None, type=int, help="stop after this many clips (default: one pass over the data)")
-    p.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend when WORLD_SIZE > 1")
+    p = common_parser()
     p.add_argument("--schedule", default="exp", type=str, help="noise schedule the classifier was trained with")
     p.add_argument("--t", default=None, type=float, help="evaluate every clip at this fixed t in [0, 1] (default: uniform draws)")
     p.add_argument("--topk", default=5, type=int, help="k of the top-k accuracy (clipped to the number of labels)")
     p.add_argument("--confusion-path", default=None, type=str, help="write the (label, prediction) count matrix here as .npy")
-    p.add_argument("checkpoint_path", type=str)
-    p.add_argument("data_dir", type=str)
     return p
 
 
@@ -114,71 +108,20 @@ class EvalState:
         return log
 
 
-def format_line(num_samples, log):
-    msg = " ".join(f"{key}={value}" if isinstance(value, int) else f"{key}={value:.06f}" for key, value in log.items())
-    return f"{num_samples} samples: {msg}"
-
-
-def run_pass(args, load_model, make_state, targets_of, diffusion_of):
-    """The loop both guidance-model scripts share: shard the loader, score every batch, merge on rank 0, print."""
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = 0
-    if world > 1:
-        import torch.distributed as dist
-
-        dist.init_process_group(args.dist_backend)
-        rank = dist.get_rank()
-    if not torch.cuda.is_available():
-        raise SystemExit("no ROCm device visible: the guidance models have no CPU path")
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count())
-    torch.cuda.set_device(device)
-
-    data_loader, num_labels = create_data_loader(directory=args.data_dir, batch_size=args.batch_size, seed=args.seed, rank=rank, world=world)
-    if rank == 0:
-        print("loading model from checkpoint...")
-    model = load_model(device, num_labels)
-    diffusion = diffusion_of(model)
-
-    state = make_state(model, device)
-    for i, data_batch in enumerate(data_loader):
-        first = (rank + i * world) * args.batch_size  # position of the batch's first clip in the shuffled pass
-        if args.max_samples is not None and first + args.batch_size > args.max_samples:
-            break
-        audio_seq = data_batch["samples"][:, None].to(device)
-        state.add_batch(model, diffusion, audio_seq, targets_of(audio_seq, data_batch), first, args.seed, getattr(args, "t", None))
-        if world == 1:
-            print(format_line(state.num_samples, state.log_dict()))
-    merged = state
-    if world > 1:
-        import torch.distributed as dist
-
-        gathered = [None] * world if rank == 0 else None
-        dist.gather_object(state.to_host(), gathered, dst=0)
-        if rank == 0:
-            merged = gathered[0]
-            for other in gathered[1:]:
-                merged.merge(other)
-            print(format_line(merged.num_samples, merged.log_dict()))
-        dist.barrier()
-        dist.destroy_process_group()
-    return merged if rank == 0 else None
-
-
 def main(argv=None):
     args = arg_parser().parse_args(argv)
     if args.t is not None and not 0.0 <= args.t <= 1.0:
         raise SystemExit(f"--t {args.t} is outside [0, 1]")
     diffusion = Diffusion(make_schedule(args.schedule))
 
-    def load_model(device, num_labels):
+    def build(device, num_labels):
         model = Classifier.load(args.checkpoint_path).to(device)
         assert model.num_labels == num_labels, f"the model has {model.num_labels} labels, the data {num_labels}"
-        model.eval()
-        model.set_precision(args.precision)
-        return model
+        model.eval().set_precision(args.precision)
+        state = EvalState(model.num_labels, device, args.topk)
+        return state, lambda audio, data_batch, first: state.add_batch(model, diffusion, audio, data_batch["label"].to(device), first, args.seed, args.t)
 
-    merged = run_pass(args, load_model, lambda model, device: EvalState(model.num_labels, device, args.topk),
-                      lambda audio, batch: batch["label"].to(audio.device), lambda model: diffusion)
+    merged = run_pass(args, build, no_device="the guidance models have no CPU path")
     if merged is not None and args.confusion_path:
         import numpy as np
 

@@ -20,10 +20,10 @@ against each other.  `--classifier PATH` adds a `Classifier` at t = 0 on the con
 target label, source_acc how often it still names the source's (left out with `--target same`).  All sums are exact -- integer
 counts, and the float64 clip sums added as fractions -- so the line does not depend on the batch size or the rank count.
 
-`data_dir`, `--batch-size`, `--precision`, `--seed`, `--max-samples` and `--dist-backend` are those of eval_vqvae.py.  Under
-torchrun (WORLD_SIZE > 1) batches are dealt round-robin, rank 0 merges the states and prints the one final line.
+`data_dir`, `--batch-size`, `--precision`, `--seed`, `--max-samples` and `--dist-backend` are the common parser's and the pass is
+the shared one (vq_voice_swap_amd/eval_pass.py).  Under torchrun (WORLD_SIZE > 1) batches are dealt round-robin, rank 0 merges
+the states and prints the one final line.
 """
-import argparse
 import os
 import sys
 from fractions import Fraction
@@ -33,20 +33,15 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from eval_classifier import format_line  # noqa: E402
 from eval_vqvae import wrong_labels  # noqa: E402
-from vq_voice_swap_amd import VQVAE, Classifier, SpectralDistance, create_data_loader, randn_clips  # noqa: E402
+from vq_voice_swap_amd import VQVAE, Classifier, SpectralDistance, randn_clips  # noqa: E402
+from vq_voice_swap_amd.eval_pass import common_parser, format_line, run_pass  # noqa: E402,F401
 
 SAMPLERS = ["ddpm", "ddim", "dpmpp"]
 
 
 def arg_parser():
-    p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
-    p.add_argument("--batch-size", type=int, default=4)
-    p.add_argument("--precision", default="fp32", choices=["fp32", "fp16", "bf16"])
-    p.add_argument("--seed", default=0, type=int)
-    p.add_argument("--max-samples", default=None, type=int, help="stop after this many clips (default: one pass over the data)")
-    p.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend when WORLD_SIZE > 1")
+    p = common_parser()
     p.add_argument("--sampler", default="ddpm", choices=SAMPLERS)
     p.add_argument("--eta", type=float, default=0.0, help="DDIM noise level: 0 deterministic, 1 the DDPM step's variance (--sampler ddim)")
     p.add_argument("--sample-steps", type=int, default=100)
@@ -54,8 +49,6 @@ def arg_parser():
     p.add_argument("--reference-steps", type=int, default=None, help="decode a second time at this many steps and score that run and the gap")
     p.add_argument("--reference-sampler", default="ddpm", choices=SAMPLERS)
     p.add_argument("--classifier", default=None, type=str, metavar="PATH", help="a Classifier checkpoint, read at t = 0 on the converted audio")
-    p.add_argument("checkpoint_path", type=str)
-    p.add_argument("data_dir", type=str)
     return p
 
 
@@ -199,56 +192,23 @@ class EvalState:
 
 def main(argv=None):
     args = parse_args(argv)
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = 0
-    if world > 1:
-        import torch.distributed as dist
 
-        dist.init_process_group(args.dist_backend)
-        rank = dist.get_rank()
-    data_loader, num_labels = create_data_loader(directory=args.data_dir, batch_size=args.batch_size, seed=args.seed, rank=rank, world=world)
-    check_target(args.target, num_labels)
-    if not torch.cuda.is_available():
-        raise SystemExit("no ROCm device visible: the encoder, the decoder and the distance kernel have no CPU path")
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count())
-    torch.cuda.set_device(device)
+    def build(device, num_labels):
+        model = VQVAE.load(args.checkpoint_path).to(device)
+        assert model.num_labels == num_labels, f"the model has {model.num_labels} labels, the data {num_labels}"
+        model.eval().set_precision(args.precision)
+        classifier = None
+        if args.classifier:
+            classifier = Classifier.load(args.classifier).to(device)
+            assert classifier.num_labels == num_labels, f"the classifier has {classifier.num_labels} labels, the data {num_labels}"
+            classifier.eval().set_precision(args.precision)
+        distance = SpectralDistance()
+        state = EvalState(reference=args.reference_steps is not None, classifier=classifier is not None, same=args.target == "same")
+        return state, lambda audio, data_batch, first: state.add_batch(model, distance, audio, data_batch["label"].to(device), first, args.seed,
+                                                                        args, classifier)
 
-    if rank == 0:
-        print("loading model from checkpoint...")
-    model = VQVAE.load(args.checkpoint_path).to(device)
-    assert model.num_labels == num_labels, f"the model has {model.num_labels} labels, the data {num_labels}"
-    model.eval()
-    model.set_precision(args.precision)
-    classifier = None
-    if args.classifier:
-        classifier = Classifier.load(args.classifier).to(device)
-        assert classifier.num_labels == num_labels, f"the classifier has {classifier.num_labels} labels, the data {num_labels}"
-        classifier.eval()
-        classifier.set_precision(args.precision)
-    distance = SpectralDistance()
-
-    state = EvalState(reference=args.reference_steps is not None, classifier=classifier is not None, same=args.target == "same")
-    for i, data_batch in enumerate(data_loader):
-        first = (rank + i * world) * args.batch_size  # position of the batch's first clip in the shuffled pass
-        if args.max_samples is not None and first + args.batch_size > args.max_samples:
-            break
-        audio_seq = data_batch["samples"][:, None].to(device)
-        labels = data_batch["label"].to(device)
-        state.add_batch(model, distance, audio_seq, labels, first, args.seed, args, classifier)
-        if world == 1:
-            print(format_line(state.num_samples, state.log_dict()))
-    if world > 1:
-        import torch.distributed as dist
-
-        gathered = [None] * world if rank == 0 else None
-        dist.gather_object(state.to_host(), gathered, dst=0)
-        if rank == 0:
-            merged = gathered[0]
-            for other in gathered[1:]:
-                merged.merge(other)
-            print(format_line(merged.num_samples, merged.log_dict()))
-        dist.barrier()
-        dist.destroy_process_group()
+    run_pass(args, build, no_device="the encoder, the decoder and the distance kernel have no CPU path",
+             check_data=lambda num_labels: check_target(args.target, num_labels))
 
 
 if __name__ == "__main__":

@@ -12,10 +12,9 @@ over the [B, num_latents, T / rate] logits).  After every batch one line, the on
     {n} samples: nll_q0=... nll_q3=... acc_q0=... acc_q3=... top5_q0=... top5_q3=... nll=... acc=...
 
 nll_* is the per-position mean -- the number `EncoderPredictor.losses` returns -- and acc_* / top5_* the fraction of positions;
-nll and acc are exact over every position so far.  The flags, the seeding and the torchrun behaviour are those of
-eval_classifier.py and eval_vqvae.py.
+nll and acc are exact over every position so far.  The common flags, the seeding and the torchrun behaviour are those of the
+shared pass (vq_voice_swap_amd/eval_pass.py).
 """
-import argparse
 import os
 import sys
 
@@ -24,43 +23,33 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch  # noqa: E402,F401
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from eval_classifier import EvalState, format_line, run_pass  # noqa: E402,F401
+from eval_classifier import EvalState, format_line  # noqa: E402,F401
 from vq_voice_swap_amd import VQVAE, EncoderPredictor  # noqa: E402
+from vq_voice_swap_amd.eval_pass import common_parser, run_pass  # noqa: E402
 
 
 def arg_parser():
-    p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
-    p.add_argument("--batch-size", type=int, default=4)
-    p.add_argument("--precision", default="fp32", choices=["fp32", "fp16", "bf16"])
-    p.add_argument("--seed", default=0, type=int)
-    p.add_argument("--max-samples", default=None, type=int, help="stop after this many clips (default: one pass over the data)")
-    p.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend when WORLD_SIZE > 1")
+    p = common_parser()
     p.add_argument("--topk", default=5, type=int, help="k of the top-k accuracy (clipped to the number of codes)")
     p.add_argument("--vq-vae-path", required=True, type=str, help="the VQ-VAE whose codes the model predicts")
-    p.add_argument("checkpoint_path", type=str)
-    p.add_argument("data_dir", type=str)
     return p
 
 
 def main(argv=None):
     args = arg_parser().parse_args(argv)
-    box = {}
 
-    def load_model(device, num_labels):
-        vq_vae = VQVAE.load(args.vq_vae_path).to(device)
-        vq_vae.eval()
+    def build(device, num_labels):
+        vq_vae = VQVAE.load(args.vq_vae_path).to(device).eval()
         model = EncoderPredictor.load(args.checkpoint_path).to(device)
         # (what the reference builds the model from: train_loop.py:633-634)
         assert model.num_latents == vq_vae.dictionary_size, f"the model predicts {model.num_latents} codes, the VQ-VAE has {vq_vae.dictionary_size}"
         rate = vq_vae.encoder.downsample_rate
         assert model.downsample_rate == rate, f"the model's downsample rate is {model.downsample_rate}, the VQ-VAE encoder's {rate}"
-        model.eval()
-        model.set_precision(args.precision)
-        box["vq_vae"] = vq_vae
-        return model
+        model.eval().set_precision(args.precision)
+        state = EvalState(model.num_latents, device, args.topk, confusion=False)
+        return state, lambda audio, data_batch, first: state.add_batch(model, vq_vae.diffusion, audio, vq_vae.encode(audio), first, args.seed)
 
-    run_pass(args, load_model, lambda model, device: EvalState(model.num_latents, device, args.topk, confusion=False),
-             lambda audio, batch: box["vq_vae"].encode(audio), lambda model: box["vq_vae"].diffusion)
+    run_pass(args, build, no_device="the guidance models have no CPU path")
 
 
 if __name__ == "__main__":

@@ -17,12 +17,11 @@ out when the model has fewer than two labels), vq_loss the StandardVQLoss over e
 those of the accumulated code histogram.  The reference's per-quartile output-std hook is not rebuilt: it measured a module
 that no longer exists.
 
-`data_dir`, `--precision`, `--seed`, `--max-samples` and `--dist-backend` are those of eval_diffusion.py: everything random is
-keyed by the seed and the clip's position in the shuffled pass, so the result does not depend on the rank count.  Under
-torchrun (WORLD_SIZE > 1) batches are dealt round-robin, rank 0 merges the trackers, adds the histograms and the error sums,
-and prints the one final line.
+`data_dir`, `--precision`, `--seed`, `--max-samples` and `--dist-backend` are the common parser's and the pass is the shared one
+(vq_voice_swap_amd/eval_pass.py): everything random is keyed by the seed and the clip's position in the shuffled pass, so the
+result does not depend on the rank count.  Under torchrun (WORLD_SIZE > 1) batches are dealt round-robin, rank 0 merges the
+trackers, adds the histograms and the error sums, and prints the one final line.
 """
-import argparse
 import os
 import sys
 from fractions import Fraction
@@ -32,19 +31,12 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in devic
 import torch  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from vq_voice_swap_amd import LossTracker, StandardVQLoss, VQVAE, code_usage, create_data_loader  # noqa: E402
+from vq_voice_swap_amd import LossTracker, StandardVQLoss, VQVAE, code_usage  # noqa: E402
+from vq_voice_swap_amd.eval_pass import common_parser, format_line, run_pass  # noqa: E402,F401
 
 
 def arg_parser():
-    p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
-    p.add_argument("--batch-size", type=int, default=4)
-    p.add_argument("--precision", default="fp32", choices=["fp32", "fp16", "bf16"])
-    p.add_argument("--seed", default=0, type=int)
-    p.add_argument("--max-samples", default=None, type=int, help="stop after this many clips (default: one pass over the data)")
-    p.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend when WORLD_SIZE > 1")
-    p.add_argument("checkpoint_path", type=str)
-    p.add_argument("data_dir", type=str)
-    return p
+    return common_parser()
 
 
 def wrong_labels(labels: torch.Tensor, num_labels: int, seed: int, first: int) -> torch.Tensor:
@@ -105,55 +97,17 @@ class EvalState:
         return log
 
 
-def format_line(num_samples, log):
-    msg = " ".join(f"{key}={value}" if isinstance(value, int) else f"{key}={value:.06f}" for key, value in log.items())
-    return f"{num_samples} samples: {msg}"
-
-
 def main(argv=None):
     args = arg_parser().parse_args(argv)
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = 0
-    if world > 1:
-        import torch.distributed as dist
 
-        dist.init_process_group(args.dist_backend)
-        rank = dist.get_rank()
-    if not torch.cuda.is_available():
-        raise SystemExit("no ROCm device visible: the encoder and the predictor have no CPU path")
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count())
-    torch.cuda.set_device(device)
+    def build(device, num_labels):
+        model = VQVAE.load(args.checkpoint_path).to(device)
+        assert model.num_labels == num_labels, f"the model has {model.num_labels} labels, the data {num_labels}"
+        model.eval().set_precision(args.precision)
+        state = EvalState(model.vq.num_codes, device)
+        return state, lambda audio, data_batch, first: state.add_batch(model, audio, data_batch["label"].to(device), first, args.seed)
 
-    data_loader, num_labels = create_data_loader(directory=args.data_dir, batch_size=args.batch_size, seed=args.seed, rank=rank, world=world)
-    if rank == 0:
-        print("loading model from checkpoint...")
-    model = VQVAE.load(args.checkpoint_path).to(device)
-    assert model.num_labels == num_labels, f"the model has {model.num_labels} labels, the data {num_labels}"
-    model.eval()
-    model.set_precision(args.precision)
-
-    state = EvalState(model.vq.num_codes, device)
-    for i, data_batch in enumerate(data_loader):
-        first = (rank + i * world) * args.batch_size  # position of the batch's first clip in the shuffled pass
-        if args.max_samples is not None and first + args.batch_size > args.max_samples:
-            break
-        audio_seq = data_batch["samples"][:, None].to(device)
-        labels = data_batch["label"].to(device)
-        state.add_batch(model, audio_seq, labels, first, args.seed)
-        if world == 1:
-            print(format_line(state.num_samples, state.log_dict()))
-    if world > 1:
-        import torch.distributed as dist
-
-        gathered = [None] * world if rank == 0 else None
-        dist.gather_object(state.to_host(), gathered, dst=0)
-        if rank == 0:
-            merged = gathered[0]
-            for other in gathered[1:]:
-                merged.merge(other)
-            print(format_line(merged.num_samples, merged.log_dict()))
-        dist.barrier()
-        dist.destroy_process_group()
+    run_pass(args, build, no_device="the encoder and the predictor have no CPU path")
 
 
 if __name__ == "__main__":

@@ -22,6 +22,7 @@ import torch  # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from vq_voice_swap_amd import Classifier, FeatureStats  # noqa: E402
 from vq_voice_swap_amd.audio import ChunkReader  # noqa: E402
+from vq_voice_swap_amd.eval_pass import close_ranks, local_device, open_ranks  # noqa: E402
 from vq_voice_swap_amd.sampler import shard_range  # noqa: E402
 
 
@@ -86,20 +87,9 @@ def batches_of_equal_length(files, batch_size, rate):
 
 def main(argv=None):
     args = parse_args(argv)
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = 0
-    if world > 1:
-        import torch.distributed as dist
-
-        dist.init_process_group(args.dist_backend)
-        rank = dist.get_rank()
-    if not torch.cuda.is_available():
-        raise SystemExit("no ROCm device visible: the classifier has no CPU path")
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count())
-    torch.cuda.set_device(device)
-    classifier = Classifier.load(args.checkpoint_path).to(device)
-    classifier.eval()
-    classifier.set_precision(args.precision)
+    rank, world = open_ranks(args.dist_backend)
+    device = local_device("the classifier has no CPU path")
+    classifier = Classifier.load(args.checkpoint_path).to(device).eval().set_precision(args.precision)
 
     files = list_samples(args.sample_dir, args.num_samples)
     begin, end = shard_range(len(files), rank, world)
@@ -115,11 +105,7 @@ def main(argv=None):
             raise SystemExit(f"{stats.n} clip(s) in {args.sample_dir}: a covariance needs at least two")
         print(f"classifier score: {stats.class_score()}")
         stats.save(args.output_path)
-    if world > 1:
-        import torch.distributed as dist
-
-        dist.barrier()
-        dist.destroy_process_group()
+    close_ranks(world)
 
 
 if __name__ == "__main__":

@@ -16,6 +16,7 @@ from vq_voice_swap_amd import SpectralDistance, VQVAE, _native, spectral_constan
 
 import spectral_ref as sr
 from mfcc_ref import FAMILIES, GATE_FACTOR
+from util import flags_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARGS = ["const float* d_a", "const float* d_b", "const float* d_window", "const double* d_twiddle", "const float* d_fb",
@@ -158,10 +159,6 @@ def test_every_mutant_lies_100_gates_from_the_reference(cfg):
 
 
 # ---------------------------------------------------------------- eval_conversion.py
-def flags_of(parser):
-    return sorted(s for a in parser._actions for s in (a.option_strings or [a.dest]) if s not in ("-h", "--help"))
-
-
 def test_script_flags_and_refusals(capsys):
     import eval_conversion
     import eval_vqvae

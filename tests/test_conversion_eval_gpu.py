@@ -11,7 +11,6 @@ Measured on MI355X (profiles/conversion_eval_margins.jsonl, the clip nearest its
 0.125 of the gate -- |got - ref| equals E_model to 6e-6 relative on every case, so the factor 8 is unused --, the largest error
 4.0e-5 dB per frame, and the 168 records whose clip has b = a are exactly 0."""
 import itertools
-import os
 import re
 from functools import lru_cache
 
@@ -24,11 +23,10 @@ from vq_voice_swap_amd.det_init import det_init_
 
 import spectral_ref as sr
 from mfcc_ref import FAMILIES
-from util import record_margin
+from util import record_margin, run_script, sample_lines
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUTPUTS = ("mcd", "lsd")
 
 
@@ -189,13 +187,11 @@ def in_process(model, argv, dev, classifier=None):
 
 
 def test_eval_conversion_script(tmp_path, dev):
-    from test_guidance_eval_gpu import run_script
-
     model = vqvae32()
     ckpt = tmp_path / "vqvae32.pt"
     model.save(str(ckpt))
     args = [str(ckpt)] + BASE
-    lines = run_script("eval_conversion.py", args)
+    lines = sample_lines(run_script("eval_conversion.py", args))
     assert len(lines) == 2
     for n, ln in zip((2, 4), lines):
         m = LINE.match(ln)
@@ -205,19 +201,17 @@ def test_eval_conversion_script(tmp_path, dev):
     state, line = in_process(model.to(dev).set_precision("fp32"), args, dev)
     assert lines[-1] == line and (state.num_samples, state.codes, state.frames) == (4, 1000, 4 * 401)
     assert state.sums["mcd"] > 0 and state.sums["lsd"] > 0  # a converted clip is not its source
-    assert run_script("eval_conversion.py", args, ranks=2) == lines[-1:]  # one merged line, the one a single rank ends with
+    assert sample_lines(run_script("eval_conversion.py", args, ranks=2)) == lines[-1:]  # one merged line, the one a single rank ends with
 
 
 def test_eval_conversion_script_reference_and_classifier(tmp_path, dev):
-    from test_guidance_eval_gpu import run_script
-
     model, clf = vqvae32(), det_model(Classifier(num_labels=3, base_channels=32))
     ckpt, clf_path = tmp_path / "vqvae32.pt", tmp_path / "clf32.pt"
     model.save(str(ckpt))
     clf.save(str(clf_path))
     # the reference run repeats the first one: same sampler, steps, codes, labels and x_T
     args = [str(ckpt)] + BASE + ["--target", "same", "--reference-steps", "2", "--reference-sampler", "ddpm", "--classifier", str(clf_path)]
-    lines = run_script("eval_conversion.py", args)
+    lines = sample_lines(run_script("eval_conversion.py", args))
     assert len(lines) == 2
     for n, ln in zip((2, 4), lines):
         m = LINE.match(ln)

@@ -18,7 +18,7 @@ from oracle import ref_cpu
 from vq_voice_swap_amd import _native
 from vq_voice_swap_amd.diffusion import Diffusion, make_schedule
 
-from util import seeded
+from util import flags_of, seeded
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STEP_REL = {"exp": 2e-6, "cos": 4e-6}  # the project's gates for the DDPM step's arithmetic (tests/test_longform_gpu.py)
@@ -245,10 +245,6 @@ def test_sampler_argument_checks():
     for bad in (("euler", 0.0), ("ddpm", 0.5)):
         with pytest.raises(ValueError):
             check_sampler(*bad)
-
-
-def flags_of(parser):
-    return sorted(s for a in parser._actions for s in (a.option_strings or [a.dest]) if s not in ("-h", "--help"))
 
 
 def test_script_flags_and_refusals(capsys):

@@ -14,6 +14,8 @@ import torch
 import vq_voice_swap_amd
 from vq_voice_swap_amd import Classifier, Diffusion, EncoderPredictor, _native, classification_scores
 
+from util import flags_of
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -74,10 +76,6 @@ def test_classification_scores_checks_raise_before_a_device():
         EncoderPredictor(base_channels=32, downsample_rate=256, num_latents=8).scores(x, ts, torch.zeros(2, 2, dtype=torch.int64))
     with pytest.raises(_native.NativeError):
         Diffusion(vq_voice_swap_amd.make_schedule("exp")).sample_q_seeded(x, ts, seed=0)
-
-
-def flags_of(parser):
-    return sorted(s for a in parser._actions for s in (a.option_strings or [a.dest]) if s not in ("-h", "--help"))
 
 
 COMMON_FLAGS = ["--batch-size", "checkpoint_path", "data_dir", "--precision", "--seed", "--max-samples", "--dist-backend"]

@@ -13,8 +13,6 @@ Measured on MI355X (profiles/guidance_eval_margins.jsonl): NLL vs float64 over t
 import json
 import os
 import re
-import subprocess
-import sys
 from functools import lru_cache
 
 import numpy as np
@@ -24,11 +22,10 @@ import torch
 from vq_voice_swap_amd import VQVAE, Classifier, Diffusion, EncoderPredictor, _native, classification_scores, create_data_loader, make_schedule, randn_clips
 from vq_voice_swap_amd.det_init import det_init_
 
-from util import seeded
+from util import run_script, sample_lines, seeded
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GRID = [(K, L) for K in (1, 2, 7, 96, 251, 512, 8192) for L in (1, 37, 64, 250) if (K, L) != (8192, 250)]
 BATCHES = (1, 3)
 U = 2.0 ** -53
@@ -334,21 +331,6 @@ def test_sample_q_seeded(dev, T):
 LINE = re.compile(r"^(\d+) samples:((?: nll_q[0-3]=\d+\.\d{6})+)((?: acc_q[0-3]=\d+\.\d{6})+)((?: top(\d+)_q[0-3]=\d+\.\d{6})+) nll=(\d+\.\d{6}) acc=(\d+\.\d{6})$")
 
 
-def run_script(script, args, ranks=1):
-    sys.path.insert(0, ROOT)
-    from bench import free_port
-
-    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""), OMP_NUM_THREADS="2")
-    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
-        env.pop(k, None)
-    launch = [sys.executable] if ranks == 1 else [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}",
-                                                  "--master-addr", "127.0.0.1", "--master-port", str(free_port())]
-    cmd = ["timeout", "-k", "10", "300"] + launch + [os.path.join(ROOT, script)] + args + (["--dist-backend", "gloo"] if ranks > 1 else [])
-    r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT)
-    assert r.returncode == 0, f"exit status {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}"
-    return [ln for ln in r.stdout.splitlines() if " samples: " in ln]
-
-
 def check_lines(lines, positions_per_clip, topk):
     assert len(lines) == 2
     for n, ln in zip((2, 4), lines):
@@ -375,14 +357,14 @@ def test_eval_classifier_script(tmp_path, dev):
     ckpt, conf_path = tmp_path / "clf32.pt", tmp_path / "confusion.npy"
     model.save(str(ckpt))
     args = [str(ckpt), "tones", "--batch-size", "2", "--seed", "1", "--max-samples", "4"]
-    lines = run_script("eval_classifier.py", args + ["--confusion-path", str(conf_path)])
+    lines = sample_lines(run_script("eval_classifier.py", args + ["--confusion-path", str(conf_path)]))
     check_lines(lines, 1, 3)
     state, line = in_process(model.to(dev), Diffusion(make_schedule("exp")), 3, lambda audio, batch: batch["label"].to(dev), dev)
     assert lines[-1] == line
     conf = np.load(conf_path)
     assert conf.shape == (3, 3) and conf.dtype == np.int64 and conf.sum() == 4 and np.array_equal(conf, state.confusion.cpu().numpy())
     assert int(np.trace(conf)) == state.correct
-    two = run_script("eval_classifier.py", args, ranks=2)
+    two = sample_lines(run_script("eval_classifier.py", args, ranks=2))
     assert two == lines[-1:]  # one merged line, the one a single rank ends with
     # a fixed t: every clip falls into one quartile
     import eval_classifier
@@ -401,9 +383,9 @@ def test_eval_enc_pred_script(tmp_path, dev):
     vq_vae.save(str(vq_path))
     model.save(str(ckpt))
     args = ["--vq-vae-path", str(vq_path), str(ckpt), "tones", "--batch-size", "2", "--seed", "1", "--max-samples", "4"]
-    lines = run_script("eval_enc_pred.py", args)
+    lines = sample_lines(run_script("eval_enc_pred.py", args))
     check_lines(lines, 250, 5)
     vq_vae.to(dev)
     state, line = in_process(model.to(dev), vq_vae.diffusion, 512, lambda audio, batch: vq_vae.encode(audio), dev, confusion=False)
     assert lines[-1] == line and state.positions == 1000
-    assert run_script("eval_enc_pred.py", args, ranks=2) == lines[-1:]
+    assert sample_lines(run_script("eval_enc_pred.py", args, ranks=2)) == lines[-1:]

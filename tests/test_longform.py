@@ -14,7 +14,7 @@ import vq_voice_swap_amd
 from oracle import ref_cpu
 from vq_voice_swap_amd import _native, plan_windows
 
-from util import seeded
+from util import flags_of, seeded
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -143,10 +143,6 @@ def test_oracle_blend_runs_from_the_left_window_to_the_right(constrain):
     # outside the overlap each window stands alone, and both rows of the window output carry the blended samples
     assert np.array_equal(got[:H], alone[0][:H]) and np.array_equal(got[W:], alone[1][V:])
     assert np.array_equal(win[0], got[:W]) and np.array_equal(win[1], got[H:])
-
-
-def flags_of(parser):
-    return sorted(s for a in parser._actions for s in (a.option_strings or [a.dest]) if s not in ("-h", "--help"))
 
 
 def test_script_flags():

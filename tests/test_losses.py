@@ -12,6 +12,8 @@ from vq_voice_swap_amd import LossTracker, create_data_loader
 from vq_voice_swap_amd.audio import ChunkWriter, encode_u_law
 from vq_voice_swap_amd.dataset import AudioFormatError, SpeakerWindows, ToneDataset
 
+from util import flags_of
+
 
 @pytest.fixture(scope="module")
 def f16(golden):
@@ -159,10 +161,6 @@ def test_directory_of_flac_only_is_refused(tmp_path):
 
 
 # ---------------------------------------------------------------- scripts' flags
-def flags_of(parser):
-    return sorted(s for a in parser._actions for s in (a.option_strings or [a.dest]) if s not in ("-h", "--help"))
-
-
 def test_eval_diffusion_flags():
     import eval_diffusion
 

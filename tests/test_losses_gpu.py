@@ -6,8 +6,6 @@ Measured on MI355X (profiles/loss_parity_margins.jsonl): noise kernel 8.6e-8 (bo
 end-to-end rows of fixtures A and B at most 4.6e-7 in fp32 (bounds ~5.8e-5) and 3.2e-5 in fp16 (bounds ~2.3e-3)."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -17,11 +15,10 @@ from vq_voice_swap_amd import DiffusionModel, LossTracker, VQVAE, _native, creat
 from vq_voice_swap_amd.audio import ChunkWriter
 from vq_voice_swap_amd.det_init import det_init_
 
-from util import seeded
+from util import run_script, sample_lines, seeded
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the project's per-forward relative-RMS bounds of the two gate modes (tests/test_parity_gpu.py: FP32_REL, FP16_REL)
 RHO = {"fp32": 1e-4, "fp16": 4e-3}
 T16 = 16384
@@ -224,22 +221,13 @@ def test_speaker_search_micro_batch_invariance(f16, dev):
 
 
 # ---------------------------------------------------------------- scripts
-def run_script(args, seconds):
-    """One fresh child process under its own time limit; a failing child fails the test at once."""
-    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    r = subprocess.run(["timeout", "-k", "10", str(seconds), sys.executable] + [str(a) for a in args], capture_output=True, text=True,
-                       env=env, cwd=ROOT)
-    assert r.returncode == 0, f"exit status {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}"
-    return r.stdout
-
-
 def test_eval_diffusion_script(tmp_path, dev):
     model = det_model(DiffusionModel("unet", 32))
     ckpt = tmp_path / "unet32.pt"
     model.save(str(ckpt))
-    cmd = [os.path.join(ROOT, "eval_diffusion.py"), ckpt, "tones", "--batch-size", "3", "--seed", "1"]
-    out = run_script(cmd, 300)
-    lines = [ln for ln in out.splitlines() if " samples: " in ln]
+    args = [ckpt, "tones", "--batch-size", "3", "--seed", "1"]
+    out = run_script("eval_diffusion.py", args)
+    lines = sample_lines(out)
     assert len(lines) == 10 and lines[-1].startswith("30 samples: ")
     assert [ln.split(" ")[0] for ln in lines] == [str(3 * (i + 1)) for i in range(10)]
     # the same pass, driven directly
@@ -250,10 +238,19 @@ def test_eval_diffusion_script(tmp_path, dev):
         tracker.add(ts, model.diffusion.denoising_losses(batch["samples"][:, None].to(dev), model.predictor, ts, seed=1, clip_offset=3 * i))
     want = " ".join(f"{k}={v:.06f}" for k, v in tracker.log_dict().items())
     assert lines[-1] == f"30 samples: {want}"
-    assert run_script(cmd, 300) == out  # two runs, identical text
+    assert run_script("eval_diffusion.py", args) == out  # two runs, identical text
     # --max-samples ends the pass early
-    short = run_script(cmd + ["--max-samples", "7"], 300)
-    assert [ln for ln in short.splitlines() if " samples: " in ln] == lines[:2]
+    assert sample_lines(run_script("eval_diffusion.py", args + ["--max-samples", "7"])) == lines[:2]
+
+
+def test_eval_diffusion_script_two_ranks(tmp_path):
+    """Two ranks print one line: the one a single rank ends with."""
+    ckpt = tmp_path / "unet32.pt"
+    det_model(DiffusionModel("unet", 32)).save(str(ckpt))
+    args = [ckpt, "tones", "--batch-size", "3", "--seed", "1", "--max-samples", "6"]
+    one = sample_lines(run_script("eval_diffusion.py", args))
+    assert len(one) == 2 and one[-1].startswith("6 samples: ")
+    assert sample_lines(run_script("eval_diffusion.py", args, ranks=2)) == one[1:]
 
 
 def test_voice_search_script(tmp_path, f16, dev):
@@ -264,8 +261,7 @@ def test_voice_search_script(tmp_path, f16, dev):
     w = ChunkWriter(str(wav), 16000)
     w.write((0.1 * seeded((64000,), 3)).clamp(-1, 1).numpy())
     w.close()
-    out = run_script([os.path.join(ROOT, "voice_search_vqvae.py"), "--input-file", wav, "--num-timesteps", "3", "--batch-size", "4",
-                      "--top-k", "3", "--seed", "2", ckpt], 300)
+    out = run_script("voice_search_vqvae.py", ["--input-file", wav, "--num-timesteps", "3", "--batch-size", "4", "--top-k", "3", "--seed", "2", ckpt])
     lines = out.splitlines()
     at = lines.index("top 3 sorted losses")
     assert lines[at + 1] == "-------"

@@ -9,8 +9,6 @@ all 256 codes equal (7 positions sit below the margin threshold), sq_err per cli
 import json
 import os
 import re
-import subprocess
-import sys
 from functools import lru_cache
 
 import numpy as np
@@ -20,7 +18,7 @@ import torch
 from vq_voice_swap_amd import VQVAE, StandardVQLoss, _native, code_usage, create_data_loader
 from vq_voice_swap_amd.det_init import det_init_
 
-from util import seeded
+from util import run_script, sample_lines, seeded
 
 pytestmark = pytest.mark.gpu
 
@@ -296,12 +294,8 @@ def test_eval_vqvae_script(tmp_path, dev):
     model = det_model(VQVAE(base_channels=32, pred_name="unet", num_labels=3))
     ckpt = tmp_path / "vqvae32.pt"
     model.save(str(ckpt))
-    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    cmd = ["timeout", "-k", "10", "300", sys.executable, os.path.join(ROOT, "eval_vqvae.py"), str(ckpt), "tones", "--batch-size", "4",
-           "--seed", "1", "--max-samples", "8"]
-    r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT)
-    assert r.returncode == 0, f"exit status {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}"
-    lines = [ln for ln in r.stdout.splitlines() if " samples: " in ln]
+    args = [ckpt, "tones", "--batch-size", "4", "--seed", "1", "--max-samples", "8"]
+    lines = sample_lines(run_script("eval_vqvae.py", args))
     assert len(lines) == 2
     for n, ln in zip((4, 8), lines):
         m = LINE.match(ln)
@@ -309,3 +303,13 @@ def test_eval_vqvae_script(tmp_path, dev):
         assert int(m.group(1)) == n
         used, perplexity = int(m.group(5)), float(m.group(6))
         assert 1 <= used <= model.vq.num_codes and 1.0 <= perplexity <= used
+    # the same pass, driven directly
+    import eval_vqvae
+
+    model.to(dev).set_precision("fp32")
+    state = eval_vqvae.EvalState(model.vq.num_codes, dev)
+    loader, _ = create_data_loader("tones", batch_size=4, seed=1)
+    for i, batch in zip(range(2), loader):
+        state.add_batch(model, batch["samples"][:, None].to(dev), batch["label"].to(dev), 4 * i, 1)
+    assert lines[-1] == eval_vqvae.format_line(state.num_samples, state.log_dict())
+    assert sample_lines(run_script("eval_vqvae.py", args, ranks=2)) == lines[-1:]  # one merged line, the one a single rank ends with

@@ -13,6 +13,40 @@ def rms(a):
     return a.pow(2).mean().sqrt().item()
 
 
+def flags_of(parser):
+    return sorted(s for a in parser._actions for s in (a.option_strings or [a.dest]) if s not in ("-h", "--help"))
+
+
+def run_script(script, args, ranks=1, seconds=300):
+    """A script of the repository root as one fresh child process under its own time limit (`ranks` > 1: that many gloo ranks under
+    torch.distributed.run); a failing child fails the test at once.  Returns the whole stdout."""
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
+        env.pop(k, None)
+    launch, tail = [sys.executable], []
+    if ranks > 1:
+        from bench import free_port
+
+        env["OMP_NUM_THREADS"] = "2"
+        launch += ["-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}", "--master-addr", "127.0.0.1",
+                   "--master-port", str(free_port())]
+        tail = ["--dist-backend", "gloo"]
+    cmd = ["timeout", "-k", "10", str(seconds)] + launch + [os.path.join(root, script)] + [str(a) for a in args] + tail
+    r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=root)
+    assert r.returncode == 0, f"exit status {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}"
+    return r.stdout
+
+
+def sample_lines(stdout):
+    """The "{n} samples: ..." lines of an eval script's output."""
+    return [ln for ln in stdout.splitlines() if " samples: " in ln]
+
+
 def record_margin(file_name, rec):
     """Print one measured margin and, when the environment names a directory in VQVS_MARGINS_DIR, append it to <file_name>
     there (the print-and-append half of `gate`, for gates that are not an RMS of a waveform; a GPU run's records are kept under
