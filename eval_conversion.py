@@ -11,19 +11,25 @@ eta=--eta, constrain=True, seed=--seed, clip_offset=first)` -- x_T and every ste
 position in the pass --, `VQVAE.code_agreement` and `SpectralDistance` (one fused kernel).  After every batch one line:
 
     {n} samples: code_match=... mcd=... lsd=... [ref_code_match=... ref_mcd=... ref_lsd=... gap_mcd=... gap_lsd=...] [target_acc=... target_nll=... source_acc=...]
+                 [f0_shift=... f0_dev=... vuv_err=... voiced=... [ref_f0_shift=... ref_f0_dev=... ref_vuv_err=... gap_f0_dev=... gap_vuv_err=...]]
 
 code_match is agreeing codes / codes; mcd and lsd are dB per frame, source against converted (sum of the clips' sums / frames).
 `--target other` (default) draws a seeded different label per clip (`wrong_labels` of eval_vqvae.py), `same` reconstructs every clip
 under its own label (a codec / vocoder style score), an integer is one fixed label.  `--reference-steps R` decodes the same codes,
 labels and x_T a second time with `--reference-sampler` at R steps: ref_* score that run against the source, gap_* the two runs
 against each other.  `--classifier PATH` adds a `Classifier` at t = 0 on the converted audio: target_acc / target_nll for the
-target label, source_acc how often it still names the source's (left out with `--target same`).  All sums are exact -- integer
+target label, source_acc how often it still names the source's (left out with `--target same`).  `--pitch` adds `PitchDistance`
+(YIN periods of the 16-bit samples, one fused kernel): f0_shift, the mean over the frames voiced in both clips of the semitones by
+which the converted clip is higher than the source; f0_dev, the RMS deviation of that distance around each clip's own mean (the
+intonation contour, the register shift removed); vuv_err, frames whose voicing differs / frames; voiced, the source's voiced frames /
+frames; with a reference run ref_* for it and gap_f0_dev, gap_vuv_err between the two runs.  All sums are exact -- integer
 counts, and the float64 clip sums added as fractions -- so the line does not depend on the batch size or the rank count.
 
 `data_dir`, `--batch-size`, `--precision`, `--seed`, `--max-samples` and `--dist-backend` are the common parser's and the pass is
 the shared one (vq_voice_swap_amd/eval_pass.py).  Under torchrun (WORLD_SIZE > 1) batches are dealt round-robin, rank 0 merges
 the states and prints the one final line.
 """
+import math
 import os
 import sys
 from fractions import Fraction
@@ -34,7 +40,7 @@ import torch  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from eval_vqvae import wrong_labels  # noqa: E402
-from vq_voice_swap_amd import VQVAE, Classifier, SpectralDistance, randn_clips  # noqa: E402
+from vq_voice_swap_amd import VQVAE, Classifier, PitchDistance, SpectralDistance, randn_clips  # noqa: E402
 from vq_voice_swap_amd.eval_pass import common_parser, format_line, run_pass  # noqa: E402,F401
 
 SAMPLERS = ["ddpm", "ddim", "dpmpp"]
@@ -55,6 +61,8 @@ def arg_parser():
 def parse_args(argv=None):
     """The command line with everything that can be refused from the flags alone."""
     parser = arg_parser()
+    # the opt-in scores join the parser here: `arg_parser()` stays the flag set the default line is made of
+    parser.add_argument("--pitch", action="store_true", help="add F0 scores (YIN on the 16-bit samples): register shift, contour deviation, voicing errors")
     args = parser.parse_args(argv)
     if args.sampler != "ddim" and args.eta:
         parser.error("--eta belongs to --sampler ddim (ddpm has its own variance, dpmpp is deterministic)")
@@ -93,30 +101,51 @@ def _exact(values) -> Fraction:
     return sum((Fraction(float(v)) for v in values), Fraction(0))
 
 
+def _pitch_scores(out, prefix=""):
+    """`PitchDistance`'s per-clip results as the lists `EvalState.add_scores` takes."""
+    return {prefix + "f0_n": out["voiced_both"].tolist(), prefix + "f0_s1": out["shift_sum"].tolist(), prefix + "f0_s2": out["shift_sq_sum"].tolist(),
+            prefix + "vuv": out["vuv"].tolist(), prefix + "voiced": out["voiced_a"].tolist()}
+
+
 class EvalState:
     """What one pass accumulates: clip, code and frame counts, the agreeing codes (integers) and the distance sums (fractions of
     the clips' float64 sums: the same whatever order batches and shards arrive in); with a reference run the same for it and for
-    the gap between the two runs; with a classifier its hits and summed NLL."""
+    the gap between the two runs; with a classifier its hits and summed NLL; with pitch the voicing counts, the summed pitch
+    distance and the summed squared deviation around each clip's own mean."""
 
-    def __init__(self, reference: bool = False, classifier: bool = False, same: bool = False):
-        self.reference, self.classifier, self.same = bool(reference), bool(classifier), bool(same)
+    def __init__(self, reference: bool = False, classifier: bool = False, same: bool = False, pitch: bool = False):
+        self.reference, self.classifier, self.same, self.pitch = bool(reference), bool(classifier), bool(same), bool(pitch)
         self.num_samples = 0
         self.codes = 0    # code positions behind the *_match counts
         self.frames = 0   # frames behind the distance sums
         self.counts = {"code_match": 0, "ref_code_match": 0, "target_correct": 0, "source_correct": 0}
         self.sums = {k: Fraction(0) for k in ("mcd", "lsd", "ref_mcd", "ref_lsd", "gap_mcd", "gap_lsd", "target_nll")}
+        if self.pitch:  # per comparison: both-voiced frames, voicing mismatches, source-voiced frames; sum of l, and of the squared
+            for prefix in ("", "ref_", "gap_"):  # deviations around each clip's own mean, sum_c (S2_c - S1_c^2 / n_c)
+                self.counts.update({prefix + k: 0 for k in ("f0_n", "vuv", "voiced")})
+                self.sums.update({prefix + k: Fraction(0) for k in ("f0_s1", "f0_within")})
 
     def add_scores(self, codes_per_clip: int, frames_per_clip: int, scores) -> None:
         """Fold in one batch: `scores` maps "code_match" (and "ref_code_match", "target_correct", "source_correct") to one integer
-        per clip and "mcd", "lsd" (and the ref_ / gap_ ones, "target_nll") to one float64 sum per clip."""
+        per clip and "mcd", "lsd" (and the ref_ / gap_ ones, "target_nll") to one float64 sum per clip; with pitch also "f0_n", "vuv",
+        "voiced" (integers: frames voiced in both, voicing mismatches, frames voiced in the first signal) and "f0_s1", "f0_s2" (the
+        float64 sums of l_f and l_f^2), each also with the ref_ and gap_ prefixes when there is a reference run."""
         n = len(scores["mcd"])
         want = {"code_match", "mcd", "lsd"}
         if self.reference:
             want |= {"ref_code_match", "ref_mcd", "ref_lsd", "gap_mcd", "gap_lsd"}
         if self.classifier:
             want |= {"target_correct", "target_nll"} | (set() if self.same else {"source_correct"})
+        prefixes = (("", "ref_", "gap_") if self.reference else ("",)) if self.pitch else ()
+        want |= {p + k for p in prefixes for k in ("f0_n", "f0_s1", "f0_s2", "vuv", "voiced")}
         if set(scores) != want or any(len(v) != n for v in scores.values()):
             raise ValueError(f"expected {sorted(want)} with {n} entries each, got {sorted(scores)}")
+        if self.pitch:  # a clip's squared deviation around its own shift, exactly; a clip with no frame voiced in both adds nothing
+            scores = dict(scores)
+            for p in prefixes:
+                s2 = scores.pop(p + "f0_s2")
+                scores[p + "f0_within"] = [Fraction(float(q)) - Fraction(float(s)) ** 2 / int(c) if int(c) else Fraction(0)
+                                           for c, s, q in zip(scores[p + "f0_n"], scores[p + "f0_s1"], s2)]
         self.num_samples += n
         self.codes += n * int(codes_per_clip)
         self.frames += n * int(frames_per_clip)
@@ -124,12 +153,15 @@ class EvalState:
             if key in self.counts:
                 self.counts[key] += sum(int(v) for v in values)
             else:
-                self.sums[key] += _exact(values)
+                self.sums[key] += sum(values, Fraction(0)) if key.endswith("f0_within") else _exact(values)
 
     def add_batch(self, model: VQVAE, distance: SpectralDistance, audio: torch.Tensor, labels: torch.Tensor, first: int, seed: int,
-                  run, classifier=None) -> None:
+                  run, classifier=None, pitch=None) -> None:
         """Convert and score one batch whose first clip is clip `first` of the pass; `run` carries target, sampler, eta,
-        sample_steps, reference_steps and reference_sampler (the parsed command line)."""
+        sample_steps, reference_steps and reference_sampler (the parsed command line); `pitch` is the `PitchDistance` of a state
+        built with pitch=True."""
+        if self.pitch and pitch is None:
+            raise ValueError("a state with pitch=True needs a PitchDistance")
         target = target_labels(labels, run.target, model.num_labels, seed, first)
         codes = model.encode(audio)
         # the draw `decode` would make itself from (seed, clip_offset): made here so that the reference run starts from the same x_T
@@ -141,8 +173,11 @@ class EvalState:
 
         def against_source(out, prefix=""):
             d = distance(audio, out)
-            return {prefix + "code_match": model.code_agreement(codes, out).tolist(), prefix + "mcd": d["mcd"].tolist(),
-                    prefix + "lsd": d["lsd"].tolist()}
+            scores = {prefix + "code_match": model.code_agreement(codes, out).tolist(), prefix + "mcd": d["mcd"].tolist(),
+                      prefix + "lsd": d["lsd"].tolist()}
+            if self.pitch:
+                scores.update(_pitch_scores(pitch(audio, out), prefix))
+            return scores
 
         converted = decode(run.sampler, run.sample_steps)
         scores = against_source(converted)
@@ -151,6 +186,8 @@ class EvalState:
             scores.update(against_source(ref, "ref_"))
             gap = distance(converted, ref)
             scores.update(gap_mcd=gap["mcd"].tolist(), gap_lsd=gap["lsd"].tolist())
+            if self.pitch:
+                scores.update(_pitch_scores(pitch(converted, ref), "gap_"))
         if self.classifier:
             ts = torch.zeros(len(audio), device=audio.device)
             out = classifier.scores(converted, ts, target)
@@ -160,7 +197,7 @@ class EvalState:
         self.add_scores(codes.shape[-1], distance.frames(audio.shape[-1]), scores)
 
     def merge(self, other: "EvalState") -> "EvalState":
-        if (other.reference, other.classifier, other.same) != (self.reference, self.classifier, self.same):
+        if (other.reference, other.classifier, other.same, other.pitch) != (self.reference, self.classifier, self.same, self.pitch):
             raise ValueError("cannot merge states of differently configured passes")
         self.num_samples += other.num_samples
         self.codes += other.codes
@@ -187,6 +224,17 @@ class EvalState:
             log["target_nll"] = per(self.sums["target_nll"], self.num_samples)
             if not self.same:
                 log["source_acc"] = per(self.counts["source_correct"], self.num_samples)
+        if self.pitch:
+            def dev(prefix):
+                # (S2_c - S1_c^2 / n_c of the clips' ROUNDED sums can fall a rounding below 0 where a clip's l_f are all equal)
+                return math.sqrt(max(0.0, per(self.sums[prefix + "f0_within"], self.counts[prefix + "f0_n"])))
+
+            log.update(f0_shift=per(self.sums["f0_s1"], self.counts["f0_n"]), f0_dev=dev(""), vuv_err=per(self.counts["vuv"], self.frames),
+                       voiced=per(self.counts["voiced"], self.frames))
+            if self.reference:
+                log.update(ref_f0_shift=per(self.sums["ref_f0_s1"], self.counts["ref_f0_n"]), ref_f0_dev=dev("ref_"),
+                           ref_vuv_err=per(self.counts["ref_vuv"], self.frames), gap_f0_dev=dev("gap_"),
+                           gap_vuv_err=per(self.counts["gap_vuv"], self.frames))
         return log
 
 
@@ -202,10 +250,11 @@ def main(argv=None):
             classifier = Classifier.load(args.classifier).to(device)
             assert classifier.num_labels == num_labels, f"the classifier has {classifier.num_labels} labels, the data {num_labels}"
             classifier.eval().set_precision(args.precision)
-        distance = SpectralDistance()
-        state = EvalState(reference=args.reference_steps is not None, classifier=classifier is not None, same=args.target == "same")
+        distance, pitch = SpectralDistance(), PitchDistance() if args.pitch else None
+        state = EvalState(reference=args.reference_steps is not None, classifier=classifier is not None, same=args.target == "same",
+                          pitch=args.pitch)
         return state, lambda audio, data_batch, first: state.add_batch(model, distance, audio, data_batch["label"].to(device), first, args.seed,
-                                                                        args, classifier)
+                                                                        args, classifier, pitch)
 
     run_pass(args, build, no_device="the encoder, the decoder and the distance kernel have no CPU path",
              check_data=lambda num_labels: check_target(args.target, num_labels))

@@ -466,6 +466,35 @@ int vqvs_spectral_distance(const float* d_a, const float* d_b, const float* d_wi
                            const float* d_fb, const float* d_dct, double* d_mcd, double* d_lsd,
                            int B, int T, int n_fft, int hop, int n_mels, int n_ceps, float eps, void* stream);
 
+/* ---- pitch scores (handle-less) -----------------------------------------------------------
+ * YIN periods of waveform batches a and b, frame for frame, and per clip the voicing counts and the sums of the pitch distance in
+ * semitones, in one kernel (pitch_kernels.hip; no frame or difference function goes to memory).  Frames F = T / hop + 1.  The
+ * definition, per signal and frame f, with S = window + tau_max:
+ *   q[n] = clamp(rint(x[n] * 32768), -32768, 32767), NaN -> 0: the samples of a 16-bit WAV; frame f reads q[s .. s + S),
+ *   s = f hop - S / 2, zeros outside [0, T);  d(tau) = sum_{j < window} (q[s+j] - q[s+j+tau])^2, c(tau) = sum_{k=1..tau} d(k):
+ *   integers below 2^53, the same in any order;  d'(tau) = 1 if c(tau) = 0, else double(d(tau) tau) / double(c(tau));
+ *   tau0 = the smallest tau in [tau_min, tau_max] with d'(tau) < threshold (none: the frame is unvoiced, period 0.0), then tau
+ *   walks up while d'(tau + 1) < d'(tau);  period = tau if tau = tau_max, else with y0, y1, y2 = d'(tau-1), d'(tau), d'(tau+1) and
+ *   den = (y0 - y1) + (y2 - y1): tau + clamp(0.5 (y0 - y2) / den, -1, 1) if den > 0, else tau -- single float64 operations in
+ *   this order, no contraction.
+ * Over the frames voiced (period > 0) in both signals: l_f = +-12 log2(hi / lo) of the larger and smaller period, positive where
+ * period_a >= period_b: the semitones by which b is higher than a.
+ *   a, b       [B,T] f32; b may be NULL: track a only (then period_b, counts and sums must be NULL and period_a given)
+ *   period_a, period_b  [B,F] f64 out or NULL: samples, 0 = unvoiced
+ *   counts     [B,4] int64 out or NULL: frames voiced in a, in b, in both, and frames whose voicing differs
+ *   sums       [B,2] f64 out or NULL: sum of l_f and of l_f^2
+ * The periods are the definition's bit for bit.  Both signals of a frame run through the same instruction sequence, a workgroup
+ * adds its four frames in frame order and one thread adds a clip's workgroup partials (32 bytes per (clip, workgroup) in the
+ * per-(device, stream) scratch buffer) in order and is the clip's only writer -- no floating-point atomics.  So b = a gives sums
+ * (0, 0) without a sign bit, swapping a and b negates the first sum bitwise, and a clip's values are the same from run to run and
+ * whatever B and its row are.  Every non-NULL output is fully written; a NULL output leaves the others unchanged.
+ * Limits: B in 1..65535; T in 1..2^30 with at most 2^25 frames; window in 16..2048; hop in 1..window; 2 <= tau_min < tau_max <=
+ * 1023; window * tau_max <= 2^20; threshold finite, in (0, 1]; an output may not overlap an input or another output.
+ * Asynchronous on `stream`; NULL a, every output NULL or anything outside the limits returns VQVS_ERR_ARG with a message before
+ * the device is touched. */
+int vqvs_pitch_distance(const float* a, const float* b, double* period_a, double* period_b, long long* counts, double* sums,
+                        int B, int T, int window, int hop, int tau_min, int tau_max, double threshold, void* stream);
+
 /* ---- test / profiling hooks ------------------------------------------------------ */
 int vqvs_debug_tap_count(const vqvs_model* m);
 int vqvs_debug_tap_info(const vqvs_model* m, int i, char* name_out, int name_cap, int* channels, int* length_shift);

@@ -16,6 +16,7 @@ from .diffusion_model import DiffusionModel
 from .encoder_predictor import EncoderPredictor
 from .longform import plan_windows
 from .losses import LossTracker, classification_scores, speaker_search_losses
+from .pitch import PitchDistance
 from .spectral import SpectralDistance, spectral_constants
 from .stats import FeatureStats, class_score, frechet_distance, wav_roundtrip
 from .unet import ResBlockModule, UNetEncoder, UNetPredictor
@@ -27,5 +28,5 @@ __all__ = [
     "DiffusionModel", "Classifier", "ConvMFCCEncoder", "EncoderPredictor", "ResBlockModule", "UNetEncoder", "UNetPredictor", "VQ", "VQVAE",
     "FeatureStats", "class_score", "frechet_distance", "wav_roundtrip", "LossTracker", "speaker_search_losses", "create_data_loader",
     "StandardVQLoss", "VQLoss", "code_usage", "classification_scores", "plan_windows",
-    "SpectralDistance", "spectral_constants",
+    "SpectralDistance", "spectral_constants", "PitchDistance",
 ]

@@ -632,6 +632,39 @@ int vqvs_spectral_distance(const float* d_a, const float* d_b, const float* d_wi
                                reinterpret_cast<hipStream_t>(stream));
 }
 
+int vqvs_pitch_distance(const float* a, const float* b, double* period_a, double* period_b, long long* counts, double* sums, int B, int T,
+                        int window, int hop, int tau_min, int tau_max, double threshold, void* stream) {
+  if (!a) VQVS_FAIL(VQVS_ERR_ARG, "a must be non-NULL");
+  if (!b && (period_b || counts || sums)) VQVS_FAIL(VQVS_ERR_ARG, "b is NULL: period_b, counts and sums must be NULL too");
+  if (!b && !period_a) VQVS_FAIL(VQVS_ERR_ARG, "b is NULL: period_a must be given");
+  if (!period_a && !period_b && !counts && !sums) VQVS_FAIL(VQVS_ERR_ARG, "every output is NULL: nothing to compute");
+  if (B < 1 || B > 65535) VQVS_FAIL(VQVS_ERR_ARG, "batch %d outside 1..65535", B);
+  if (T < 1 || T > (1 << 30)) VQVS_FAIL(VQVS_ERR_ARG, "clip of %d samples outside 1..2^30", T);
+  if (window < 16 || window > 2048) VQVS_FAIL(VQVS_ERR_ARG, "window=%d outside 16..2048", window);
+  if (hop < 1 || hop > window) VQVS_FAIL(VQVS_ERR_ARG, "hop=%d outside 1..window=%d", hop, window);
+  if (T / hop + 1 > (1 << 25)) VQVS_FAIL(VQVS_ERR_ARG, "T=%d at hop=%d is more than 2^25 frames per clip", T, hop);
+  if (tau_max < 3 || tau_max > 1023) VQVS_FAIL(VQVS_ERR_ARG, "tau_max=%d outside 3..1023", tau_max);
+  if (tau_min < 2 || tau_min >= tau_max) VQVS_FAIL(VQVS_ERR_ARG, "tau_min=%d outside 2..tau_max-1=%d", tau_min, tau_max - 1);
+  if ((int64_t)window * tau_max > (1 << 20))
+    VQVS_FAIL(VQVS_ERR_ARG, "window=%d times tau_max=%d is more than 2^20: the sums would not stay below 2^53", window, tau_max);
+  if (!std::isfinite(threshold) || !(threshold > 0.0) || threshold > 1.0) VQVS_FAIL(VQVS_ERR_ARG, "threshold=%g must lie in (0, 1]", threshold);
+  const int64_t N = (int64_t)B * T, NF = (int64_t)B * (T / hop + 1);
+  const struct { const void* p; int64_t bytes; const char* name; } outs[] = {
+      {period_a, NF * 8, "period_a"}, {period_b, NF * 8, "period_b"}, {counts, (int64_t)B * 32, "counts"}, {sums, (int64_t)B * 16, "sums"}};
+  for (const auto& out : outs) {
+    if (bytes_overlap(out.p, out.bytes, a, N * 4) || bytes_overlap(out.p, out.bytes, b, N * 4))
+      VQVS_FAIL(VQVS_ERR_ARG, "%s must not overlap a or b", out.name);
+    for (const auto& other : outs)
+      if (&other != &out && bytes_overlap(out.p, out.bytes, other.p, other.bytes))
+        VQVS_FAIL(VQVS_ERR_ARG, "%s must not overlap %s", out.name, other.name);
+  }
+  ScratchLease lease;
+  if (counts || sums)
+    if (int e = scratch_get(pitch_distance_scratch_bytes(B, T, hop), stream, lease)) return e;
+  return run_pitch_distance(a, b, period_a, period_b, counts, sums, lease.p, B, T, window, hop, tau_min, tau_max, threshold,
+                            reinterpret_cast<hipStream_t>(stream));
+}
+
 int vqvs_vq_embed(const int64_t* d_idx, const float* d_dict, float* d_out, int B, int Cd, int T1, int K, void* stream) {
   if (!d_idx || !d_dict || !d_out) VQVS_FAIL(VQVS_ERR_ARG, "idx, dict and out must be non-NULL");
   if (B < 1 || Cd < 1 || T1 < 1 || K < 1) VQVS_FAIL(VQVS_ERR_ARG, "bad shape B=%d Cd=%d T1=%d K=%d", B, Cd, T1, K);

@@ -316,6 +316,15 @@ int run_spectral_distance(const float* a, const float* b, const float* window, c
                           void* scratch, double* mcd, double* lsd, int B, int T, int n_fft, int hop, int n_mels, int n_ceps, float eps,
                           hipStream_t st);
 
+// ----------------------------------------------------------------------------------
+// Pitch scores (pitch_kernels.hip): per-frame YIN periods of one or two waveform batches, per-clip voicing counts and sums of the
+// frame-wise pitch distance in semitones; scratch holds pitch_distance_scratch_bytes(B, T, hop) bytes of tile partials.  b may be
+// nullptr (then only period_a may be asked for); every output may be nullptr.
+// ----------------------------------------------------------------------------------
+size_t pitch_distance_scratch_bytes(int B, int T, int hop);
+int run_pitch_distance(const float* a, const float* b, double* period_a, double* period_b, long long* counts, double* sums, void* scratch,
+                       int B, int T, int window, int hop, int tau_min, int tau_max, double threshold, hipStream_t st);
+
 // layout changes at the library boundary (reference tensors are NCT float32)
 int launch_nct_to_ntc(const float* in, void* out, float* stats, int B, int C, int L, int ntiles, int precision, hipStream_t st);
 int launch_ntc_to_nct(const void* in, float* out, int B, int C, int L, int in_precision, hipStream_t st);
