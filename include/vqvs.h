@@ -52,6 +52,13 @@ extern "C" {
                                   reserved[2] = input_ulaw.  fp32 precision only.  Its parameter table starts with the three
                                   buffers of torchaudio.transforms.MFCC that a reference checkpoint carries (mfcc.dct_mat, ...) */
 
+#define VQVS_KIND_PREDICTOR_GRAD 6 /* UNetPredictor for speaker enrolment (reference train_vqvae_add.py, train_loop.py:438-485): the cfg
+                                  fields and the parameter table of VQVS_KIND_PREDICTOR with num_labels > 0 and out_channels == 1,
+                                  cond_channels 0 or not; runs vqvs_unet_embed_grad.  fp32 precision only; VQVS_ERR_ARG for a 2-byte
+                                  precision, a padded width (reserved[4] != 0), num_labels == 0 or out_channels != 1.  The handle keeps
+                                  every intermediate of the batch resident.  class_embed.weight is in the table but not read: the
+                                  conditioning vector of every clip is an argument of the call */
+
 /* activation storage / arithmetic */
 #define VQVS_PREC_F32 0  /* fp32 activations; convs as 3-term bf16-split MFMA, fp32 accumulate (~2^-17 rel.) */
 #define VQVS_PREC_BF16 1 /* bf16 activations; bf16 MFMA, fp32 accumulate */
@@ -207,6 +214,40 @@ int vqvs_encpred_forward(vqvs_model* m, const float* d_x, const float* d_ts, flo
  *   d_targets [B,T/rate] int64, d_grad [B,1,T] f32 out, d_logits [B,num_latents,T/rate] f32 out or NULL */
 int vqvs_encpred_guidance(vqvs_model* m, const float* d_x, const float* d_ts, const int64_t* d_targets, float scale,
                           float* d_grad, float* d_logits, int B, int T, void* stream);
+
+/* ---- speaker enrolment ----------------------------------------------------------------
+ * The gradient of every clip's noise-prediction MSE with respect to its conditioning vector: what the reference obtains with
+ * loss.backward() when only predictor.label_parameters() -- the class_embed table -- is trained (train_loop.py:438-485, 76;
+ * unet.py:133-135, 307-316).  VQVS_KIND_PREDICTOR_GRAD handles.  With emb_b = time_mlp(ts_b) + vec_b in place of
+ * class_embed[label_b], the call runs the predictor's forward schedule and then an explicit backward schedule that reaches only the
+ * FiLM coefficients of every ResBlock:
+ *   pred = UNetPredictor(x_t, ts, cond) under emb: bit for bit vqvs_unet_forward of an fp32 VQVS_KIND_PREDICTOR handle whose
+ *          class_embed rows are the vectors
+ *   mse[b]  = mean_t (eps[b,t] - pred[b,t])^2, summed exactly as vqvs_ddpm_sqerr sums it
+ *   grad[b] = d mse[b] / d vec_b = gelu'(emb_b) * Wall^T (d a | d b of every block), d a_c = sum_l du2[c,l] h^[c,l], d b_c = sum_l du2[c,l]
+ * The batch mean and the sum over the clips that share a row are vqvs_embed_adamw's.  Deterministic: every reduction has a fixed
+ * order and one writer per output, no atomics; the same call gives the same bits.
+ *   d_x_t [B,in_channels,T] f32, d_ts [B] f32, d_cond as for vqvs_unet_forward (NULL iff cond_channels == 0)
+ *   d_vec [B,E] f32, E = 4 * base_channels;  d_eps [B,1,T] f32
+ *   d_mse [B] f32 out, d_grad [B,E] f32 out;  d_pred [B,1,T] f32 out or NULL
+ *   d_mse == NULL and d_grad == NULL: the forward schedule alone (d_pred is then required and d_eps is not read)
+ * VQVS_ERR_ARG before the device is touched: a NULL required pointer, d_cond not matching the cfg, exactly one of d_mse / d_grad
+ * NULL, B or T outside the handle's limits. */
+int vqvs_unet_embed_grad(vqvs_model* m, const float* d_x_t, const float* d_ts, const float* d_cond, const float* d_vec,
+                         const float* d_eps, float* d_mse, float* d_grad, float* d_pred, int B, int T, void* stream);
+/* One AdamW step on n embedding rows from per-clip gradients (handle-less; torch.optim.AdamW's update, decoupled weight decay and
+ * bias correction; `step` is the 1-based count of this step).  One kernel, one thread per (row, e):
+ *   g = (sum of d_grad[b, e] over the clips with d_row_of_clip[b] == row, in clip order) / B      -- losses.mean(), train_loop.py:76
+ *   p *= 1 - lr * weight_decay;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2
+ *   p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ * evaluated in fp64 from the fp32 state and rounded once per stored value.  A row that no clip names has g = 0: with weight_decay 0
+ * and zero moments it is bitwise unchanged.  A clip whose index is outside 0..n-1 contributes to no row (the Python binding raises
+ * IndexError first).
+ *   d_rows, d_m, d_v [n,E] f32 in/out;  d_grad [B,E] f32;  d_row_of_clip [B] int64
+ * VQVS_ERR_ARG before the device is touched: a NULL pointer; n, B or E not positive; step < 1; lr, eps or weight_decay negative or
+ * not finite; a beta outside [0, 1). */
+int vqvs_embed_adamw(float* d_rows, float* d_m, float* d_v, const float* d_grad, const int64_t* d_row_of_clip, int n, int B, int E,
+                     int step, float lr, float beta1, float beta2, float eps, float weight_decay, void* stream);
 
 /* ---- DDPM reverse step --------------------------------------------------------
  * x_prev = Diffusion.ddpm_previous(x_t, ts, step, eps, noise, sigma_large, constrain)
@@ -505,6 +546,9 @@ int vqvs_debug_read_tap(vqvs_model* m, int i, int B, int T, float* h_out);
 /* copies the conditioning vector of the LAST forward -- time_embed_extra(time_embed(ts)) [+ class_embed(labels)], reference
  * unet.py:133-135 with wavegrad.py:359-373 -- to host as float32 [B][4*base_channels]; returns its width; synchronises */
 int vqvs_debug_read_embedding(vqvs_model* m, int B, float* h_out);
+/* copies d mse_b / d (FiLM rows) of the LAST vqvs_unet_embed_grad -- per clip the (d a | d b) rows of every ResBlock in the order
+ * down_blocks, middle_blocks, up_blocks, 2 * cout rows each -- to host as float32 [B][R]; returns R; synchronises */
+int vqvs_debug_read_dfilm(vqvs_model* m, int B, float* h_out);
 /* number of kernels one forward enqueues, and the algorithmic activation bytes it moves (SURVEY 8d Model A) */
 int vqvs_forward_kernel_count(const vqvs_model* m);
 int64_t vqvs_forward_model_bytes(const vqvs_model* m, int B, int T);

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VQVS_LIB_PATH") or os.path.join(_HERE, "libvqvs_hip.so")  # override: instrumented builds (tools/)
 CSRC = os.path.join(_HERE, "csrc")
 
-KIND_PREDICTOR, KIND_ENCODER, KIND_RESBLOCK, KIND_CLASSIFIER, KIND_ENCPRED, KIND_MFCC_ENCODER = 0, 1, 2, 3, 4, 5
+KIND_PREDICTOR, KIND_ENCODER, KIND_RESBLOCK, KIND_CLASSIFIER, KIND_ENCPRED, KIND_MFCC_ENCODER, KIND_PREDICTOR_GRAD = 0, 1, 2, 3, 4, 5, 6
 PREC_F32, PREC_BF16, PREC_F16 = 0, 1, 2
 DDPM_SIGMA_LARGE, DDPM_CONSTRAIN = 1, 2
 DDIM_CONSTRAIN, DDIM_INVERT = 2, 4
@@ -74,6 +74,7 @@ EXPORTS = [
     "vqvs_ddpm_guided_eps", "vqvs_randn", "vqvs_ddpm_noise", "vqvs_ddpm_sqerr", "vqvs_vq_argmin", "vqvs_vq_quantize", "vqvs_vq_embed", "vqvs_xent_score", "vqvs_spectral_distance", "vqvs_pitch_distance", "vqvs_debug_tap_count",
     "vqvs_debug_tap_info", "vqvs_debug_tap_rows", "vqvs_debug_read_tap", "vqvs_debug_read_embedding", "vqvs_forward_kernel_count", "vqvs_forward_model_bytes",
     "vqvs_forward_flops", "vqvs_set_profiling", "vqvs_op_info", "vqvs_op_desc", "vqvs_profile_read", "vqvs_last_error", "vqvs_version",
+    "vqvs_unet_embed_grad", "vqvs_embed_adamw", "vqvs_debug_read_dfilm",
 ]
 
 _lib = None
@@ -128,6 +129,9 @@ def lib():
     L.vqvs_model_device_bytes.argtypes = [vp]
     L.vqvs_model_device_bytes.restype = i64
     L.vqvs_unet_forward.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp]
+    L.vqvs_unet_embed_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
+    L.vqvs_embed_adamw.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp]
+    L.vqvs_debug_read_dfilm.argtypes = [vp, i32, vp]
     L.vqvs_encoder_forward.argtypes = [vp, vp, vp, i32, i32, vp]
     L.vqvs_mfcc_encoder_forward.argtypes = [vp, vp, vp, i32, i32, vp]
     L.vqvs_mfcc_encoder_forward_logmel.argtypes = [vp, vp, vp, i32, i32, vp]
@@ -328,6 +332,19 @@ class Handle:
         if r < 0:
             check(r)
         return out[:, :r]
+
+    def read_dfilm(self, B: int):
+        """d mse_b / d (FiLM rows) [B, R] of the last `vqvs_unet_embed_grad` on a predictor-gradient handle: per clip the (d a | d b)
+        rows of every ResBlock in the order down, middle, up."""
+        import torch
+
+        R = sum(shape[0] for name, shape in param_table(self.cfg) if name.endswith("cond_layers.1.bias"))  # 2 * cout rows per block
+        out = torch.empty(B, R, dtype=torch.float32)
+        r = lib().vqvs_debug_read_dfilm(self._h, B, out.data_ptr())
+        if r < 0:
+            check(r)
+        assert r == R, (r, R)
+        return out
 
     def read_tap(self, i: int, B: int, T: int):
         import torch

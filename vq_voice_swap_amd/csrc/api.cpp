@@ -193,6 +193,44 @@ int vqvs_unet_forward(vqvs_model* m, const float* d_x, const float* d_ts, const 
   return run_model(m, c);
 }
 
+int vqvs_unet_embed_grad(vqvs_model* m, const float* d_x_t, const float* d_ts, const float* d_cond, const float* d_vec, const float* d_eps,
+                         float* d_mse, float* d_grad, float* d_pred, int B, int T, void* stream) {
+  if (int e = check_run(m, VQVS_KIND_PREDICTOR_GRAD, B, T)) return e;
+  if (!d_x_t || !d_ts || !d_vec) VQVS_FAIL(VQVS_ERR_ARG, "x_t, ts and vec must be non-NULL");
+  if ((d_cond == nullptr) != (m->cfg.cond_channels == 0)) VQVS_FAIL(VQVS_ERR_ARG, "must provide cond sequence if and only if model is conditional");
+  if ((d_mse == nullptr) != (d_grad == nullptr)) VQVS_FAIL(VQVS_ERR_ARG, "mse and grad must be given together (both NULL: the forward alone)");
+  const bool backward = d_grad != nullptr;
+  if (backward && !d_eps) VQVS_FAIL(VQVS_ERR_ARG, "eps must be non-NULL when mse and grad are asked for");
+  if (!backward && !d_pred) VQVS_FAIL(VQVS_ERR_ARG, "nothing to compute: mse, grad and pred are all NULL");
+  RunCtx c;
+  c.B = B;
+  c.Lbase = T;
+  c.x = d_x_t;
+  c.ts = d_ts;
+  c.cond = d_cond;
+  c.class_vec = d_vec;
+  c.eps = d_eps;
+  c.mse = d_mse;
+  c.egrad = d_grad;
+  c.out = d_pred;
+  c.backward = backward;
+  c.st = reinterpret_cast<hipStream_t>(stream);
+  return run_model(m, c);
+}
+
+int vqvs_embed_adamw(float* d_rows, float* d_m, float* d_v, const float* d_grad, const int64_t* d_row_of_clip, int n, int B, int E,
+                     int step, float lr, float beta1, float beta2, float eps, float weight_decay, void* stream) {
+  if (!d_rows || !d_m || !d_v || !d_grad || !d_row_of_clip) VQVS_FAIL(VQVS_ERR_ARG, "rows, m, v, grad and row_of_clip must be non-NULL");
+  if (n < 1 || B < 1 || E < 1) VQVS_FAIL(VQVS_ERR_ARG, "bad shape n=%d B=%d E=%d", n, B, E);
+  if (step < 1) VQVS_FAIL(VQVS_ERR_ARG, "step=%d: the count of this step starts at 1", step);
+  if (!std::isfinite(lr) || lr < 0.f) VQVS_FAIL(VQVS_ERR_ARG, "lr=%g must be finite and not negative", (double)lr);
+  if (!std::isfinite(eps) || eps < 0.f) VQVS_FAIL(VQVS_ERR_ARG, "eps=%g must be finite and not negative", (double)eps);
+  if (!std::isfinite(weight_decay) || weight_decay < 0.f) VQVS_FAIL(VQVS_ERR_ARG, "weight_decay=%g must be finite and not negative", (double)weight_decay);
+  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) VQVS_FAIL(VQVS_ERR_ARG, "betas (%g, %g) must lie in [0, 1)", (double)beta1, (double)beta2);
+  return run_embed_adamw(d_rows, d_m, d_v, d_grad, d_row_of_clip, n, B, E, step, lr, beta1, beta2, eps, weight_decay,
+                         reinterpret_cast<hipStream_t>(stream));
+}
+
 int vqvs_encoder_forward(vqvs_model* m, const float* d_x, float* d_z, int B, int T, void* stream) {
   if (int e = check_run(m, VQVS_KIND_ENCODER, B, T)) return e;
   if (!d_x || !d_z) VQVS_FAIL(VQVS_ERR_ARG, "x and z must be non-NULL");
@@ -720,6 +758,16 @@ int vqvs_debug_read_embedding(vqvs_model* m, int B, float* h_out) {
   const float* src = reinterpret_cast<const float*>(m->d_arena + m->misc_off) + m->emb_misc_off;
   VQVS_HIP(hipMemcpy(h_out, src, (size_t)B * m->emb_E * sizeof(float), hipMemcpyDeviceToHost));
   return m->emb_E;
+}
+
+int vqvs_debug_read_dfilm(vqvs_model* m, int B, float* h_out) {
+  if (!m || !h_out || B < 1 || B > m->cfg.max_batch) VQVS_FAIL(VQVS_ERR_ARG, "bad argument");
+  if (!m->dfilm_R) VQVS_FAIL(VQVS_ERR_STATE, "this model kind has no FiLM-gradient buffer");
+  VQVS_HIP(hipSetDevice(m->device));
+  VQVS_HIP(hipDeviceSynchronize());
+  const float* src = reinterpret_cast<const float*>(m->d_arena + m->misc_off) + m->dfilm_misc_off;
+  VQVS_HIP(hipMemcpy(h_out, src, (size_t)B * m->dfilm_R * sizeof(float), hipMemcpyDeviceToHost));
+  return m->dfilm_R;
 }
 
 int vqvs_forward_kernel_count(const vqvs_model* m) { return m ? (int)m->ops.size() : 0; }

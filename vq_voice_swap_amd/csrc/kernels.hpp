@@ -156,6 +156,7 @@ struct TimeEmbedArgs {  // wavegrad.py:359-373 + unet.py:41-45, 133-135
   const float *w2, *b2; // time_embed_extra.1
   const float* class_embed;  // [num_labels][E] or nullptr
   const int64_t* labels;     // [B] or nullptr
+  const float* class_vec;    // [B][E] or nullptr: an explicit vector per clip, added where class_embed[labels[b]] is added
   int num_labels;
   float* emb;   // [B][E]
   float* gemb;  // [B][E] = gelu(emb), input of every block's cond_layers (unet.py:273-278)
@@ -233,6 +234,51 @@ struct InConvBwArgs {  // dx[b][t] = sum_k sum_c w[c][k] * dh[b][t-k+1][c]   (ba
   float out_scale;  // the result is multiplied by this (undoes the gradient scaling of the fp16 mode)
 };
 int launch_in_conv_bw(const InConvBwArgs& a, int B, int precision, hipStream_t st);
+
+// ----------------------------------------------------------------------------------
+// Speaker enrolment (enroll_kernels.hip; VQVS_KIND_PREDICTOR_GRAD handles, fp32 activations): what the guidance backward schedule
+// lacks to carry the gradient of the noise-prediction MSE to the conditioning vector.
+// ----------------------------------------------------------------------------------
+// dout[b][t] = 2 (pred - eps) / T and mse[b] = mean_t (eps - pred)^2, summed as vqvs_ddpm_sqerr sums it; scratch holds
+// mse_head_scratch_doubles(B, T) doubles
+int mse_head_scratch_doubles(int B, int T);
+int run_mse_head(const float* pred, const float* eps, float* dout, float* mse, double* scratch, int B, int T, hipStream_t st);
+
+struct OutConvBwArgs {  // backward of OutConvArgs' Conv1d(C -> 1, k=3) and of the GELU in front of it: du = conv^T(dout) * gelu'(u)
+  const float* dout;  // [B][L] f32
+  const void* xf;     // [B][L][C] the tensor the head's GroupNorm read
+  const float2* ss;   // [B][C] forward (scale, shift)
+  const float* w;     // [3][C] (tap-major, as OutConvArgs)
+  void* du;           // out [B][L][C]
+  float* partials;    // out [B][ntiles][C][2]: (sum du, sum du * u) per tile of STAT_TILE rows, what gn_bw reads
+  int C, L;
+};
+int launch_out_conv_bw(const OutConvBwArgs& a, int B, hipStream_t st);
+
+struct FilmGradArgs {  // d a_c = sum_l du2 * h^, d b_c = sum_l du2, with h^ = gamma * rstd * (h1 - mean) + beta (unet.py:311-314)
+  const void* du;      // [B][L][C]: du2 = conv2^T(dout) * gelu'(u2)
+  const void* h1;      // [B][L][C]: output of the block's first convolution
+  const float2* mr;    // [B][C] (mean, rstd) of GroupNorm 2
+  const float* gamma;  // [C] pre_cond.3
+  const float* beta;   // [C]
+  float* partials;     // scratch [B][ntiles][C][2], tiles of STAT_TILE rows
+  float* dfilm;        // [B][film_stride]: d a at film_off .. film_off + C, d b behind it
+  int film_stride, film_off;
+  int C, L, ntiles;
+};
+int launch_film_grad(const FilmGradArgs& a, int B, hipStream_t st);
+
+struct FilmBwArgs {  // grad[b][e] = gelu'(emb[b][e]) * sum_r wT[e][r] * dfilm[b][r]
+  const float* dfilm;  // [B][R]
+  const float* wT;     // [E][R]: FilmArgs.w
+  const float* emb;    // [B][E]: TimeEmbedArgs.emb
+  float* grad;         // out [B][E]
+  int E, R;
+};
+int launch_film_bw(const FilmBwArgs& a, int B, hipStream_t st);
+
+int run_embed_adamw(float* rows, float* m, float* v, const float* grad, const int64_t* row_of_clip, int n, int B, int E, int step, float lr,
+                    float beta1, float beta2, float eps, float weight_decay, hipStream_t st);
 
 // Classifier head (classifier.py:98-104, 153-191, 26-28): GroupNorm+GELU, attention pool whose only consumed output
 // is the prepended zero token, c_proj, GELU, Linear -- and, when labels are given, the gradient of

@@ -350,6 +350,7 @@ __global__ __launch_bounds__(256) void time_embed_kernel(const TimeEmbedArgs a) 
     }
     float v = (acc0 + acc1) + (acc2 + acc3) + a.b2[r];
     if (ce) v += ce[r];
+    if (a.class_vec) v += a.class_vec[(size_t)b * E + r];
     a.emb[(size_t)b * E + r] = v;
     a.gemb[(size_t)b * E + r] = gelu_f(v);
   }

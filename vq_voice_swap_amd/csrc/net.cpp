@@ -29,7 +29,8 @@ struct Topo {
 };
 Topo topo_of(const vqvs_cfg& c) {
   Topo t;
-  const bool custom = c.topology_set != 0 && (c.kind == VQVS_KIND_PREDICTOR || c.kind == VQVS_KIND_ENCODER || c.kind == VQVS_KIND_CLASSIFIER);
+  const bool custom = c.topology_set != 0 && (c.kind == VQVS_KIND_PREDICTOR || c.kind == VQVS_KIND_PREDICTOR_GRAD || c.kind == VQVS_KIND_ENCODER ||
+                                              c.kind == VQVS_KIND_CLASSIFIER);
   if (custom) {
     t.mult.assign(c.channel_mult, c.channel_mult + std::max(0, std::min(c.n_levels, (int)VQVS_MAX_LEVELS)));
     t.depth = c.depth_mult;
@@ -243,7 +244,12 @@ class Builder {
     es_ = m->cfg.precision == VQVS_PREC_F32 ? 4 : 2;
     maxB_ = m->cfg.max_batch;
     maxL_ = m->cfg.max_T;
+    ws_f32_kind = m->cfg.kind == VQVS_KIND_PREDICTOR || m->cfg.kind == VQVS_KIND_RESBLOCK || m->cfg.kind == VQVS_KIND_PREDICTOR_GRAD;
   }
+  // fp32 mode: may the convolutions added from here on run on conv_ws_kernel's fp32 form?  The forward of a predictor-gradient handle
+  // must (its prediction is the predictor handle's bit for bit); its backward phase turns this off and runs where the guidance
+  // schedules' transposed convolutions run.
+  bool ws_f32_kind = false;
 
   const float* P(const std::string& name) const {
     auto it = pidx_.find(name);
@@ -461,7 +467,7 @@ class Builder {
       // fp32 storage: a tile geometry other than the default one may only be chosen where conv_ws_kernel is certain to take the
       // launch (conv_mfma_kernel has one geometry): its fp32 form has no avg-pooled sources, wants 32-channel chunks, and
       // addresses a clip's rows through 32-bit descriptors -- checked here against the model's largest clip
-      const bool kind_ok = m_->cfg.kind == VQVS_KIND_PREDICTOR || m_->cfg.kind == VQVS_KIND_RESBLOCK;
+      const bool kind_ok = ws_f32_kind;
       bool ok = kind_ok && Cout % 64 == 0 && !(skip && skip_resize == RESIZE_AVG2);
       auto clip_bytes = [&](const TensorH& t) { return (long long)shiftL(m_->cfg.max_T, t.lshift) * t.C * 4; };
       for (auto& g : segs) ok = ok && g.resize != RESIZE_AVG2 && g.C % 32 == 0 && (g.ntaps == 1 || g.ntaps == 3) && clip_bytes(g.t) < (1LL << 29);
@@ -489,7 +495,7 @@ class Builder {
     for (auto& s : segs) desc += (desc.empty() ? "" : "+") + std::to_string(s.C) + "x" + std::to_string(s.ntaps) + (s.resize == RESIZE_AVG2 ? "v" : s.resize == RESIZE_UP2 ? "^" : "") + (s.ntaps == 3 && s.dil > 1 ? "d" + std::to_string(s.dil) : "");
     desc += "->" + std::to_string(Cout) + " L>>" + std::to_string(out.lshift) + (skip ? " +id" : "");
     m_->meta.push_back({"conv", desc, conv_elems, conv_f32, conv_flops});
-    const int ws_f32 = (m_->cfg.kind == VQVS_KIND_PREDICTOR || m_->cfg.kind == VQVS_KIND_RESBLOCK) ? 1 : 0;
+    const int ws_f32 = ws_f32_kind ? 1 : 0;
     const int rev = (conv_seq_++) & 1;  // consecutive convolutions walk their tiles in opposite directions (ConvArgs.rev)
     auto build = [=](const RunCtx& c, ConvArgs& a) {
       a.nseg = (int)S.size();
@@ -776,7 +782,12 @@ class Builder {
   //   out = skip(resize(x)) + conv2(gelu(GN2(conv1(resize(gelu(GN1(x)))))))       (unet.py:307-316)
   // x may be the concatenation [x, x2] (up path, unet.py:156).  Consumes `dout` (released); returns dx and sets
   // *dx2 to the gradient of the second input when the block concatenates.
-  TensorH resblock_backward(const BlockRec& r, const TensorH& dout, TensorH* dx2 = nullptr) {
+  // on_du2 (predictor-gradient handles): called once du2 = conv2^T(dout) * gelu'(u2) exists and before anything overwrites or
+  // releases it -- where the FiLM-coefficient gradient of the block is reduced.  input_grad = false: the block's input gradient is
+  // not wanted (the first block of such a handle): everything behind du2 is left out and an empty handle is returned.  A
+  // concatenating block called without dx2 leaves the second input's gradient out.
+  std::function<void(const BlockRec&, const TensorH&)> on_du2;
+  TensorH resblock_backward(const BlockRec& r, const TensorH& dout, TensorH* dx2 = nullptr, bool input_grad = true) {
     const BlockSpec& s = r.s;
     const std::string pre = s.prefix.empty() ? "" : s.prefix + ".";
     const int cin = s.cin, cout = s.cout;
@@ -792,6 +803,12 @@ class Builder {
     const BwFuse f2{{r.h1}, r.ss2, cout, pa};
     const int tr2 = add_conv_t(dout, P(c2 + ".weight"), cout, cout, 3, s.dil, t1, fuse ? &f2 : nullptr);
     if (!fuse) add_bw_act(t1, BW_SAME, r.h1, r.ss2, t1, pa);
+    if (on_du2) on_du2(r, t1);
+    if (!input_grad) {
+      release(t1);
+      release(dout);
+      return TensorH{};
+    }
     const size_t cf2 = add_gn_bw(cout, out_shift, pa, r.ss2, r.mr2, fuse ? tr2 : STAT_TILE);
     // d h1 = P * du2 + Q * h1 + R: evaluated by conv1^T while it stages its input (kernels.hpp SegDesc.src2) instead of a streaming
     // pass that writes d h1 and a convolution that reads it back.  VQVS_BW_AFF2=0: the separate bw_affine launch (A/B measurements).
@@ -835,7 +852,7 @@ class Builder {
     release(dout);
     TensorH outs[2];
     c0 = 0;
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < (dx2 ? 2 : 1); ++i) {
       outs[i] = new_tensor(srcs[i].C, in_shift, false, false);
       add_bw_affine(t2, srcs[i], cf1, nullptr, BW_SAME, &t3, outs[i], c0, cin);
       c0 += srcs[i].C;
@@ -844,6 +861,30 @@ class Builder {
     release(t3);
     if (dx2) *dx2 = outs[1];
     return outs[0];
+  }
+
+  // The blocks of a whole UNet in reverse, from the gradient `g` of the last block's output.  Gradients of skip-stack tensors wait in
+  // `pending` until the down path reaches their producer.  input_grad: return the gradient of recs[0].x (the in_conv output, which is
+  // also the first skip-stack entry); otherwise neither it nor the skip gradient that would be added to it is computed.
+  TensorH unet_backward(const std::vector<BlockRec>& recs, TensorH g, bool input_grad = true) {
+    std::map<int, TensorH> pending;
+    auto add_pending = [&](const TensorH& produced) {  // produced = forward tensor whose gradient g currently is
+      auto it = pending.find(produced.id);
+      if (it == pending.end()) return;
+      add_bw_add(g, it->second, g);
+      release(it->second);
+      pending.erase(it);
+    };
+    for (size_t i = recs.size(); i-- > 0;) {
+      add_pending(recs[i].out);
+      TensorH dsk{};
+      const bool cat = recs[i].x2.id >= 0;
+      const bool want_dsk = cat && (input_grad || recs[i].x2.id != recs[0].x.id);
+      g = resblock_backward(recs[i], g, cat && !want_dsk ? nullptr : &dsk, input_grad || i > 0);
+      if (want_dsk) pending[recs[i].x2.id] = dsk;
+    }
+    if (input_grad) add_pending(recs[0].x);
+    return g;
   }
 
   void tap(const std::string& name, const TensorH& t) { m_->taps.push_back({name, t}); }
@@ -949,7 +990,7 @@ int real_base(const vqvs_cfg& c) {
 }
 
 static int check_topology(const vqvs_cfg& c) {
-  if (c.topology_set && c.kind != VQVS_KIND_PREDICTOR && c.kind != VQVS_KIND_ENCODER && c.kind != VQVS_KIND_CLASSIFIER)
+  if (c.topology_set && c.kind != VQVS_KIND_PREDICTOR && c.kind != VQVS_KIND_PREDICTOR_GRAD && c.kind != VQVS_KIND_ENCODER && c.kind != VQVS_KIND_CLASSIFIER)
     VQVS_FAIL(VQVS_ERR_ARG, "a custom topology is built for predictor, encoder and classifier handles only (kind %d)", c.kind);
   if (c.topology_set) {
     if (c.n_levels < 1 || c.n_levels > VQVS_MAX_LEVELS) VQVS_FAIL(VQVS_ERR_ARG, "n_levels must be in 1..%d (got %d)", VQVS_MAX_LEVELS, c.n_levels);
@@ -964,7 +1005,7 @@ static int check_topology(const vqvs_cfg& c) {
     // * predictor: the output head (out.0.0 GroupNorm + out.1 conv, unet.py:113-116) is built for base_channels, the last up block
     //   returns channel_mult[0] * base_channels -- the reference constructs such a model and fails in forward;
     // * classifier: the attention pool splits the final width into heads of 64 channels (classifier.py:131-150 asserts the same).
-    if (c.kind == VQVS_KIND_PREDICTOR && c.channel_mult[0] != 1)
+    if ((c.kind == VQVS_KIND_PREDICTOR || c.kind == VQVS_KIND_PREDICTOR_GRAD) && c.channel_mult[0] != 1)
       VQVS_FAIL(VQVS_ERR_ARG, "predictor channel_mult[0] must be 1 (got %d): the output head is built for base_channels", c.channel_mult[0]);
     if (c.kind == VQVS_KIND_CLASSIFIER) {
       const int cur = c.channel_mult[c.n_levels - 1] * c.base_channels;
@@ -987,12 +1028,25 @@ static long long widest_clip_elems(const vqvs_cfg& c) {
   return best;
 }
 
+// What a predictor-gradient handle (speaker enrolment) is built for: the class-conditional fp32 predictor with one output channel at a
+// width that needs no padding.  Checked by every entry point that takes a vqvs_cfg.
+static int check_grad_kind(const vqvs_cfg& c) {
+  if (c.kind != VQVS_KIND_PREDICTOR_GRAD) return 0;
+  if (c.precision != VQVS_PREC_F32) VQVS_FAIL(VQVS_ERR_ARG, "predictor-gradient handle: precision %d is not built, fp32 (precision 0) only", c.precision);
+  if (c.reserved[4] != 0)
+    VQVS_FAIL(VQVS_ERR_ARG, "predictor-gradient handle: a padded width (reserved[4] = %d) is not built, base_channels must be a multiple of 32", c.reserved[4]);
+  if (c.num_labels < 1) VQVS_FAIL(VQVS_ERR_ARG, "predictor-gradient handle: num_labels must be positive (got %d): the model has no class embedding", c.num_labels);
+  if (c.out_channels != 1) VQVS_FAIL(VQVS_ERR_ARG, "predictor-gradient handle: out_channels must be 1 (got %d): the loss is the noise-prediction MSE", c.out_channels);
+  return 0;
+}
+
 int enumerate_params(const vqvs_cfg& c, std::vector<ParamDef>& out) {
   out.clear();
+  if (int e = check_grad_kind(c)) return e;
   if (int e = check_topology(c)) return e;
   const int base = c.base_channels;
   const bool drop = cfg_dropout(c);
-  if (c.kind == VQVS_KIND_PREDICTOR || c.kind == VQVS_KIND_ENCPRED) {
+  if (c.kind == VQVS_KIND_PREDICTOR || c.kind == VQVS_KIND_ENCPRED || c.kind == VQVS_KIND_PREDICTOR_GRAD) {
     const int E = 4 * base;
     out.push_back({"time_embed.proj.weight", {E, E}});
     out.push_back({"time_embed.proj.bias", {E}});
@@ -1076,6 +1130,7 @@ int enumerate_params(const vqvs_cfg& c, std::vector<ParamDef>& out) {
 }
 
 static int check_cfg(const vqvs_cfg& c) {
+  if (int e = check_grad_kind(c)) return e;
   if (c.precision != VQVS_PREC_F32 && c.precision != VQVS_PREC_BF16 && c.precision != VQVS_PREC_F16) VQVS_FAIL(VQVS_ERR_ARG, "bad precision %d", c.precision);
   if (c.max_batch < 1 || c.max_T < 1) VQVS_FAIL(VQVS_ERR_ARG, "max_batch/max_T must be positive");
   if (c.kind == VQVS_KIND_RESBLOCK) {
@@ -1102,7 +1157,7 @@ static int check_cfg(const vqvs_cfg& c) {
                 c.reserved[4] >= 1 ? padded_base(c.reserved[4]) : 0);
   }
   if (c.in_channels < 1 || c.in_channels > 64) VQVS_FAIL(VQVS_ERR_ARG, "in_channels must be in 1..64 (got %d)", c.in_channels);
-  if (c.in_channels != 1 && c.kind != VQVS_KIND_PREDICTOR && c.kind != VQVS_KIND_ENCODER)
+  if (c.in_channels != 1 && c.kind != VQVS_KIND_PREDICTOR && c.kind != VQVS_KIND_PREDICTOR_GRAD && c.kind != VQVS_KIND_ENCODER)
     VQVS_FAIL(VQVS_ERR_ARG, "in_channels = %d: only predictor and encoder handles take more than one input channel (the classifier stem and the "
                             "encoder predictor are mono in the reference too, classifier.py:73, encoder_predictor.py:40)", c.in_channels);
   if (c.kind == VQVS_KIND_MFCC_ENCODER) {
@@ -1121,7 +1176,7 @@ static int check_cfg(const vqvs_cfg& c) {
   // (4 bytes per element in the fp32 mode; the widest tensor a launch addresses is a level's concatenated input, 2 x its width)
   if (widest_clip_elems(c) * 4 > 0x7fffffffLL)
     VQVS_FAIL(VQVS_ERR_ARG, "max_T=%d is too long for base_channels=%d with this topology (a clip's widest tensor would exceed 2 GiB)", c.max_T, c.base_channels);
-  if (c.kind == VQVS_KIND_PREDICTOR) {
+  if (c.kind == VQVS_KIND_PREDICTOR || c.kind == VQVS_KIND_PREDICTOR_GRAD) {
     if (c.out_channels != 1 && (c.out_channels % 32)) VQVS_FAIL(VQVS_ERR_ARG, "out_channels must be 1 or a multiple of 32");
     if (c.cond_channels % 32) VQVS_FAIL(VQVS_ERR_ARG, "cond_channels must be a multiple of 32");
     if (c.reserved[3] != 0 && c.reserved[3] != 1 && (c.reserved[3] <= LEN_ABS || c.reserved[3] > LEN_ABS + (1 << 20)))
@@ -1188,12 +1243,16 @@ int build_model(vqvs_model* m, const float* const* hp) {
       return launch_ntc_to_nct(bp->act(y.off), r.out, r.B, Cout, shiftL(r.Lbase, y.lshift), prec, r.st);
     });
     b.tap("out", y);
-  } else if (c.kind == VQVS_KIND_PREDICTOR || c.kind == VQVS_KIND_ENCPRED) {
+  } else if (c.kind == VQVS_KIND_PREDICTOR || c.kind == VQVS_KIND_ENCPRED || c.kind == VQVS_KIND_PREDICTOR_GRAD) {
     // ENCPRED (encoder_predictor.py:25-58): the same UNet under the "unet." prefix with a bottleneck output, every
     // intermediate kept resident for the backward schedule appended below
+    // PREDICTOR_GRAD (speaker enrolment): the class-conditional predictor's own forward ops with the conditioning vector given per
+    // clip, every intermediate kept resident too, and the embedding-gradient schedule behind the output convolution
     const bool encpred = c.kind == VQVS_KIND_ENCPRED;
+    const bool gradk = c.kind == VQVS_KIND_PREDICTOR_GRAD;
+    const bool keep_bw = encpred || gradk;
     const std::string px = encpred ? "unet." : "";
-    b.persist = encpred;
+    b.persist = keep_bw;
     const int E = 4 * base;
     std::vector<BlockSpec> d, mdl, u;
     predictor_blocks(base, topo_of(c), d, mdl, u);
@@ -1213,7 +1272,7 @@ int build_model(vqvs_model* m, const float* const* hp) {
     const size_t freq_off = b.blob.add(freqs.data(), freqs.size() * 4);
     const size_t w1 = b.blob_f32_transposed(b.P(px + "time_embed.proj.weight"), E, E), b1 = b.blob_f32(px + "time_embed.proj.bias");
     const size_t w2 = b.blob_f32_transposed(b.P(px + "time_embed_extra.1.weight"), E, E), b2 = b.blob_f32(px + "time_embed_extra.1.bias");
-    const size_t ce = c.num_labels > 0 ? b.blob_f32(px + "class_embed.weight") : 0;
+    const size_t ce = c.num_labels > 0 && !gradk ? b.blob_f32(px + "class_embed.weight") : 0;
     const size_t emb_off = b.alloc_misc((size_t)c.max_batch * E);
     const size_t gemb_off = b.alloc_misc((size_t)c.max_batch * E);
     m->emb_misc_off = emb_off;
@@ -1228,8 +1287,9 @@ int build_model(vqvs_model* m, const float* const* hp) {
       a.b1 = reinterpret_cast<const float*>(bp->wp(b1));
       a.w2 = reinterpret_cast<const float*>(bp->wp(w2));
       a.b2 = reinterpret_cast<const float*>(bp->wp(b2));
-      a.class_embed = NL > 0 ? reinterpret_cast<const float*>(bp->wp(ce)) : nullptr;
+      a.class_embed = NL > 0 && !gradk ? reinterpret_cast<const float*>(bp->wp(ce)) : nullptr;
       a.labels = r.labels;
+      a.class_vec = gradk ? r.class_vec : nullptr;
       a.num_labels = NL;
       a.emb = bp->miscp(emb_off);
       a.gemb = bp->miscp(gemb_off);
@@ -1311,7 +1371,7 @@ int build_model(vqvs_model* m, const float* const* hp) {
     b.retain(h);  // one reference held by `h`, one by the stack
     size_t bi = 0;
     std::vector<Builder::BlockRec> recs(all.size());
-    auto recp = [&](size_t i) { return encpred ? &recs[i] : nullptr; };
+    auto recp = [&](size_t i) { return keep_bw ? &recs[i] : nullptr; };
     for (auto& s : d) {
       TensorH o = b.resblock(s.prefix, s, {h}, true, film_row[bi], R, film_off, recp(bi));
       ++bi;
@@ -1345,8 +1405,8 @@ int build_model(vqvs_model* m, const float* const* hp) {
     }
     // ---- output head (unet.py:113-116, 162)
     const size_t ss = b.alloc_ss(base);
-    const size_t mr_out = encpred ? b.alloc_ss(base) : 0;
-    b.add_gn({h}, px + "out.0.0", false, 0, 0, 0, ss, encpred, mr_out);
+    const size_t mr_out = keep_bw ? b.alloc_ss(base) : 0;
+    b.add_gn({h}, px + "out.0.0", false, 0, 0, 0, ss, keep_bw, mr_out);
     if (c.out_channels == 1) {
       const float* W = b.P(px + "out.1.weight");  // [1][base][3] -> [3][base]
       std::vector<float> wt(3 * base);
@@ -1354,6 +1414,7 @@ int build_model(vqvs_model* m, const float* const* hp) {
         for (int ci = 0; ci < base; ++ci) wt[k * base + ci] = W[ci * 3 + k];
       const size_t w = b.blob.add(wt.data(), wt.size() * 4);
       const float bias = b.P(px + "out.1.bias")[0];
+      const TensorH pred = gradk ? b.new_tensor(1, 0, true, false) : TensorH{};  // (the prediction of a call that does not ask for it)
       m->meta.push_back({"out_conv", std::to_string(base) + "->1", (double)base, 4.0, 0});
       m->add_op([=](const RunCtx& r) -> int {
         OutConvArgs a{};
@@ -1361,11 +1422,83 @@ int build_model(vqvs_model* m, const float* const* hp) {
         a.ss = reinterpret_cast<const float2*>(bp->ssp(ss));
         a.w = reinterpret_cast<const float*>(bp->wp(w));
         a.bias = bias;
-        a.out = r.out;
+        a.out = gradk && !r.out ? reinterpret_cast<float*>(bp->act(pred.off)) : r.out;
         a.C = base;
         a.L = r.Lbase;
         return launch_out_conv(a, r.B, prec, r.st);
       });
+      if (gradk) {
+        // ---- loss head + the embedding-gradient schedule (phase 1): d mse_b / d v_b for every clip b
+        b.persist = false;
+        b.ws_f32_kind = false;  // (the transposed convolutions run where the guidance schedules' run)
+        m->cur_phase = 1;
+        TensorH dout = b.new_tensor(1, 0, true, false);
+        const size_t sq_off = b.alloc_misc(2 * (size_t)mse_head_scratch_doubles(c.max_batch, c.max_T));
+        m->meta.push_back({"mse_head", "", 0, 12.0, 0});
+        m->add_op([=](const RunCtx& r) -> int {
+          const float* p = r.out ? r.out : reinterpret_cast<const float*>(bp->act(pred.off));
+          return run_mse_head(p, r.eps, reinterpret_cast<float*>(bp->act(dout.off)), r.mse, reinterpret_cast<double*>(bp->miscp(sq_off)), r.B,
+                              r.Lbase, r.st);
+        });
+        // out.1 (3-tap conv base -> 1 over gelu(GN(h))) backwards: conv^T and gelu' in one kernel, then GroupNorm backward
+        TensorH t = b.new_tensor(base, 0, false, false);
+        const size_t po = b.alloc_stats(base, 0);
+        m->meta.push_back({"out_conv_bw", "1->" + std::to_string(base), 2.0 * base, 4.0, 0});
+        m->add_op([=](const RunCtx& r) -> int {
+          OutConvBwArgs a{};
+          a.dout = reinterpret_cast<const float*>(bp->act(dout.off));
+          a.xf = bp->act(h.off);
+          a.ss = reinterpret_cast<const float2*>(bp->ssp(ss));
+          a.w = reinterpret_cast<const float*>(bp->wp(w));
+          a.du = bp->act(t.off);
+          a.partials = bp->statp(po);
+          a.C = base;
+          a.L = r.Lbase;
+          return launch_out_conv_bw(a, r.B, r.st);
+        });
+        b.release(dout);
+        const size_t cfo = b.add_gn_bw(base, 0, po, ss, mr_out, STAT_TILE);
+        b.add_bw_affine(t, h, cfo, nullptr, BW_SAME, nullptr, t);
+        // per block, as soon as du2 exists: (d a | d b) into the block's rows of dfilm [B][R]
+        const size_t dfilm_off = b.alloc_misc((size_t)c.max_batch * R);
+        m->dfilm_misc_off = dfilm_off;
+        m->dfilm_R = R;
+        std::map<std::string, int> row_of;
+        for (size_t i = 0; i < all.size(); ++i) row_of[all[i]->prefix] = film_row[i];
+        b.on_du2 = [&](const Builder::BlockRec& rec, const TensorH& du2) {
+          const int C = rec.s.cout, row = row_of.at(rec.s.prefix), ls = rec.out.lshift;
+          const size_t g_off = b.blob_f32(rec.s.prefix + ".pre_cond.3.weight"), be_off = b.blob_f32(rec.s.prefix + ".pre_cond.3.bias");
+          const size_t pf = b.alloc_stats(C, ls);
+          const TensorH D = du2, H1 = rec.h1;
+          const size_t mr2 = rec.mr2;
+          m->meta.push_back({"film_grad", "C=" + std::to_string(C) + " L>>" + std::to_string(ls), 2.0 * C * lscale(ls), 0, 0});
+          m->add_op([=](const RunCtx& r) -> int {
+            FilmGradArgs a{};
+            a.du = bp->act(D.off);
+            a.h1 = bp->act(H1.off);
+            a.mr = reinterpret_cast<const float2*>(bp->ssp(mr2));
+            a.gamma = reinterpret_cast<const float*>(bp->wp(g_off));
+            a.beta = reinterpret_cast<const float*>(bp->wp(be_off));
+            a.partials = bp->statp(pf);
+            a.dfilm = bp->miscp(dfilm_off);
+            a.film_stride = R;
+            a.film_off = row;
+            a.C = C;
+            a.L = shiftL(r.Lbase, ls);
+            a.ntiles = ntiles_of(a.L);
+            return launch_film_grad(a, r.B, r.st);
+          });
+        };
+        b.unet_backward(recs, t, false);  // (the first block's input gradient and the skip path into in_conv are not needed)
+        b.on_du2 = nullptr;
+        // d v = gelu'(emb) * Wall^T dfilm
+        m->meta.push_back({"film_bw", "", 0, 0, 0});
+        m->add_op([=](const RunCtx& r) -> int {
+          FilmBwArgs a{bp->miscp(dfilm_off), reinterpret_cast<const float*>(bp->wp(wall_off)), bp->miscp(emb_off), r.egrad, E, R};
+          return launch_film_bw(a, r.B, r.st);
+        });
+        m->cur_phase = 0;
+      }
     } else {
       TensorH o = b.new_tensor(c.out_channels, 0, true, false);
       PackedConv pk(prec);
@@ -1413,24 +1546,7 @@ int build_model(vqvs_model* m, const float* const* hp) {
         if (!fuse) b.add_bw_act(t, BW_SAME, h, ss, t, po);
         const size_t cfo = b.add_gn_bw(base, 0, po, ss, mr_out, fuse ? tro : STAT_TILE);
         b.add_bw_affine(t, h, cfo, nullptr, BW_SAME, nullptr, t);
-        // blocks in reverse; gradients of skip-stack tensors wait in `pending` until the down path reaches their producer
-        std::map<int, TensorH> pending;
-        TensorH g2 = t;
-        auto add_pending = [&](const TensorH& produced) {  // produced = forward tensor whose gradient g2 currently is
-          auto it = pending.find(produced.id);
-          if (it == pending.end()) return;
-          b.add_bw_add(g2, it->second, g2);
-          b.release(it->second);
-          pending.erase(it);
-        };
-        for (size_t i = all.size(); i-- > 0;) {
-          add_pending(recs[i].out);
-          TensorH dsk{};
-          g2 = b.resblock_backward(recs[i], g2, &dsk);
-          if (recs[i].x2.id >= 0) pending[recs[i].x2.id] = dsk;
-        }
-        add_pending(recs[0].x);  // in_conv output: also the first skip-stack entry
-        const TensorH gi = g2;
+        const TensorH gi = b.unet_backward(recs, t);  // blocks in reverse, down to the in_conv output
         const size_t inw = b.blob_f32(px + "in_conv.weight");
         m->meta.push_back({"in_conv_bw", std::to_string(base) + "->1", (double)base, 4.0, 0});
         m->add_op([=](const RunCtx& r) -> int {

@@ -52,6 +52,12 @@ struct RunCtx {
   // classifier handles, vqvs_classifier_features: [B][F] features and [B][num_labels] probabilities, or nullptr (out may be too)
   float* feat = nullptr;
   float* probs = nullptr;
+  // predictor-gradient handles (vqvs_unet_embed_grad): the conditioning vector of every clip [B][E] in place of class_embed[labels],
+  // the target noise [B][T], and the outputs mse [B] and egrad [B][E]; `out` (the prediction) may be nullptr
+  const float* class_vec = nullptr;
+  const float* eps = nullptr;
+  float* mse = nullptr;
+  float* egrad = nullptr;
   hipStream_t st = nullptr;
 };
 
@@ -102,6 +108,8 @@ struct vqvs_model {
   size_t status_misc_off = (size_t)-1;  // device status word (misc region, floats) or -1: the handle has no GroupNorm
   size_t emb_misc_off = 0;  // conditioning vector [max_batch][emb_E] of the last forward (misc region, floats); emb_E = 0: none
   int emb_E = 0;
+  size_t dfilm_misc_off = 0;  // predictor-gradient handles: d loss / d FiLM rows [max_batch][dfilm_R] of the last call (misc region, floats)
+  int dfilm_R = 0;
   std::shared_ptr<void> keepalive;  // schedule builder (resolves arena/weight offsets for the ops)
 };
 

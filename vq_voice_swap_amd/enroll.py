@@ -1,0 +1,166 @@
+"""
+Speaker enrolment: learn `class_embed` rows for new speakers of a trained class-conditional model, everything else frozen
+(reference train_vqvae_add.py, `VQVAEAddClassesTrainLoop`, train_loop.py:438-485: `add_labels(n)`, freeze all but
+`predictor.label_parameters()`, AdamW on the noise-prediction MSE).
+
+Nothing here runs torch autograd or a torch optimiser: the gradient of every clip's MSE with respect to its conditioning vector comes
+from `UNetPredictor.embedding_grad` (`vqvs_unet_embed_grad`: the predictor's forward schedule and an explicit backward schedule that
+reaches only the FiLM coefficients), and the batch mean, the sum over clips that share a speaker and the AdamW update are one kernel,
+`vqvs_embed_adamw`.  The model itself is not touched until `finish()`.
+"""
+
+from __future__ import annotations
+
+from typing import Dict, Optional, Tuple, Union
+
+import torch
+
+from . import _native
+from .diffusion import fresh_seed, randn_clips
+from .diffusion_model import DiffusionModel
+
+
+def init_rows(old: torch.Tensor, num_new: int, init: Union[str, int], seed: int) -> torch.Tensor:
+    """The starting rows [num_new, E], float32 on the CPU.  "normal": N(0, 1), what a fresh nn.Embedding holds (the reference's
+    `add_labels`), from a generator seeded by `seed`; "mean": the mean of the existing rows; an integer: that speaker's row."""
+    old = old.detach().to(device="cpu", dtype=torch.float32)
+    E = old.shape[1]
+    if isinstance(init, bool):
+        raise ValueError(f"init={init!r}: use 'normal', 'mean' or the index of an existing speaker")
+    if isinstance(init, int):
+        if not 0 <= init < old.shape[0]:
+            raise IndexError(f"init={init}: the model has speakers 0..{old.shape[0] - 1}")
+        return old[init].clone().expand(num_new, E).contiguous()
+    if init == "normal":
+        return torch.randn(num_new, E, generator=torch.Generator().manual_seed(int(seed)))
+    if init == "mean":
+        return old.double().mean(dim=0).float().expand(num_new, E).contiguous()
+    raise ValueError(f"init={init!r}: use 'normal', 'mean' or the index of an existing speaker")
+
+
+def adamw_step(rows: torch.Tensor, m: torch.Tensor, v: torch.Tensor, grads: torch.Tensor, row_of_clip: torch.Tensor, step: int,
+               lr: float, betas: Tuple[float, float], eps: float, weight_decay: float) -> None:
+    """`vqvs_embed_adamw` in place on rows / m / v [n, E] from per-clip gradients [B, E]: the mean over the batch, summed per named row."""
+    n, E = rows.shape
+    B = grads.shape[0]
+    _native.check_index_range(row_of_clip, n, "new speaker labels")
+    with torch.cuda.device(rows.device):
+        _native.check(_native.lib().vqvs_embed_adamw(rows.data_ptr(), m.data_ptr(), v.data_ptr(), grads.data_ptr(), row_of_clip.data_ptr(),
+                                                     n, B, E, int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                                     float(weight_decay), _native._stream_ptr()))
+
+
+class SpeakerEnroller:
+    """Rows, AdamW moments and step count of `num_new` new speakers of `model`, a class-conditional `VQVAE` or `DiffusionModel` in
+    `eval()`.  `step()` takes one optimiser step on a batch; `finish()` grows the model by the rows; `state_dict()` /
+    `load_state_dict()` resume.  New speaker k is row k here and label `first_label + k` of the finished model."""
+
+    def __init__(self, model: DiffusionModel, num_new: int, lr: float = 1e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, init: Union[str, int] = "normal", seed: int = 0):
+        if not isinstance(model, DiffusionModel) or model.num_labels is None:
+            raise ValueError("SpeakerEnroller needs a class-conditional VQVAE or DiffusionModel (num_labels is None)")
+        if model.training:
+            raise RuntimeError("SpeakerEnroller: the model's own parameters stay frozen; call .eval()")
+        if int(num_new) != num_new or num_new < 1:
+            raise ValueError(f"num_new={num_new!r} must be a positive integer")
+        self.model = model
+        self.num_new = int(num_new)
+        self.first_label = int(model.num_labels)
+        self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+        old = model.predictor.class_embed.weight
+        self.rows = init_rows(old, self.num_new, init, seed).to(old.device)
+        self.exp_avg = torch.zeros_like(self.rows)
+        self.exp_avg_sq = torch.zeros_like(self.rows)
+        self.steps = 0
+        self.finished = False
+
+    def _cond(self, inputs: torch.Tensor) -> Optional[torch.Tensor]:
+        """The decoder's conditioning of a batch: encode and quantise as `VQVAE.losses` does; None for a plain DiffusionModel."""
+        if not hasattr(self.model, "encoder"):
+            return None
+        with torch.no_grad():
+            return self.model.vq.quantize(self.model.encoder(inputs))["embedded"]
+
+    def losses(self, inputs: torch.Tensor, new_labels: torch.Tensor, *, ts: Optional[torch.Tensor] = None,
+               noise: Optional[torch.Tensor] = None, seed: Optional[int] = None, clip_offset: int = 0):
+        """(mses [B], grads [B, E], ts) of a batch under the current rows, without an optimiser step."""
+        _native.require_cuda(inputs, noise)
+        if self.finished:
+            raise RuntimeError("SpeakerEnroller.finish() was called: the rows are part of the model now")
+        if inputs.dim() != 3:
+            raise ValueError(f"expected inputs of shape [N, 1, T], got {tuple(inputs.shape)}")
+        x0 = inputs.detach().to(torch.float32).contiguous()
+        B, T = x0.shape[0], x0.shape[-1]
+        labels = new_labels.detach().to(device=x0.device, dtype=torch.int64).contiguous()
+        if labels.shape != (B,):
+            raise ValueError(f"expected new_labels of shape [{B}], got {tuple(labels.shape)}")
+        _native.check_index_range(labels, self.num_new, "new speaker labels")
+        if seed is None:
+            seed = fresh_seed()
+        diffusion = self.model.diffusion
+        if ts is None:
+            ts = diffusion.draw_ts(B, seed, clip_offset)
+        ts = ts.detach().to(device=x0.device, dtype=torch.float32).contiguous()
+        if ts.shape != (B,):
+            raise ValueError(f"expected ts of shape [{B}], got {tuple(ts.shape)}")
+        # the noise of clip clip_offset + b from the counter-based generator's loss stream: what `sample_q_seeded` draws in-kernel
+        eps = randn_clips(B, T, x0.device, seed, clip_offset, _native.STREAM_LOSS) if noise is None else noise.detach().to(torch.float32).contiguous()
+        if tuple(eps.shape) != tuple(x0.shape):
+            raise ValueError(f"noise of shape {tuple(eps.shape)} does not match inputs of shape {tuple(x0.shape)}")
+        alpha = diffusion.schedule(ts.cpu()).to(device=x0.device, dtype=torch.float32).contiguous()
+        x_t = torch.empty_like(x0)
+        with torch.cuda.device(x0.device):
+            _native.check(_native.lib().vqvs_ddpm_noise(x0.data_ptr(), B, alpha.data_ptr(), eps.data_ptr(), B, None, x_t.data_ptr(), B, T,
+                                                        int(seed), int(clip_offset), _native._stream_ptr()))
+        mses, grads = self.model.predictor.embedding_grad(x_t, ts, eps, self.rows[labels], cond=self._cond(x0))
+        return mses, grads, ts, labels
+
+    def step(self, inputs: torch.Tensor, new_labels: torch.Tensor, *, ts: Optional[torch.Tensor] = None,
+             noise: Optional[torch.Tensor] = None, seed: Optional[int] = None, clip_offset: int = 0) -> Dict[str, torch.Tensor]:
+        """One AdamW step on the batch `inputs` [B, 1, T] whose clips belong to new speakers `new_labels` [B] (0 .. num_new - 1).
+        `ts` and `noise` as given, else drawn from (`seed`, `clip_offset` + b) as `Diffusion.denoising_losses` draws them.
+        Returns {"loss": the batch mean BEFORE the step, "mses" [B], "ts" [B]}."""
+        mses, grads, ts, labels = self.losses(inputs, new_labels, ts=ts, noise=noise, seed=seed, clip_offset=clip_offset)
+        self.steps += 1
+        adamw_step(self.rows, self.exp_avg, self.exp_avg_sq, grads, labels, self.steps, self.lr, self.betas, self.eps, self.weight_decay)
+        return {"loss": mses.mean(), "mses": mses, "ts": ts}
+
+    def finish(self) -> DiffusionModel:
+        """`model.add_labels(num_new)` with the learned rows behind the checkpoint's own, which stay bit for bit; returns the model."""
+        if self.finished:
+            raise RuntimeError("SpeakerEnroller.finish() was already called")
+        self.model.add_labels(self.num_new)
+        with torch.no_grad():
+            w = self.model.predictor.class_embed.weight
+            w[self.first_label:].copy_(self.rows.to(w.device))
+        self.model.predictor.invalidate()
+        self.finished = True
+        return self.model
+
+    def checkpoint(self) -> Dict[str, object]:
+        """The {"kwargs", "state_dict"} checkpoint of the model grown by the rows as they stand, without touching the model: what
+        `finish()` followed by `save_dict()` would hold.  `VQVAE.load` / `DiffusionModel.load` read it."""
+        if self.finished:
+            return self.model.save_dict()
+        state = self.model.save_dict()
+        kwargs = dict(state["kwargs"], num_labels=self.first_label + self.num_new)
+        sd = {k: v.detach().cpu().clone() for k, v in state["state_dict"].items()}
+        key = "predictor.class_embed.weight"
+        sd[key] = torch.cat([sd[key], self.rows.detach().cpu().to(sd[key].dtype)], dim=0)
+        return {"kwargs": kwargs, "state_dict": sd}
+
+    def state_dict(self) -> Dict[str, object]:
+        return {"rows": self.rows.detach().cpu().clone(), "exp_avg": self.exp_avg.detach().cpu().clone(),
+                "exp_avg_sq": self.exp_avg_sq.detach().cpu().clone(), "steps": self.steps, "first_label": self.first_label}
+
+    def load_state_dict(self, state: Dict[str, object]) -> None:
+        rows = state["rows"]
+        if tuple(rows.shape) != tuple(self.rows.shape):
+            raise ValueError(f"state holds rows of shape {tuple(rows.shape)}, this enroller has {tuple(self.rows.shape)}")
+        if int(state["first_label"]) != self.first_label:
+            raise ValueError(f"state was made for a model of {state['first_label']} speakers, this one has {self.first_label}")
+        dev = self.rows.device
+        self.rows = rows.to(device=dev, dtype=torch.float32).clone()
+        self.exp_avg = state["exp_avg"].to(device=dev, dtype=torch.float32).clone()
+        self.exp_avg_sq = state["exp_avg_sq"].to(device=dev, dtype=torch.float32).clone()
+        self.steps = int(state["steps"])

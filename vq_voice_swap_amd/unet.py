@@ -262,10 +262,12 @@ class _NativeModule(nn.Module):
         fp16's 65504) but equally for a sustained RMS of ~1.9e3 over the tile, which fp16 holds without loss; a true overflow
         always sets bit 0.  VQVS_STRICT_RANGE=1 turns the warning into the error.  Tensors that feed no GroupNorm (the network's
         final output, the sampler's x_t) are not covered by either bit."""
-        h = self._handle
-        if h is None:
+        handles = [h for h in (self._handle, self.__dict__.get("_alt_handles", {}).get("grad", (None, None))[0]) if h is not None]
+        if not handles:
             return
-        w = h.status()
+        w = 0
+        for h in handles:  # (the forward handle and, beside it, the embedding-gradient handle of UNetPredictor.embedding_grad)
+            w |= h.status()
         if w & 1:
             raise _native.NativeError("range guard: non-finite GroupNorm statistics (an activation overflowed the storage type, or the "
                                       "input held NaN/inf); run this model with set_precision('fp32')")
@@ -485,6 +487,71 @@ class UNetPredictor(_NativeModule):
     def label_parameters(self) -> List[nn.Parameter]:
         assert self.num_labels is not None
         return list(self.class_embed.parameters())
+
+    def _grad_handle(self, device: torch.device, B: int, T: int) -> _native.Handle:
+        """The predictor-gradient handle (VQVS_KIND_PREDICTOR_GRAD, fp32) of `embedding_grad`, built lazily beside the forward handle
+        and kept under `_alt_handles["grad"]`: `invalidate()` and `release_alt_handles()` close it, `check_status()` reads it."""
+        if self.out_channels != 1:
+            raise ValueError(f"embedding_grad: out_channels={self.out_channels}: the loss is the MSE of a one-channel noise prediction")
+        if physical_base(self.base_channels) != self.base_channels:
+            raise ValueError(f"embedding_grad: base_channels={self.base_channels} is a padded width; the gradient schedule is built for multiples of 32")
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        key = (idx, self._weights_token(), self._cond_code)
+        alt = self.__dict__.setdefault("_alt_handles", {})
+        h, k = alt.get("grad", (None, None))
+        if h is not None and k == key and h.cfg.max_batch >= B and h.cfg.max_T >= T:
+            return h
+        if h is not None:
+            if k == key:
+                B, T = max(B, h.cfg.max_batch), max(T, h.cfg.max_T)
+            h.close()
+            del alt["grad"]
+        cfg = self._cfg()
+        cfg.kind = _native.KIND_PREDICTOR_GRAD
+        cfg.precision = _native.PREC_F32
+        cfg.max_batch = B
+        cfg.max_T = T
+        torch.cuda.synchronize(idx)
+        h = _native.Handle(cfg, self.state_dict(), "", idx)
+        alt["grad"] = (h, key)
+        return h
+
+    def embedding_grad(self, x_t: torch.Tensor, ts: torch.Tensor, eps: torch.Tensor, vectors: torch.Tensor, *,
+                       cond: Optional[torch.Tensor] = None, return_pred: bool = False):
+        """(mses [B], grads [B, E]) -- with `return_pred` also the prediction [B, 1, T] -- of the class-conditional predictor run with
+        the conditioning vector `vectors[b]` in place of `class_embed[labels[b]]`: mses[b] = mean_t (eps - pred)^2 and grads[b] =
+        d mses[b] / d vectors[b], by `vqvs_unet_embed_grad`'s explicit backward schedule (fp32; no autograd).  What the reference's
+        enrolment loop obtains from loss.backward() with only `label_parameters()` trainable (train_loop.py:438-485)."""
+        assert self.num_labels is not None, "embedding_grad needs a class-conditional model"
+        assert (cond is None) == (self.cond_channels is None), "must provide cond sequence if and only if model is conditional"
+        _native.require_cuda(x_t, ts, eps, vectors, cond)
+        if x_t.dim() != 3 or x_t.shape[1] != self.in_channels:
+            raise ValueError(f"expected x_t of shape [N, {self.in_channels}, T], got {tuple(x_t.shape)}")
+        B, _, T = x_t.shape
+        if T % self.downsample_rate:
+            raise ValueError(f"T={T} is not a multiple of the UNet downsample rate {self.downsample_rate}")
+        E = 4 * self.base_channels
+        x_t = x_t.detach().to(torch.float32).contiguous()
+        ts = ts.detach().to(device=x_t.device, dtype=torch.float32).contiguous()
+        eps = eps.detach().to(torch.float32).contiguous()
+        vectors = vectors.detach().to(device=x_t.device, dtype=torch.float32).contiguous()
+        if ts.shape != (B,) or tuple(eps.shape) != (B, 1, T) or tuple(vectors.shape) != (B, E):
+            raise ValueError(f"expected ts [{B}], eps [{B}, 1, {T}] and vectors [{B}, {E}], got {tuple(ts.shape)}, {tuple(eps.shape)}, {tuple(vectors.shape)}")
+        if cond is not None:
+            cond = cond.detach().to(torch.float32).contiguous()
+            if tuple(cond.shape[:2]) != (B, self.cond_channels) or cond.shape[2] < 1:
+                raise ValueError(f"expected cond of shape {(B, self.cond_channels)} x L, got {tuple(cond.shape)}")
+            lens = {(T // 160 + 1 - 2) // 2 + 1: 1, T // 256: 0}  # (the length codes of forward())
+            self._cond_code = lens.get(cond.shape[2], 1000 + cond.shape[2])
+        h = self._grad_handle(x_t.device, B, T)
+        mses = torch.empty(B, device=x_t.device, dtype=torch.float32)
+        grads = torch.empty(B, E, device=x_t.device, dtype=torch.float32)
+        pred = torch.empty(B, 1, T, device=x_t.device, dtype=torch.float32) if return_pred else None
+        with torch.cuda.device(x_t.device):
+            _native.check(_native.lib().vqvs_unet_embed_grad(
+                h.ptr, x_t.data_ptr(), ts.data_ptr(), _native._ptr(cond), vectors.data_ptr(), eps.data_ptr(), mses.data_ptr(),
+                grads.data_ptr(), _native._ptr(pred), B, T, _native._stream_ptr()))
+        return (mses, grads, pred) if return_pred else (mses, grads)
 
     @property
     def downsample_rate(self) -> int:
