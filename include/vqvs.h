@@ -249,6 +249,51 @@ int vqvs_unet_embed_grad(vqvs_model* m, const float* d_x_t, const float* d_ts, c
 int vqvs_embed_adamw(float* d_rows, float* d_m, float* d_v, const float* d_grad, const int64_t* d_row_of_clip, int n, int B, int E,
                      int step, float lr, float beta1, float beta2, float eps, float weight_decay, void* stream);
 
+/* ---- classifier enrolment (handle-less) -------------------------------------------------
+ * New speakers of a trained Classifier are new rows of its head, GELU -> Linear(F, num_labels) on the stem's feature vector
+ * (vqvs_classifier_features, F = output_mult * base_channels).  With the stem and the K old rows frozen, the gradient of the loss
+ * the reference trains the classifier on (train_loop.py:551-561: the NLL of the label) has a closed form in the n new rows,
+ *   d nll_b / d W[K+j, :] = (softmax_b[K+j] - [y_b == K+j]) * gelu(feat_b),   d nll_b / d bias[K+j] = softmax_b[K+j] - [y_b == K+j],
+ * so there is no backward schedule: this call gives the per-clip loss and the coefficients, vqvs_head_adamw the gradient and the step.
+ *   d_feat [B,F] f32       stem features, before the head's GELU
+ *   d_w_old [K,F] f32, d_b_old [K] f32   the checkpoint's head (out.1.weight, out.1.bias), read only
+ *   d_new [n,F+1] f32      the new rows, column F is the bias
+ *   d_targets [B] int64    labels of the grown model, 0..K+n-1; a target < K is a replay clip of an old speaker
+ *   d_act [B,F] f32 out, or NULL: gelu_f(feat), the library's f32 GELU: exactly the value vqvs_classifier_forward's head forms
+ *   d_logits [B,K+n] f32 out, or NULL: logit_k = bias_k + sum_f w[k,f] act[f].  Products and sums in f64 from the f32 inputs (a
+ *               product of two f32 values is exact in f64: only the sums round); lane l of a wave adds f = l, l+64, ... in
+ *               ascending order, the 64 lanes fold by a fixed xor tree (32, 16, ... 1), the bias is added last; rounded to f32
+ *               once, on store.  Everything below is taken from the f64 logits, never from the stored ones.
+ *   d_nll [B] f64 out:  logsumexp_k logit_k - logit_y.  The maximum M is exact; d_k = logit_k - M, exp, the sum S (thread t of
+ *               256 adds k = t, t+256, ..., lanes fold by the xor tree, the four waves are added in order), log S and
+ *               log S - d_y are f64
+ *   d_top1 [B] int64 out, or NULL: 1 if the first index of the maximum of the f64 logits is y, else 0
+ *   d_new_mass [B] f64 out, or NULL: sum_j softmax[K+j] = (sum of exp d_k over k >= K, in the order of S) / S: what the grown
+ *               head gives to any new label; on a replay clip the number to watch
+ *   d_coef [B,n] f64 out: exp(d_{K+j}) / S - [y == K+j]
+ * One workgroup per clip, one writer per output, no floating-point atomics: a clip's outputs are bitwise the same whatever B and
+ * its row are, and the same call gives the same bits.  A target outside 0..K+n-1 is never used as an index: that clip's d_nll and
+ * its d_coef row become NaN and its d_top1 is 0 (the Python binding raises IndexError first).
+ * B in 1..65535, F in 1..4096, K >= 1, n >= 1, K+n <= 8192.  Asynchronous on `stream`.  VQVS_ERR_ARG before the device is touched:
+ * NULL d_feat / d_w_old / d_b_old / d_new / d_targets / d_nll / d_coef, or a size outside the limits. */
+int vqvs_head_xent_grad(const float* d_feat, const float* d_w_old, const float* d_b_old, const float* d_new, const int64_t* d_targets,
+                        float* d_act, float* d_logits, double* d_nll, int64_t* d_top1, double* d_new_mass, double* d_coef, int B, int F,
+                        int K, int n, void* stream);
+/* The gradient of the batch-mean NLL with respect to the new rows and one AdamW step on them, in one kernel, one thread per
+ * (row j, column f) of [n, F+1]:
+ *   g[j,f] = (sum over b ascending of d_coef[b,j] * act[b,f], fused multiply-adds in f64) / B,  act[b,F] = 1 for the bias column
+ *            -- nlls.mean().backward() of train_loop.py:551-561 restricted to the new rows
+ *   p *= 1 - lr * weight_decay;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2
+ *   p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ * vqvs_embed_adamw's update to the letter: torch.optim.AdamW's, decoupled weight decay and bias correction, `step` the 1-based count
+ * of this step, evaluated in f64 from the f32 state and rounded once per stored value.  A row whose d_coef column is all zero has
+ * g = 0: with weight_decay 0 and zero moments it is bitwise unchanged.  No atomics; the same call gives the same bits.
+ *   d_new, d_m, d_v [n,F+1] f32 in/out;  d_act [B,F] f32 and d_coef [B,n] f64 as vqvs_head_xent_grad wrote them
+ * VQVS_ERR_ARG before the device is touched: a NULL pointer; n, B or F not positive (or above 8192, 65535, 4096, the limits of
+ * vqvs_head_xent_grad); step < 1; lr, eps or weight_decay negative or not finite; a beta outside [0, 1). */
+int vqvs_head_adamw(float* d_new, float* d_m, float* d_v, const float* d_act, const double* d_coef, int n, int B, int F, int step,
+                    float lr, float beta1, float beta2, float eps, float weight_decay, void* stream);
+
 /* ---- DDPM reverse step --------------------------------------------------------
  * x_prev = Diffusion.ddpm_previous(x_t, ts, step, eps, noise, sigma_large, constrain)
  * reference diffusion/diffusion.py:48-90 (without cond_fn; with cond_fn the caller

@@ -14,7 +14,7 @@ from .dataset import create_data_loader
 from .diffusion import CosSchedule, Diffusion, ExpSchedule, Schedule, make_schedule, randn_clips
 from .diffusion_model import DiffusionModel
 from .encoder_predictor import EncoderPredictor
-from .enroll import SpeakerEnroller
+from .enroll import ClassifierEnroller, SpeakerEnroller
 from .longform import plan_windows
 from .losses import LossTracker, classification_scores, speaker_search_losses
 from .pitch import PitchDistance
@@ -29,5 +29,5 @@ __all__ = [
     "DiffusionModel", "Classifier", "ConvMFCCEncoder", "EncoderPredictor", "ResBlockModule", "UNetEncoder", "UNetPredictor", "VQ", "VQVAE",
     "FeatureStats", "class_score", "frechet_distance", "wav_roundtrip", "LossTracker", "speaker_search_losses", "create_data_loader",
     "StandardVQLoss", "VQLoss", "code_usage", "classification_scores", "plan_windows",
-    "SpectralDistance", "spectral_constants", "PitchDistance", "SpeakerEnroller",
+    "SpectralDistance", "spectral_constants", "PitchDistance", "SpeakerEnroller", "ClassifierEnroller",
 ]

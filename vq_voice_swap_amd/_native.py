@@ -74,7 +74,7 @@ EXPORTS = [
     "vqvs_ddpm_guided_eps", "vqvs_randn", "vqvs_ddpm_noise", "vqvs_ddpm_sqerr", "vqvs_vq_argmin", "vqvs_vq_quantize", "vqvs_vq_embed", "vqvs_xent_score", "vqvs_spectral_distance", "vqvs_pitch_distance", "vqvs_debug_tap_count",
     "vqvs_debug_tap_info", "vqvs_debug_tap_rows", "vqvs_debug_read_tap", "vqvs_debug_read_embedding", "vqvs_forward_kernel_count", "vqvs_forward_model_bytes",
     "vqvs_forward_flops", "vqvs_set_profiling", "vqvs_op_info", "vqvs_op_desc", "vqvs_profile_read", "vqvs_last_error", "vqvs_version",
-    "vqvs_unet_embed_grad", "vqvs_embed_adamw", "vqvs_debug_read_dfilm",
+    "vqvs_unet_embed_grad", "vqvs_embed_adamw", "vqvs_debug_read_dfilm", "vqvs_head_xent_grad", "vqvs_head_adamw",
 ]
 
 _lib = None
@@ -132,6 +132,8 @@ def lib():
     L.vqvs_unet_embed_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
     L.vqvs_embed_adamw.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp]
     L.vqvs_debug_read_dfilm.argtypes = [vp, i32, vp]
+    L.vqvs_head_xent_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
+    L.vqvs_head_adamw.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp]
     L.vqvs_encoder_forward.argtypes = [vp, vp, vp, i32, i32, vp]
     L.vqvs_mfcc_encoder_forward.argtypes = [vp, vp, vp, i32, i32, vp]
     L.vqvs_mfcc_encoder_forward_logmel.argtypes = [vp, vp, vp, i32, i32, vp]

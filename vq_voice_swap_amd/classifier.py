@@ -87,6 +87,24 @@ class Classifier(_NativeModule, Savable):
         return dict(num_labels=self.num_labels, base_channels=s.base_channels, channel_mult=s.channel_mult,
                     output_mult=s.output_mult, depth_mult=s.depth_mult)
 
+    def add_labels(self, n: int) -> None:
+        """Grow the head by `n` labels behind the existing ones: n zero rows of `out.1.weight` and n zero biases (what a fresh head
+        holds: the reference zero-scales it).  The old rows and biases stay bit for bit, so every old logit does."""
+        if int(n) != n or n < 1:
+            raise ValueError(f"n={n!r} must be a positive integer")
+        if self.num_labels + int(n) > 8192:
+            raise ValueError(f"{self.num_labels} + {n} labels: the head kernels take at most 8192")
+        old = self.out[1]
+        new = nn.Linear(old.in_features, self.num_labels + int(n)).to(device=old.weight.device, dtype=old.weight.dtype)
+        with torch.no_grad():
+            new.weight.zero_()
+            new.bias.zero_()
+            new.weight[:self.num_labels].copy_(old.weight)
+            new.bias[:self.num_labels].copy_(old.bias)
+        self.out[1] = new
+        self.num_labels += int(n)
+        self.invalidate()
+
     @property
     def downsample_rate(self) -> int:
         return 2 ** len(self.stem.channel_mult)

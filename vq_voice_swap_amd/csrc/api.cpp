@@ -231,6 +231,32 @@ int vqvs_embed_adamw(float* d_rows, float* d_m, float* d_v, const float* d_grad,
                          reinterpret_cast<hipStream_t>(stream));
 }
 
+int vqvs_head_xent_grad(const float* d_feat, const float* d_w_old, const float* d_b_old, const float* d_new, const int64_t* d_targets,
+                        float* d_act, float* d_logits, double* d_nll, int64_t* d_top1, double* d_new_mass, double* d_coef, int B, int F,
+                        int K, int n, void* stream) {
+  if (!d_feat || !d_w_old || !d_b_old || !d_new || !d_targets || !d_nll || !d_coef)
+    VQVS_FAIL(VQVS_ERR_ARG, "feat, w_old, b_old, new, targets, nll and coef must be non-NULL");
+  if (B < 1 || B > 65535) VQVS_FAIL(VQVS_ERR_ARG, "batch %d outside 1..65535", B);
+  if (F < 1 || F > 4096) VQVS_FAIL(VQVS_ERR_ARG, "feature width %d outside 1..4096", F);
+  if (K < 1 || n < 1 || K > 8192 || n > 8192 || K + n > 8192) VQVS_FAIL(VQVS_ERR_ARG, "K=%d old and n=%d new labels: each at least 1, together at most 8192", K, n);
+  return run_head_xent_grad(d_feat, d_w_old, d_b_old, d_new, d_targets, d_act, d_logits, d_nll, d_top1, d_new_mass, d_coef, B, F, K, n,
+                            reinterpret_cast<hipStream_t>(stream));
+}
+
+int vqvs_head_adamw(float* d_new, float* d_m, float* d_v, const float* d_act, const double* d_coef, int n, int B, int F, int step,
+                    float lr, float beta1, float beta2, float eps, float weight_decay, void* stream) {
+  if (!d_new || !d_m || !d_v || !d_act || !d_coef) VQVS_FAIL(VQVS_ERR_ARG, "new, m, v, act and coef must be non-NULL");
+  if (n < 1 || B < 1 || F < 1) VQVS_FAIL(VQVS_ERR_ARG, "bad shape n=%d B=%d F=%d", n, B, F);
+  if (n > 8192 || B > 65535 || F > 4096) VQVS_FAIL(VQVS_ERR_ARG, "n=%d B=%d F=%d outside 1..8192, 1..65535, 1..4096", n, B, F);
+  if (step < 1) VQVS_FAIL(VQVS_ERR_ARG, "step=%d: the count of this step starts at 1", step);
+  if (!std::isfinite(lr) || lr < 0.f) VQVS_FAIL(VQVS_ERR_ARG, "lr=%g must be finite and not negative", (double)lr);
+  if (!std::isfinite(eps) || eps < 0.f) VQVS_FAIL(VQVS_ERR_ARG, "eps=%g must be finite and not negative", (double)eps);
+  if (!std::isfinite(weight_decay) || weight_decay < 0.f) VQVS_FAIL(VQVS_ERR_ARG, "weight_decay=%g must be finite and not negative", (double)weight_decay);
+  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) VQVS_FAIL(VQVS_ERR_ARG, "betas (%g, %g) must lie in [0, 1)", (double)beta1, (double)beta2);
+  return run_head_adamw(d_new, d_m, d_v, d_act, d_coef, n, B, F, step, lr, beta1, beta2, eps, weight_decay,
+                        reinterpret_cast<hipStream_t>(stream));
+}
+
 int vqvs_encoder_forward(vqvs_model* m, const float* d_x, float* d_z, int B, int T, void* stream) {
   if (int e = check_run(m, VQVS_KIND_ENCODER, B, T)) return e;
   if (!d_x || !d_z) VQVS_FAIL(VQVS_ERR_ARG, "x and z must be non-NULL");

@@ -288,6 +288,166 @@ __global__ __launch_bounds__(256) void embed_adamw_kernel(const AdamArgs a) {
   a.rows[i] = (float)p;
 }
 
+// ------------------------------------------------------------------------------------
+// head_xent_grad: classifier enrolment (vqvs_head_xent_grad).  The head of the grown classifier, GELU -> Linear(F, K + n), on the stem's
+// feature vector, its softmax cross-entropy, and the coefficients of the closed-form gradient of the n new rows:
+//   d nll_b / d W[K + j, :] = (softmax_b[K + j] - [y_b == K + j]) * gelu(feat_b),   d nll_b / d bias[K + j] = the same coefficient.
+// One workgroup of four waves per clip; nothing it does depends on B or on the clip's row.
+//   1. act[f] = gelu_f(feat[f]) in f32: the value cls_head_kernel forms (common.hpp), kept in LDS.
+//   2. wave w takes logits w, w + 4, ...: lane l adds the products of f = l, l + 64, ... into one f64 accumulator (the product of two
+//      f32 values is exact in f64, so only the sums round), the 64 accumulators fold by xor-shuffles 32, 16, ... 1, the bias is added
+//      last.  The f64 logits stay in LDS (8 bytes each: 64 KiB at the limit of 8192).
+//   3. maximum and its first index over the f64 logits (comparisons: exact in any order).
+//   4. S = sum exp(logit - max), and the same sum over the new labels alone: thread t adds k = t, t + 256, ..., lanes fold by
+//      xor-shuffles, the four waves in wave order.  Every thread then holds the same S.
+// One writer per output, no atomics.
+// ------------------------------------------------------------------------------------
+constexpr int HX_NT = 256, HX_NW = HX_NT / 64;
+struct HeadXentArgs {
+  const float* feat;        // [B][F]
+  const float* w_old;       // [K][F]
+  const float* b_old;       // [K]
+  const float* rows;        // [n][F + 1], column F is the bias
+  const int64_t* targets;   // [B]
+  float* act;               // [B][F] or nullptr
+  float* logits;            // [B][K + n] or nullptr
+  double* nll;              // [B]
+  int64_t* top1;            // [B] or nullptr
+  double* new_mass;         // [B] or nullptr
+  double* coef;             // [B][n]
+  int F, K, n;
+};
+__global__ __launch_bounds__(HX_NT) void head_xent_grad_kernel(const HeadXentArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char hx_lds[];
+  __shared__ double s_m[HX_NW], s_sum[HX_NW], s_new[HX_NW];
+  __shared__ int s_am[HX_NW];
+  const int F = a.F, K = a.K, N = a.K + a.n;
+  double* lg = reinterpret_cast<double*>(hx_lds);  // [N]
+  float* act = reinterpret_cast<float*>(lg + N);   // [F]
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int b = blockIdx.x;
+
+  for (int f = t; f < F; f += HX_NT) {
+    const float g = gelu_f(a.feat[(size_t)b * F + f]);
+    act[f] = g;
+    if (a.act) a.act[(size_t)b * F + f] = g;
+  }
+  __syncthreads();
+
+  for (int k = w; k < N; k += HX_NW) {
+    const float* row = k < K ? a.w_old + (size_t)k * F : a.rows + (size_t)(k - K) * (F + 1);
+    double acc = 0.0;
+    for (int f = lane; f < F; f += 64) acc += (double)row[f] * (double)act[f];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+    if (lane == 0) lg[k] = acc + (double)(k < K ? a.b_old[k] : row[F]);
+  }
+  __syncthreads();
+
+  double m = -INFINITY;
+  int am = -1;
+  for (int k = t; k < N; k += HX_NT) {
+    const double x = lg[k];
+    if (a.logits) a.logits[(size_t)b * N + k] = (float)x;
+    if (x > m) {
+      m = x;
+      am = k;
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const double om = __shfl_xor(m, d, 64);
+    const int oi = __shfl_xor(am, d, 64);
+    if (oi >= 0 && (am < 0 || om > m || (om == m && oi < am))) {
+      m = om;
+      am = oi;
+    }
+  }
+  if (lane == 0) {
+    s_m[w] = m;
+    s_am[w] = am;
+  }
+  __syncthreads();
+  m = s_m[0];
+  am = s_am[0];
+#pragma unroll
+  for (int i = 1; i < HX_NW; ++i) {
+    const double om = s_m[i];
+    const int oi = s_am[i];
+    if (oi >= 0 && (am < 0 || om > m || (om == m && oi < am))) {
+      m = om;
+      am = oi;
+    }
+  }
+
+  double s = 0.0, sn = 0.0;
+  for (int k = t; k < N; k += HX_NT) {
+    const double e = exp(lg[k] - m);
+    s += e;
+    if (k >= K) sn += e;
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    s += __shfl_xor(s, d, 64);
+    sn += __shfl_xor(sn, d, 64);
+  }
+  if (lane == 0) {
+    s_sum[w] = s;
+    s_new[w] = sn;
+  }
+  __syncthreads();
+  double S = s_sum[0], Sn = s_new[0];
+#pragma unroll
+  for (int i = 1; i < HX_NW; ++i) {
+    S += s_sum[i];
+    Sn += s_new[i];
+  }
+
+  const int64_t y = a.targets[b];
+  const bool valid = y >= 0 && y < (int64_t)N;  // (an invalid target is never used as an index)
+  for (int j = t; j < a.n; j += HX_NT) {
+    const double p = exp(lg[K + j] - m) / S;
+    a.coef[(size_t)b * a.n + j] = valid ? p - (y == (int64_t)(K + j) ? 1.0 : 0.0) : (double)NAN;
+  }
+  if (t != 0) return;
+  a.nll[b] = valid ? log(S) - (lg[valid ? y : 0] - m) : (double)NAN;
+  if (a.top1) a.top1[b] = (valid && (int64_t)am == y) ? 1 : 0;
+  if (a.new_mass) a.new_mass[b] = Sn / S;
+}
+
+// ------------------------------------------------------------------------------------
+// head_adamw: the gradient of the batch-mean NLL with respect to the new rows and one AdamW step on them (vqvs_head_adamw).  One thread
+// per (row j, column f): g = (sum over b ascending of coef[b][j] * act[b][f], fused multiply-adds in f64) / B, act[b][F] = 1 for the
+// bias column; then embed_adamw_kernel's update, to the letter.
+// ------------------------------------------------------------------------------------
+struct HeadAdamArgs {
+  float *rows, *m, *v;  // [n][F + 1]
+  const float* act;     // [B][F]
+  const double* coef;   // [B][n]
+  int n, B, F;
+  double lr, beta1, beta2, eps, wd, bc1, bc2_sqrt;
+};
+__global__ __launch_bounds__(256) void head_adamw_kernel(const HeadAdamArgs a) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int W = a.F + 1;
+  if (i >= (long long)a.n * W) return;
+  const int j = (int)(i / W), f = (int)(i % W);
+  double g = 0.0;
+  if (f < a.F) {
+    for (int b = 0; b < a.B; ++b) g = fma(a.coef[(size_t)b * a.n + j], (double)a.act[(size_t)b * a.F + f], g);
+  } else {
+    for (int b = 0; b < a.B; ++b) g += a.coef[(size_t)b * a.n + j];
+  }
+  g /= (double)a.B;
+  const double m = a.beta1 * (double)a.m[i] + (1.0 - a.beta1) * g;
+  const double v = a.beta2 * (double)a.v[i] + (1.0 - a.beta2) * g * g;
+  double p = (double)a.rows[i] * (1.0 - a.lr * a.wd);
+  p -= (a.lr / a.bc1) * m / (sqrt(v) / a.bc2_sqrt + a.eps);
+  a.m[i] = (float)m;
+  a.v[i] = (float)v;
+  a.rows[i] = (float)p;
+}
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
@@ -338,6 +498,32 @@ int run_embed_adamw(float* rows, float* m, float* v, const float* grad, const in
   a.bc2_sqrt = std::sqrt(1.0 - std::pow(a.beta2, (double)step));
   const long long items = (long long)n * E;
   hipLaunchKernelGGL(embed_adamw_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, a);
+  VQVS_HIP(hipGetLastError());
+  return 0;
+}
+
+int run_head_xent_grad(const float* feat, const float* w_old, const float* b_old, const float* rows, const int64_t* targets, float* act,
+                       float* logits, double* nll, int64_t* top1, double* new_mass, double* coef, int B, int F, int K, int n,
+                       hipStream_t st) {
+  const HeadXentArgs a{feat, w_old, b_old, rows, targets, act, logits, nll, top1, new_mass, coef, F, K, n};
+  const size_t lds = (size_t)(K + n) * sizeof(double) + (size_t)F * sizeof(float);  // at most 64 KiB + 16 KiB
+  static bool attr_set = false;
+  if (!attr_set) {
+    VQVS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&head_xent_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(head_xent_grad_kernel, dim3(B), dim3(HX_NT), lds, st, a);
+  VQVS_HIP(hipGetLastError());
+  return 0;
+}
+
+int run_head_adamw(float* rows, float* m, float* v, const float* act, const double* coef, int n, int B, int F, int step, float lr,
+                   float beta1, float beta2, float eps, float weight_decay, hipStream_t st) {
+  HeadAdamArgs a{rows, m, v, act, coef, n, B, F, (double)lr, (double)beta1, (double)beta2, (double)eps, (double)weight_decay, 0.0, 0.0};
+  a.bc1 = 1.0 - std::pow(a.beta1, (double)step);
+  a.bc2_sqrt = std::sqrt(1.0 - std::pow(a.beta2, (double)step));
+  const long long items = (long long)n * (F + 1);
+  hipLaunchKernelGGL(head_adamw_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, a);
   VQVS_HIP(hipGetLastError());
   return 0;
 }

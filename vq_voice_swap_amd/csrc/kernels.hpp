@@ -280,6 +280,15 @@ int launch_film_bw(const FilmBwArgs& a, int B, hipStream_t st);
 int run_embed_adamw(float* rows, float* m, float* v, const float* grad, const int64_t* row_of_clip, int n, int B, int E, int step, float lr,
                     float beta1, float beta2, float eps, float weight_decay, hipStream_t st);
 
+// Classifier enrolment (enroll_kernels.hip): the grown head GELU -> Linear(F, K + n) on stem features [B][F], its per-clip softmax
+// cross-entropy in f64 and the coefficients softmax[K + j] - [y == K + j] of the new rows' closed-form gradient; then the gradient
+// GEMM over the batch and one AdamW step on the new rows [n][F + 1] (column F is the bias) in one kernel.
+int run_head_xent_grad(const float* feat, const float* w_old, const float* b_old, const float* rows, const int64_t* targets, float* act,
+                       float* logits, double* nll, int64_t* top1, double* new_mass, double* coef, int B, int F, int K, int n,
+                       hipStream_t st);
+int run_head_adamw(float* rows, float* m, float* v, const float* act, const double* coef, int n, int B, int F, int step, float lr,
+                   float beta1, float beta2, float eps, float weight_decay, hipStream_t st);
+
 // Classifier head (classifier.py:98-104, 153-191, 26-28): GroupNorm+GELU, attention pool whose only consumed output
 // is the prepended zero token, c_proj, GELU, Linear -- and, when labels are given, the gradient of
 // gscale * log_softmax(logits)[label] with respect to the head's input.  One workgroup per clip.
