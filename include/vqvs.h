@@ -420,6 +420,38 @@ int vqvs_dpmpp_step(const float* d_x_t, const float* d_eps, const float* d_grad,
 int vqvs_dpmpp_step_windows(const float* d_x, const float* d_eps, const float* d_grad, const float* d_x0_prev, const float* d_alpha_from,
                             const float* d_alpha_t, const float* d_alpha_to, float* d_x_to, float* d_x0_out, float* d_windows, int n, int W,
                             int H, uint32_t flags, void* stream);
+/* ---- Packed window steps (handle-less) ----
+ * The three ..._step_windows calls on a PACK of R recordings in one launch (two with CONSTRAIN), for converting a corpus: the windows of
+ * many short recordings fill one forward, and the step that follows is one call whatever R is.
+ *   d_first [R + 1] int32 (device): prefix sums of the recordings' window counts.  first[0] = 0, first[R] = N, the pack's window total;
+ *     recording r has n_r = first[r + 1] - first[r] >= 1 windows.
+ *   long arrays (d_x, d_noise, d_x_prev / d_x_to, d_x0_prev, d_x0_out): the recordings' rows end to end.  Recording r starts at
+ *     off_r = first[r] * H + r * V (V = W - H) and holds n_r * H + V samples; N * H + R * V < 2^31 in all.
+ *   window arrays (d_eps, d_grad, d_windows) [N, W]: recording r's windows are rows first[r] .. first[r + 1] - 1.
+ *   ONE d_alpha_* each: the recordings of a pack are at the same step.
+ * Recording r's slices of the outputs are EXACTLY what the single-recording call writes for (n = n_r, clip = clip + r) on recording r's
+ * slices of the inputs, bit for bit: the same cross-fade weights, each window's own CONSTRAIN mean from the same fp64 chunk partials in
+ * the same order, drawn noise philox_normal4(seed, quad = (p - off_r) / 4, clip + r, step_index, stream 0).  The last window of
+ * recording r and the first of r + 1 are neighbours in [N, W] and are NOT an overlap: nothing of one recording reaches another.
+ * Every off_r is a multiple of 4, so a quad never straddles two recordings and every access stays 16 bytes wide.
+ * N is read on the device.  The grid is fixed and strides over the pack; with CONSTRAIN the per-(device, stream) scratch buffer is
+ * leased at the bound min(65535, (2^31 - 1) / H) * ceil(W / 4096) doubles.  The kernel clamps first[R] to 1..65535 and every other entry
+ * to 0..N, and steps a quad only inside the row the table gives it: a table that is not one of prefix sums gives wrong samples, never
+ * an access outside N * H + R * V samples or N windows.
+ * VQVS_ERR_ARG before the device is touched: every rule of the single-recording call on (W, H, flags, eta, NULL pointers); R outside
+ * 1..65535; NULL d_first; and the aliasing rules of the single-recording call, checked over the R * W samples that every array of a pack
+ * of R recordings holds at the least (the true extents are on the device). */
+int vqvs_ddpm_step_windows_packed(const float* d_x, const float* d_eps, const float* d_noise, const float* d_alpha_t,
+                                  const float* d_alpha_prev, float* d_x_prev, float* d_windows, const int32_t* d_first, int R, int W, int H,
+                                  uint32_t flags, float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index, void* stream);
+int vqvs_ddim_step_windows_packed(const float* d_x, const float* d_eps, const float* d_grad, const float* d_noise, const float* d_alpha_t,
+                                  const float* d_alpha_to, float* d_x_to, float* d_windows, const int32_t* d_first, int R, int W, int H,
+                                  uint32_t flags, float eta, float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index,
+                                  void* stream);
+int vqvs_dpmpp_step_windows_packed(const float* d_x, const float* d_eps, const float* d_grad, const float* d_x0_prev,
+                                   const float* d_alpha_from, const float* d_alpha_t, const float* d_alpha_to, float* d_x_to,
+                                   float* d_x0_out, float* d_windows, const int32_t* d_first, int R, int W, int H, uint32_t flags,
+                                   void* stream);
 /* ---- Keep region (handle-less; the "replacement" method of Song et al., "Score-based generative modeling through stochastic
  * differential equations", 2021, as in RePaint and SDEdit -- the reference has no counterpart) ----
  * IN PLACE on the state d_x [B,T]: every sample with d_keep[row,p] != 0 -- every sample when d_keep is NULL -- is put back on the

@@ -15,7 +15,7 @@ from .diffusion import CosSchedule, Diffusion, ExpSchedule, Schedule, make_sched
 from .diffusion_model import DiffusionModel
 from .encoder_predictor import EncoderPredictor
 from .enroll import ClassifierEnroller, SpeakerEnroller
-from .longform import plan_windows
+from .longform import plan_pack, plan_windows
 from .losses import LossTracker, classification_scores, speaker_search_losses
 from .pitch import PitchDistance
 from .spectral import SpectralDistance, spectral_constants
@@ -28,6 +28,6 @@ __all__ = [
     "Savable", "atomic_save", "CosSchedule", "Diffusion", "ExpSchedule", "Schedule", "make_schedule", "randn_clips",
     "DiffusionModel", "Classifier", "ConvMFCCEncoder", "EncoderPredictor", "ResBlockModule", "UNetEncoder", "UNetPredictor", "VQ", "VQVAE",
     "FeatureStats", "class_score", "frechet_distance", "wav_roundtrip", "LossTracker", "speaker_search_losses", "create_data_loader",
-    "StandardVQLoss", "VQLoss", "code_usage", "classification_scores", "plan_windows",
+    "StandardVQLoss", "VQLoss", "code_usage", "classification_scores", "plan_windows", "plan_pack",
     "SpectralDistance", "spectral_constants", "PitchDistance", "SpeakerEnroller", "ClassifierEnroller",
 ]

@@ -70,7 +70,8 @@ class Cfg(C.Structure):
 EXPORTS = [
     "vqvs_param_count", "vqvs_param_info", "vqvs_model_create", "vqvs_model_destroy", "vqvs_model_device_bytes",
     "vqvs_unet_forward", "vqvs_encoder_forward", "vqvs_mfcc_encoder_forward", "vqvs_mfcc_encoder_forward_logmel", "vqvs_model_status", "vqvs_resblock_forward", "vqvs_classifier_forward",
-    "vqvs_classifier_guidance", "vqvs_classifier_features", "vqvs_feature_moments", "vqvs_encpred_forward", "vqvs_encpred_guidance", "vqvs_ddpm_step", "vqvs_ddpm_step_windows", "vqvs_ddim_step", "vqvs_ddim_step_windows", "vqvs_dpmpp_step", "vqvs_dpmpp_step_windows", "vqvs_keep_region", "vqvs_keep_region_windows", "vqvs_ddpm_mean",
+    "vqvs_classifier_guidance", "vqvs_classifier_features", "vqvs_feature_moments", "vqvs_encpred_forward", "vqvs_encpred_guidance", "vqvs_ddpm_step", "vqvs_ddpm_step_windows", "vqvs_ddim_step", "vqvs_ddim_step_windows", "vqvs_dpmpp_step", "vqvs_dpmpp_step_windows",
+    "vqvs_ddpm_step_windows_packed", "vqvs_ddim_step_windows_packed", "vqvs_dpmpp_step_windows_packed", "vqvs_keep_region", "vqvs_keep_region_windows", "vqvs_ddpm_mean",
     "vqvs_ddpm_guided_eps", "vqvs_randn", "vqvs_ddpm_noise", "vqvs_ddpm_sqerr", "vqvs_vq_argmin", "vqvs_vq_quantize", "vqvs_vq_embed", "vqvs_xent_score", "vqvs_spectral_distance", "vqvs_pitch_distance", "vqvs_debug_tap_count",
     "vqvs_debug_tap_info", "vqvs_debug_tap_rows", "vqvs_debug_read_tap", "vqvs_debug_read_embedding", "vqvs_forward_kernel_count", "vqvs_forward_model_bytes",
     "vqvs_forward_flops", "vqvs_set_profiling", "vqvs_op_info", "vqvs_op_desc", "vqvs_profile_read", "vqvs_last_error", "vqvs_version",
@@ -151,6 +152,9 @@ def lib():
     L.vqvs_ddim_step_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, u32, f32, f32, u64, u64, u32, vp]
     L.vqvs_dpmpp_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, u32, vp]
     L.vqvs_dpmpp_step_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, u32, vp]
+    L.vqvs_ddpm_step_windows_packed.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, u32, f32, u64, u64, u32, vp]
+    L.vqvs_ddim_step_windows_packed.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, u32, f32, f32, u64, u64, u32, vp]
+    L.vqvs_dpmpp_step_windows_packed.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, u32, vp]
     L.vqvs_keep_region.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, u64, u64, u32, vp]
     L.vqvs_keep_region_windows.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, u64, u64, u32, vp]
     L.vqvs_ddpm_mean.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]

@@ -1,0 +1,86 @@
+"""
+Converting a whole data set (convert_dataset.py): the host-side bookkeeping, no device and no model.
+
+The files of a LibriSpeech-layout tree (`dataset.build_file_index`) are sorted by relative path, and a file's GLOBAL ID is its place in
+that list.  The id keys everything random about the file's conversion, so its output does not depend on how the files are grouped
+into packs, on the window batch or on the number of ranks.  A pack is a run of CONSECUTIVE ids -- `decode_long_batch` keys recording r
+of a pack as clip_offset + r -- of at most a budget of windows; packs are dealt to the ranks round-robin.
+"""
+import os
+from typing import Dict, List, Optional, Sequence, Tuple
+
+
+def list_files(index: dict) -> List[Tuple[str, float]]:
+    """(relative path, seconds) of every file of a `build_file_index` tree, sorted by relative path: position = global id."""
+    out: List[Tuple[str, float]] = []
+
+    def walk(node: dict, prefix: str) -> None:
+        for name, item in node.items():
+            rel = os.path.join(prefix, name) if prefix else name
+            if isinstance(item, dict):
+                walk(item, rel)
+            else:
+                out.append((rel, float(item)))
+
+    walk(index, "")
+    return sorted(out)
+
+
+def top_directory(rel_path: str) -> str:
+    return rel_path.replace("\\", "/").split("/", 1)[0]
+
+
+def read_label_map(path: str, directories: Optional[Sequence[str]] = None) -> Dict[str, int]:
+    """`--label-map FILE`: lines `top-level-directory<TAB>label` (blank lines and lines starting with # are skipped) -> {directory:
+    label}.  ValueError for a line without exactly one tab, an empty directory, a label that is not a non-negative integer, a
+    directory named twice, and -- with `directories`, the top-level directories of the data -- a directory the file does not map."""
+    mapping: Dict[str, int] = {}
+    with open(path, "rt") as f:
+        for number, line in enumerate(f, 1):
+            line = line.rstrip("\r\n")
+            if not line.strip() or line.lstrip().startswith("#"):
+                continue
+            fields = line.split("\t")
+            if len(fields) != 2 or not fields[0].strip():
+                raise ValueError(f"{path}:{number}: expected `directory<TAB>label`, got {line!r}")
+            name, text = fields[0].strip(), fields[1].strip()
+            if not text.isdigit():
+                raise ValueError(f"{path}:{number}: label {text!r} is not a non-negative integer")
+            if name in mapping:
+                raise ValueError(f"{path}:{number}: directory {name!r} is mapped twice")
+            mapping[name] = int(text)
+    if directories is not None:
+        missing = sorted(set(directories) - set(mapping))
+        if missing:
+            raise ValueError(f"{path} maps no label to {missing}")
+    return mapping
+
+
+def make_packs(windows: Sequence[int], budget: int, ids: Optional[Sequence[int]] = None) -> List[List[int]]:
+    """Files of `windows[i]` windows each, with global ids `ids` (default 0, 1, ...; ascending) -> packs of ids, in order.  A pack is
+    a run of consecutive ids whose windows add up to at most `budget`; a file with more windows than that is a pack of its own, and
+    a gap in the ids (a file left out) ends a pack."""
+    if budget < 1:
+        raise ValueError(f"a pack holds at least 1 window, got a budget of {budget}")
+    ids = list(range(len(windows))) if ids is None else [int(i) for i in ids]
+    if len(ids) != len(windows) or any(b <= a for a, b in zip(ids, ids[1:])):
+        raise ValueError("ids must be ascending, one per file")
+    packs: List[List[int]] = []
+    used = 0
+    for i, n in zip(ids, windows):
+        if int(n) < 1:
+            raise ValueError(f"file {i} has {n} windows: at least 1")
+        if packs and used + int(n) <= budget and packs[-1][-1] + 1 == i:
+            packs[-1].append(i)
+            used += int(n)
+        else:
+            packs.append([i])
+            used = int(n)
+    return packs
+
+
+def deal_packs(packs: Sequence[List[int]], rank: int, world: int) -> List[List[int]]:
+    """The packs of rank `rank` of `world`: every world-th one."""
+    if not 0 <= rank < world:
+        raise ValueError(f"rank {rank} outside 0..{world - 1}")
+    return [list(p) for p in packs[rank::world]]

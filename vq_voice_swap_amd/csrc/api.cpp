@@ -547,6 +547,71 @@ int vqvs_dpmpp_step_windows(const float* d_x, const float* d_eps, const float* d
                                 reinterpret_cast<double*>(lease.p), n, W, H, flags, reinterpret_cast<hipStream_t>(stream));
 }
 
+// The geometry of the three ..._windows_packed entry points: R recordings in windows of W every H.  The window total is on the device;
+// *least = R * W is what every array of such a pack holds at the least, the extent the aliasing rules are checked over.
+static int check_pack_geometry(const int32_t* d_first, int R, int W, int H, int64_t* least) {
+  if (R < 1 || R > 65535) VQVS_FAIL(VQVS_ERR_ARG, "recording count R=%d outside 1..65535", R);
+  if (!d_first) VQVS_FAIL(VQVS_ERR_ARG, "first must be non-NULL");
+  int64_t Np;
+  if (int e = check_window_geometry(1, W, H, &Np)) return e;
+  *least = (int64_t)R * W;
+  return 0;
+}
+static int lease_x0sum_packed(bool constrain, int W, int H, void* stream, ScratchLease& lease) {
+  return constrain ? scratch_get(packed_scratch_doubles(W, H) * 8, stream, lease) : 0;
+}
+
+int vqvs_ddpm_step_windows_packed(const float* d_x, const float* d_eps, const float* d_noise, const float* d_alpha_t,
+                                  const float* d_alpha_prev, float* d_x_prev, float* d_windows, const int32_t* d_first, int R, int W, int H,
+                                  uint32_t flags, float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index, void* stream) {
+  if (!d_x || !d_eps || !d_alpha_t || !d_alpha_prev || !d_x_prev) VQVS_FAIL(VQVS_ERR_ARG, "x, eps, alpha_t, alpha_prev and x_prev must be non-NULL");
+  int64_t L;
+  if (int e = check_pack_geometry(d_first, R, W, H, &L)) return e;
+  if (bytes_overlap(d_x_prev, L * 4, d_x, L * 4)) VQVS_FAIL(VQVS_ERR_ARG, "x_prev must not overlap x");
+  ScratchLease lease;
+  if (int e = lease_x0sum_packed(flags & VQVS_DDPM_CONSTRAIN, W, H, stream, lease)) return e;
+  return run_ddpm_step_packed(d_x, d_eps, d_noise, d_alpha_t, d_alpha_prev, d_x_prev, d_windows, reinterpret_cast<double*>(lease.p), d_first, R,
+                              W, H, flags, noise_scale, seed, clip, step_index, reinterpret_cast<hipStream_t>(stream));
+}
+
+int vqvs_ddim_step_windows_packed(const float* d_x, const float* d_eps, const float* d_grad, const float* d_noise, const float* d_alpha_t,
+                                  const float* d_alpha_to, float* d_x_to, float* d_windows, const int32_t* d_first, int R, int W, int H,
+                                  uint32_t flags, float eta, float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index,
+                                  void* stream) {
+  if (!d_x || !d_eps || !d_alpha_t || !d_alpha_to || !d_x_to) VQVS_FAIL(VQVS_ERR_ARG, "x, eps, alpha_t, alpha_to and x_to must be non-NULL");
+  int64_t L;
+  if (int e = check_pack_geometry(d_first, R, W, H, &L)) return e;
+  if (int e = check_ddim_args(flags, eta)) return e;
+  const struct { const void* p; int64_t len; } ins[] = {{d_x, L}, {d_eps, L}, {d_grad, L}, {d_noise, L}, {d_alpha_t, 1}, {d_alpha_to, 1},
+                                                        {d_first, R + 1}};
+  for (const auto& in : ins)
+    if (bytes_overlap(d_x_to, L * 4, in.p, in.len * 4) || bytes_overlap(d_windows, L * 4, in.p, in.len * 4))
+      VQVS_FAIL(VQVS_ERR_ARG, "x_to and windows must not overlap x, eps, grad, noise, the alphas or first");
+  if (bytes_overlap(d_x_to, L * 4, d_windows, L * 4)) VQVS_FAIL(VQVS_ERR_ARG, "x_to must not overlap windows");
+  ScratchLease lease;
+  if (int e = lease_x0sum_packed(flags & VQVS_DDIM_CONSTRAIN, W, H, stream, lease)) return e;
+  return run_ddim_step_packed(d_x, d_eps, d_grad, d_noise, d_alpha_t, d_alpha_to, d_x_to, d_windows, reinterpret_cast<double*>(lease.p), d_first,
+                              R, W, H, flags, eta, noise_scale, seed, clip, step_index, reinterpret_cast<hipStream_t>(stream));
+}
+
+int vqvs_dpmpp_step_windows_packed(const float* d_x, const float* d_eps, const float* d_grad, const float* d_x0_prev,
+                                   const float* d_alpha_from, const float* d_alpha_t, const float* d_alpha_to, float* d_x_to,
+                                   float* d_x0_out, float* d_windows, const int32_t* d_first, int R, int W, int H, uint32_t flags,
+                                   void* stream) {
+  if (!d_x || !d_eps || !d_alpha_t || !d_alpha_to || !d_x_to) VQVS_FAIL(VQVS_ERR_ARG, "x, eps, alpha_t, alpha_to and x_to must be non-NULL");
+  int64_t L;
+  if (int e = check_pack_geometry(d_first, R, W, H, &L)) return e;
+  if (int e = check_dpmpp_args(flags, {d_x0_prev, L},
+                               {{d_x, L}, {d_eps, L}, {d_grad, L}, {d_alpha_from, 1}, {d_alpha_t, 1}, {d_alpha_to, 1},
+                                {reinterpret_cast<const float*>(d_first), R + 1}},
+                               {{d_x0_out, L}, {d_x_to, L}, {d_windows, L}}))
+    return e;
+  ScratchLease lease;
+  if (int e = lease_x0sum_packed(flags & VQVS_DDIM_CONSTRAIN, W, H, stream, lease)) return e;
+  return run_dpmpp_step_packed(d_x, d_eps, d_grad, d_x0_prev, d_alpha_from, d_alpha_t, d_alpha_to, d_x_to, d_x0_out, d_windows,
+                               reinterpret_cast<double*>(lease.p), d_first, R, W, H, flags, reinterpret_cast<hipStream_t>(stream));
+}
+
 // Shared argument rules of the two keep-region entry points.  N: samples of the state (and of x0, keep, noise); n_alpha: entries of
 // d_alpha; NW: samples of d_windows (0 when the entry point has none).
 static int check_keep_args(const float* d_x, const float* d_windows, const float* d_x0, const uint8_t* d_keep, const float* d_noise,

@@ -1,6 +1,7 @@
 // DDPM, DDIM and DPM-Solver++(2M) reverse-step kernels, the keep region, the counter-based normal generator, and the VQ codebook search.
 // All of these are HBM-bound elementwise / small-reduction kernels.  The step and keep kernels come as a batch of clips [B, T] and as
 // ONE long row seen through overlapping windows; the forms share block_sum_256, step_noise_tail / _quad, quad_windows and store_quad.
+// The window steps also come PACKED: many such rows end to end, stepped by one launch through the same per-quad bodies.
 #include "kernels.hpp"
 #include "philox.hpp"
 #include "sampler_kernels.hpp"
@@ -110,17 +111,20 @@ __device__ __forceinline__ void store_quad(float* x, float* win, int p, const Qu
 // sum over time of x0 = (x_t - sqrt(1-a_t) eps) rsqrt(a_t), per (clip, chunk); fp64 partials.  Row b of eps is [T] contiguous; row b of
 // x_t starts at b * x_stride and its alpha is a_t[b * a_stride]: (T, 1) for a batch of clips, (hop, 0) for the overlapping windows
 // of one long signal (ddpm_step_windows_kernel), which are then summed exactly as a clip is.
+// (the body, one chunk of one row: shared with the packed form below, which finds its rows in a table)
+__device__ __forceinline__ void ddpm_x0sum_chunk(const float* x_row, const float* eps_row, float at, double* out, int T, int chunk) {
+  const float sq = sqrtf(1.0f - at), rs = 1.0f / sqrtf(at);
+  const int beg = chunk * SUM_CHUNK, end = min(T, beg + SUM_CHUNK);
+  double s = 0.0;
+  for (int t = beg + threadIdx.x; t < end; t += 256) {
+    s += (double)((x_row[t] - sq * eps_row[t]) * rs);
+  }
+  block_sum_256(s, out);
+}
 __global__ __launch_bounds__(256) void ddpm_x0sum_kernel(const float* x_t, const float* eps, const float* a_t, double* partial, int T, int nchunk,
                                                          int x_stride, int a_stride) {
   const int b = blockIdx.y;
-  const float at = a_t[b * a_stride];
-  const float sq = sqrtf(1.0f - at), rs = 1.0f / sqrtf(at);
-  const int beg = blockIdx.x * SUM_CHUNK, end = min(T, beg + SUM_CHUNK);
-  double s = 0.0;
-  for (int t = beg + threadIdx.x; t < end; t += 256) {
-    s += (double)((x_t[(size_t)b * x_stride + t] - sq * eps[(size_t)b * T + t]) * rs);
-  }
-  block_sum_256(s, partial + (size_t)b * nchunk + blockIdx.x);
+  ddpm_x0sum_chunk(x_t + (size_t)b * x_stride, eps + (size_t)b * T, a_t[b * a_stride], partial + (size_t)b * nchunk + blockIdx.x, T, blockIdx.x);
 }
 
 // mean of x0 over one clip / window: the chunk partials of ddpm_x0sum_kernel added in chunk order
@@ -179,15 +183,13 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const float* x_t, const 
 // cover a quad their predictions are cross-faded with w = (u + 1/2) / V.  The noise is one draw per absolute position -- row 0 of a
 // [1, Np] batch at `clip`, as ddpm_step_kernel draws it -- so the overlapping windows share it, and the result goes to x_prev [Np]
 // and to win [n, W] (store_quad).  partial: n * nchunk chunk sums of ddpm_x0sum_kernel.
-__global__ __launch_bounds__(256) void ddpm_step_windows_kernel(const float* x, const float* eps, const float* noise, const float* a_t,
-                                                                const float* a_prev, const double* partial, int nchunk, float* x_prev,
-                                                                float* win, int n, int W, int H, uint32_t flags, float noise_scale,
-                                                                uint64_t seed, uint64_t clip, uint32_t step_index) {
-  const int q = blockIdx.x * 256 + threadIdx.x;
-  const int Np = (n - 1) * H + W, V = W - H;
-  if (q >= Np / 4) return;
+// (the body: quad q < Np / 4 of ONE row, every pointer at that row's first sample / window / partial.  ddpm_step_windows_kernel runs it
+// on the only row there is, ddpm_step_packed_kernel on the row of a pack that PackRow finds.)
+__device__ __forceinline__ void ddpm_windows_quad(int q, const StepCoef& k, const float* x, const float* eps, const float* noise,
+                                                  const double* partial, int nchunk, float* x_prev, float* win, int n, int W, int H,
+                                                  uint32_t flags, float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index) {
+  const int V = W - H;
   const int p = q * 4;
-  const StepCoef k = step_coef(a_t[0], a_prev[0], flags & 1u);
   const bool constrain = flags & 2u;
   const QuadWindows g = quad_windows(p, n, W, H);
   const f32x4 xv = *reinterpret_cast<const f32x4*>(x + p);
@@ -211,6 +213,15 @@ __global__ __launch_bounds__(256) void ddpm_step_windows_kernel(const float* x, 
     for (int j = 0; j < 4; ++j) o[j] = step_sample<false>(k, constrain, xv[j], nv[j], er[j], mean_r);
   }
   store_quad(x_prev, win, p, g, [&](float* dst) { *reinterpret_cast<f32x4*>(dst) = o; });
+}
+__global__ __launch_bounds__(256) void ddpm_step_windows_kernel(const float* x, const float* eps, const float* noise, const float* a_t,
+                                                                const float* a_prev, const double* partial, int nchunk, float* x_prev,
+                                                                float* win, int n, int W, int H, uint32_t flags, float noise_scale,
+                                                                uint64_t seed, uint64_t clip, uint32_t step_index) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= ((n - 1) * H + W) / 4) return;
+  ddpm_windows_quad(q, step_coef(a_t[0], a_prev[0], flags & 1u), x, eps, noise, partial, nchunk, x_prev, win, n, W, H, flags, noise_scale,
+                    seed, clip, step_index);
 }
 
 // mean = eps_to_prev(eps)
@@ -279,18 +290,23 @@ __device__ __forceinline__ DdimCoef ddim_coef(float a_t, float a_to, float eta, 
 // ddpm_x0sum_kernel for the DDIM step: the clip's (window's) sum of x0 OF THE GUIDED PREDICTION, e = eps - sqrt(1 - a_t) grad (grad
 // NULL: e = eps).  Same rows, strides, chunks and partial layout; the summand is formed in fp64 from the fp32 inputs and the fp64
 // scalars, so the mean that x0_mean rounds to fp32 carries that one rounding.
+__device__ __forceinline__ void ddim_x0sum_chunk(const float* x_row, const float* eps_row, const float* grad_row, float at, double* out, int T,
+                                                 int chunk) {
+  const DdimX0Coef k = ddim_x0_coef(at);
+  const int beg = chunk * SUM_CHUNK, end = min(T, beg + SUM_CHUNK);
+  double s = 0.0;
+  for (int t = beg + threadIdx.x; t < end; t += 256) {
+    double e = (double)eps_row[t];
+    if (grad_row) e -= k.sq1mat * (double)grad_row[t];
+    s += ((double)x_row[t] - k.sq1mat * e) * k.rsat;
+  }
+  block_sum_256(s, out);
+}
 __global__ __launch_bounds__(256) void ddim_x0sum_kernel(const float* x_t, const float* eps, const float* grad, const float* a_t,
                                                          double* partial, int T, int nchunk, int x_stride, int a_stride) {
   const int b = blockIdx.y;
-  const DdimX0Coef k = ddim_x0_coef(a_t[b * a_stride]);
-  const int beg = blockIdx.x * SUM_CHUNK, end = min(T, beg + SUM_CHUNK);
-  double s = 0.0;
-  for (int t = beg + threadIdx.x; t < end; t += 256) {
-    double e = (double)eps[(size_t)b * T + t];
-    if (grad) e -= k.sq1mat * (double)grad[(size_t)b * T + t];
-    s += ((double)x_t[(size_t)b * x_stride + t] - k.sq1mat * e) * k.rsat;
-  }
-  block_sum_256(s, partial + (size_t)b * nchunk + blockIdx.x);
+  ddim_x0sum_chunk(x_t + (size_t)b * x_stride, eps + (size_t)b * T, grad ? grad + (size_t)b * T : nullptr, a_t[b * a_stride],
+                   partial + (size_t)b * nchunk + blockIdx.x, T, blockIdx.x);
 }
 
 // (x0, e') of one sample under one clip's / window's prediction e and gradient g (guided: e <- e - sqrt(1 - a_t) g)
@@ -353,15 +369,12 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const float* x_t, const 
 // ddpm_step_windows_kernel's per-window means, shared noise and outputs, for the DDIM step; grad [n, W] enters per window, before
 // the blend.
 template <bool GUIDED>
-__global__ __launch_bounds__(256) void ddim_step_windows_kernel(const float* x, const float* eps, const float* grad, const float* noise,
-                                                                const float* a_t, const float* a_to, const double* partial, int nchunk,
-                                                                float* x_to, float* win, int n, int W, int H, uint32_t flags, float eta,
-                                                                float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index) {
-  const int q = blockIdx.x * 256 + threadIdx.x;
-  const int Np = (n - 1) * H + W, V = W - H;
-  if (q >= Np / 4) return;
+__device__ __forceinline__ void ddim_windows_quad(int q, const DdimCoef& k, const float* x, const float* eps, const float* grad,
+                                                  const float* noise, const double* partial, int nchunk, float* x_to, float* win, int n,
+                                                  int W, int H, uint32_t flags, float noise_scale, uint64_t seed, uint64_t clip,
+                                                  uint32_t step_index) {
+  const int V = W - H;
   const int p = q * 4;
-  const DdimCoef k = ddim_coef(a_t[0], a_to[0], eta, flags & 4u);
   const bool constrain = flags & 2u;
   const QuadWindows g = quad_windows(p, n, W, H);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -390,6 +403,16 @@ __global__ __launch_bounds__(256) void ddim_step_windows_kernel(const float* x, 
     for (int j = 0; j < 4; ++j) o[j] = ddim_sample<false, GUIDED>(k, constrain, xv[j], nv[j], er[j], gr[j], mean_r);
   }
   store_quad(x_to, win, p, g, [&](float* dst) { *reinterpret_cast<f32x4*>(dst) = o; });
+}
+template <bool GUIDED>
+__global__ __launch_bounds__(256) void ddim_step_windows_kernel(const float* x, const float* eps, const float* grad, const float* noise,
+                                                                const float* a_t, const float* a_to, const double* partial, int nchunk,
+                                                                float* x_to, float* win, int n, int W, int H, uint32_t flags, float eta,
+                                                                float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= ((n - 1) * H + W) / 4) return;
+  ddim_windows_quad<GUIDED>(q, ddim_coef(a_t[0], a_to[0], eta, flags & 4u), x, eps, grad, noise, partial, nchunk, x_to, win, n, W, H, flags,
+                            noise_scale, seed, clip, step_index);
 }
 
 // ---------------------------------------------------------------------------------
@@ -503,19 +526,12 @@ __global__ __launch_bounds__(256) void dpmpp_step_kernel(const float* x_t, const
 // ddim_step_windows_kernel's geometry, per-window gradients and means and outputs, for the 2M step: the windows' x0 are blended, and
 // the history x0_prev / x0_out [Np] holds the BLENDED x0 per absolute position (x0_out may be x0_prev itself, as above).
 template <bool GUIDED>
-__global__ __launch_bounds__(256) void dpmpp_step_windows_kernel(const float* x, const float* eps, const float* grad, const float* x0_prev,
-                                                                 const float* a_from, const float* a_t, const float* a_to,
-                                                                 const double* partial, int nchunk, float* x_to, float* x0_out, float* win,
-                                                                 int n, int W, int H, uint32_t flags) {
+__device__ __forceinline__ void dpmpp_windows_quad(int q, const DpmppCoef& k, const float* x, const float* eps, const float* grad,
+                                                   const float* x0_prev, const double* partial, int nchunk, float* x_to, float* x0_out,
+                                                   float* win, int n, int W, int H, uint32_t flags) {
 #pragma clang fp contract(off)
-  __shared__ DpmppCoef ks;
-  if (threadIdx.x == 0) ks = dpmpp_coef(a_from, x0_prev != nullptr, a_t[0], a_to[0]);
-  __syncthreads();
-  const int q = blockIdx.x * 256 + threadIdx.x;
-  const int Np = (n - 1) * H + W, V = W - H;
-  if (q >= Np / 4) return;
+  const int V = W - H;
   const int p = q * 4;
-  const DpmppCoef k = ks;
   const bool constrain = flags & 2u;
   const QuadWindows g = quad_windows(p, n, W, H);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -546,7 +562,167 @@ __global__ __launch_bounds__(256) void dpmpp_step_windows_kernel(const float* x,
   store_quad(x_to, win, p, g, [&](float* dst) { *reinterpret_cast<f32x4*>(dst) = o; });
   if (x0_out) *reinterpret_cast<f32x4*>(x0_out + p) = x0;
 }
+template <bool GUIDED>
+__global__ __launch_bounds__(256) void dpmpp_step_windows_kernel(const float* x, const float* eps, const float* grad, const float* x0_prev,
+                                                                 const float* a_from, const float* a_t, const float* a_to,
+                                                                 const double* partial, int nchunk, float* x_to, float* x0_out, float* win,
+                                                                 int n, int W, int H, uint32_t flags) {
+  __shared__ DpmppCoef ks;
+  if (threadIdx.x == 0) ks = dpmpp_coef(a_from, x0_prev != nullptr, a_t[0], a_to[0]);
+  __syncthreads();
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= ((n - 1) * H + W) / 4) return;
+  const DpmppCoef k = ks;
+  dpmpp_windows_quad<GUIDED>(q, k, x, eps, grad, x0_prev, partial, nchunk, x_to, x0_out, win, n, W, H, flags);
+}
 
+// ---------------------------------------------------------------------------------
+// Packed window steps (include/vqvs.h "Packed window steps"): R recordings of n_r windows each, their long
+// rows laid end to end and their windows stacked in [N, W] arrays, stepped by ONE launch.  `first` [R + 1] holds the prefix sums of
+// the window counts: recording r owns windows first[r] .. first[r + 1] - 1 and starts at sample first[r] * H + r * V of the long
+// arrays (every row is n_r * H + V long).  A quad is handed, with every pointer moved to its recording's first sample / window /
+// partial, to the ..._windows_quad body the single-recording kernels run, at clip + r: the arithmetic IS that kernel's on that
+// recording alone, and the last window of one recording never meets the first of the next.
+//
+// N = first[R] lives on the device, so the host cannot size a grid by it: a fixed grid walks the quads in strides of one grid.  A
+// workgroup covers 1024 consecutive samples per stride; the recording of its FIRST sample is found by a binary search whose every
+// operand is uniform over the workgroup (scalar loads of a table that stays in the scalar cache), and a thread whose quad lies beyond that recording's end walks on from there -- at most a step or two, since a
+// recording holds W samples or more.  Table entries are clamped to 0..N and N to 1..65535, and a quad is stepped only where it lies
+// inside the row the table gives it, so a malformed table cannot send an access outside N * H + R * V samples or N windows.
+// ---------------------------------------------------------------------------------
+constexpr int PACK_GRID = 2048;  // 256 CUs x 8 workgroups of 256: every CU full, the rest of a long pack in further strides
+
+struct PackRow {
+  int r, fb, n, q;  // recording, its first window, its window count, the quad's index in the recording's own row
+  bool ok;          // the quad lies in that row: a quad that a malformed table puts nowhere is left alone
+  size_t off;       // the recording's first sample in the long arrays
+};
+struct PackTable {
+  const int* first;
+  int R, N, H, V;
+  __device__ __forceinline__ int at(int i) const { return i <= 0 ? 0 : i >= R ? N : min(max(first[i], 0), N); }
+  __device__ __forceinline__ int64_t off(int i, int f) const { return (int64_t)f * H + (int64_t)i * V; }
+  __device__ __forceinline__ int64_t total() const { return min(off(R, N), ((int64_t)1 << 31) - 4); }
+};
+__device__ __forceinline__ PackTable pack_table(const int* first, int R, int W, int H) {
+  return PackTable{first, R, min(max(first[R], 1), 65535), H, W - H};
+}
+// p0: a position at or before p that is uniform over the workgroup (its first thread's)
+__device__ __forceinline__ PackRow pack_row(const PackTable& t, int64_t p0, int64_t p) {
+  int lo = 0, hi = t.R;  // off(lo) <= p0 < off(hi)
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (t.off(mid, t.at(mid)) <= p0) lo = mid; else hi = mid;
+  }
+  int r = lo, f0 = t.at(r), f1 = t.at(r + 1);
+  while (r + 1 < t.R && t.off(r + 1, f1) <= p) {
+    ++r;
+    f0 = f1;
+    f1 = t.at(r + 1);
+  }
+  PackRow w;
+  w.r = r;
+  w.n = f1 - f0;
+  w.fb = f0;
+  w.off = (size_t)t.off(r, f0);
+  const int64_t u = p - t.off(r, f0);
+  w.ok = w.n >= 1 && u >= 0 && u < (int64_t)w.n * t.H + t.V;  // (always, unless the table is not one of prefix sums)
+  w.q = (int)(u / 4);
+  return w;
+}
+// window b's recording: the last r with first[r] <= b (b uniform over the workgroup: scalar loads again)
+__device__ __forceinline__ int pack_window_row(const PackTable& t, int b) {
+  int lo = 0, hi = t.R;  // at(lo) <= b < at(hi)
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (t.at(mid) <= b) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+__device__ __forceinline__ const float* pack_shift(const float* p, size_t by) { return p ? p + by : nullptr; }
+__device__ __forceinline__ float* pack_shift(float* p, size_t by) { return p ? p + by : nullptr; }
+
+// The x0 sums of every window of a pack, partial [N, nchunk]: window b starts at b * H + rec(b) * V of x.  One (window, chunk) per
+// workgroup and stride, summed by the body -- and so in the order -- of the single-recording launch.
+__global__ __launch_bounds__(256) void ddpm_x0sum_packed_kernel(const float* x, const float* eps, const float* a_t, double* partial,
+                                                                const int* first, int R, int W, int H, int nchunk) {
+  const PackTable t = pack_table(first, R, W, H);
+  for (int item = blockIdx.x; item < t.N * nchunk; item += gridDim.x) {
+    const int b = item / nchunk;
+    const size_t start = (size_t)t.off(pack_window_row(t, b), b);
+    ddpm_x0sum_chunk(x + start, eps + (size_t)b * W, a_t[0], partial + item, W, item - b * nchunk);
+  }
+}
+__global__ __launch_bounds__(256) void ddim_x0sum_packed_kernel(const float* x, const float* eps, const float* grad, const float* a_t,
+                                                                double* partial, const int* first, int R, int W, int H, int nchunk) {
+  const PackTable t = pack_table(first, R, W, H);
+  for (int item = blockIdx.x; item < t.N * nchunk; item += gridDim.x) {
+    const int b = item / nchunk;
+    const size_t start = (size_t)t.off(pack_window_row(t, b), b);
+    ddim_x0sum_chunk(x + start, eps + (size_t)b * W, pack_shift(grad, (size_t)b * W), a_t[0], partial + item, W, item - b * nchunk);
+  }
+}
+
+__global__ __launch_bounds__(256) void ddpm_step_packed_kernel(const float* x, const float* eps, const float* noise, const float* a_t,
+                                                               const float* a_prev, const double* partial, int nchunk, float* x_prev,
+                                                               float* win, const int* first, int R, int W, int H, uint32_t flags,
+                                                               float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index) {
+  const PackTable t = pack_table(first, R, W, H);
+  const StepCoef k = step_coef(a_t[0], a_prev[0], flags & 1u);
+  const int64_t total = t.total();
+  for (int64_t p0 = (int64_t)blockIdx.x * 1024; p0 < total; p0 += (int64_t)gridDim.x * 1024) {
+    const int64_t p = p0 + threadIdx.x * 4;
+    if (p >= total) continue;
+    const PackRow w = pack_row(t, p0, p);
+    if (!w.ok) continue;
+    const size_t wo = (size_t)w.fb * W;
+    ddpm_windows_quad(w.q, k, x + w.off, eps + wo, pack_shift(noise, w.off), partial + (size_t)w.fb * nchunk, nchunk, x_prev + w.off,
+                      pack_shift(win, wo), w.n, W, H, flags, noise_scale, seed, clip + w.r, step_index);
+  }
+}
+
+template <bool GUIDED>
+__global__ __launch_bounds__(256) void ddim_step_packed_kernel(const float* x, const float* eps, const float* grad, const float* noise,
+                                                               const float* a_t, const float* a_to, const double* partial, int nchunk,
+                                                               float* x_to, float* win, const int* first, int R, int W, int H,
+                                                               uint32_t flags, float eta, float noise_scale, uint64_t seed, uint64_t clip,
+                                                               uint32_t step_index) {
+  const PackTable t = pack_table(first, R, W, H);
+  const DdimCoef k = ddim_coef(a_t[0], a_to[0], eta, flags & 4u);
+  const int64_t total = t.total();
+  for (int64_t p0 = (int64_t)blockIdx.x * 1024; p0 < total; p0 += (int64_t)gridDim.x * 1024) {
+    const int64_t p = p0 + threadIdx.x * 4;
+    if (p >= total) continue;
+    const PackRow w = pack_row(t, p0, p);
+    if (!w.ok) continue;
+    const size_t wo = (size_t)w.fb * W;
+    ddim_windows_quad<GUIDED>(w.q, k, x + w.off, eps + wo, pack_shift(grad, wo), pack_shift(noise, w.off), partial + (size_t)w.fb * nchunk,
+                              nchunk, x_to + w.off, pack_shift(win, wo), w.n, W, H, flags, noise_scale, seed, clip + w.r, step_index);
+  }
+}
+
+template <bool GUIDED>
+__global__ __launch_bounds__(256) void dpmpp_step_packed_kernel(const float* x, const float* eps, const float* grad, const float* x0_prev,
+                                                                const float* a_from, const float* a_t, const float* a_to,
+                                                                const double* partial, int nchunk, float* x_to, float* x0_out, float* win,
+                                                                const int* first, int R, int W, int H, uint32_t flags) {
+  __shared__ DpmppCoef ks;
+  if (threadIdx.x == 0) ks = dpmpp_coef(a_from, x0_prev != nullptr, a_t[0], a_to[0]);
+  __syncthreads();
+  const DpmppCoef k = ks;
+  const PackTable t = pack_table(first, R, W, H);
+  const int64_t total = t.total();
+  for (int64_t p0 = (int64_t)blockIdx.x * 1024; p0 < total; p0 += (int64_t)gridDim.x * 1024) {
+    const int64_t p = p0 + threadIdx.x * 4;
+    if (p >= total) continue;
+    const PackRow w = pack_row(t, p0, p);
+    if (!w.ok) continue;
+    const size_t wo = (size_t)w.fb * W;
+    dpmpp_windows_quad<GUIDED>(w.q, k, x + w.off, eps + wo, pack_shift(grad, wo), pack_shift(x0_prev, w.off),
+                               partial + (size_t)w.fb * nchunk, nchunk, x_to + w.off, pack_shift(x0_out, w.off), pack_shift(win, wo), w.n, W,
+                               H, flags);
+  }
+}
 // ---------------------------------------------------------------------------------
 // Keep region (the "replacement" method of Song et al. 2021; the reference has none), include/vqvs.h "Keep region".  Kept samples of a
 // state are put back on the forward process of a source at alpha_bar = alpha:
@@ -963,6 +1139,54 @@ int run_dpmpp_step_windows(const float* x, const float* eps, const float* grad, 
   auto kernel = grad ? dpmpp_step_windows_kernel<true> : dpmpp_step_windows_kernel<false>;
   hipLaunchKernelGGL(kernel, dim3((quads + 255) / 256), dim3(256), 0, st, x, eps, grad, x0_prev, a_from, a_t, a_to, scratch, nchunk, x_to,
                      x0_out, windows, n, W, H, flags);
+  VQVS_HIP(hipGetLastError());
+  return 0;
+}
+
+// The partials of a packed CONSTRAIN step: N * nchunk doubles, N on the device.  The host leases the most a pack of this geometry can
+// need: N <= 65535 and N * H + R * V < 2^31.
+size_t packed_scratch_doubles(int W, int H) {
+  const int64_t most = std::min<int64_t>(65535, (((int64_t)1 << 31) - 1) / H);
+  return (size_t)most * ((W + SUM_CHUNK - 1) / SUM_CHUNK);
+}
+
+int run_ddpm_step_packed(const float* x, const float* eps, const float* noise, const float* a_t, const float* a_prev, float* x_prev,
+                         float* windows, double* scratch, const int* first, int R, int W, int H, uint32_t flags, float noise_scale,
+                         uint64_t seed, uint64_t clip, uint32_t step_index, hipStream_t st) {
+  const int nchunk = (W + SUM_CHUNK - 1) / SUM_CHUNK;
+  if (flags & 2u) {
+    hipLaunchKernelGGL(ddpm_x0sum_packed_kernel, dim3(PACK_GRID), dim3(256), 0, st, x, eps, a_t, scratch, first, R, W, H, nchunk);
+  }
+  hipLaunchKernelGGL(ddpm_step_packed_kernel, dim3(PACK_GRID), dim3(256), 0, st, x, eps, noise, a_t, a_prev, scratch, nchunk, x_prev, windows,
+                     first, R, W, H, flags, noise_scale, seed, clip, step_index);
+  VQVS_HIP(hipGetLastError());
+  return 0;
+}
+
+int run_ddim_step_packed(const float* x, const float* eps, const float* grad, const float* noise, const float* a_t, const float* a_to,
+                         float* x_to, float* windows, double* scratch, const int* first, int R, int W, int H, uint32_t flags, float eta,
+                         float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index, hipStream_t st) {
+  const int nchunk = (W + SUM_CHUNK - 1) / SUM_CHUNK;
+  if (flags & 2u) {
+    hipLaunchKernelGGL(ddim_x0sum_packed_kernel, dim3(PACK_GRID), dim3(256), 0, st, x, eps, grad, a_t, scratch, first, R, W, H, nchunk);
+  }
+  auto kernel = grad ? ddim_step_packed_kernel<true> : ddim_step_packed_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(PACK_GRID), dim3(256), 0, st, x, eps, grad, noise, a_t, a_to, scratch, nchunk, x_to, windows, first, R, W, H,
+                     flags, eta, noise_scale, seed, clip, step_index);
+  VQVS_HIP(hipGetLastError());
+  return 0;
+}
+
+int run_dpmpp_step_packed(const float* x, const float* eps, const float* grad, const float* x0_prev, const float* a_from, const float* a_t,
+                          const float* a_to, float* x_to, float* x0_out, float* windows, double* scratch, const int* first, int R, int W,
+                          int H, uint32_t flags, hipStream_t st) {
+  const int nchunk = (W + SUM_CHUNK - 1) / SUM_CHUNK;
+  if (flags & 2u) {
+    hipLaunchKernelGGL(ddim_x0sum_packed_kernel, dim3(PACK_GRID), dim3(256), 0, st, x, eps, grad, a_t, scratch, first, R, W, H, nchunk);
+  }
+  auto kernel = grad ? dpmpp_step_packed_kernel<true> : dpmpp_step_packed_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(PACK_GRID), dim3(256), 0, st, x, eps, grad, x0_prev, a_from, a_t, a_to, scratch, nchunk, x_to, x0_out,
+                     windows, first, R, W, H, flags);
   VQVS_HIP(hipGetLastError());
   return 0;
 }

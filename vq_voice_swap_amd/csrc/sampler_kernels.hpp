@@ -26,6 +26,19 @@ int run_dpmpp_step(const float* x_t, const float* eps, const float* grad, const 
 int run_dpmpp_step_windows(const float* x, const float* eps, const float* grad, const float* x0_prev, const float* a_from, const float* a_t,
                            const float* a_to, float* x_to, float* x0_out, float* windows, double* scratch, int n, int W, int H, uint32_t flags,
                            hipStream_t st);
+// The three window steps on a PACK of R recordings in one launch: first [R + 1] (device) holds the prefix sums of the recordings' window
+// counts, the long arrays hold the rows end to end, the window arrays the windows stacked; recording r is stepped as clip + r.
+// scratch: packed_scratch_doubles(W, H) doubles when flags has CONSTRAIN -- the window total is on the device, so this is its bound.
+size_t packed_scratch_doubles(int W, int H);
+int run_ddpm_step_packed(const float* x, const float* eps, const float* noise, const float* a_t, const float* a_prev, float* x_prev,
+                         float* windows, double* scratch, const int* first, int R, int W, int H, uint32_t flags, float noise_scale,
+                         uint64_t seed, uint64_t clip, uint32_t step_index, hipStream_t st);
+int run_ddim_step_packed(const float* x, const float* eps, const float* grad, const float* noise, const float* a_t, const float* a_to,
+                         float* x_to, float* windows, double* scratch, const int* first, int R, int W, int H, uint32_t flags, float eta,
+                         float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index, hipStream_t st);
+int run_dpmpp_step_packed(const float* x, const float* eps, const float* grad, const float* x0_prev, const float* a_from, const float* a_t,
+                          const float* a_to, float* x_to, float* x0_out, float* windows, double* scratch, const int* first, int R, int W,
+                          int H, uint32_t flags, hipStream_t st);
 // kept samples of x (NULL keep: all) put back on the forward process of x0 at alpha, in place: B rows of T, and one long state with
 // its window copies
 int run_keep_region(float* x, const float* x0, const uint8_t* keep, const float* noise, const float* alpha, int B, int T, float noise_scale,

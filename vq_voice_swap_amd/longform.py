@@ -11,11 +11,16 @@ step and the step has the variance a single clip's has.
 `Diffusion.ddpm_sample_windows`, `VQVAE.encode_long` and `VQVAE.decode_long` are the functions below; `Diffusion.ddim_sample_windows`
 is the same walk with the DDIM step `vqvs_ddim_step_windows`, `Diffusion.dpmpp_sample_windows` with the
 DPM-Solver++(2M) step `vqvs_dpmpp_step_windows` (section 3.12).
+
+A corpus is converted in PACKS (section 3.17): with `counts=` the three loops run several recordings' rows laid end to end, their
+windows in one batch that fills the forwards, and the step is the `..._packed` entry point, which keeps the recordings apart.
+`VQVAE.encode_long_batch` / `decode_long_batch` are below as well; recording r of a pack is, bit for bit, what `decode_long` returns
+for it alone at clip_offset + r.
 """
 
 from __future__ import annotations
 
-from typing import Callable, Optional, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -40,6 +45,34 @@ def plan_windows(num_samples: int, window: int, hop: int) -> Tuple[int, int]:
     if n > MAX_WINDOWS or padded_len >= 2 ** 31:
         raise ValueError(f"{num_samples} samples need {n} windows spanning {padded_len} samples: more than {MAX_WINDOWS} windows or 2^31 samples")
     return n, padded_len
+
+
+def pack_layout(counts: Sequence[int], window: int, hop: int) -> Tuple[List[int], List[int], int]:
+    """(first, offsets, total) of a pack of recordings of `counts` windows each, their long rows laid end to end (include/vqvs.h,
+    "Packed window steps"): first [R + 1] the prefix sums of the counts, offsets[r] = first[r] * hop + r * (window - hop) the first
+    sample of recording r, total = N * hop + R * (window - hop).  Refused: no recording, a count below 1, more than MAX_WINDOWS
+    windows or recordings, 2^31 samples or more."""
+    counts = [int(c) for c in counts]
+    plan_windows(1, window, hop)  # (the rules on window and hop)
+    if not counts or min(counts) < 1:
+        raise ValueError(f"counts={counts} must hold at least one recording, each of at least 1 window")
+    first = [0]
+    for c in counts:
+        first.append(first[-1] + c)
+    overlap = int(window) - int(hop)
+    offsets = [first[r] * int(hop) + r * overlap for r in range(len(counts))]
+    total = first[-1] * int(hop) + len(counts) * overlap
+    if first[-1] > MAX_WINDOWS or total >= 2 ** 31:
+        raise ValueError(f"a pack of {len(counts)} recordings holds {first[-1]} windows and {total} samples: more than {MAX_WINDOWS} windows or 2^31 samples")
+    return first, offsets, total
+
+
+def plan_pack(num_samples_list: Sequence[int], window: int, hop: int) -> Tuple[List[int], List[int], int]:
+    """(counts, offsets, total) of the pack of recordings of `num_samples_list` samples: each recording's `plan_windows` count, the
+    first sample of its padded row in the concatenation, and the concatenation's length (`pack_layout`)."""
+    counts = [plan_windows(n, window, hop)[0] for n in num_samples_list]
+    _, offsets, total = pack_layout(counts, window, hop)
+    return counts, offsets, total
 
 
 def gather_windows(x: torch.Tensor, window: int, hop: int) -> torch.Tensor:
@@ -114,24 +147,33 @@ def _ddim_fill(rule, xw, e, tables, i, b0, cond_fn, eps, grad, st) -> None:
         grad[b0:b0 + m].copy_(g.detach())
 
 
+def _entry(name: str, geom):
+    """The C entry point of a window step and its geometry arguments: `geom` is the window count n of one recording, or the `_Pack`
+    of several -- the packed form takes (d_first, R) where the single one takes n."""
+    if isinstance(geom, int):
+        return getattr(_native.lib(), name), (geom,)
+    return getattr(_native.lib(), name + "_packed"), (geom.first.data_ptr(), geom.R)
+
+
 def _ddpm_step_windows(rule, x, eps, grad, nz, a_t, a_to, x_to, next_windows, n, window, hop, noise_scale, seed, clip_offset, step_index, st) -> None:
-    _native.check(_native.lib().vqvs_ddpm_step_windows(x.data_ptr(), eps.data_ptr(), _native._ptr(nz), a_t.data_ptr(), a_to.data_ptr(),
-                                                       x_to.data_ptr(), next_windows.data_ptr(), n, window, hop, rule.flags, noise_scale,
-                                                       int(seed), int(clip_offset), step_index, st))
+    fn, geom = _entry("vqvs_ddpm_step_windows", n)
+    _native.check(fn(x.data_ptr(), eps.data_ptr(), _native._ptr(nz), a_t.data_ptr(), a_to.data_ptr(), x_to.data_ptr(), next_windows.data_ptr(),
+                     *geom, window, hop, rule.flags, noise_scale, int(seed), int(clip_offset), step_index, st))
 
 
 def _ddim_step_windows(rule, x, eps, grad, nz, a_t, a_to, x_to, next_windows, n, window, hop, noise_scale, seed, clip_offset, step_index, st) -> None:
-    _native.check(_native.lib().vqvs_ddim_step_windows(x.data_ptr(), eps.data_ptr(), _native._ptr(grad), _native._ptr(nz), a_t.data_ptr(),
-                                                       a_to.data_ptr(), x_to.data_ptr(), next_windows.data_ptr(), n, window, hop,
-                                                       rule.flags, float(rule.eta), noise_scale, int(seed), int(clip_offset), step_index, st))
+    fn, geom = _entry("vqvs_ddim_step_windows", n)
+    _native.check(fn(x.data_ptr(), eps.data_ptr(), _native._ptr(grad), _native._ptr(nz), a_t.data_ptr(), a_to.data_ptr(), x_to.data_ptr(),
+                     next_windows.data_ptr(), *geom, window, hop, rule.flags, float(rule.eta), noise_scale, int(seed), int(clip_offset),
+                     step_index, st))
 
 
 def dpmpp_step_windows_(x, eps, grad, x0_prev, a_from, a_t, a_to, x_to, x0_out, next_windows, n, window, hop, flags, st) -> None:
     """`vqvs_dpmpp_step_windows` on the long state x [Np] and the window batches eps / grad [n,1,window]: x_to and x0_out [Np] and the
-    next forward's windows are written; x0_prev / a_from None: no history."""
-    _native.check(_native.lib().vqvs_dpmpp_step_windows(x.data_ptr(), eps.data_ptr(), _native._ptr(grad), _native._ptr(x0_prev), _native._ptr(a_from),
-                                                        a_t.data_ptr(), a_to.data_ptr(), x_to.data_ptr(), x0_out.data_ptr(),
-                                                        next_windows.data_ptr(), n, window, hop, flags, st))
+    next forward's windows are written; x0_prev / a_from None: no history.  (n a `_Pack`: the packed form, `_entry`.)"""
+    fn, geom = _entry("vqvs_dpmpp_step_windows", n)
+    _native.check(fn(x.data_ptr(), eps.data_ptr(), _native._ptr(grad), _native._ptr(x0_prev), _native._ptr(a_from), a_t.data_ptr(), a_to.data_ptr(),
+                     x_to.data_ptr(), x0_out.data_ptr(), next_windows.data_ptr(), *geom, window, hop, flags, st))
 
 
 def _dpmpp_step_windows(rule, x, eps, grad, nz, a_t, a_to, x_to, next_windows, n, window, hop, noise_scale, seed, clip_offset, step_index, st) -> None:
@@ -161,14 +203,18 @@ class _Windows:
             raise ValueError(f"x_T_long has {self.Np} samples: {self.n} windows of {self.window} every {self.hop} span {padded} (see plan_windows)")
         if self.window_batch < 1:
             raise ValueError(f"window_batch={self.window_batch} must be at least 1")
+        self.geom = self.n  # (what the step's entry point is told: `_entry`)
         self.mb = min(self.n, int(self.window_batch))
         return self.mb
 
     def start(self, x_T_long, source, keep, alpha, **kw):
-        x, self.windows = start_windows(x_T_long, source, keep, alpha, n=self.n, window=self.window, hop=self.hop, **kw)
+        x, self.windows = self.gather(x_T_long, source, keep, alpha, **kw)
         self.eps = torch.empty_like(self.windows)
         self.grad = torch.empty_like(self.windows) if self.cond_fn is not None and self.rule.name != "ddpm" else None
         return x
+
+    def gather(self, x_T_long, source, keep, alpha, **kw):
+        return start_windows(x_T_long, source, keep, alpha, n=self.n, window=self.window, hop=self.hop, **kw)
 
     def predict(self, x, tables, i) -> None:
         self.st = _native._stream_ptr()  # (of this step: the slices' kernels and the step kernel)
@@ -188,7 +234,7 @@ class _Windows:
             if nz.numel() != self.Np:
                 raise ValueError(f"noise of step {i} has {nz.numel()} values: expected [1, 1, {self.Np}]")
         x_to, next_windows = torch.empty_like(x), torch.empty_like(self.windows)
-        self.step_windows(self.rule, x, self.eps, self.grad, nz, tables[1][i], tables[2][i], x_to, next_windows, self.n, self.window, self.hop,
+        self.step_windows(self.rule, x, self.eps, self.grad, nz, tables[1][i], tables[2][i], x_to, next_windows, self.geom, self.window, self.hop,
                           noise_scale, seed, clip_offset, i, self.st)
         self.windows = next_windows
         return x_to
@@ -197,11 +243,51 @@ class _Windows:
         keep_windows_(x, self.windows, source, keep, alpha, n=self.n, window=self.window, hop=self.hop, **kw)
 
 
+class _Pack(_Windows):
+    """`_Windows` for a pack of recordings of `counts` windows each (`pack_layout`): the long rows end to end in one [total] state,
+    the windows of all of them in one [N,1,window] batch, so the predictor's slices run across recordings; the step is the packed
+    entry point (`_entry`), which keys recording r by clip_offset + r and blends nothing across recordings.  Only the geometry
+    differs: the table instead of n, and the gather that starts the run."""
+
+    def __init__(self, counts: Sequence[int], *args):
+        super().__init__(*args)
+        self.counts = counts
+
+    def rows(self, x_T_long) -> int:
+        if x_T_long.dim() != 3 or x_T_long.shape[0] != 1 or x_T_long.shape[1] != 1:
+            raise ValueError(f"x_T_long must be [1, 1, total], got {tuple(x_T_long.shape)}")
+        first, self.offsets, self.Np = pack_layout(self.counts, self.window, self.hop)
+        if x_T_long.shape[2] != self.Np:
+            raise ValueError(f"x_T_long has {x_T_long.shape[2]} samples: recordings of {list(self.counts)} windows of {self.window} every "
+                             f"{self.hop} are {self.Np} laid end to end (see plan_pack)")
+        if self.window_batch < 1:
+            raise ValueError(f"window_batch={self.window_batch} must be at least 1")
+        self.n, self.R, self.geom = first[-1], len(first) - 1, self
+        self.first = torch.tensor(first, dtype=torch.int32, device=x_T_long.device)
+        self.mb = min(self.n, int(self.window_batch))
+        return self.mb
+
+    def gather(self, x_T_long, source, keep, alpha, **kw):
+        x = x_T_long.detach().to(torch.float32).contiguous()
+        rows = [x[..., o:o + (c - 1) * self.hop + self.window] for o, c in zip(self.offsets, self.counts)]
+        return x, torch.cat([gather_windows(r, self.window, self.hop) for r in rows])
+
+
+def _layout(counts, source, keep, start_step, *args):
+    """`_Windows` for one recording; with `counts` the `_Pack` of several, for which `source`, `keep` and `start_step` are not built
+    (vqvs_keep_region_windows has no packed form)."""
+    if counts is None:
+        return _Windows(*args)
+    if source is not None or keep is not None or start_step:
+        raise ValueError("source, keep and start_step are not built for a pack of recordings (counts=): convert such a recording on its own")
+    return _Pack(counts, *args)
+
+
 def ddpm_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, steps: int, *, window: int, hop: int,
                         window_batch: int = 64, constrain: bool = False, sigma_large: bool = False, cond_fn: Optional[Callable] = None,
                         schedule: Optional[Callable] = None, noise=None, seed: Optional[int] = None, clip_offset: int = 0,
                         progress: bool = False, source: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
-                        start_step: int = 0) -> torch.Tensor:
+                        start_step: int = 0, counts: Optional[Sequence[int]] = None) -> torch.Tensor:
     """`Diffusion.ddpm_sample` for one long state x_T_long [1,1,Np], Np = (n - 1) * hop + window (`plan_windows`): the same
     host-side tables of t and alpha_bar(t), the same step numbering, zero noise on the last step.
 
@@ -211,10 +297,15 @@ def ddpm_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, 
     windows' predictions meet in `vqvs_ddpm_step_windows`.  `noise` is a list or callable giving [1,1,Np] per step; None draws in the
     kernel from (seed, clip_offset, step): the draws of row `clip_offset` of a batch of clips of length Np.
     `source`, `keep` ([1,1,Np]) and `start_step` are `ddpm_sample`'s, applied by `vqvs_keep_region_windows` to the long state and to
-    both window copies of an overlap sample."""
+    both window copies of an overlap sample.
+
+    `counts` makes the run a PACK of recordings of that many windows each: x_T_long (and `noise` per step) is their rows end to end,
+    [1,1,total] (`plan_pack`), recording r is keyed clip_offset + r, and the predictor's and cond_fn's slices run across recordings
+    (`first` indexes the pack's window batch).  Recording r's slice of the result is what the run of that recording alone returns at
+    clip_offset + r, bit for bit.  `source`, `keep` and `start_step` are not built for a pack and raise ValueError."""
     from .diffusion import _Ddpm
 
-    layout = _Windows(_Ddpm(sigma_large, constrain), predictor, cond_fn, window, hop, window_batch, _ddpm_fill, _ddpm_step_windows)
+    layout = _layout(counts, source, keep, start_step, _Ddpm(sigma_large, constrain), predictor, cond_fn, window, hop, window_batch, _ddpm_fill, _ddpm_step_windows)
     return diffusion._sample("ddpm_sample_windows", layout, x_T_long, steps, schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset,
                              progress=progress, source=source, keep=keep, start_step=start_step)
 
@@ -223,15 +314,15 @@ def ddim_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, 
                         window_batch: int = 64, eta: float = 0.0, constrain: bool = False, cond_fn: Optional[Callable] = None,
                         schedule: Optional[Callable] = None, noise=None, seed: Optional[int] = None, clip_offset: int = 0,
                         progress: bool = False, source: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
-                        start_step: int = 0) -> torch.Tensor:
+                        start_step: int = 0, counts: Optional[Sequence[int]] = None) -> torch.Tensor:
     """`Diffusion.ddim_sample` for one long state x_T_long [1,1,Np]: `ddpm_sample_windows` with `vqvs_ddim_step_windows` as the step.
     `predictor` and `noise` are as there.  `cond_fn(x [m,1,window], ts [m], first=b0)` is evaluated on each slice of windows AT the
     windows the predictor saw and at their t; its gradients fill a [n, window] batch that the step kernel applies per window, before
     the windows' predictions are blended -- one kernel after the forwards, no half-steps.  `source`, `keep` and `start_step` are as
-    there, the kept samples replaced at the alpha_bar stepped TO."""
+    there, the kept samples replaced at the alpha_bar stepped TO; `counts` (a pack of recordings) is as there."""
     from .diffusion import _Ddim
 
-    layout = _Windows(_Ddim(eta, constrain), predictor, cond_fn, window, hop, window_batch, _ddim_fill, _ddim_step_windows)
+    layout = _layout(counts, source, keep, start_step, _Ddim(eta, constrain), predictor, cond_fn, window, hop, window_batch, _ddim_fill, _ddim_step_windows)
     return diffusion._sample("ddim_sample_windows", layout, x_T_long, steps, schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset,
                              progress=progress, source=source, keep=keep, start_step=start_step)
 
@@ -240,14 +331,15 @@ def dpmpp_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable,
                          window_batch: int = 64, constrain: bool = False, cond_fn: Optional[Callable] = None,
                          schedule: Optional[Callable] = None, noise=None, seed: Optional[int] = None, clip_offset: int = 0,
                          progress: bool = False, source: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
-                         start_step: int = 0) -> torch.Tensor:
+                         start_step: int = 0, counts: Optional[Sequence[int]] = None) -> torch.Tensor:
     """`Diffusion.dpmpp_sample` for one long state x_T_long [1,1,Np]: `ddim_sample_windows` at eta = 0 with `vqvs_dpmpp_step_windows` as
     the step.  `predictor` and `cond_fn` are as there (the gradient is taken at the windows the predictor saw and applied per window,
     before the blend); the history is the BLENDED x0 of the long row, one value per absolute position, kept by the rule.  `noise` is
-    accepted and never asked for anything; `source`, `keep` and `start_step` are as there and leave the history alone."""
+    accepted and never asked for anything; `source`, `keep` and `start_step` are as there and leave the history alone; `counts` (a
+    pack of recordings) is as there, the history the pack's rows end to end."""
     from .diffusion import _Dpmpp
 
-    layout = _Windows(_Dpmpp(constrain), predictor, cond_fn, window, hop, window_batch, _ddim_fill, _dpmpp_step_windows)
+    layout = _layout(counts, source, keep, start_step, _Dpmpp(constrain), predictor, cond_fn, window, hop, window_batch, _ddim_fill, _dpmpp_step_windows)
     return diffusion._sample("dpmpp_sample_windows", layout, x_T_long, steps, schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset,
                              progress=progress, source=source, keep=keep, start_step=start_step)
 
@@ -265,10 +357,46 @@ def encode_long(model, wave: torch.Tensor, window: int, hop: int, window_batch: 
     return torch.cat([model.encode(windows[b0:b0 + mb]) for b0 in range(0, n, mb)])
 
 
+def encode_long_batch(model, waves: Sequence[torch.Tensor], window: int, hop: int, window_batch: int = 64) -> Tuple[torch.Tensor, List[int]]:
+    """`encode_long` for several recordings [1,1,N_r]: (codes [N, window / rate], counts), the windows of recording r -- zero-padded to
+    its own `plan_windows` length -- at rows sum(counts[:r]) ... of the codes.  Windows are encoded in slices of `window_batch` that run
+    across recordings (one at a time behind the version-2 front end, as there), so the codes are `encode_long`'s of each recording."""
+    if not len(waves):
+        raise ValueError("waves must hold at least one recording")
+    for w in waves:
+        if w.dim() != 3 or w.shape[0] != 1 or w.shape[1] != 1:
+            raise ValueError(f"every wave must be [1, 1, N], got {tuple(w.shape)}")
+    check_rate(model, window, hop)
+    counts, _, _ = plan_pack([w.shape[2] for w in waves], window, hop)
+    windows = torch.cat([gather_windows(torch.nn.functional.pad(w, (0, (c - 1) * hop + window - w.shape[2])), window, hop)
+                         for w, c in zip(waves, counts)])
+    mb = 1 if getattr(model.encoder, "version", 1) == 2 else max(1, int(window_batch))
+    return torch.cat([model.encode(windows[b0:b0 + mb]) for b0 in range(0, windows.shape[0], mb)]), counts
+
+
 def check_rate(model, window: int, hop: int) -> None:
     rate = model.downsample_rate
     if window % rate or hop % rate:
         raise ValueError(f"window={window} and hop={hop} must be multiples of the model's downsample rate {rate}")
+
+
+def _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale):
+    """(predictor, cond_fn) of a window batch: each slice of windows sees its own rows of the conditioning [n,C,T1], of `labels` [n]
+    (or None) and -- with `enc_pred` -- guidance towards its own codes (VQVAE.decode)."""
+    cond_fn = None
+    if enc_pred is not None:
+        targets = model.vq.encode(cond_seq)
+
+        def cond_fn(x, ts, first):
+            return enc_pred.guidance_grad(x, ts, targets[first:first + x.shape[0]], enc_pred_scale)
+
+        cond_fn.native_modules = (enc_pred,)
+
+    def predictor(xs, ts, first):
+        sl = slice(first, first + xs.shape[0])
+        return model.predictor(xs, ts, cond=cond_seq[sl], labels=None if labels is None else labels[sl])
+
+    return predictor, cond_fn
 
 
 def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, *, num_samples: int, window: int, hop: int,
@@ -299,21 +427,9 @@ def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = Non
         if labels.shape != (n,):
             raise ValueError(f"labels must hold one label or one per window ({n}), got {labels.numel()}")
         labels = labels.contiguous()
-    cond_fn = None
-    if enc_pred is not None:  # guidance towards each window's own codes (VQVAE.decode)
-        targets = model.vq.encode(cond_seq)
-
-        def cond_fn(x, ts, first):
-            return enc_pred.guidance_grad(x, ts, targets[first:first + x.shape[0]], enc_pred_scale)
-
-        cond_fn.native_modules = (enc_pred,)
+    predictor, cond_fn = _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale)
     if seed is None:
         seed = fresh_seed()
-
-    def predictor(xs, ts, first):
-        sl = slice(first, first + xs.shape[0])
-        return model.predictor(xs, ts, cond=cond_seq[sl], labels=None if labels is None else labels[sl])
-
     if source is not None:
         source, keep = pad_source_keep(source, keep, num_samples, padded)
         kwargs.update(source=source, keep=keep, start_step=start_step)
@@ -323,3 +439,47 @@ def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = Non
                  clip_offset=clip_offset, progress=progress, **sampler_kw, **kwargs)
     model.predictor.check_status()  # range guard of the decoder's mode (once per sample)
     return out[..., :num_samples]
+
+
+def decode_long_batch(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, *, counts: Sequence[int], num_samples: Sequence[int],
+                      window: int, hop: int, steps: int = 100, progress: bool = False, constrain: bool = False, enc_pred=None,
+                      enc_pred_scale: float = 1.0, seed: Optional[int] = None, clip_offset: int = 0, window_batch: int = 64,
+                      sampler: str = "ddpm", eta: float = 0.0) -> List[torch.Tensor]:
+    """`decode_long` for a pack of recordings (`encode_long_batch`): codes [N,T1] or [N,C,T1] of all their windows, `counts` windows and
+    `num_samples` samples per recording -> one [1,1,num_samples[r]] waveform each.  The windows of all recordings fill the forwards
+    together (`window_batch` at a time) and one packed step kernel follows, so many short recordings cost what one long one does.
+    `labels` is one label, one per recording, or one per window.  x_T is each recording's own row keyed clip_offset + r, and recording
+    r's result is what `decode_long` returns for it alone at clip_offset + r, bit for bit, whatever else is in the pack and whatever
+    `window_batch` is.  `source`, `keep` and `strength` are not built for a pack."""
+    from .diffusion import fresh_seed, pick_sampler, randn_clips
+
+    cond_seq = model.cond_sequence(codes)
+    check_rate(model, window, hop)
+    counts, num_samples = [int(c) for c in counts], [int(n) for n in num_samples]
+    planned, offsets, total = plan_pack(num_samples, window, hop)
+    if planned != counts:
+        raise ValueError(f"recordings of {num_samples} samples in windows of {window} every {hop} are {planned} windows, not counts={counts}")
+    N, R = sum(counts), len(counts)
+    if cond_seq.shape[0] != N:
+        raise ValueError(f"counts={counts} are {N} windows; codes hold {cond_seq.shape[0]}")
+    if codes.shape[-1] * model.encoder.downsample_rate != window:
+        raise ValueError(f"codes of length {codes.shape[-1]} describe {codes.shape[-1] * model.encoder.downsample_rate} samples, not window={window}")
+    if labels is not None:
+        labels = labels.reshape(-1)
+        if labels.numel() == 1:
+            labels = labels.expand(N)
+        elif labels.numel() == R:
+            labels = labels.repeat_interleave(torch.tensor(counts, device=labels.device))
+        if labels.shape != (N,):
+            raise ValueError(f"labels must hold one label, one per recording ({R}) or one per window ({N}), got {labels.numel()}")
+        labels = labels.contiguous()
+    predictor, cond_fn = _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale)
+    if seed is None:
+        seed = fresh_seed()
+    padded = [(c - 1) * hop + window for c in counts]
+    x_T = torch.cat([randn_clips(1, padded[r], codes.device, seed, clip_offset + r) for r in range(R)], dim=-1)
+    sample, sampler_kw = pick_sampler(model.diffusion, sampler, eta, windows=True)
+    out = sample(x_T, predictor, steps, window=window, hop=hop, window_batch=window_batch, constrain=constrain, cond_fn=cond_fn, seed=seed,
+                 clip_offset=clip_offset, progress=progress, counts=counts, **sampler_kw)
+    model.predictor.check_status()  # range guard of the decoder's mode (once per sample)
+    return [out[..., o:o + n].clone() for o, n in zip(offsets, num_samples)]

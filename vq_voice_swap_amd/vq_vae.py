@@ -172,6 +172,21 @@ class VQVAE(DiffusionModel):
 
         return decode_long(self, codes, labels, **kwargs)
 
+    def encode_long_batch(self, waves, window: int, hop: int, window_batch: int = 64):
+        """Several recordings [1,1,N_r] -> (codes [N, window / rate] of all their windows, counts per recording)
+        (longform.encode_long_batch)."""
+        from .longform import encode_long_batch
+
+        return encode_long_batch(self, waves, window, hop, window_batch)
+
+    def decode_long_batch(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, **kwargs):
+        """The codes of a pack of recordings -> one [1,1,num_samples[r]] waveform each, the windows of all of them packed into the
+        same forwards (longform.decode_long_batch; keywords counts, num_samples, window, hop, steps, sampler, eta, constrain, enc_pred,
+        enc_pred_scale, seed, clip_offset, window_batch, progress)."""
+        from .longform import decode_long_batch
+
+        return decode_long_batch(self, codes, labels, **kwargs)
+
     def decode_uncond_guidance(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, steps: int = 100,
                                progress: bool = False, constrain: bool = False, label_scale: float = 0.0, vq_scale: float = 0.0,
                                x_T: Optional[torch.Tensor] = None, sampler: str = "ddpm", eta: float = 0.0, **kwargs) -> torch.Tensor:
