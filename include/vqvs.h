@@ -584,6 +584,49 @@ int vqvs_spectral_distance(const float* d_a, const float* d_b, const float* d_wi
                            const float* d_fb, const float* d_dct, double* d_mcd, double* d_lsd,
                            int B, int T, int n_fft, int hop, int n_mels, int n_ceps, float eps, void* stream);
 
+/* ---- mel cepstra per frame (handle-less) --------------------------------------------------
+ * The per-frame values that vqvs_spectral_distance forms and throws away, written to memory for recordings of different lengths
+ * in one batch (spectral_kernels.hip).  The arithmetic is that of "conversion-quality scores" above bit for bit, rounding points
+ * included: both kernels call one copy of the front end (window, DFT, power, mel, log, DCT).
+ *   d_x       [B,T] f32; row b holds len_b samples, what lies at or beyond len_b is never read (zeros, garbage or NaN alike)
+ *   d_len     [B] int32: device data, clamped into n_fft/2+1 .. T before use, so that no value can index outside an array
+ *   d_window, d_twiddle, d_fb, d_dct: the constant tables of vqvs_spectral_distance
+ *   d_ceps    [B, Fmax, n_ceps] f32 out, Fmax = T / hop + 1;  d_logmel [B, Fmax, n_mels] f32 out or NULL
+ *   d_frames  [B] int32 out: F_b = len_b / hop + 1 (of the clamped length)
+ * Row b has F_b frames, centred and reflect-padded about ITS OWN ends 0 and len_b; frames f >= F_b are written as 0.  One writer
+ * per output and no atomics: a row's values are bitwise the same whatever B, its row index, T and the padding are, and equal those
+ * of the row alone at T = len_b.
+ * Limits: those of vqvs_spectral_distance (B, n_fft, T, hop, n_mels, n_ceps, eps); an output may not overlap an input or another
+ * output.  Asynchronous on `stream`; a NULL required pointer (everything but d_logmel) or anything outside the limits returns
+ * VQVS_ERR_ARG with a message before the device is touched. */
+int vqvs_mel_cepstra(const float* d_x, const int* d_len, const float* d_window, const double* d_twiddle, const float* d_fb,
+                     const float* d_dct, float* d_ceps, float* d_logmel, int* d_frames,
+                     int B, int T, int n_fft, int hop, int n_mels, int n_ceps, float eps, void* stream);
+
+/* ---- alignment: dynamic time warping under the mel-cepstral cost (handle-less) -------------
+ * For B pairs of cepstral sequences, the cheapest monotone warping path and what it carries (dtw_kernels.hip; DESIGN.md section
+ * 3.18).  With Fa, Fb the pair's frame counts:
+ *   local cost, f64 from the f32 cepstra, c in index order, single operations without contraction:
+ *     d(i,j) = (10 / ln 10) sqrt(2 sum_{c=1}^{n_ceps-1} (ca[i,c] - cb[j,c])^2)              (coefficient 0 is left out)
+ *   D(0,0) = d(0,0);  D(i,j) = d(i,j) + min(D(i-1,j-1), D(i-1,j), D(i,j-1)) over the predecessors that exist; of equal ones the
+ *   first in that order (diagonal, then i-1, then j-1) is chosen.  The path runs from (0,0) to (Fa-1,Fb-1): no band, no slope
+ *   constraint.  Every cell carries what its chosen predecessor carried plus its own contribution: steps (cells on the path so
+ *   far), and with tracks both (cells where ta[i] and tb[j] are finite), vuv (cells where exactly one is), and sum l, sum l^2 over
+ *   the `both` cells, l = tb[j] - ta[i].  The path itself is not an output.
+ *   d_ca [B, Fa_max, n_ceps], d_cb [B, Fb_max, n_ceps] f32;  d_fa, d_fb [B] int32: device data, clamped into 1..F*_max
+ *   d_ta [B, Fa_max], d_tb [B, Fb_max] f64 or NULL (both or neither): per-frame tracks, NaN = no value in this frame
+ *   d_cost [B] f64 out: D(Fa-1, Fb-1);  d_steps [B] int32 out: the path's length
+ *   d_track_counts [B,2] int64 out: both, vuv;  d_track_sums [B,2] f64 out: sum l, sum l^2 -- required if and only if tracks are given
+ * One workgroup per pair walks the anti-diagonals i + j with one barrier per diagonal; the live diagonals sit in LDS (at most
+ * 128 KiB) and the thread of the last cell is the pair's only writer -- no scratch, no direction matrix, no atomics.  A pair's
+ * outputs are bitwise the same from run to run and whatever B, its row and F*_max are; cost(a,b) == cost(b,a).
+ * Limits: B in 1..65535; Fa_max, Fb_max in 1..2048; n_ceps in 2..64; an output may not overlap an input or another output.
+ * Asynchronous on `stream`; a NULL required pointer, exactly one track, exactly one track output, track outputs without tracks or
+ * tracks without track outputs, or a size outside the limits returns VQVS_ERR_ARG with a message before the device is touched. */
+int vqvs_dtw_distance(const float* d_ca, const float* d_cb, const int* d_fa, const int* d_fb, const double* d_ta, const double* d_tb,
+                      double* d_cost, int* d_steps, long long* d_track_counts, double* d_track_sums,
+                      int B, int Fa_max, int Fb_max, int n_ceps, void* stream);
+
 /* ---- pitch scores (handle-less) -----------------------------------------------------------
  * YIN periods of waveform batches a and b, frame for frame, and per clip the voicing counts and the sums of the pitch distance in
  * semitones, in one kernel (pitch_kernels.hip; no frame or difference function goes to memory).  Frames F = T / hop + 1.  The

@@ -13,6 +13,7 @@ from .conv_encoder import ConvMFCCEncoder
 from .dataset import create_data_loader
 from .diffusion import CosSchedule, Diffusion, ExpSchedule, Schedule, make_schedule, randn_clips
 from .diffusion_model import DiffusionModel
+from .dtw import AlignedDistance, dtw_distance
 from .encoder_predictor import EncoderPredictor
 from .enroll import ClassifierEnroller, SpeakerEnroller
 from .longform import plan_pack, plan_windows
@@ -30,4 +31,5 @@ __all__ = [
     "FeatureStats", "class_score", "frechet_distance", "wav_roundtrip", "LossTracker", "speaker_search_losses", "create_data_loader",
     "StandardVQLoss", "VQLoss", "code_usage", "classification_scores", "plan_windows", "plan_pack",
     "SpectralDistance", "spectral_constants", "PitchDistance", "SpeakerEnroller", "ClassifierEnroller",
+    "AlignedDistance", "dtw_distance",
 ]

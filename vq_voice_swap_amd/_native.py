@@ -76,6 +76,7 @@ EXPORTS = [
     "vqvs_debug_tap_info", "vqvs_debug_tap_rows", "vqvs_debug_read_tap", "vqvs_debug_read_embedding", "vqvs_forward_kernel_count", "vqvs_forward_model_bytes",
     "vqvs_forward_flops", "vqvs_set_profiling", "vqvs_op_info", "vqvs_op_desc", "vqvs_profile_read", "vqvs_last_error", "vqvs_version",
     "vqvs_unet_embed_grad", "vqvs_embed_adamw", "vqvs_debug_read_dfilm", "vqvs_head_xent_grad", "vqvs_head_adamw",
+    "vqvs_mel_cepstra", "vqvs_dtw_distance",
 ]
 
 _lib = None
@@ -168,6 +169,8 @@ def lib():
     L.vqvs_xent_score.argtypes = [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp]
     L.vqvs_spectral_distance.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp]
     L.vqvs_pitch_distance.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.c_double, vp]
+    L.vqvs_mel_cepstra.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp]
+    L.vqvs_dtw_distance.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     L.vqvs_debug_tap_count.argtypes = [vp]
     L.vqvs_debug_tap_info.argtypes = [vp, i32, C.c_char_p, i32, C.POINTER(i32), C.POINTER(i32)]
     L.vqvs_debug_tap_rows.argtypes = [vp, i32, i32]

@@ -761,6 +761,67 @@ int vqvs_spectral_distance(const float* d_a, const float* d_b, const float* d_wi
                                reinterpret_cast<hipStream_t>(stream));
 }
 
+int vqvs_mel_cepstra(const float* d_x, const int* d_len, const float* d_window, const double* d_twiddle, const float* d_fb, const float* d_dct,
+                     float* d_ceps, float* d_logmel, int* d_frames, int B, int T, int n_fft, int hop, int n_mels, int n_ceps, float eps,
+                     void* stream) {
+  if (!d_x || !d_len || !d_window || !d_twiddle || !d_fb || !d_dct) VQVS_FAIL(VQVS_ERR_ARG, "x, len, window, twiddle, fb and dct must be non-NULL");
+  if (!d_ceps || !d_frames) VQVS_FAIL(VQVS_ERR_ARG, "ceps and frames must be non-NULL");
+  if (B < 1 || B > 65535) VQVS_FAIL(VQVS_ERR_ARG, "batch %d outside 1..65535", B);
+  if (n_fft < 16 || n_fft > 512 || n_fft % 2) VQVS_FAIL(VQVS_ERR_ARG, "n_fft=%d must be even and in 16..512", n_fft);
+  if (T <= n_fft / 2) VQVS_FAIL(VQVS_ERR_ARG, "rows of %d samples are no longer than the reflect padding (%d)", T, n_fft / 2);
+  if (T > (1 << 30)) VQVS_FAIL(VQVS_ERR_ARG, "rows of %d samples: more than 2^30", T);
+  if (hop < 1 || hop > n_fft) VQVS_FAIL(VQVS_ERR_ARG, "hop=%d outside 1..n_fft=%d", hop, n_fft);
+  if (T / hop + 1 > (1 << 25)) VQVS_FAIL(VQVS_ERR_ARG, "T=%d at hop=%d is more than 2^25 frames per row", T, hop);
+  if (n_mels < 1 || n_mels > 128) VQVS_FAIL(VQVS_ERR_ARG, "n_mels=%d outside 1..128", n_mels);
+  if (n_ceps < 2 || n_ceps > (n_mels < 64 ? n_mels : 64)) VQVS_FAIL(VQVS_ERR_ARG, "n_ceps=%d outside 2..min(n_mels=%d, 64)", n_ceps, n_mels);
+  if (!std::isfinite(eps) || !(eps > 0.f)) VQVS_FAIL(VQVS_ERR_ARG, "eps=%g must be finite and positive", (double)eps);
+  const int64_t NF = (int64_t)B * (T / hop + 1);
+  const struct { const void* p; int64_t bytes; const char* name; } ins[] = {
+      {d_x, (int64_t)B * T * 4, "x"}, {d_len, (int64_t)B * 4, "len"}, {d_window, (int64_t)n_fft * 4, "window"},
+      {d_twiddle, (int64_t)n_fft * 16, "twiddle"}, {d_fb, (int64_t)(n_fft / 2 + 1) * n_mels * 4, "fb"}, {d_dct, (int64_t)n_mels * n_ceps * 4, "dct"}};
+  const struct { const void* p; int64_t bytes; const char* name; } outs[] = {
+      {d_ceps, NF * n_ceps * 4, "ceps"}, {d_logmel, NF * n_mels * 4, "logmel"}, {d_frames, (int64_t)B * 4, "frames"}};
+  for (const auto& out : outs) {
+    for (const auto& in : ins)
+      if (bytes_overlap(out.p, out.bytes, in.p, in.bytes)) VQVS_FAIL(VQVS_ERR_ARG, "%s must not overlap %s", out.name, in.name);
+    for (const auto& other : outs)
+      if (&other != &out && bytes_overlap(out.p, out.bytes, other.p, other.bytes))
+        VQVS_FAIL(VQVS_ERR_ARG, "%s must not overlap %s", out.name, other.name);
+  }
+  return run_mel_cepstra(d_x, d_len, d_window, d_twiddle, d_fb, d_dct, d_ceps, d_logmel, d_frames, B, T, n_fft, hop, n_mels, n_ceps, eps,
+                         reinterpret_cast<hipStream_t>(stream));
+}
+
+int vqvs_dtw_distance(const float* d_ca, const float* d_cb, const int* d_fa, const int* d_fb, const double* d_ta, const double* d_tb,
+                      double* d_cost, int* d_steps, long long* d_track_counts, double* d_track_sums, int B, int Fa_max, int Fb_max,
+                      int n_ceps, void* stream) {
+  if (!d_ca || !d_cb || !d_fa || !d_fb) VQVS_FAIL(VQVS_ERR_ARG, "ca, cb, fa and fb must be non-NULL");
+  if (!d_cost || !d_steps) VQVS_FAIL(VQVS_ERR_ARG, "cost and steps must be non-NULL");
+  if (!d_ta != !d_tb) VQVS_FAIL(VQVS_ERR_ARG, "the tracks ta and tb come together: both or neither");
+  if (!d_track_counts != !d_track_sums) VQVS_FAIL(VQVS_ERR_ARG, "track_counts and track_sums come together: both or neither");
+  if (!d_ta != !d_track_counts) VQVS_FAIL(VQVS_ERR_ARG, "track_counts and track_sums are required if and only if the tracks are given");
+  if (B < 1 || B > 65535) VQVS_FAIL(VQVS_ERR_ARG, "batch %d outside 1..65535", B);
+  if (Fa_max < 1 || Fa_max > 2048) VQVS_FAIL(VQVS_ERR_ARG, "Fa_max=%d outside 1..2048", Fa_max);
+  if (Fb_max < 1 || Fb_max > 2048) VQVS_FAIL(VQVS_ERR_ARG, "Fb_max=%d outside 1..2048", Fb_max);
+  if (n_ceps < 2 || n_ceps > 64) VQVS_FAIL(VQVS_ERR_ARG, "n_ceps=%d outside 2..64", n_ceps);
+  const int64_t NA = (int64_t)B * Fa_max, NB = (int64_t)B * Fb_max;
+  const struct { const void* p; int64_t bytes; const char* name; } ins[] = {
+      {d_ca, NA * n_ceps * 4, "ca"}, {d_cb, NB * n_ceps * 4, "cb"}, {d_fa, (int64_t)B * 4, "fa"}, {d_fb, (int64_t)B * 4, "fb"},
+      {d_ta, NA * 8, "ta"}, {d_tb, NB * 8, "tb"}};
+  const struct { const void* p; int64_t bytes; const char* name; } outs[] = {
+      {d_cost, (int64_t)B * 8, "cost"}, {d_steps, (int64_t)B * 4, "steps"}, {d_track_counts, (int64_t)B * 16, "track_counts"},
+      {d_track_sums, (int64_t)B * 16, "track_sums"}};
+  for (const auto& out : outs) {
+    for (const auto& in : ins)
+      if (bytes_overlap(out.p, out.bytes, in.p, in.bytes)) VQVS_FAIL(VQVS_ERR_ARG, "%s must not overlap %s", out.name, in.name);
+    for (const auto& other : outs)
+      if (&other != &out && bytes_overlap(out.p, out.bytes, other.p, other.bytes))
+        VQVS_FAIL(VQVS_ERR_ARG, "%s must not overlap %s", out.name, other.name);
+  }
+  return run_dtw_distance(d_ca, d_cb, d_fa, d_fb, d_ta, d_tb, d_cost, d_steps, d_track_counts, d_track_sums, B, Fa_max, Fb_max, n_ceps,
+                          reinterpret_cast<hipStream_t>(stream));
+}
+
 int vqvs_pitch_distance(const float* a, const float* b, double* period_a, double* period_b, long long* counts, double* sums, int B, int T,
                         int window, int hop, int tau_min, int tau_max, double threshold, void* stream) {
   if (!a) VQVS_FAIL(VQVS_ERR_ARG, "a must be non-NULL");

@@ -371,6 +371,18 @@ int run_spectral_distance(const float* a, const float* b, const float* window, c
                           void* scratch, double* mcd, double* lsd, int B, int T, int n_fft, int hop, int n_mels, int n_ceps, float eps,
                           hipStream_t st);
 
+// the per-frame cepstra (and log-mel values, unless nullptr) of the same front end, for rows of true lengths len[b] <= T
+int run_mel_cepstra(const float* x, const int* len, const float* window, const double* twiddle, const float* fb, const float* dct, float* ceps,
+                    float* logmel, int* frames, int B, int T, int n_fft, int hop, int n_mels, int n_ceps, float eps, hipStream_t st);
+
+// ----------------------------------------------------------------------------------
+// Alignment (dtw_kernels.hip): per pair of cepstral sequences the cost and length of the cheapest warping path and, with tracks
+// (ta and tb both, then counts and sums both), the counts and sums of the track difference along it.  No scratch: the live
+// anti-diagonals are in LDS.
+// ----------------------------------------------------------------------------------
+int run_dtw_distance(const float* ca, const float* cb, const int* fa, const int* fb, const double* ta, const double* tb, double* cost, int* steps,
+                     long long* counts, double* sums, int B, int fa_max, int fb_max, int n_ceps, hipStream_t st);
+
 // ----------------------------------------------------------------------------------
 // Pitch scores (pitch_kernels.hip): per-frame YIN periods of one or two waveform batches, per-clip voicing counts and sums of the
 // frame-wise pitch distance in semitones; scratch holds pitch_distance_scratch_bytes(B, T, hop) bytes of tile partials.  b may be

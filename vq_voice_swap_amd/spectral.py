@@ -2,7 +2,8 @@
 Objective scores of a finished conversion: per clip, the sum over frames of the mel-cepstral distortion (MCD, dB) and of the
 log-mel spectral distance (LSD, dB) between two waveforms, frame for frame, through `vqvs_spectral_distance` (one fused kernel,
 csrc/spectral_kernels.hip; definitions in include/vqvs.h and DESIGN.md section 3.13).  The conversion preserves timing, so the
-recordings are compared without alignment.
+recordings are compared without alignment.  `SpectralDistance.cepstra` (`vqvs_mel_cepstra`, the same front end) writes the per-frame
+cepstra of recordings of different lengths out, for the aligned comparison with a parallel recording (dtw.py, section 3.18).
 """
 
 from __future__ import annotations
@@ -91,3 +92,58 @@ class SpectralDistance:
                 a.data_ptr(), b.data_ptr(), c["window"].data_ptr(), c["twiddle"].data_ptr(), c["fb"].data_ptr(), c["dct"].data_ptr(),
                 mcd.data_ptr(), lsd.data_ptr(), B, T, self.n_fft, self.hop, self.n_mels, self.n_ceps, self.eps, _native._stream_ptr()))
         return {"mcd": mcd, "lsd": lsd, "frames": self.frames(T)}
+
+    def cepstra(self, x: torch.Tensor, lengths, logmel: bool = False) -> Dict[str, torch.Tensor]:
+        """The per-frame values behind the distances, through `vqvs_mel_cepstra`: `x` [B,1,T] or [B,T] float32 holds recordings of
+        `lengths[b]` samples (n_fft / 2 < length <= T; what lies beyond is never read) -> {"ceps": float32 [B, T // hop + 1, n_ceps],
+        "frames": int32 [B], the rows' own frame counts length // hop + 1} and with `logmel` also {"logmel": float32 [B, T // hop + 1,
+        n_mels]}.  Frames at or beyond a row's count are 0.  A row's values are those of the recording alone."""
+        if not torch.is_tensor(x):
+            raise ValueError("x must be a tensor")
+        if x.dim() == 3 and x.shape[1] == 1:
+            x = x[:, 0]
+        if x.dim() != 2:
+            raise ValueError(f"expected waveforms of shape [B, 1, T] or [B, T], got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise ValueError(f"x must be float32, got {x.dtype}")
+        B, T = int(x.shape[0]), int(x.shape[1])
+        if not (1 <= B <= 65535 and self.n_fft // 2 < T <= 2 ** 30):
+            raise ValueError(f"B={B}, T={T} outside the limits 1..65535, {self.n_fft // 2 + 1}..2^30")
+        lengths = check_lengths(lengths, B, self.n_fft // 2 + 1, T, "lengths")
+        _native.require_cuda(x)
+        x = x.detach().contiguous()
+        c = self.constants(x.device)
+        F = self.frames(T)
+        d_len = lengths.to(x.device)
+        ceps = torch.empty(B, F, self.n_ceps, device=x.device, dtype=torch.float32)
+        mel = torch.empty(B, F, self.n_mels, device=x.device, dtype=torch.float32) if logmel else None
+        frames = torch.empty(B, device=x.device, dtype=torch.int32)
+        with torch.cuda.device(x.device):
+            _native.check(_native.lib().vqvs_mel_cepstra(
+                x.data_ptr(), d_len.data_ptr(), c["window"].data_ptr(), c["twiddle"].data_ptr(), c["fb"].data_ptr(), c["dct"].data_ptr(),
+                ceps.data_ptr(), _native._ptr(mel), frames.data_ptr(), B, T, self.n_fft, self.hop, self.n_mels, self.n_ceps, self.eps,
+                _native._stream_ptr()))
+        out = {"ceps": ceps, "frames": frames}
+        if logmel:
+            out["logmel"] = mel
+        return out
+
+
+def check_lengths(lengths, B: int, lo: int, hi: int, what: str) -> torch.Tensor:
+    """`lengths` (a sequence of integers or an integer tensor) as a host int32 tensor [B] with every entry in lo..hi, or ValueError."""
+    if torch.is_tensor(lengths):
+        if lengths.dtype not in (torch.int32, torch.int64) or lengths.dim() != 1:
+            raise ValueError(f"{what} must be a one-dimensional int32 or int64 tensor, got {lengths.dtype} {tuple(lengths.shape)}")
+        values = lengths.detach().cpu().tolist()
+    else:
+        try:
+            values = list(lengths)
+        except TypeError:
+            raise ValueError(f"{what} must be a sequence of integers") from None
+        if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in values):
+            raise ValueError(f"{what} must be integers, got {values}")
+    if len(values) != B:
+        raise ValueError(f"{len(values)} {what} for {B} rows")
+    if any(not lo <= int(v) <= hi for v in values):
+        raise ValueError(f"{what} {values} outside {lo}..{hi}")
+    return torch.tensor([int(v) for v in values], dtype=torch.int32)
