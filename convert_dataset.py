@@ -16,6 +16,11 @@ ranks, and with `--whole-file` flags to match it is what `sample_vqvae.py --whol
 was interrupted resumes with `--skip-existing` and ends with the files an uninterrupted run would have written.
 `--label N` converts everything to speaker N; `--label-map FILE` (lines `top-level-directory<TAB>label`) picks the target by the
 file's top-level directory.  An unreadable or empty file is skipped with a warning and counted.
+
+`--guide-label-scale S` / `--guide-vq-scale S` (both off by default) decode with the classifier-free-style guidance of
+sample_vqvae_uncond.py (`VQVAE.decode_long_batch_uncond_guidance`).  With either set the checkpoint is taken to have the unconditional
+label at 0 (`enroll_speaker.py --uncond` makes one) and `--label` / `--label-map` are speaker numbers WITHOUT that offset; a file's
+output is then what `sample_vqvae_uncond.py --whole-file` writes for the file with id 0 under the same scales.
 """
 import argparse
 import os
@@ -30,7 +35,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from vq_voice_swap_amd import VQVAE, EncoderPredictor  # noqa: E402
 from vq_voice_swap_amd.audio import ChunkReader, ChunkWriter  # noqa: E402
-from vq_voice_swap_amd.corpus import deal_packs, list_files, make_packs, read_label_map, top_directory  # noqa: E402
+from vq_voice_swap_amd.corpus import add_guidance_flags, deal_packs, guided, list_files, make_packs, read_label_map, top_directory  # noqa: E402
 from vq_voice_swap_amd.dataset import build_file_index  # noqa: E402
 from vq_voice_swap_amd.eval_pass import close_ranks, local_device, open_ranks  # noqa: E402
 from vq_voice_swap_amd.longform import plan_windows  # noqa: E402
@@ -66,6 +71,7 @@ def arg_parser():
 
 def parse_args(argv=None):
     parser = arg_parser()
+    add_guidance_flags(parser)  # (they join here: `arg_parser()` stays the flag set of the unguided run, which they leave as it was)
     args = parser.parse_args(argv)
     if args.sampler != "ddim" and args.eta:
         parser.error("--eta belongs to --sampler ddim (ddpm has its own variance, dpmpp is deterministic)")
@@ -127,9 +133,12 @@ def convert_pack(args, model, enc_pred, device, files, labels, pack, window: int
         batch = [torch.from_numpy(waves[i][None, None]).to(device) for i in run]
         codes, run_counts = model.encode_long_batch(batch, window, hop, args.window_batch)
         target = torch.tensor([labels[i] for i in run]).long().to(device)
-        outs = model.decode_long_batch(codes, target, counts=run_counts, num_samples=[b.shape[-1] for b in batch], window=window, hop=hop,
-                                       steps=args.sample_steps, constrain=True, seed=args.seed, clip_offset=run[0], enc_pred=enc_pred,
-                                       enc_pred_scale=args.enc_pred_scale, window_batch=args.window_batch, sampler=args.sampler, eta=args.eta)
+        decode, guide_kw = model.decode_long_batch, {}
+        if guided(args):  # (labels are not offset here: the guided decode shifts them past the unconditional label itself)
+            decode, guide_kw = model.decode_long_batch_uncond_guidance, dict(label_scale=args.guide_label_scale, vq_scale=args.guide_vq_scale)
+        outs = decode(codes, target, counts=run_counts, num_samples=[b.shape[-1] for b in batch], window=window, hop=hop,
+                      steps=args.sample_steps, constrain=True, seed=args.seed, clip_offset=run[0], enc_pred=enc_pred,
+                      enc_pred_scale=args.enc_pred_scale, window_batch=args.window_batch, sampler=args.sampler, eta=args.eta, **guide_kw)
         for i, out in zip(run, outs):
             path = out_path(args.out_dir, files[i][0])
             os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
@@ -160,9 +169,10 @@ def main(argv=None):
     if rank == 0:
         print(f"{len(files)} files, {sum(len(p) for p in packs)} to convert in {len(packs)} packs; loading model from checkpoint...")
     model = VQVAE.load(args.checkpoint_path)
-    bad = sorted({l for l in labels if not 0 <= l < model.num_labels})
+    speakers = model.num_labels - 1 if guided(args) else model.num_labels  # (guided: label 0 of the checkpoint is the unconditional one)
+    bad = sorted({l for l in labels if not 0 <= l < speakers})
     if bad:
-        raise SystemExit(f"labels {bad} outside the model's 0..{model.num_labels - 1}")
+        raise SystemExit(f"labels {bad} outside the model's 0..{speakers - 1}" + (" (speakers, the unconditional label not counted)" if guided(args) else ""))
     model.to(device)
     model.eval()
     model.set_precision(args.precision)

@@ -16,6 +16,13 @@ training -- chosen by index from `--seed`, left out of every pass and of a resum
 printed at every save), `--seconds` (clip length; `data_dir` may also be the synthetic set "tones", whose clips are 4 s).  `<output-dir>/model.pt` is a
 checkpoint that `sample_vqvae.py --label <old_count + k>` loads as it is; `<output-dir>/enroll.pt` holds the rows, the AdamW moments
 and the step count; a run that finds it resumes from there: the same held-out clips, the next batch of the pass it stopped in.
+
+`--uncond` learns the UNCONDITIONAL ("null") label instead (`NullLabelEnroller`): `data_dir` is any tree of recordings of the speakers
+the model already knows, its directory labels are ignored, and every clip trains one row that is written in FRONT of the table -- label
+0 of the written checkpoint, old speaker k its label k + 1, the layout of the reference's train_vqvae_uncond.py, which
+sample_vqvae_uncond.py and the `--guide-label-scale` of convert_dataset.py / eval_conversion.py expect.  The output directory is then
+ckpt_vqvae_uncond unless `--output-dir` names one; `--init mean` is the start to prefer (the centre of the known speakers); a run never
+resumes the enroll.pt of the other kind.
 """
 import argparse
 import os
@@ -27,7 +34,9 @@ import torch  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from vq_voice_swap_amd import VQVAE, LossTracker, atomic_save, create_data_loader  # noqa: E402
-from vq_voice_swap_amd.enroll import SpeakerEnroller  # noqa: E402
+from vq_voice_swap_amd.enroll import NullLabelEnroller, SpeakerEnroller  # noqa: E402
+
+UNCOND_OUTPUT_DIR = "ckpt_vqvae_uncond"
 
 
 def arg_parser():
@@ -46,6 +55,20 @@ def arg_parser():
     p.add_argument("--seconds", default=4.0, type=float, help="clip length")
     p.add_argument("data_dir", type=str)
     return p
+
+
+def parse_args(argv=None):
+    """The arguments; under `--uncond` an `--output-dir` that was not given is UNCOND_OUTPUT_DIR (the flag's own default stays)."""
+    parser = arg_parser()
+    # the null-label mode joins the parser here: `arg_parser()` stays the flag set of the reference's train_vqvae_add.py and this script's own
+    parser.add_argument("--uncond", action="store_true",
+                        help=f"learn the unconditional label (row 0, old speakers one up) from recordings of the known speakers; writes to "
+                             f"{UNCOND_OUTPUT_DIR} unless --output-dir is given")
+    args = parser.parse_args(argv)
+    given = parser.parse_args(argv, argparse.Namespace(output_dir=None)).output_dir is not None
+    if args.uncond and not given:
+        args.output_dir = UNCOND_OUTPUT_DIR
+    return args
 
 
 def parse_init(text: str):
@@ -104,7 +127,7 @@ def save(enroller: SpeakerEnroller, output_dir: str) -> None:
 
 
 def main(argv=None):
-    args = arg_parser().parse_args(argv)
+    args = parse_args(argv)
     if args.steps < 0 or args.save_interval < 1 or args.holdout < 0:
         raise SystemExit("--steps and --holdout must not be negative, --save-interval must be positive")
     if args.data_dir == "tones" and args.seconds != 4.0:
@@ -126,15 +149,24 @@ def main(argv=None):
     device = local_device()
     model.to(device).eval()
     old_count = model.num_labels
-    print(f"{old_count} speakers in the checkpoint, {num_new} new: labels {old_count} .. {old_count + num_new - 1}")
-    enroller = SpeakerEnroller(model, num_new, lr=args.lr, weight_decay=args.weight_decay, init=parse_init(args.init), seed=args.seed)
+    if args.uncond:
+        print(f"{old_count} speakers in the checkpoint: learning the unconditional label 0, speakers become labels 1 .. {old_count}")
+        enroller = NullLabelEnroller(model, lr=args.lr, weight_decay=args.weight_decay, init=parse_init(args.init), seed=args.seed)
+    else:
+        print(f"{old_count} speakers in the checkpoint, {num_new} new: labels {old_count} .. {old_count + num_new - 1}")
+        enroller = SpeakerEnroller(model, num_new, lr=args.lr, weight_decay=args.weight_decay, init=parse_init(args.init), seed=args.seed)
     os.makedirs(args.output_dir, exist_ok=True)
     resume = os.path.join(args.output_dir, "enroll.pt")
     if os.path.exists(resume):
         print(f"resuming from {resume} ...")
-        enroller.load_state_dict(torch.load(resume, map_location="cpu"))
+        try:
+            enroller.load_state_dict(torch.load(resume, map_location="cpu"))
+        except ValueError as e:
+            raise SystemExit(f"{resume}: {e}")
 
     def rows_of(loader_labels):
+        if args.uncond:  # (directory labels are ignored: every clip trains the one row)
+            return torch.zeros_like(loader_labels, dtype=torch.int64).to(device)
         return (model_labels(loader_labels, old_count) - enroller.first_label).to(device)
 
     held, held_rows = None, None
@@ -162,7 +194,10 @@ def main(argv=None):
     if args.steps == 0:
         save(enroller, args.output_dir)
     model.predictor.check_status()
-    print(f"wrote {os.path.join(args.output_dir, 'model.pt')}: {old_count + num_new} speakers")
+    if args.uncond:
+        print(f"wrote {os.path.join(args.output_dir, 'model.pt')}: the unconditional label and {old_count} speakers")
+    else:
+        print(f"wrote {os.path.join(args.output_dir, 'model.pt')}: {old_count + num_new} speakers")
 
 
 if __name__ == "__main__":

@@ -25,6 +25,12 @@ intonation contour, the register shift removed); vuv_err, frames whose voicing d
 frames; with a reference run ref_* for it and gap_f0_dev, gap_vuv_err between the two runs.  All sums are exact -- integer
 counts, and the float64 clip sums added as fractions -- so the line does not depend on the batch size or the rank count.
 
+`--guide-label-scale S` / `--guide-vq-scale S` (both off by default) decode -- the reference run too -- with the classifier-free-style
+guidance of sample_vqvae_uncond.py (`VQVAE.decode_uncond_guidance`).  With either set the checkpoint is taken to have the
+unconditional label at 0 (`enroll_speaker.py --uncond` makes one: one label more than the data has speakers) and `--target` and the
+data's labels are speaker numbers WITHOUT that offset, as the classifier counts them.  The line is the usual one: run it at several S
+with `--classifier` to see what a scale does to target_acc, target_nll, mcd and code_match.
+
 `data_dir`, `--batch-size`, `--precision`, `--seed`, `--max-samples` and `--dist-backend` are the common parser's and the pass is
 the shared one (vq_voice_swap_amd/eval_pass.py).  Under torchrun (WORLD_SIZE > 1) batches are dealt round-robin, rank 0 merges
 the states and prints the one final line.
@@ -41,6 +47,7 @@ import torch  # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from eval_vqvae import wrong_labels  # noqa: E402
 from vq_voice_swap_amd import VQVAE, Classifier, PitchDistance, SpectralDistance, randn_clips  # noqa: E402
+from vq_voice_swap_amd.corpus import add_guidance_flags, guided  # noqa: E402
 from vq_voice_swap_amd.eval_pass import common_parser, format_line, run_pass  # noqa: E402,F401
 
 SAMPLERS = ["ddpm", "ddim", "dpmpp"]
@@ -63,6 +70,7 @@ def parse_args(argv=None):
     parser = arg_parser()
     # the opt-in scores join the parser here: `arg_parser()` stays the flag set the default line is made of
     parser.add_argument("--pitch", action="store_true", help="add F0 scores (YIN on the 16-bit samples): register shift, contour deviation, voicing errors")
+    add_guidance_flags(parser)
     args = parser.parse_args(argv)
     if args.sampler != "ddim" and args.eta:
         parser.error("--eta belongs to --sampler ddim (ddpm has its own variance, dpmpp is deterministic)")
@@ -162,14 +170,18 @@ class EvalState:
         built with pitch=True."""
         if self.pitch and pitch is None:
             raise ValueError("a state with pitch=True needs a PitchDistance")
-        target = target_labels(labels, run.target, model.num_labels, seed, first)
+        # under guidance label 0 of the checkpoint is the unconditional one: the speakers, and every label here, are counted without it
+        guide = guided(run)
+        target = target_labels(labels, run.target, model.num_labels - 1 if guide else model.num_labels, seed, first)
         codes = model.encode(audio)
         # the draw `decode` would make itself from (seed, clip_offset): made here so that the reference run starts from the same x_T
         x_T = randn_clips(len(audio), codes.shape[-1] * model.encoder.downsample_rate, audio.device, seed, first)
 
         def decode(sampler, steps):
-            return model.decode(codes, target, steps=steps, constrain=True, x_T=x_T, sampler=sampler, eta=run.eta if sampler == "ddim" else 0.0,
-                                seed=seed, clip_offset=first)
+            kw = dict(steps=steps, constrain=True, x_T=x_T, sampler=sampler, eta=run.eta if sampler == "ddim" else 0.0, seed=seed, clip_offset=first)
+            if guide:
+                return model.decode_uncond_guidance(codes, target, label_scale=run.guide_label_scale, vq_scale=run.guide_vq_scale, **kw)
+            return model.decode(codes, target, **kw)
 
         def against_source(out, prefix=""):
             d = distance(audio, out)
@@ -243,7 +255,11 @@ def main(argv=None):
 
     def build(device, num_labels):
         model = VQVAE.load(args.checkpoint_path).to(device)
-        assert model.num_labels == num_labels, f"the model has {model.num_labels} labels, the data {num_labels}"
+        if guided(args):
+            assert model.num_labels == num_labels + 1, (f"the model has {model.num_labels} labels, the data {num_labels}: under guidance the "
+                                                        "checkpoint holds the unconditional label 0 and then the data's speakers")
+        else:
+            assert model.num_labels == num_labels, f"the model has {model.num_labels} labels, the data {num_labels}"
         model.eval().set_precision(args.precision)
         classifier = None
         if args.classifier:

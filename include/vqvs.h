@@ -335,6 +335,21 @@ int vqvs_ddpm_mean(const float* d_x_t, const float* d_eps, const float* d_alpha_
                    float* d_mean, int B, int T, void* stream);
 int vqvs_ddpm_guided_eps(const float* d_x_t, const float* d_mean, const float* d_grad, const float* d_alpha_t,
                          const float* d_alpha_prev, float* d_eps_out, int B, int T, uint32_t flags, void* stream);
+/* ---- Guidance mix (handle-less): the extrapolation of classifier-free-style guidance (reference vq_vae.py:205-214) in one pass ----
+ * d_outs [reps * rows, row_len] f32, contiguous: the predictor's output on the reps-fold batch.  Block k is rows k * rows ..
+ * (k + 1) * rows - 1; block 0 is the fully conditioned prediction `base`, blocks 1 and 2 (o1, o2) the predictions with something
+ * dropped.  d_eps [rows, row_len] f32 out:
+ *   reps == 1: eps = base
+ *   reps == 2: eps = base + s1 * (base - o1)
+ *   reps == 3: eps = (base + s1 * (base - o1)) + s2 * (base - o2)
+ * Every subtraction, product and sum is an fp32 operation rounded on its own, in the order written (contraction off): the result is,
+ * bit for bit, what the tensor expressions `pred = base; pred = pred + s * (base - o_k)` give, whatever the batch the elements came in.
+ * reps reads and one write per element, 16 bytes wide when d_outs and d_eps are 16-byte aligned and -- for reps > 1 -- rows * row_len
+ * is a multiple of 4 (blocks 1 and 2 start rows * row_len floats in); one float per access otherwise.  Elements are indexed in 64 bits.
+ * d_eps == d_outs is allowed (in place over block 0).
+ * VQVS_ERR_ARG before the device is touched: NULL d_outs or d_eps; rows < 1; row_len < 1; reps outside 1..3; d_eps overlapping
+ * d_outs in any other way (blocks 1 or 2, or block 0 at an offset). */
+int vqvs_guidance_mix(const float* d_outs, float* d_eps, int rows, int64_t row_len, int reps, float s1, float s2, void* stream);
 /* ---- DDIM step (handle-less; Song, Meng, Ermon: "Denoising diffusion implicit models", 2020 -- the reference has no counterpart) ----
  * One step from the time the state is at, alpha_bar = a_t, to the time stepped TO, alpha_bar = a_to, of B rows of T samples:
  *   e    = eps                       or, with d_grad, e = fmaf(-sqrt(1-a_t), grad, eps): a cond_fn's gradient at (x_t, t) enters the

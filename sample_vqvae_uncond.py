@@ -2,10 +2,14 @@
 """
 Encode a clip with a VQ-VAE and decode it with unconditional ("classifier-free"-style) guidance towards the VQ codes and / or
 the speaker label, on MI355X.  Counterpart of the reference's sample_vqvae_uncond.py (same flags and positionals; reference
-sample_vqvae_uncond.py:14-92): the model is one fine-tuned by train_vqvae_uncond.py, whose label 0 is the unconditional label
-(hence `--label + 1 < num_labels`).  Differences: WAV in / out directly (no ffmpeg); `--schedule` is parsed, not eval()ed;
+sample_vqvae_uncond.py:14-92): the model is one fine-tuned by train_vqvae_uncond.py -- or a class-conditional checkpoint whose null
+label `enroll_speaker.py --uncond` learned --, whose label 0 is the unconditional label (hence `--label + 1 < num_labels`).
+Differences: WAV in / out directly (no ffmpeg); `--schedule` is parsed, not eval()ed;
 eval mode; `--seed`, `--precision`, `--sampler {ddpm,ddim,dpmpp}` and `--eta` are new; any combination of the two guidance scales works (the reference's always-tripled
-batch only lines up when both are non-zero, vq_vae.py:188-203).
+batch only lines up when both are non-zero, vq_vae.py:188-203).  `--whole-file`, `--window-seconds`, `--overlap-seconds`,
+`--window-batch`, `--keep` and `--strength` are sample_vqvae.py's, with its meanings and defaults: the whole input through
+`encode_long` / `decode_long_uncond_guidance`, regions of the input left as they are, a start from the noised input.  `--schedule`
+works with all of them (every sampling loop takes it).
 """
 import argparse
 import os
@@ -13,11 +17,13 @@ import sys
 
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments in device memory: a process-level HIP switch, set before the runtime starts
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from sample_vqvae import source_kwargs  # noqa: E402
 from vq_voice_swap_amd import VQVAE  # noqa: E402
-from vq_voice_swap_amd.audio import ChunkReader, ChunkWriter, parse_time_schedule  # noqa: E402
+from vq_voice_swap_amd.audio import ChunkReader, ChunkWriter, parse_keep_range, parse_time_schedule  # noqa: E402
 
 
 def arg_parser():
@@ -37,6 +43,15 @@ def arg_parser():
     p.add_argument("--precision", default="fp32", choices=["fp32", "fp16", "bf16"])
     p.add_argument("--sampler", default="ddpm", choices=["ddpm", "ddim", "dpmpp"])
     p.add_argument("--eta", type=float, default=0.0, help="DDIM noise level: 0 deterministic, 1 the DDPM step's variance (--sampler ddim)")
+    p.add_argument("--whole-file", action="store_true",
+                   help="convert the whole input, not its first --seconds: overlapping windows of one long signal, blended at every step")
+    p.add_argument("--window-seconds", type=float, default=None, help="window length with --whole-file (default: --seconds)")
+    p.add_argument("--overlap-seconds", type=float, default=0.4, help="overlap of neighbouring windows with --whole-file")
+    p.add_argument("--window-batch", type=int, default=64, help="windows per forward with --whole-file")
+    p.add_argument("--keep", action="append", default=[], metavar="START:END",
+                   help="seconds of the input to leave as they are (repeatable; an empty side is the start / end of the file)")
+    p.add_argument("--strength", type=float, default=1.0,
+                   help="in (0, 1]: below 1 the conversion starts from the noised input and runs the last ceil(S * steps) steps")
     p.add_argument("checkpoint_path", type=str)
     p.add_argument("output_file", type=str)
     return p
@@ -49,7 +64,26 @@ def parse_args(argv=None):
         parser.error("--eta belongs to --sampler ddim (ddpm has its own variance, dpmpp is deterministic)")
     if args.eta < 0:
         parser.error("--eta must not be negative")
+    try:
+        args.keep = [parse_keep_range(text) for text in args.keep]
+    except ValueError as e:
+        parser.error(str(e))
+    if not 0.0 < args.strength <= 1.0:
+        parser.error("--strength must lie in (0, 1]")
+    if args.window_batch < 1:
+        parser.error("--window-batch must be at least 1")
+    if args.whole_file and args.no_vq:
+        parser.error("--no-vq is not available with --whole-file (the windows are decoded from their codes)")
     return args
+
+
+def write_wave(args, sample: torch.Tensor) -> None:
+    print(f"saving result to {args.output_file}...")
+    writer = ChunkWriter(args.output_file, sample_rate=args.sample_rate, encoding=args.encoding)
+    try:
+        writer.write(sample.clamp(-1, 1).cpu().numpy().flatten())
+    finally:
+        writer.close()
 
 
 def main(argv=None):
@@ -64,6 +98,9 @@ def main(argv=None):
     model.to(device)
     model.eval()
     model.set_precision(args.precision)
+
+    if args.whole_file:
+        return convert_whole_file(args, model, schedule, device)
 
     print(f"loading waveform from {args.input_file}...")
     reader = ChunkReader(args.input_file, sample_rate=args.sample_rate, encoding=args.encoding)
@@ -81,19 +118,49 @@ def main(argv=None):
     labels = torch.tensor([args.label]).long().to(device)
     sample = model.decode_uncond_guidance(encoded, labels, steps=args.sample_steps, progress=True, constrain=True,
                                           label_scale=args.guide_label_scale, vq_scale=args.guide_vq_scale, schedule=schedule,
-                                          seed=args.seed, sampler=args.sampler, eta=args.eta)
+                                          seed=args.seed, sampler=args.sampler, eta=args.eta, **source_kwargs(args, in_seq))
 
     if args.check_vq:
         assert not args.no_vq
         count = (encoded == model.encode(sample)).float().mean()
         print(f"fraction of consistent VQ codes: {count}")
 
-    print(f"saving result to {args.output_file}...")
-    writer = ChunkWriter(args.output_file, sample_rate=args.sample_rate, encoding=args.encoding)
+    write_wave(args, sample)
+
+
+def convert_whole_file(args, model, schedule, device):
+    """--whole-file: every sample of the input, through `encode_long` / `decode_long_uncond_guidance`; the output has the input's
+    length (sample_vqvae.py's `convert_whole_file` under guidance)."""
+    window = round((args.seconds if args.window_seconds is None else args.window_seconds) * args.sample_rate)
+    hop = window - round(args.overlap_seconds * args.sample_rate)
+    print(f"loading waveform from {args.input_file}...")
+    reader = ChunkReader(args.input_file, sample_rate=args.sample_rate, encoding=args.encoding)
     try:
-        writer.write(sample.clamp(-1, 1).cpu().numpy().flatten())
+        chunks = []
+        while (chunk := reader.read(1 << 20)) is not None:
+            chunks.append(chunk)
     finally:
-        writer.close()
+        reader.close()
+    if not chunks:
+        raise SystemExit(f"{args.input_file} holds no samples")
+    wave = torch.from_numpy(np.concatenate(chunks)[None, None]).to(device)
+    num_samples = wave.shape[-1]
+
+    print(f"encoding {num_samples} samples in windows of {window} every {hop}...")
+    encoded = model.encode_long(wave, window, hop, args.window_batch)
+
+    print(f"decoding {encoded.shape[0]} windows...")
+    labels = torch.tensor([args.label]).long().to(device)
+    sample = model.decode_long_uncond_guidance(encoded, labels, label_scale=args.guide_label_scale, vq_scale=args.guide_vq_scale,
+                                               num_samples=num_samples, window=window, hop=hop, steps=args.sample_steps, progress=True,
+                                               constrain=True, seed=args.seed, window_batch=args.window_batch, sampler=args.sampler,
+                                               eta=args.eta, schedule=schedule, **source_kwargs(args, wave))
+
+    if args.check_vq:
+        count = (encoded == model.encode_long(sample, window, hop, args.window_batch)).float().mean()
+        print(f"fraction of consistent VQ codes: {count}")
+
+    write_wave(args, sample)
 
 
 if __name__ == "__main__":

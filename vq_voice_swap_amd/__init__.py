@@ -11,11 +11,11 @@ from .base import Savable, atomic_save
 from .classifier import Classifier
 from .conv_encoder import ConvMFCCEncoder
 from .dataset import create_data_loader
-from .diffusion import CosSchedule, Diffusion, ExpSchedule, Schedule, make_schedule, randn_clips
+from .diffusion import CosSchedule, Diffusion, ExpSchedule, Schedule, guidance_mix, make_schedule, randn_clips
 from .diffusion_model import DiffusionModel
 from .dtw import AlignedDistance, dtw_distance
 from .encoder_predictor import EncoderPredictor
-from .enroll import ClassifierEnroller, SpeakerEnroller
+from .enroll import ClassifierEnroller, NullLabelEnroller, SpeakerEnroller
 from .longform import plan_pack, plan_windows
 from .losses import LossTracker, classification_scores, speaker_search_losses
 from .pitch import PitchDistance
@@ -31,5 +31,5 @@ __all__ = [
     "FeatureStats", "class_score", "frechet_distance", "wav_roundtrip", "LossTracker", "speaker_search_losses", "create_data_loader",
     "StandardVQLoss", "VQLoss", "code_usage", "classification_scores", "plan_windows", "plan_pack",
     "SpectralDistance", "spectral_constants", "PitchDistance", "SpeakerEnroller", "ClassifierEnroller",
-    "AlignedDistance", "dtw_distance",
+    "AlignedDistance", "dtw_distance", "NullLabelEnroller", "guidance_mix",
 ]

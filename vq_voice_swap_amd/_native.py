@@ -76,7 +76,7 @@ EXPORTS = [
     "vqvs_debug_tap_info", "vqvs_debug_tap_rows", "vqvs_debug_read_tap", "vqvs_debug_read_embedding", "vqvs_forward_kernel_count", "vqvs_forward_model_bytes",
     "vqvs_forward_flops", "vqvs_set_profiling", "vqvs_op_info", "vqvs_op_desc", "vqvs_profile_read", "vqvs_last_error", "vqvs_version",
     "vqvs_unet_embed_grad", "vqvs_embed_adamw", "vqvs_debug_read_dfilm", "vqvs_head_xent_grad", "vqvs_head_adamw",
-    "vqvs_mel_cepstra", "vqvs_dtw_distance",
+    "vqvs_mel_cepstra", "vqvs_dtw_distance", "vqvs_guidance_mix",
 ]
 
 _lib = None
@@ -160,6 +160,7 @@ def lib():
     L.vqvs_keep_region_windows.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, u64, u64, u32, vp]
     L.vqvs_ddpm_mean.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
     L.vqvs_ddpm_guided_eps.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, u32, vp]
+    L.vqvs_guidance_mix.argtypes = [vp, vp, i32, i64, i32, f32, f32, vp]
     L.vqvs_randn.argtypes = [vp, i32, i32, u64, u64, u32, vp]
     L.vqvs_ddpm_noise.argtypes = [vp, i32, vp, vp, i32, vp, vp, i32, i32, u64, u64, vp]
     L.vqvs_ddpm_sqerr.argtypes = [vp, vp, i32, vp, vp, i32, i32, u64, u64, vp]

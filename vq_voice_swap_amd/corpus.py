@@ -26,6 +26,21 @@ def list_files(index: dict) -> List[Tuple[str, float]]:
     return sorted(out)
 
 
+def add_guidance_flags(parser) -> None:
+    """`--guide-label-scale` / `--guide-vq-scale` of convert_dataset.py and eval_conversion.py, both off by default."""
+    parser.add_argument("--guide-label-scale", type=float, default=0.0, metavar="S",
+                        help="classifier-free-style guidance towards the target label (sample_vqvae_uncond.py); needs a checkpoint whose label 0 "
+                             "is the unconditional one (enroll_speaker.py --uncond); labels are then speaker numbers without that offset")
+    parser.add_argument("--guide-vq-scale", type=float, default=0.0, metavar="S",
+                        help="the same towards the VQ codes; meaningful only for a model fine-tuned with dropped codes")
+
+
+def guided(args) -> bool:
+    """Whether a parsed command line asks for label / code guidance: the checkpoint then has the unconditional label at 0 and every
+    label on the command line is a speaker number without that offset.  (The flags absent: a namespace of the unguided parser.)"""
+    return bool(getattr(args, "guide_label_scale", 0.0)) or bool(getattr(args, "guide_vq_scale", 0.0))
+
+
 def top_directory(rel_path: str) -> str:
     return rel_path.replace("\\", "/").split("/", 1)[0]
 

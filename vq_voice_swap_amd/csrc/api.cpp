@@ -663,6 +663,20 @@ int vqvs_ddpm_guided_eps(const float* d_x_t, const float* d_mean, const float* d
   return run_ddpm_guided_eps(d_x_t, d_mean, d_grad, d_alpha_t, d_alpha_prev, d_eps_out, B, T, flags, reinterpret_cast<hipStream_t>(stream));
 }
 
+int vqvs_guidance_mix(const float* d_outs, float* d_eps, int rows, int64_t row_len, int reps, float s1, float s2, void* stream) {
+  if (!d_outs || !d_eps) VQVS_FAIL(VQVS_ERR_ARG, "d_outs and d_eps must be non-NULL");
+  if (rows < 1) VQVS_FAIL(VQVS_ERR_ARG, "rows=%d must be at least 1", rows);
+  if (row_len < 1) VQVS_FAIL(VQVS_ERR_ARG, "row_len=%lld must be at least 1", (long long)row_len);
+  if (reps < 1 || reps > 3) VQVS_FAIL(VQVS_ERR_ARG, "reps=%d outside 1..3", reps);
+  if (row_len > (INT64_MAX / 16) / rows) VQVS_FAIL(VQVS_ERR_ARG, "rows=%d of row_len=%lld: too many elements", rows, (long long)row_len);
+  const int64_t total = (int64_t)rows * row_len;
+  // in place means eps IS block 0: element i is read and written by the same thread.  Any other overlap -- blocks 1 and 2, or block 0
+  // at an offset -- would let one thread's store reach another's load.
+  if (d_eps != d_outs && bytes_overlap(d_eps, total * 4, d_outs, (int64_t)reps * total * 4))
+    VQVS_FAIL(VQVS_ERR_ARG, "d_eps must be d_outs itself (in place over block 0) or not overlap d_outs at all");
+  return run_guidance_mix(d_outs, d_eps, total, reps, s1, s2, reinterpret_cast<hipStream_t>(stream));
+}
+
 int vqvs_randn(float* d_out, int B, int T, uint64_t seed, uint64_t clip_offset, uint32_t stream_id, void* stream) {
   if (!d_out || B < 1 || T < 1) VQVS_FAIL(VQVS_ERR_ARG, "bad argument");
   return run_randn(d_out, B, T, seed, clip_offset, stream_id, reinterpret_cast<hipStream_t>(stream));

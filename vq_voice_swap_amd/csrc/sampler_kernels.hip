@@ -1230,6 +1230,82 @@ int run_ddpm_guided_eps(const float* x_t, const float* mean, const float* grad, 
   return 0;
 }
 
+// ---------------------------------------------------------------------------------
+// Guidance mix (include/vqvs.h "Guidance mix"): eps = base + s1 (base - o1) [+ s2 (base - o2)] over the REPS blocks of one predictor
+// output, `total` floats each.  The tensor expressions it replaces round every subtraction, product and sum on its own, left to right,
+// so contraction is off here and the result is theirs bit for bit.  Each element is read REPS times and written once by the thread
+// that read it, which is what lets eps lie over block 0.
+// ---------------------------------------------------------------------------------
+namespace {
+
+template <int REPS>
+__device__ __forceinline__ float guidance_mix_one(float base, float o1, float o2, float s1, float s2) {
+#pragma clang fp contract(off)
+  float p = base;
+  if (REPS >= 2) {
+    const float d = base - o1;
+    const float m = s1 * d;
+    p = p + m;
+  }
+  if (REPS >= 3) {
+    const float d = base - o2;
+    const float m = s2 * d;
+    p = p + m;
+  }
+  return p;
+}
+
+// VEC: every block and eps start on 16 bytes (the launcher checks): quads [0, total / 4) as 16-byte accesses, grid-stride, and the
+// total % 4 trailing floats -- REPS == 1 only, else total % 4 == 0 -- by the first threads of the grid.  Otherwise one float per thread.
+template <int REPS, bool VEC>
+__global__ __launch_bounds__(256) void guidance_mix_kernel(const float* outs, float* eps, int64_t total, float s1, float s2) {
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  const float* b1 = outs + (REPS >= 2 ? total : 0);
+  const float* b2 = outs + (REPS >= 3 ? 2 * total : 0);
+  if (VEC) {
+    const int64_t quads = total / 4;
+    for (int64_t q = tid; q < quads; q += stride) {
+      const f32x4 base = *reinterpret_cast<const f32x4*>(outs + q * 4);
+      f32x4 o1 = base, o2 = base;
+      if (REPS >= 2) o1 = *reinterpret_cast<const f32x4*>(b1 + q * 4);
+      if (REPS >= 3) o2 = *reinterpret_cast<const f32x4*>(b2 + q * 4);
+      f32x4 r;
+      for (int j = 0; j < 4; ++j) r[j] = guidance_mix_one<REPS>(base[j], o1[j], o2[j], s1, s2);
+      *reinterpret_cast<f32x4*>(eps + q * 4) = r;
+    }
+    const int64_t i = quads * 4 + tid;
+    if (i < total) eps[i] = guidance_mix_one<REPS>(outs[i], b1[i], b2[i], s1, s2);
+  } else {
+    for (int64_t i = tid; i < total; i += stride) eps[i] = guidance_mix_one<REPS>(outs[i], b1[i], b2[i], s1, s2);
+  }
+}
+
+template <int REPS>
+void launch_guidance_mix(const float* outs, float* eps, int64_t total, float s1, float s2, hipStream_t st) {
+  const bool blocks_aligned = REPS == 1 || total % 4 == 0;
+  const bool vec = blocks_aligned && (reinterpret_cast<uintptr_t>(outs) | reinterpret_cast<uintptr_t>(eps)) % 16 == 0;
+  const int64_t items = vec ? (total + 3) / 4 : total;  // (covers the tail: total % 4 < 4 <= the grid's threads)
+  const int grid = (int)std::min<int64_t>((items + 255) / 256, 2048);
+  if (vec)
+    hipLaunchKernelGGL((guidance_mix_kernel<REPS, true>), dim3(grid), dim3(256), 0, st, outs, eps, total, s1, s2);
+  else
+    hipLaunchKernelGGL((guidance_mix_kernel<REPS, false>), dim3(grid), dim3(256), 0, st, outs, eps, total, s1, s2);
+}
+
+}  // namespace
+
+int run_guidance_mix(const float* outs, float* eps, int64_t total, int reps, float s1, float s2, hipStream_t st) {
+  if (reps == 1)
+    launch_guidance_mix<1>(outs, eps, total, s1, s2, st);
+  else if (reps == 2)
+    launch_guidance_mix<2>(outs, eps, total, s1, s2, st);
+  else
+    launch_guidance_mix<3>(outs, eps, total, s1, s2, st);
+  VQVS_HIP(hipGetLastError());
+  return 0;
+}
+
 int run_vq_argmin(const float* z, const float* dict, float* en_scratch, int64_t* idx, int B, int Cd, int T1, int K, hipStream_t st) {
   hipLaunchKernelGGL(vq_norms_kernel, dim3((K + 255) / 256), dim3(256), 0, st, dict, en_scratch, K, Cd);
   hipLaunchKernelGGL(vq_argmin_kernel, dim3((T1 + VQ_POS - 1) / VQ_POS, B), dim3(256), 0, st, z, dict, en_scratch, idx, Cd, T1, K);

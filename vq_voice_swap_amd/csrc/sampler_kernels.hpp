@@ -48,6 +48,9 @@ int run_keep_region_windows(float* x, float* windows, const float* x0, const uin
 int run_ddpm_mean(const float* x_t, const float* eps, const float* a_t, const float* a_prev, float* out, int B, int T, hipStream_t st);
 int run_ddpm_guided_eps(const float* x_t, const float* mean, const float* grad, const float* a_t, const float* a_prev, float* out,
                         int B, int T, uint32_t flags, hipStream_t st);
+// guidance mix over the `reps` (1..3) blocks of `total` floats of one predictor output: eps = base + s1 (base - o1) + s2 (base - o2),
+// every operation rounded on its own; eps may be block 0
+int run_guidance_mix(const float* outs, float* eps, int64_t total, int reps, float s1, float s2, hipStream_t st);
 // forward process and denoising loss (loss_kernels.hip)
 int sqerr_scratch_doubles(int B, int T);
 int run_ddpm_noise(const float* x0, int x0_rows, const float* alpha, const float* eps, int eps_rows, const int64_t* noise_index,

@@ -819,6 +819,27 @@ class _Clips:
         self.diffusion._keep_(x_t, source, keep, alpha, **kw)
 
 
+def guidance_mix(outs: torch.Tensor, reps: int, s1: float = 0.0, s2: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`vqvs_guidance_mix` on the predictor's output `outs` [reps * n, ...] of a reps-fold batch (block 0 the fully conditioned
+    prediction): base + s1 * (base - block 1) + s2 * (base - block 2), every operation rounded on its own -- bit for bit what those
+    tensor expressions give.  Written into `out` [n, ...] (contiguous float32), or -- None -- IN PLACE over block 0 of a contiguous
+    float32 `outs` (a copy of anything else); the [n, ...] result is returned."""
+    _native.require_cuda(outs, out)
+    reps = int(reps)
+    if reps < 1 or outs.dim() < 2 or outs.shape[0] < reps or outs.shape[0] % reps or not outs[0].numel():
+        raise ValueError(f"outs of shape {tuple(outs.shape)} is not a {reps}-fold batch of rows")
+    outs = outs.detach().to(torch.float32).contiguous()
+    n = outs.shape[0] // reps
+    if out is None:
+        out = outs[:n]
+    elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (n, *outs.shape[1:]):
+        raise ValueError(f"out must be contiguous float32 of shape {(n, *outs.shape[1:])}, got {out.dtype} {tuple(out.shape)}")
+    with torch.cuda.device(outs.device):
+        _native.check(_native.lib().vqvs_guidance_mix(outs.data_ptr(), out.data_ptr(), n, outs[0].numel(), reps, float(s1), float(s2),
+                                                      _native._stream_ptr()))
+    return out
+
+
 def randn_clips(n: int, T: int, device, seed: int, clip_offset: int = 0, stream_id: int = 1) -> torch.Tensor:
     """x_T ~ N(0,1) of shape [n,1,T] from the counter-based generator (keyed by global clip index)."""
     out = torch.empty(n, 1, T, device=device, dtype=torch.float32)

@@ -62,6 +62,8 @@ class SpeakerEnroller:
     `eval()`.  `step()` takes one optimiser step on a batch; `finish()` grows the model by the rows; `state_dict()` /
     `load_state_dict()` resume.  New speaker k is row k here and label `first_label + k` of the finished model."""
 
+    front = False  # (NullLabelEnroller: the row goes in FRONT of the table; its state_dict says so and a resume of the other kind is refused)
+
     def __init__(self, model: DiffusionModel, num_new: int, lr: float = 1e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, init: Union[str, int] = "normal", seed: int = 0):
         if not isinstance(model, DiffusionModel) or model.num_labels is None:
@@ -161,6 +163,10 @@ class SpeakerEnroller:
                 "exp_avg_sq": self.exp_avg_sq.detach().cpu().clone(), "steps": self.steps, "first_label": self.first_label}
 
     def load_state_dict(self, state: Dict[str, object]) -> None:
+        front = bool(state.get("front", False))
+        if front != self.front:
+            kinds = {True: "the null label (NullLabelEnroller, a row in front of the table)", False: "new speakers (SpeakerEnroller, rows behind the table)"}
+            raise ValueError(f"state was made by an enroller of {kinds[front]}, this one learns {kinds[self.front]}")
         rows = state["rows"]
         if tuple(rows.shape) != tuple(self.rows.shape):
             raise ValueError(f"state holds rows of shape {tuple(rows.shape)}, this enroller has {tuple(self.rows.shape)}")
@@ -171,6 +177,68 @@ class SpeakerEnroller:
         self.exp_avg = state["exp_avg"].to(device=dev, dtype=torch.float32).clone()
         self.exp_avg_sq = state["exp_avg_sq"].to(device=dev, dtype=torch.float32).clone()
         self.steps = int(state["steps"])
+
+
+class NullLabelEnroller(SpeakerEnroller):
+    """The unconditional ("null") label of a class-conditional model, learned with everything else frozen: ONE row, trained by every
+    clip of a batch whatever its speaker, that `finish()` puts in FRONT of the table -- `add_labels(1, end=False)`, the layout of the
+    reference's `VQVAEUncondTrainLoop.load_from_pretrained`: label 0 is the null label, old speaker k is label k + 1, its row bit for
+    bit.  That is the model `VQVAE.decode_uncond_guidance` and sample_vqvae_uncond.py expect.
+
+    The reference (train_vqvae_uncond.py) gives a clip label 0 with probability `--no-class-prob` and fine-tunes every parameter; with
+    all but row 0 frozen the clips that keep their label have zero gradient, so training every clip on row 0 is the reference's
+    gradient for that row up to the factor no_class_prob, a learning-rate scale.  What a frozen model cannot learn is the reference's
+    code dropout (`--no-vq-prob`): guidance towards the codes stays meaningful only for models the reference fine-tuned itself.
+
+    The interface is `SpeakerEnroller`'s with `num_new` = 1; `step(inputs)` and `losses(inputs)` need no labels."""
+
+    front = True
+
+    def __init__(self, model: DiffusionModel, lr: float = 1e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, init: Union[str, int] = "normal", seed: int = 0):
+        super().__init__(model, 1, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, init=init, seed=seed)
+
+    @staticmethod
+    def _row_zero(inputs: torch.Tensor, new_labels: Optional[torch.Tensor]) -> torch.Tensor:
+        if new_labels is not None:
+            return new_labels
+        if inputs.dim() != 3:
+            raise ValueError(f"expected inputs of shape [N, 1, T], got {tuple(inputs.shape)}")
+        return torch.zeros(inputs.shape[0], dtype=torch.int64, device=inputs.device)
+
+    def losses(self, inputs: torch.Tensor, new_labels: Optional[torch.Tensor] = None, **kwargs):
+        """`SpeakerEnroller.losses` with every clip on the one row (`new_labels`, if given at all, is all zeros)."""
+        return super().losses(inputs, self._row_zero(inputs, new_labels), **kwargs)
+
+    def step(self, inputs: torch.Tensor, new_labels: Optional[torch.Tensor] = None, **kwargs) -> Dict[str, torch.Tensor]:
+        """`SpeakerEnroller.step` with every clip on the one row: the row's gradient is the mean over the batch."""
+        return super().step(inputs, self._row_zero(inputs, new_labels), **kwargs)
+
+    def finish(self) -> DiffusionModel:
+        """`model.add_labels(1, end=False)` with the learned row at index 0; the checkpoint's own rows stay bit for bit, one up."""
+        if self.finished:
+            raise RuntimeError("NullLabelEnroller.finish() was already called")
+        self.model.add_labels(1, end=False)
+        with torch.no_grad():
+            w = self.model.predictor.class_embed.weight
+            w[:1].copy_(self.rows.to(w.device))
+        self.model.predictor.invalidate()
+        self.finished = True
+        return self.model
+
+    def checkpoint(self) -> Dict[str, object]:
+        """`SpeakerEnroller.checkpoint` with the row in front of the old rows."""
+        if self.finished:
+            return self.model.save_dict()
+        state = self.model.save_dict()
+        kwargs = dict(state["kwargs"], num_labels=self.first_label + 1)
+        sd = {k: v.detach().cpu().clone() for k, v in state["state_dict"].items()}
+        key = "predictor.class_embed.weight"
+        sd[key] = torch.cat([self.rows.detach().cpu().to(sd[key].dtype), sd[key]], dim=0)
+        return {"kwargs": kwargs, "state_dict": sd}
+
+    def state_dict(self) -> Dict[str, object]:
+        return dict(super().state_dict(), front=True)
 
 
 # ---- the classifier's head ----------------------------------------------------------------------------------------------------------

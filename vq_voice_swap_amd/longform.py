@@ -380,9 +380,10 @@ def check_rate(model, window: int, hop: int) -> None:
         raise ValueError(f"window={window} and hop={hop} must be multiples of the model's downsample rate {rate}")
 
 
-def _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale):
+def _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale, guidance=None):
     """(predictor, cond_fn) of a window batch: each slice of windows sees its own rows of the conditioning [n,C,T1], of `labels` [n]
-    (or None) and -- with `enc_pred` -- guidance towards its own codes (VQVAE.decode)."""
+    (or None) and -- with `enc_pred` -- guidance towards its own codes (VQVAE.decode).  `guidance` (label_scale, vq_scale) makes the
+    predictor the guided one of `VQVAE.decode_uncond_guidance` (vq_vae.guided_predictor): labels are then NOT offset by the caller."""
     cond_fn = None
     if enc_pred is not None:
         targets = model.vq.encode(cond_seq)
@@ -391,6 +392,11 @@ def _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale):
             return enc_pred.guidance_grad(x, ts, targets[first:first + x.shape[0]], enc_pred_scale)
 
         cond_fn.native_modules = (enc_pred,)
+
+    if guidance is not None:
+        from .vq_vae import guided_predictor
+
+        return guided_predictor(model, cond_seq, labels, *guidance)[0], cond_fn
 
     def predictor(xs, ts, first):
         sl = slice(first, first + xs.shape[0])
@@ -403,13 +409,14 @@ def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = Non
                 steps: int = 100, progress: bool = False, constrain: bool = False, enc_pred=None, enc_pred_scale: float = 1.0,
                 seed: Optional[int] = None, clip_offset: int = 0, window_batch: int = 64, sampler: str = "ddpm", eta: float = 0.0,
                 source: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None, strength: float = 1.0,
-                **kwargs) -> torch.Tensor:
+                guidance: Optional[Tuple[float, float]] = None, **kwargs) -> torch.Tensor:
     """Window codes [n,T1] int or [n,C,T1] float (`encode_long`) -> [1,1,num_samples] waveform: `VQVAE.decode` on one long state.
     x_T is ONE row of (n - 1) * hop + window samples keyed by `clip_offset`; `labels` is one label for every window, or [n].
     With one window the result is `decode`'s, bit for bit, at the same seed and clip_offset.  `sampler` "ddim" runs
     `ddim_sample_windows` with `eta` instead of `ddpm_sample_windows`, "dpmpp" `dpmpp_sample_windows`.  `source` [1,1,num_samples] (the recording itself), `keep`
     (bool / uint8, [1,1,num_samples]: samples that stay the source's) and `strength` in (0, 1] (below 1: start from the noised
-    source, `strength_to_start_step`) are `VQVAE.decode`'s."""
+    source, `strength_to_start_step`) are `VQVAE.decode`'s.  `guidance` (label_scale, vq_scale) is what
+    `VQVAE.decode_long_uncond_guidance` passes: the guided window predictor of `_conditioned`, labels not offset by the caller."""
     from .diffusion import fresh_seed, pick_sampler, randn_clips, source_start_step
 
     start_step = source_start_step(source, keep, strength, steps)
@@ -427,7 +434,7 @@ def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = Non
         if labels.shape != (n,):
             raise ValueError(f"labels must hold one label or one per window ({n}), got {labels.numel()}")
         labels = labels.contiguous()
-    predictor, cond_fn = _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale)
+    predictor, cond_fn = _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale, guidance)
     if seed is None:
         seed = fresh_seed()
     if source is not None:
@@ -444,13 +451,14 @@ def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = Non
 def decode_long_batch(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, *, counts: Sequence[int], num_samples: Sequence[int],
                       window: int, hop: int, steps: int = 100, progress: bool = False, constrain: bool = False, enc_pred=None,
                       enc_pred_scale: float = 1.0, seed: Optional[int] = None, clip_offset: int = 0, window_batch: int = 64,
-                      sampler: str = "ddpm", eta: float = 0.0) -> List[torch.Tensor]:
+                      sampler: str = "ddpm", eta: float = 0.0, guidance: Optional[Tuple[float, float]] = None) -> List[torch.Tensor]:
     """`decode_long` for a pack of recordings (`encode_long_batch`): codes [N,T1] or [N,C,T1] of all their windows, `counts` windows and
     `num_samples` samples per recording -> one [1,1,num_samples[r]] waveform each.  The windows of all recordings fill the forwards
     together (`window_batch` at a time) and one packed step kernel follows, so many short recordings cost what one long one does.
     `labels` is one label, one per recording, or one per window.  x_T is each recording's own row keyed clip_offset + r, and recording
     r's result is what `decode_long` returns for it alone at clip_offset + r, bit for bit, whatever else is in the pack and whatever
-    `window_batch` is.  `source`, `keep` and `strength` are not built for a pack."""
+    `window_batch` is.  `source`, `keep` and `strength` are not built for a pack.  `guidance` (label_scale, vq_scale) is `decode_long`'s,
+    what `VQVAE.decode_long_batch_uncond_guidance` passes."""
     from .diffusion import fresh_seed, pick_sampler, randn_clips
 
     cond_seq = model.cond_sequence(codes)
@@ -473,7 +481,7 @@ def decode_long_batch(model, codes: torch.Tensor, labels: Optional[torch.Tensor]
         if labels.shape != (N,):
             raise ValueError(f"labels must hold one label, one per recording ({R}) or one per window ({N}), got {labels.numel()}")
         labels = labels.contiguous()
-    predictor, cond_fn = _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale)
+    predictor, cond_fn = _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale, guidance)
     if seed is None:
         seed = fresh_seed()
     padded = [(c - 1) * hop + window for c in counts]

@@ -6,11 +6,12 @@ signatures; every stage runs in libvqvs_hip.so.
 
 from __future__ import annotations
 
+import contextlib
 from typing import Any, Dict, Optional
 
 import torch
 
-from .diffusion import fresh_seed, pick_sampler, randn_clips, source_start_step
+from .diffusion import fresh_seed, guidance_mix, pick_sampler, randn_clips, source_start_step
 from .diffusion_model import DiffusionModel
 from .conv_encoder import ConvMFCCEncoder
 from .unet import UNetEncoder
@@ -29,6 +30,47 @@ def make_encoder(enc_name: str, base_channels: int = 32, cond_mult: int = 16):
         return ConvMFCCEncoder(base_channels=base_channels, out_channels=base_channels * cond_mult, input_ulaw=False)
     raise ValueError(f"encoder {enc_name!r} is outside the accelerated hot path (SURVEY.md section 2a): "
                      "'unet' and the 'conv-mfcc-*' encoders are built")
+
+
+def _guided(labels, label_scale: float, vq_scale: float) -> bool:
+    """Whether a guidance call extrapolates at all: a label scale counts only with labels."""
+    return bool(vq_scale) or (labels is not None and bool(label_scale))
+
+
+def guided_predictor(model, cond_seq: torch.Tensor, labels: Optional[torch.Tensor], label_scale: float, vq_scale: float):
+    """(predictor(xs, ts, first=0), guided) of classifier-free-style guidance on the rows of `cond_seq` [n,C,T1] and `labels` [n] (not
+    offset; None: no labels).  A slice of m rows starting at `first` runs the decoder's predictor on the reps-fold batch
+    [own cond, labels + 1 | zero cond, labels + 1 | own cond, label 0] -- a block only for a non-zero scale (reference
+    vq_vae.py:188-214, whose always-tripled batch lines up only when both are) -- and `vqvs_guidance_mix` extrapolates in place over
+    block 0.  The batches of a slice are built once and kept: the sampling loop asks for the same slices at every step."""
+    use_vq = bool(vq_scale)
+    use_label = labels is not None and bool(label_scale)
+    reps = 1 + int(use_vq) + int(use_label)
+    scales = [float(s) for flag, s in ((use_vq, vq_scale), (use_label, label_scale)) if flag] + [0.0, 0.0]
+    shifted = None if labels is None else labels + 1
+    batches = {}
+
+    def batch(first: int, m: int):
+        if (first, m) not in batches:
+            sl = slice(first, first + m)
+            conds = [cond_seq[sl]]
+            labs = [shifted[sl]] if shifted is not None else None
+            if use_vq:
+                conds.append(torch.zeros_like(cond_seq[sl]))
+                if labs is not None:
+                    labs.append(shifted[sl])
+            if use_label:
+                conds.append(cond_seq[sl])
+                labs.append(torch.zeros_like(shifted[sl]))
+            batches[first, m] = (torch.cat(conds, dim=0), torch.cat(labs, dim=0) if labs is not None else None)
+        return batches[first, m]
+
+    def predictor(xs, ts, first: int = 0):
+        cond_batch, label_batch = batch(int(first), xs.shape[0])
+        outs = model.predictor(torch.cat([xs] * reps, dim=0), torch.cat([ts] * reps, dim=0), cond=cond_batch, labels=label_batch)
+        return guidance_mix(outs, reps, scales[0], scales[1])
+
+    return predictor, reps > 1
 
 
 class VQVAE(DiffusionModel):
@@ -189,56 +231,62 @@ class VQVAE(DiffusionModel):
 
     def decode_uncond_guidance(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, steps: int = 100,
                                progress: bool = False, constrain: bool = False, label_scale: float = 0.0, vq_scale: float = 0.0,
-                               x_T: Optional[torch.Tensor] = None, sampler: str = "ddpm", eta: float = 0.0, **kwargs) -> torch.Tensor:
+                               x_T: Optional[torch.Tensor] = None, sampler: str = "ddpm", eta: float = 0.0,
+                               source: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None, strength: float = 1.0,
+                               **kwargs) -> torch.Tensor:
         """Decode with classifier-free-style guidance towards the VQ codes and/or the label (reference
         vq_vae.py:147-220): the predictor runs on a 1x-3x batch [conditional | codes dropped | label dropped] and the
-        prediction is base + scale * (base - dropped).  Labels are NOT offset by the caller: label 0 is the
-        unconditional label of such a model, so `labels + 1` is used as in the reference."""
+        prediction is base + scale * (base - dropped), mixed by `vqvs_guidance_mix`.  Labels are NOT offset by the caller: label 0 is
+        the unconditional label of such a model, so `labels + 1` is used as in the reference.  `source`, `keep` and `strength` are
+        `decode`'s."""
+        start_step = source_start_step(source, keep, strength, steps)
+        if source is not None:
+            kwargs.update(source=source, keep=keep, start_step=start_step)
         cond_seq = self.cond_sequence(codes)
-        n = cond_seq.shape[0]
         seed, x_T = self._seed_and_x_T(codes, x_T, kwargs)
-
-        use_vq = bool(vq_scale)
-        use_label = labels is not None and bool(label_scale)
-        reps = 1 + int(use_vq) + int(use_label)
-        cond_batch = [cond_seq]
-        label_batch = [labels + 1] if labels is not None else None
-        if use_vq:
-            cond_batch.append(torch.zeros_like(cond_seq))
-            if label_batch is not None:
-                label_batch.append(labels + 1)
-        if use_label:
-            cond_batch.append(cond_seq)
-            label_batch.append(torch.zeros_like(labels))
-        cond_batch = torch.cat(cond_batch, dim=0)
-        label_batch = torch.cat(label_batch, dim=0) if label_batch is not None else None
-
-        def pred_fn(xs, ts):
-            outs = self.predictor(torch.cat([xs] * reps, dim=0), torch.cat([ts] * reps, dim=0), cond=cond_batch, labels=label_batch)
-            base = outs[:n]
-            pred, k = base, 1
-            for flag, scale in ((use_vq, vq_scale), (use_label, label_scale)):
-                if flag:
-                    pred = pred + scale * (base - outs[k * n:(k + 1) * n])
-                    k += 1
-            return pred
-
-        # The extrapolation base + s_vq (base - a) + s_label (base - b) multiplies the predictor's rounding error by up to
-        # 1 + 2 (s_vq + s_label): a 2-byte decoder mode does not hold the 1e-3 waveform contract here (fixtures F11 / F11b), so the
-        # guided predictor runs in the fp32 mode for this call, whatever mode the decoder is set to.
-        prev = self.predictor.precision
-        promote = (use_vq or use_label) and prev != "fp32"
-        if promote:
-            import warnings
-
-            warnings.warn(f"decode_uncond_guidance: the predictor runs in the fp32 mode for this call (decoder mode {prev!r} does not "
-                          "meet the 1e-3 waveform contract under guidance extrapolation)", stacklevel=2)
-        # (precision_override keeps the decoder's own handle and arena; the fp32 handle is cached beside it for the next call)
+        pred_fn, guided = guided_predictor(self, cond_seq, labels, label_scale, vq_scale)
         sample, sampler_kw = pick_sampler(self.diffusion, sampler, eta)
-        with self.predictor.precision_override("fp32" if promote else prev):
+        with self.guidance_precision(guided, "decode_uncond_guidance"):
             out = sample(x_T, pred_fn, steps=steps, progress=progress, constrain=constrain, seed=seed, **sampler_kw, **kwargs)
             self.predictor.check_status()
         return out
+
+    @contextlib.contextmanager
+    def guidance_precision(self, guided: bool, what: str, stacklevel: int = 4):
+        """The decoder's mode for a guided call: the extrapolation base + s_vq (base - a) + s_label (base - b) multiplies the predictor's
+        rounding error by up to 1 + 2 (s_vq + s_label), and a 2-byte decoder mode does not hold the 1e-3 waveform contract there
+        (fixtures F11 / F11b), so the guided predictor runs in the fp32 mode for the call, whatever mode the decoder is set to.
+        (precision_override keeps the decoder's own handle and arena; the fp32 handle is cached beside it for the next call.)"""
+        prev = self.predictor.precision
+        promote = guided and prev != "fp32"
+        if promote:
+            import warnings
+
+            warnings.warn(f"{what}: the predictor runs in the fp32 mode for this call (decoder mode {prev!r} does not "
+                          "meet the 1e-3 waveform contract under guidance extrapolation)", stacklevel=stacklevel)
+        with self.predictor.precision_override("fp32" if promote else prev):
+            yield
+
+    def decode_long_uncond_guidance(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, *, label_scale: float = 0.0,
+                                    vq_scale: float = 0.0, **kwargs) -> torch.Tensor:
+        """`decode_uncond_guidance` on one long state: `decode_long` (its keywords: num_samples, window, hop, steps, constrain, seed,
+        clip_offset, window_batch, sampler, eta, source, keep, strength ...) whose window predictor is the guided one -- each slice of
+        windows runs as [own cond, labels + 1 | zero cond, labels + 1 | own cond, label 0] and is mixed by `vqvs_guidance_mix`.
+        Labels are NOT offset by the caller.  With one window the result is `decode_uncond_guidance`'s, bit for bit."""
+        from .longform import decode_long
+
+        with self.guidance_precision(_guided(labels, label_scale, vq_scale), "decode_long_uncond_guidance"):
+            return decode_long(self, codes, labels, guidance=(label_scale, vq_scale), **kwargs)
+
+    def decode_long_batch_uncond_guidance(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, *, label_scale: float = 0.0,
+                                          vq_scale: float = 0.0, **kwargs):
+        """`decode_long_uncond_guidance` for a pack of recordings: `decode_long_batch` (its keywords: counts, num_samples, window, hop
+        ...) with the guided window predictor.  Recording r is what `decode_long_uncond_guidance` returns for it alone at
+        clip_offset + r, bit for bit."""
+        from .longform import decode_long_batch
+
+        with self.guidance_precision(_guided(labels, label_scale, vq_scale), "decode_long_batch_uncond_guidance"):
+            return decode_long_batch(self, codes, labels, guidance=(label_scale, vq_scale), **kwargs)
 
     @property
     def downsample_rate(self) -> int:
