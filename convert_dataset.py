@@ -21,6 +21,13 @@ file's top-level directory.  An unreadable or empty file is skipped with a warni
 sample_vqvae_uncond.py (`VQVAE.decode_long_batch_uncond_guidance`).  With either set the checkpoint is taken to have the unconditional
 label at 0 (`enroll_speaker.py --uncond` makes one) and `--label` / `--label-map` are speaker numbers WITHOUT that offset; a file's
 output is then what `sample_vqvae_uncond.py --whole-file` writes for the file with id 0 under the same scales.
+
+`--voice SPEC` converts everything to a voice given as a spec (vq_voice_swap_amd/speakers.py: "3:0.7,251:0.3" a blend of speakers,
+"@voice.npy" a vector file of `enroll_speaker.py --input-file`), and the second column of `--label-map` may be a spec as well.
+`--anonymize K` gives every top-level directory a voice that is nobody's: `pseudo_voice(--seed, directory, speakers, K)`, a convex blend
+of K speakers that depends on the seed and the directory's name alone; the mapping goes to `out_dir/pseudo_voices.tsv` (a label map this
+script reads back).  A file's output then depends on (checkpoint, flags, --seed, its directory's name, its global id) only, and is what
+`sample_vqvae.py --whole-file --voice <the spec>` writes for the file with id 0.
 """
 import argparse
 import os
@@ -39,6 +46,7 @@ from vq_voice_swap_amd.corpus import add_guidance_flags, deal_packs, guided, lis
 from vq_voice_swap_amd.dataset import build_file_index  # noqa: E402
 from vq_voice_swap_amd.eval_pass import close_ranks, local_device, open_ranks  # noqa: E402
 from vq_voice_swap_amd.longform import plan_windows  # noqa: E402
+from vq_voice_swap_amd.speakers import as_entries, parse_voice, pseudo_voice, voice_vectors  # noqa: E402
 
 SAMPLE_RATE = 16000
 
@@ -72,7 +80,21 @@ def arg_parser():
 def parse_args(argv=None):
     parser = arg_parser()
     add_guidance_flags(parser)  # (they join here: `arg_parser()` stays the flag set of the unguided run, which they leave as it was)
+    # the voice targets join the group of --label / --label-map here, for the same reason; a flag that is not given leaves no
+    # attribute behind (`voice_of` / `anonymize_of` read them), so the namespace of a run without them is what it was
+    target = parser._mutually_exclusive_groups[0]
+    target.add_argument("--voice", type=str, default=argparse.SUPPRESS, metavar="SPEC",
+                        help="the voice every file is converted to: a label, a blend `3:0.7,251:0.3`, a vector file `@voice.npy`")
+    target.add_argument("--anonymize", type=int, default=argparse.SUPPRESS, metavar="K",
+                        help="every top-level directory gets a pseudo-voice blended of K speakers, listed in out_dir/pseudo_voices.tsv")
     args = parser.parse_args(argv)
+    if voice_of(args) is not None:
+        try:
+            parse_voice(args.voice)
+        except ValueError as e:
+            parser.error(str(e))
+    if anonymize_of(args) is not None and not 1 <= args.anonymize <= 8:
+        parser.error("--anonymize takes 1..8 speakers per pseudo-voice")
     if args.sampler != "ddim" and args.eta:
         parser.error("--eta belongs to --sampler ddim (ddpm has its own variance, dpmpp is deterministic)")
     if args.eta < 0:
@@ -84,18 +106,32 @@ def parse_args(argv=None):
     return args
 
 
+def voice_of(args):
+    return getattr(args, "voice", None)
+
+
+def anonymize_of(args):
+    return getattr(args, "anonymize", None)
+
+
 def out_path(out_dir: str, rel: str) -> str:
     return os.path.join(out_dir, os.path.splitext(rel)[0] + ".wav")
 
 
 def plan(args, window: int, hop: int):
-    """Everything that needs no device: (files, labels by id, packs of ids of ALL ranks).  Raises ValueError for a bad label map."""
+    """Everything that needs no device: (files, labels by id, packs of ids of ALL ranks).  Raises ValueError for a bad label map.
+    A label is an int, or a voice spec as text (--voice, a spec in the label map); under --anonymize it is the file's top-level
+    directory for now: `main` turns the directories into pseudo-voices once the checkpoint says how many speakers there are."""
     files = list_files(build_file_index(args.data_dir))
     if args.max_files is not None:
         files = files[:args.max_files]
     if args.label_map is not None:
         mapping = read_label_map(args.label_map, sorted({top_directory(rel) for rel, _ in files}))
         labels = [mapping[top_directory(rel)] for rel, _ in files]
+    elif anonymize_of(args) is not None:
+        labels = [top_directory(rel) for rel, _ in files]
+    elif voice_of(args) is not None:
+        labels = [args.voice] * len(files)
     else:
         labels = [args.label] * len(files)
     ids = [i for i, (rel, _) in enumerate(files) if not (args.skip_existing and os.path.exists(out_path(args.out_dir, rel)))]
@@ -132,10 +168,14 @@ def convert_pack(args, model, enc_pred, device, files, labels, pack, window: int
     for run in make_packs(counts, max(args.pack_windows, max(counts, default=1)), got):
         batch = [torch.from_numpy(waves[i][None, None]).to(device) for i in run]
         codes, run_counts = model.encode_long_batch(batch, window, hop, args.window_batch)
-        target = torch.tensor([labels[i] for i in run]).long().to(device)
         decode, guide_kw = model.decode_long_batch, {}
         if guided(args):  # (labels are not offset here: the guided decode shifts them past the unconditional label itself)
             decode, guide_kw = model.decode_long_batch_uncond_guidance, dict(label_scale=args.guide_label_scale, vq_scale=args.guide_vq_scale)
+        if all(isinstance(labels[i], int) for i in run):
+            target = torch.tensor([labels[i] for i in run]).long().to(device)
+        else:  # voice specs: one vector per recording, made on the device (specs name speakers without the null label's offset)
+            target = None
+            guide_kw["vectors"] = voice_vectors(model.predictor, [labels[i] for i in run], label_offset=1 if guided(args) else 0)
         outs = decode(codes, target, counts=run_counts, num_samples=[b.shape[-1] for b in batch], window=window, hop=hop,
                       steps=args.sample_steps, constrain=True, seed=args.seed, clip_offset=run[0], enc_pred=enc_pred,
                       enc_pred_scale=args.enc_pred_scale, window_batch=args.window_batch, sampler=args.sampler, eta=args.eta, **guide_kw)
@@ -170,7 +210,17 @@ def main(argv=None):
         print(f"{len(files)} files, {sum(len(p) for p in packs)} to convert in {len(packs)} packs; loading model from checkpoint...")
     model = VQVAE.load(args.checkpoint_path)
     speakers = model.num_labels - 1 if guided(args) else model.num_labels  # (guided: label 0 of the checkpoint is the unconditional one)
-    bad = sorted({l for l in labels if not 0 <= l < speakers})
+    if anonymize_of(args) is not None:
+        try:
+            voices = {d: pseudo_voice(args.seed, d, speakers, args.anonymize) for d in sorted(set(labels))}
+        except ValueError as e:
+            raise SystemExit(str(e))
+        labels = [voices[d] for d in labels]
+        if rank == 0:
+            os.makedirs(args.out_dir, exist_ok=True)
+            with open(os.path.join(args.out_dir, "pseudo_voices.tsv"), "w") as f:
+                f.write("".join(f"{d}\t{spec}\n" for d, spec in voices.items()))
+    bad = sorted({l for spec in set(labels) for l, _ in as_entries(spec) if not isinstance(l, str) and not 0 <= l < speakers})
     if bad:
         raise SystemExit(f"labels {bad} outside the model's 0..{speakers - 1}" + (" (speakers, the unconditional label not counted)" if guided(args) else ""))
     model.to(device)

@@ -23,6 +23,12 @@ the model already knows, its directory labels are ignored, and every clip trains
 sample_vqvae_uncond.py and the `--guide-label-scale` of convert_dataset.py / eval_conversion.py expect.  The output directory is then
 ckpt_vqvae_uncond unless `--output-dir` names one; `--init mean` is the start to prefer (the centre of the known speakers); a run never
 resumes the enroll.pt of the other kind.
+
+`--input-file ref.wav` (repeatable) `--vector-out voice.npy`, in place of `data_dir`: a voice from a recording.  The recordings are cut
+into `--seconds` clips (the last partial clip is dropped), ONE row is learned from them with the same `SpeakerEnroller`, and the row is
+written as a voice file (vq_voice_swap_amd/speakers.py: the .npy vector bit for bit, a side-car .json) that `sample_vqvae.py --voice
+@voice.npy` and the other scripts' voice specs read; no checkpoint is written and nothing resumes.  In the directory mode
+`--vectors-out DIR` writes such a file per new speaker (named after its directory) beside the checkpoint.
 """
 import argparse
 import os
@@ -35,6 +41,9 @@ import torch  # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from vq_voice_swap_amd import VQVAE, LossTracker, atomic_save, create_data_loader  # noqa: E402
 from vq_voice_swap_amd.enroll import NullLabelEnroller, SpeakerEnroller  # noqa: E402
+from vq_voice_swap_amd.speakers import save_voice  # noqa: E402
+
+SAMPLE_RATE = 16000
 
 UNCOND_OUTPUT_DIR = "ckpt_vqvae_uncond"
 
@@ -64,10 +73,33 @@ def parse_args(argv=None):
     parser.add_argument("--uncond", action="store_true",
                         help=f"learn the unconditional label (row 0, old speakers one up) from recordings of the known speakers; writes to "
                              f"{UNCOND_OUTPUT_DIR} unless --output-dir is given")
+    # ... and so does the voice-file mode: recordings in place of data_dir, which stops being required on its own
+    for action in parser._actions:
+        if action.dest == "data_dir":
+            action.nargs, action.default = "?", None
+    parser.add_argument("--input-file", action="append", default=[], metavar="WAV",
+                        help="in place of data_dir (repeatable): learn ONE row from these recordings and write it to --vector-out")
+    parser.add_argument("--vector-out", default=None, type=str, metavar="NPY", help="the voice file of the --input-file mode")
+    parser.add_argument("--vectors-out", default=None, type=str, metavar="DIR",
+                        help="directory mode: also write one voice file per new speaker, DIR/<speaker directory>.npy")
     args = parser.parse_args(argv)
     given = parser.parse_args(argv, argparse.Namespace(output_dir=None)).output_dir is not None
     if args.uncond and not given:
         args.output_dir = UNCOND_OUTPUT_DIR
+    if args.input_file:
+        if args.data_dir is not None:
+            parser.error("--input-file takes the place of data_dir: give one or the other")
+        if args.vector_out is None or not args.vector_out.endswith(".npy"):
+            parser.error("--input-file needs --vector-out FILE.npy")
+        if args.uncond or args.vectors_out is not None:
+            parser.error("--input-file learns one speaker's row: --uncond and --vectors-out belong to the directory mode")
+    else:
+        if args.data_dir is None:
+            parser.error("data_dir (or --input-file) is required")
+        if args.vector_out is not None:
+            parser.error("--vector-out belongs to --input-file (the directory mode has --vectors-out DIR)")
+        if args.vectors_out is not None and args.uncond:
+            parser.error("--vectors-out writes the new speakers' rows: --uncond learns none")
     return args
 
 
@@ -126,10 +158,84 @@ def save(enroller: SpeakerEnroller, output_dir: str) -> None:
     atomic_save(enroller.state_dict(), os.path.join(output_dir, "enroll.pt"))
 
 
+def cut_clips(waves, clip: int) -> torch.Tensor:
+    """Recordings (float32 [N_r] arrays) -> [n, 1, clip]: each cut into whole clips from its start, the last partial clip dropped."""
+    clips = [torch.from_numpy(w[i:i + clip].copy()) for w in waves for i in range(0, len(w) - clip + 1, clip)]
+    if not clips:
+        raise ValueError(f"the recordings hold fewer than one clip of {clip} samples")
+    return torch.stack(clips)[:, None]
+
+
+def voice_meta(args, model, enroller, holdout=None) -> dict:
+    meta = dict(base_channels=int(model.predictor.base_channels), steps=int(enroller.steps), pretrained_path=args.pretrained_path)
+    if holdout is not None:
+        meta["holdout_loss"] = float(holdout)
+    return meta
+
+
+def enroll_files(args) -> None:
+    """--input-file: one row from the clips of the recordings, written as a voice file.  Step s takes batch s % per_epoch of pass
+    s // per_epoch of `epoch_batches` over the clips (the held-out ones left out), keyed as the directory mode keys its steps."""
+    from vq_voice_swap_amd.audio import ChunkReader
+
+    waves = []
+    for path in args.input_file:
+        reader = ChunkReader(path, sample_rate=SAMPLE_RATE, encoding=args.encoding)
+        try:
+            chunks = []
+            while (chunk := reader.read(1 << 20)) is not None:
+                chunks.append(chunk)
+        finally:
+            reader.close()
+        if chunks:
+            import numpy as np
+
+            waves.append(np.concatenate(chunks))
+    try:
+        clips = cut_clips(waves, round(args.seconds * SAMPLE_RATE))
+        held_idx, train_idx = split_holdout(len(clips), args.holdout, args.seed)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if not train_idx:
+        raise SystemExit(f"--holdout {args.holdout} leaves no clip to train on ({len(clips)} clips)")
+    batch_size = min(args.batch_size, len(train_idx))
+    per_epoch = len(train_idx) // batch_size
+    print(f"loading from pretrained model: {args.pretrained_path} ...")
+    model = VQVAE.load(args.pretrained_path)
+    if model.num_labels is None:
+        raise SystemExit("the pretrained model is not class-conditional: a voice is a vector in the place of its class_embed rows")
+    device = local_device()
+    model.to(device).eval()
+    clips = clips.to(device)
+    print(f"{len(clips)} clips of {args.seconds} s from {len(waves)} recordings: learning one row in batches of {batch_size}")
+    enroller = SpeakerEnroller(model, 1, lr=args.lr, weight_decay=args.weight_decay, init=parse_init(args.init), seed=args.seed)
+    tracker = LossTracker()
+    while enroller.steps < args.steps:
+        epoch, at = divmod(enroller.steps, per_epoch)
+        for batch in epoch_batches(train_idx, batch_size, args.seed, epoch)[at:]:
+            out = enroller.step(clips[batch], torch.zeros(len(batch), dtype=torch.int64, device=device), seed=args.seed,
+                                clip_offset=enroller.steps * batch_size)
+            tracker.add(out["ts"], out["mses"])
+            quartiles = " ".join(f"{k}={v:.6f}" for k, v in tracker.log_dict().items())
+            print(f"step {enroller.steps}: loss={out['loss'].item():.6f} {quartiles}")
+            if enroller.steps == args.steps:
+                break
+    held = None
+    if held_idx:
+        held = holdout_loss(enroller, clips[held_idx], torch.zeros(len(held_idx), dtype=torch.int64, device=device), batch_size, args.seed + 1)
+        print(f"step {enroller.steps}: holdout={held:.6f} ({len(held_idx)} clips)")
+    model.predictor.check_status()
+    os.makedirs(os.path.dirname(args.vector_out) or ".", exist_ok=True)
+    save_voice(args.vector_out, enroller.rows[0], voice_meta(args, model, enroller, held))
+    print(f"wrote {args.vector_out}: a voice of {enroller.rows.shape[1]} entries")
+
+
 def main(argv=None):
     args = parse_args(argv)
     if args.steps < 0 or args.save_interval < 1 or args.holdout < 0:
         raise SystemExit("--steps and --holdout must not be negative, --save-interval must be positive")
+    if args.input_file:
+        return enroll_files(args)
     if args.data_dir == "tones" and args.seconds != 4.0:
         raise SystemExit("the synthetic set 'tones' has clips of 4 s: --seconds does not apply to it")
     loader_kw = {} if args.data_dir == "tones" else dict(window_duration=args.seconds)
@@ -194,6 +300,13 @@ def main(argv=None):
     if args.steps == 0:
         save(enroller, args.output_dir)
     model.predictor.check_status()
+    if args.vectors_out is not None:
+        os.makedirs(args.vectors_out, exist_ok=True)
+        names = [str(s) for s in dataset.speaker_ids]
+        last_held = holdout_loss(enroller, held, held_rows, args.batch_size, args.seed + 1) if held is not None else None
+        for k in range(num_new):
+            save_voice(os.path.join(args.vectors_out, f"{names[k]}.npy"), enroller.rows[k], voice_meta(args, model, enroller, last_held))
+        print(f"wrote {num_new} voice files to {args.vectors_out}")
     if args.uncond:
         print(f"wrote {os.path.join(args.output_dir, 'model.pt')}: the unconditional label and {old_count} speakers")
     else:

@@ -31,6 +31,10 @@ unconditional label at 0 (`enroll_speaker.py --uncond` makes one: one label more
 data's labels are speaker numbers WITHOUT that offset, as the classifier counts them.  The line is the usual one: run it at several S
 with `--classifier` to see what a scale does to target_acc, target_nll, mcd and code_match.
 
+`--voice SPEC` in place of `--target` converts every clip to a voice spec (vq_voice_swap_amd/speakers.py: a blend "3:0.7,251:0.3", a
+vector file "@voice.npy"); a spec that is one label is `--target N`.  A blend or a file is nobody's label, so with `--classifier` only
+source_acc is printed for it: target_acc and target_nll need a label to score against.
+
 `data_dir`, `--batch-size`, `--precision`, `--seed`, `--max-samples` and `--dist-backend` are the common parser's and the pass is
 the shared one (vq_voice_swap_amd/eval_pass.py).  Under torchrun (WORLD_SIZE > 1) batches are dealt round-robin, rank 0 merges
 the states and prints the one final line.
@@ -49,6 +53,7 @@ from eval_vqvae import wrong_labels  # noqa: E402
 from vq_voice_swap_amd import VQVAE, Classifier, PitchDistance, SpectralDistance, randn_clips  # noqa: E402
 from vq_voice_swap_amd.corpus import add_guidance_flags, guided  # noqa: E402
 from vq_voice_swap_amd.eval_pass import common_parser, format_line, run_pass  # noqa: E402,F401
+from vq_voice_swap_amd.speakers import as_entries, parse_voice, single_label, voice_vectors  # noqa: E402
 
 SAMPLERS = ["ddpm", "ddim", "dpmpp"]
 
@@ -71,7 +76,20 @@ def parse_args(argv=None):
     # the opt-in scores join the parser here: `arg_parser()` stays the flag set the default line is made of
     parser.add_argument("--pitch", action="store_true", help="add F0 scores (YIN on the 16-bit samples): register shift, contour deviation, voicing errors")
     add_guidance_flags(parser)
+    parser.add_argument("--voice", type=str, default=None, metavar="SPEC",
+                        help="convert every clip to this voice spec instead of --target: a blend `3:0.7,251:0.3`, a vector file `@voice.npy`")
     args = parser.parse_args(argv)
+    if args.voice is not None:
+        import argparse
+
+        if parser.parse_args(argv, argparse.Namespace(target=None)).target is not None:
+            parser.error("--voice takes the place of --target: give one or the other")
+        try:
+            parse_voice(args.voice)
+        except ValueError as e:
+            parser.error(str(e))
+        if single_label(args.voice) is not None:  # (one label at weight 1 IS --target N, classifier scores included)
+            args.target, args.voice = str(single_label(args.voice)), None
     if args.sampler != "ddim" and args.eta:
         parser.error("--eta belongs to --sampler ddim (ddpm has its own variance, dpmpp is deterministic)")
     if args.eta < 0:
@@ -88,8 +106,13 @@ def parse_args(argv=None):
     return args
 
 
-def check_target(target, num_labels: int) -> None:
+def check_target(target, num_labels: int, voice=None) -> None:
     """The refusals that need the label count (known from the data, before the model loads)."""
+    if voice is not None:
+        bad = sorted({l for l, _ in as_entries(voice) if not isinstance(l, str) and not 0 <= l < num_labels})
+        if bad:
+            raise SystemExit(f"--voice {voice!r}: labels {bad} are outside the labels 0..{num_labels - 1}")
+        return
     if target == "other" and num_labels < 2:
         raise SystemExit(f"--target other needs at least two labels, the data has {num_labels}")
     if isinstance(target, int) and not 0 <= target < num_labels:
@@ -119,10 +142,12 @@ class EvalState:
     """What one pass accumulates: clip, code and frame counts, the agreeing codes (integers) and the distance sums (fractions of
     the clips' float64 sums: the same whatever order batches and shards arrive in); with a reference run the same for it and for
     the gap between the two runs; with a classifier its hits and summed NLL; with pitch the voicing counts, the summed pitch
-    distance and the summed squared deviation around each clip's own mean."""
+    distance and the summed squared deviation around each clip's own mean.  `voice`: the target is a voice spec that is no single
+    label, so there is no label to score the classifier against: target_correct / target_nll are left out."""
 
-    def __init__(self, reference: bool = False, classifier: bool = False, same: bool = False, pitch: bool = False):
+    def __init__(self, reference: bool = False, classifier: bool = False, same: bool = False, pitch: bool = False, voice: bool = False):
         self.reference, self.classifier, self.same, self.pitch = bool(reference), bool(classifier), bool(same), bool(pitch)
+        self.voice = bool(voice)
         self.num_samples = 0
         self.codes = 0    # code positions behind the *_match counts
         self.frames = 0   # frames behind the distance sums
@@ -143,7 +168,7 @@ class EvalState:
         if self.reference:
             want |= {"ref_code_match", "ref_mcd", "ref_lsd", "gap_mcd", "gap_lsd"}
         if self.classifier:
-            want |= {"target_correct", "target_nll"} | (set() if self.same else {"source_correct"})
+            want |= (set() if self.voice else {"target_correct", "target_nll"}) | (set() if self.same else {"source_correct"})
         prefixes = (("", "ref_", "gap_") if self.reference else ("",)) if self.pitch else ()
         want |= {p + k for p in prefixes for k in ("f0_n", "f0_s1", "f0_s2", "vuv", "voiced")}
         if set(scores) != want or any(len(v) != n for v in scores.values()):
@@ -172,7 +197,11 @@ class EvalState:
             raise ValueError("a state with pitch=True needs a PitchDistance")
         # under guidance label 0 of the checkpoint is the unconditional one: the speakers, and every label here, are counted without it
         guide = guided(run)
-        target = target_labels(labels, run.target, model.num_labels - 1 if guide else model.num_labels, seed, first)
+        voice = getattr(run, "voice", None)
+        if voice is None:
+            target = dict(labels=target_labels(labels, run.target, model.num_labels - 1 if guide else model.num_labels, seed, first))
+        else:  # (the spec names speakers without the null label's offset, as --target does)
+            target = dict(vectors=voice_vectors(model.predictor, [voice], label_offset=1 if guide else 0).expand(len(audio), -1))
         codes = model.encode(audio)
         # the draw `decode` would make itself from (seed, clip_offset): made here so that the reference run starts from the same x_T
         x_T = randn_clips(len(audio), codes.shape[-1] * model.encoder.downsample_rate, audio.device, seed, first)
@@ -180,8 +209,8 @@ class EvalState:
         def decode(sampler, steps):
             kw = dict(steps=steps, constrain=True, x_T=x_T, sampler=sampler, eta=run.eta if sampler == "ddim" else 0.0, seed=seed, clip_offset=first)
             if guide:
-                return model.decode_uncond_guidance(codes, target, label_scale=run.guide_label_scale, vq_scale=run.guide_vq_scale, **kw)
-            return model.decode(codes, target, **kw)
+                return model.decode_uncond_guidance(codes, **target, label_scale=run.guide_label_scale, vq_scale=run.guide_vq_scale, **kw)
+            return model.decode(codes, **target, **kw)
 
         def against_source(out, prefix=""):
             d = distance(audio, out)
@@ -202,14 +231,15 @@ class EvalState:
                 scores.update(_pitch_scores(pitch(converted, ref), "gap_"))
         if self.classifier:
             ts = torch.zeros(len(audio), device=audio.device)
-            out = classifier.scores(converted, ts, target)
-            scores.update(target_correct=out["top1"].tolist(), target_nll=out["nll"].tolist())
+            if not self.voice:
+                out = classifier.scores(converted, ts, target["labels"])
+                scores.update(target_correct=out["top1"].tolist(), target_nll=out["nll"].tolist())
             if not self.same:
                 scores.update(source_correct=classifier.scores(converted, ts, labels)["top1"].tolist())
         self.add_scores(codes.shape[-1], distance.frames(audio.shape[-1]), scores)
 
     def merge(self, other: "EvalState") -> "EvalState":
-        if (other.reference, other.classifier, other.same, other.pitch) != (self.reference, self.classifier, self.same, self.pitch):
+        if (other.reference, other.classifier, other.same, other.pitch, other.voice) != (self.reference, self.classifier, self.same, self.pitch, self.voice):
             raise ValueError("cannot merge states of differently configured passes")
         self.num_samples += other.num_samples
         self.codes += other.codes
@@ -232,8 +262,9 @@ class EvalState:
             for key in ("ref_mcd", "ref_lsd", "gap_mcd", "gap_lsd"):
                 log[key] = per(self.sums[key], self.frames)
         if self.classifier:
-            log["target_acc"] = per(self.counts["target_correct"], self.num_samples)
-            log["target_nll"] = per(self.sums["target_nll"], self.num_samples)
+            if not self.voice:
+                log["target_acc"] = per(self.counts["target_correct"], self.num_samples)
+                log["target_nll"] = per(self.sums["target_nll"], self.num_samples)
             if not self.same:
                 log["source_acc"] = per(self.counts["source_correct"], self.num_samples)
         if self.pitch:
@@ -268,12 +299,12 @@ def main(argv=None):
             classifier.eval().set_precision(args.precision)
         distance, pitch = SpectralDistance(), PitchDistance() if args.pitch else None
         state = EvalState(reference=args.reference_steps is not None, classifier=classifier is not None, same=args.target == "same",
-                          pitch=args.pitch)
+                          pitch=args.pitch, voice=args.voice is not None)
         return state, lambda audio, data_batch, first: state.add_batch(model, distance, audio, data_batch["label"].to(device), first, args.seed,
                                                                         args, classifier, pitch)
 
     run_pass(args, build, no_device="the encoder, the decoder and the distance kernel have no CPU path",
-             check_data=lambda num_labels: check_target(args.target, num_labels))
+             check_data=lambda num_labels: check_target(args.target, num_labels, args.voice))
 
 
 if __name__ == "__main__":

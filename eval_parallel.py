@@ -7,7 +7,8 @@ Score voice conversions against PARALLEL target recordings on MI355X: the standa
     torchrun --nproc-per-node 8 eval_parallel.py pairs.tsv data/ --checkpoint model_vqvae.pt
 
 `pairs.tsv` holds lines `source<TAB>target<TAB>label`: two recordings of the SAME sentence, read by the source and by the target
-speaker (paths relative to `data_dir`; CMU Arctic or VCTK style), and the target speaker's label.  The converted source is
+speaker (paths relative to `data_dir`; CMU Arctic or VCTK style), and the target speaker's label -- or a voice spec in its place
+(vq_voice_swap_amd/speakers.py: a blend "3:0.7,251:0.3", a vector file "@voice.npy" fitted to the target).  The converted source is
 compared with the target speaker's own recording, aligned by dynamic time warping under the mel-cepstral cost because the two
 readings differ in timing (`AlignedDistance`: `vqvs_mel_cepstra` and `vqvs_dtw_distance`), and the
 unconverted source is scored the same way: the number a conversion has to beat.
@@ -48,6 +49,7 @@ from vq_voice_swap_amd.corpus import deal_packs, make_packs  # noqa: E402
 from vq_voice_swap_amd.dtw import MAX_FRAMES, AlignedDistance  # noqa: E402
 from vq_voice_swap_amd.eval_pass import close_ranks, local_device, open_ranks  # noqa: E402
 from vq_voice_swap_amd.longform import plan_windows  # noqa: E402
+from vq_voice_swap_amd.speakers import parse_voice, voice_vectors  # noqa: E402
 
 SAMPLE_RATE = 16000
 SIDES = ("", "src_")  # converted against target, source against target
@@ -113,7 +115,7 @@ def sample_limits(spectral: SpectralDistance):
 
 def read_pairs(path: str, data_dir: str, *, num_labels=None, converted_dir=None, max_pairs=None, limits=None, length=None):
     """`pairs.tsv` -> [(source, target, label, source samples)].  Blank lines and lines starting with # are skipped.  ValueError with
-    `path:line` for a line that is not `source<TAB>target<TAB>label`, a label that is no non-negative integer or lies outside
+    `path:line` for a line that is not `source<TAB>target<TAB>label`, a label that is neither a non-negative integer nor a voice spec (kept as text) or lies outside
     0..num_labels-1, a file (source, target or, with `converted_dir`, the converted one) that is missing, cannot be read, or holds
     fewer than limits[0] or more than limits[1] samples.  `length(path)` returns a file's sample count (default: it is read)."""
     limits = sample_limits(SpectralDistance()) if limits is None else limits
@@ -131,11 +133,17 @@ def read_pairs(path: str, data_dir: str, *, num_labels=None, converted_dir=None,
             if len(fields) != 3 or not fields[0] or not fields[1]:
                 raise ValueError(f"{where}: expected `source<TAB>target<TAB>label`, got {line!r}")
             source, target, text = fields
-            if not text.isdigit():
-                raise ValueError(f"{where}: label {text!r} is not a non-negative integer")
-            label = int(text)
-            if num_labels is not None and label >= num_labels:
-                raise ValueError(f"{where}: label {label} outside the model's 0..{num_labels - 1}")
+            if text.isdigit():
+                label, named = int(text), [int(text)]
+            else:  # a voice spec in the label's place: kept as text, its labels held to the model's like any other
+                try:
+                    named = [l for l, _ in parse_voice(text) if not isinstance(l, str)]
+                except ValueError as e:
+                    raise ValueError(f"{where}: label {text!r} is not a non-negative integer or a voice spec ({e})") from None
+                label = text
+            for l in named:
+                if num_labels is not None and l >= num_labels:
+                    raise ValueError(f"{where}: label {l} outside the model's 0..{num_labels - 1}")
             files = [os.path.join(data_dir, source), os.path.join(data_dir, target)]
             if converted_dir is not None:
                 files.append(converted_path(converted_dir, source))
@@ -253,8 +261,11 @@ def convert_run(args, model, device, waves, labels, first: int, window: int, hop
     """Recordings with consecutive ids first, first + 1, ... -> what convert_dataset.py's files hold for them once read back."""
     batch = [torch.from_numpy(w[None, None]).to(device) for w in waves]
     codes, counts = model.encode_long_batch(batch, window, hop, args.window_batch)
-    target = torch.tensor(labels).long().to(device)
-    outs = model.decode_long_batch(codes, target, counts=counts, num_samples=[b.shape[-1] for b in batch], window=window, hop=hop,
+    if all(isinstance(l, int) for l in labels):
+        target = dict(labels=torch.tensor(labels).long().to(device))
+    else:  # voice specs: one vector per recording, made on the device
+        target = dict(vectors=voice_vectors(model.predictor, labels))
+    outs = model.decode_long_batch(codes, **target, counts=counts, num_samples=[b.shape[-1] for b in batch], window=window, hop=hop,
                                    steps=args.sample_steps, constrain=True, seed=args.seed, clip_offset=first, window_batch=args.window_batch,
                                    sampler=args.sampler, eta=args.eta)
     return [wav_roundtrip(out.reshape(-1), "linear") for out in outs]

@@ -143,6 +143,21 @@ int64_t vqvs_model_device_bytes(const vqvs_model* m);
 int vqvs_unet_forward(vqvs_model* m, const float* d_x, const float* d_ts, const float* d_cond,
                       const int64_t* d_labels, float* d_out, int B, int T, void* stream);
 
+/* The same forward with an EXPLICIT conditioning vector per clip in place of class_embed[labels[b]]: the embedding is
+ * emb = time_mlp(t) + v (unet.py:133-135), so any v is a voice -- a blend of rows, a vector fitted to a recording.
+ * VQVS_KIND_PREDICTOR handles with num_labels > 0, every precision mode.
+ *   d_vec [B,E] f32, E = 4 * base_channels OF THE HANDLE (the physical width): on a padded handle (cfg.reserved[4]) the real
+ *         entries sit where class_embed.weight's columns sit (entry c at (c / q) * q_p + c % q) and the rest are zero
+ *   everything else as vqvs_unet_forward
+ * The schedule is vqvs_unet_forward's with one argument changed: time_embed adds d_vec[b][r] where it adds class_embed[label][r], one
+ * fp32 add of the same value in the same position.  So with d_vec[b] == class_embed[labels[b]] the result equals
+ * vqvs_unet_forward(..., d_labels, ...) bit for bit in every precision mode, and in fp32 the forward-only form of
+ * vqvs_unet_embed_grad.
+ * VQVS_ERR_ARG before the device is touched: NULL d_x, d_ts, d_vec or d_out; d_cond not matching cfg; a handle of another kind or
+ * with num_labels == 0; B or T outside the handle's limits. */
+int vqvs_unet_forward_vec(vqvs_model* m, const float* d_x, const float* d_ts, const float* d_cond,
+                          const float* d_vec, float* d_out, int B, int T, void* stream);
+
 /* z = UNetEncoder.forward(x)   reference unet.py:229-241
  *   d_x [B,in_channels,T] f32 -> d_z [B,out_channels,T/downsample_rate] f32 (NCT) */
 int vqvs_encoder_forward(vqvs_model* m, const float* d_x, float* d_z, int B, int T, void* stream);
@@ -350,6 +365,18 @@ int vqvs_ddpm_guided_eps(const float* d_x_t, const float* d_mean, const float* d
  * VQVS_ERR_ARG before the device is touched: NULL d_outs or d_eps; rows < 1; row_len < 1; reps outside 1..3; d_eps overlapping
  * d_outs in any other way (blocks 1 or 2, or block 0 at an offset). */
 int vqvs_guidance_mix(const float* d_outs, float* d_eps, int rows, int64_t row_len, int reps, float s1, float s2, void* stream);
+/* ---- Speaker mix (handle-less): conditioning vectors for vqvs_unet_forward_vec made on the device from rows of a table ----
+ *   d_table [K,E] f32   the rows (class_embed.weight, possibly with further rows behind it)
+ *   d_idx   [B,J] int32 row indices; a NEGATIVE index marks an unused slot      d_w [B,J] f32 weights
+ *   d_out   [B,E] f32:  out[b][e] = sum over the used slots j, in slot order, of w[b][j] * table[idx[b][j]][e]
+ * Every product and every sum is an fp32 operation rounded on its own (contraction off, as in vqvs_guidance_mix), and the first used
+ * slot's product is the initial value -- nothing is added to a zero.  A float32 restatement on the host gives the same bits; one used
+ * slot of weight 1 copies the row bit for bit.  A row without a used slot is all zeros.  An index >= K reads row K - 1 (never outside
+ * the table; callers are expected to have checked).  One thread per four entries of a row, 16 bytes per access when E % 4 == 0 and
+ * d_table and d_out are 16-byte aligned, one float at a time otherwise; the grid strides over B.
+ * VQVS_ERR_ARG before the device is touched: a NULL pointer; K, E or B below 1; J outside 1..16; d_out overlapping an input. */
+int vqvs_speaker_mix(const float* d_table, int K, int E, const int32_t* d_idx, const float* d_w, int J,
+                     float* d_out, int B, void* stream);
 /* ---- DDIM step (handle-less; Song, Meng, Ermon: "Denoising diffusion implicit models", 2020 -- the reference has no counterpart) ----
  * One step from the time the state is at, alpha_bar = a_t, to the time stepped TO, alpha_bar = a_to, of B rows of T samples:
  *   e    = eps                       or, with d_grad, e = fmaf(-sqrt(1-a_t), grad, eps): a cond_fn's gradient at (x_t, t) enters the

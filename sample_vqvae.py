@@ -8,6 +8,9 @@ sample_vqvae.py (same flags and positionals; reference sample_vqvae.py:76-92): r
 `--source-label L` it starts from `VQVAE.invert` of the input under its own codes and label L instead of from a fresh draw.
 `--keep START:END` (seconds, repeatable) leaves those ranges of the input as they are and converts the rest around them;
 `--strength S` below 1 starts from the noised input instead of from pure noise.  Both work with either sampler and with `--whole-file`.
+`--voice SPEC` in place of `--label` names the target as a voice spec (vq_voice_swap_amd/speakers.py): "3:0.7,251:0.3" blends speakers,
+"@voice.npy" is a vector fitted to a recording by `enroll_speaker.py --input-file`.  `--voice-at SEC:SPEC` (two or more, with
+`--whole-file`) moves the voice along the file: each window takes the voice at its centre, interpolated between the points.
 Differences: WAV in/out directly (no ffmpeg); the model is put in eval mode (the reference's train-mode VQ
 bookkeeping crashes on current numpy; outputs are identical).  `--enc-pred-path` loads an
 EncoderPredictor whose guidance gradient comes from the library's explicit backward schedule (no autograd).
@@ -24,6 +27,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from vq_voice_swap_amd import VQVAE, EncoderPredictor  # noqa: E402
 from vq_voice_swap_amd.audio import ChunkReader, ChunkWriter, keep_mask, parse_keep_range  # noqa: E402
+from vq_voice_swap_amd.speakers import as_entries, morph_vectors, parse_voice, voice_vectors  # noqa: E402
 
 
 def arg_parser(sampler_flags: bool = False, keep_flags: bool = False):
@@ -62,9 +66,72 @@ def arg_parser(sampler_flags: bool = False, keep_flags: bool = False):
     return p
 
 
+def add_voice_flags(parser) -> None:
+    """--voice / --voice-at beside --label, which stops being required on its own: `check_voice_flags` asks for exactly one target.
+    (They join in `parse_args`: `arg_parser()` stays the flag set it was.)"""
+    for action in parser._actions:
+        if "--label" in action.option_strings:
+            action.required = False
+    parser.add_argument("--voice", type=str, default=None, metavar="SPEC",
+                        help="the target as a voice spec instead of --label: a label, a blend `3:0.7,251:0.3`, a vector file `@voice.npy`")
+    parser.add_argument("--voice-at", action="append", default=[], metavar="SEC:SPEC",
+                        help="with --whole-file, two or more times: the voice at that second of the file; windows between two points blend them")
+
+
+def check_voice_flags(parser, args) -> None:
+    """Exactly one of --label / --voice / --voice-at; args.voice_at becomes the sorted-as-given [(seconds, spec)]."""
+    points = []
+    for text in args.voice_at:
+        sec, sep, spec = text.partition(":")
+        try:
+            if not sep:
+                raise ValueError(f"--voice-at {text!r}: expected SEC:SPEC")
+            parse_voice(spec)
+            points.append((float(sec), spec))
+        except ValueError as e:
+            parser.error(str(e) if "voice" in str(e) else f"--voice-at {text!r}: {sec!r} is not a number of seconds")
+    args.voice_at = points
+    if (args.label is not None) + (args.voice is not None) + bool(points) != 1:
+        parser.error("give exactly one target: --label, --voice or --voice-at")
+    if args.voice is not None:
+        try:
+            parse_voice(args.voice)
+        except ValueError as e:
+            parser.error(str(e))
+    if points:
+        if not args.whole_file:
+            parser.error("--voice-at moves the voice along a whole file: it needs --whole-file")
+        if len(points) < 2:
+            parser.error("--voice-at needs at least two points (one voice for the whole file is --voice)")
+        if any(b[0] <= a[0] for a, b in zip(points, points[1:])) or points[0][0] < 0:
+            parser.error("--voice-at points must be given in order of strictly increasing, non-negative seconds")
+
+
+def check_voice_labels(args, speakers: int) -> None:
+    """The labels that --label / --voice / --voice-at name against the model's speaker count (before any device work)."""
+    specs = [args.label] if args.label is not None else [args.voice] if args.voice is not None else [spec for _, spec in args.voice_at]
+    bad = sorted({l for spec in specs for l, _ in as_entries(spec) if not isinstance(l, str) and not 0 <= l < speakers})
+    if bad:
+        raise SystemExit(f"labels {bad} outside the model's speakers 0..{speakers - 1}")
+
+
+def target_kwargs(args, model, device, label_offset: int = 0, windows=None):
+    """The decode keywords that name the target: labels= for --label, vectors= for --voice ([1,E]) and --voice-at (`windows` =
+    (n, window, hop): [n,E], one per window).  `label_offset` 1: a checkpoint with the null label in front, for the VECTORS only --
+    the guided decode offsets labels itself."""
+    if args.voice_at:
+        n, window, hop = windows
+        return dict(vectors=morph_vectors(model.predictor, args.voice_at, n, window, hop, args.sample_rate, label_offset))
+    if args.voice is not None:
+        return dict(vectors=voice_vectors(model.predictor, [args.voice], label_offset))
+    return dict(labels=torch.tensor([args.label]).long().to(device))
+
+
 def parse_args(argv=None):
     parser = arg_parser(sampler_flags=True, keep_flags=True)
+    add_voice_flags(parser)
     args = parser.parse_args(argv)
+    check_voice_flags(parser, args)
     if args.sampler != "ddim" and args.eta:
         parser.error("--eta belongs to --sampler ddim (ddpm has its own variance, dpmpp is deterministic)")
     if args.eta < 0:
@@ -103,7 +170,7 @@ def main(argv=None):
     args = parse_args(argv)
     print("loading model from checkpoint...")
     model = VQVAE.load(args.checkpoint_path)
-    assert args.label < model.num_labels
+    check_voice_labels(args, model.num_labels)
     assert args.source_label is None or 0 <= args.source_label < model.num_labels
     if not torch.cuda.is_available():
         raise SystemExit("no ROCm device visible: the sampler has no CPU path")
@@ -135,12 +202,11 @@ def main(argv=None):
     encoded = model.encoder(in_seq) if args.no_vq else model.encode(in_seq)
 
     print("decoding audio samples...")
-    labels = torch.tensor([args.label]).long().to(device)
     x_T = None
     if args.source_label is not None:
         print("inverting the input to its latent...")
         x_T = model.invert(in_seq, torch.tensor([args.source_label]).long().to(device), steps=args.sample_steps, codes=encoded)
-    sample = model.decode(encoded, labels, steps=args.sample_steps, progress=True, constrain=True, seed=args.seed,
+    sample = model.decode(encoded, **target_kwargs(args, model, device), steps=args.sample_steps, progress=True, constrain=True, seed=args.seed,
                           enc_pred=enc_pred, enc_pred_scale=args.enc_pred_scale, x_T=x_T, sampler=args.sampler, eta=args.eta,
                           **source_kwargs(args, in_seq))
 
@@ -180,8 +246,8 @@ def convert_whole_file(args, model, enc_pred, device):
     encoded = model.encode_long(wave, window, hop, args.window_batch)
 
     print(f"decoding {encoded.shape[0]} windows...")
-    labels = torch.tensor([args.label]).long().to(device)
-    sample = model.decode_long(encoded, labels, num_samples=num_samples, window=window, hop=hop, steps=args.sample_steps, progress=True,
+    target = target_kwargs(args, model, device, windows=(encoded.shape[0], window, hop))
+    sample = model.decode_long(encoded, **target, num_samples=num_samples, window=window, hop=hop, steps=args.sample_steps, progress=True,
                                constrain=True, seed=args.seed, enc_pred=enc_pred, enc_pred_scale=args.enc_pred_scale,
                                window_batch=args.window_batch, sampler=args.sampler, eta=args.eta, **source_kwargs(args, wave))
 

@@ -9,7 +9,8 @@ eval mode; `--seed`, `--precision`, `--sampler {ddpm,ddim,dpmpp}` and `--eta` ar
 batch only lines up when both are non-zero, vq_vae.py:188-203).  `--whole-file`, `--window-seconds`, `--overlap-seconds`,
 `--window-batch`, `--keep` and `--strength` are sample_vqvae.py's, with its meanings and defaults: the whole input through
 `encode_long` / `decode_long_uncond_guidance`, regions of the input left as they are, a start from the noised input.  `--schedule`
-works with all of them (every sampling loop takes it).
+works with all of them (every sampling loop takes it).  `--voice SPEC` and `--voice-at SEC:SPEC` are sample_vqvae.py's too; their
+specs name speakers as `--label` does here, without the null label's offset.
 """
 import argparse
 import os
@@ -21,7 +22,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from sample_vqvae import source_kwargs  # noqa: E402
+from sample_vqvae import add_voice_flags, check_voice_flags, check_voice_labels, source_kwargs, target_kwargs  # noqa: E402
 from vq_voice_swap_amd import VQVAE  # noqa: E402
 from vq_voice_swap_amd.audio import ChunkReader, ChunkWriter, parse_keep_range, parse_time_schedule  # noqa: E402
 
@@ -59,7 +60,9 @@ def arg_parser():
 
 def parse_args(argv=None):
     parser = arg_parser()
+    add_voice_flags(parser)
     args = parser.parse_args(argv)
+    check_voice_flags(parser, args)
     if args.sampler != "ddim" and args.eta:
         parser.error("--eta belongs to --sampler ddim (ddpm has its own variance, dpmpp is deterministic)")
     if args.eta < 0:
@@ -91,7 +94,7 @@ def main(argv=None):
     schedule = parse_time_schedule(args.schedule)
     print("loading model from checkpoint...")
     model = VQVAE.load(args.checkpoint_path)
-    assert args.label + 1 < model.num_labels
+    check_voice_labels(args, model.num_labels - 1)  # (label 0 of the checkpoint is the unconditional one)
     if not torch.cuda.is_available():
         raise SystemExit("no ROCm device visible: the sampler has no CPU path")
     device = torch.device("cuda")
@@ -115,8 +118,7 @@ def main(argv=None):
     encoded = model.encoder(in_seq) if args.no_vq else model.encode(in_seq)
 
     print("decoding audio samples...")
-    labels = torch.tensor([args.label]).long().to(device)
-    sample = model.decode_uncond_guidance(encoded, labels, steps=args.sample_steps, progress=True, constrain=True,
+    sample = model.decode_uncond_guidance(encoded, **target_kwargs(args, model, device, label_offset=1), steps=args.sample_steps, progress=True, constrain=True,
                                           label_scale=args.guide_label_scale, vq_scale=args.guide_vq_scale, schedule=schedule,
                                           seed=args.seed, sampler=args.sampler, eta=args.eta, **source_kwargs(args, in_seq))
 
@@ -150,8 +152,8 @@ def convert_whole_file(args, model, schedule, device):
     encoded = model.encode_long(wave, window, hop, args.window_batch)
 
     print(f"decoding {encoded.shape[0]} windows...")
-    labels = torch.tensor([args.label]).long().to(device)
-    sample = model.decode_long_uncond_guidance(encoded, labels, label_scale=args.guide_label_scale, vq_scale=args.guide_vq_scale,
+    target = target_kwargs(args, model, device, label_offset=1, windows=(encoded.shape[0], window, hop))
+    sample = model.decode_long_uncond_guidance(encoded, **target, label_scale=args.guide_label_scale, vq_scale=args.guide_vq_scale,
                                                num_samples=num_samples, window=window, hop=hop, steps=args.sample_steps, progress=True,
                                                constrain=True, seed=args.seed, window_batch=args.window_batch, sampler=args.sampler,
                                                eta=args.eta, schedule=schedule, **source_kwargs(args, wave))

@@ -19,6 +19,7 @@ from .enroll import ClassifierEnroller, NullLabelEnroller, SpeakerEnroller
 from .longform import plan_pack, plan_windows
 from .losses import LossTracker, classification_scores, speaker_search_losses
 from .pitch import PitchDistance
+from .speakers import load_voice, morph_vectors, parse_voice, pseudo_voice, save_voice, speaker_mix, voice_vectors
 from .spectral import SpectralDistance, spectral_constants
 from .stats import FeatureStats, class_score, frechet_distance, wav_roundtrip
 from .unet import ResBlockModule, UNetEncoder, UNetPredictor
@@ -32,4 +33,5 @@ __all__ = [
     "StandardVQLoss", "VQLoss", "code_usage", "classification_scores", "plan_windows", "plan_pack",
     "SpectralDistance", "spectral_constants", "PitchDistance", "SpeakerEnroller", "ClassifierEnroller",
     "AlignedDistance", "dtw_distance", "NullLabelEnroller", "guidance_mix",
+    "parse_voice", "voice_vectors", "morph_vectors", "pseudo_voice", "save_voice", "load_voice", "speaker_mix",
 ]

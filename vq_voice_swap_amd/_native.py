@@ -76,7 +76,7 @@ EXPORTS = [
     "vqvs_debug_tap_info", "vqvs_debug_tap_rows", "vqvs_debug_read_tap", "vqvs_debug_read_embedding", "vqvs_forward_kernel_count", "vqvs_forward_model_bytes",
     "vqvs_forward_flops", "vqvs_set_profiling", "vqvs_op_info", "vqvs_op_desc", "vqvs_profile_read", "vqvs_last_error", "vqvs_version",
     "vqvs_unet_embed_grad", "vqvs_embed_adamw", "vqvs_debug_read_dfilm", "vqvs_head_xent_grad", "vqvs_head_adamw",
-    "vqvs_mel_cepstra", "vqvs_dtw_distance", "vqvs_guidance_mix",
+    "vqvs_mel_cepstra", "vqvs_dtw_distance", "vqvs_guidance_mix", "vqvs_unet_forward_vec", "vqvs_speaker_mix",
 ]
 
 _lib = None
@@ -131,6 +131,7 @@ def lib():
     L.vqvs_model_device_bytes.argtypes = [vp]
     L.vqvs_model_device_bytes.restype = i64
     L.vqvs_unet_forward.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp]
+    L.vqvs_unet_forward_vec.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp]
     L.vqvs_unet_embed_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
     L.vqvs_embed_adamw.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp]
     L.vqvs_debug_read_dfilm.argtypes = [vp, i32, vp]
@@ -161,6 +162,7 @@ def lib():
     L.vqvs_ddpm_mean.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
     L.vqvs_ddpm_guided_eps.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, u32, vp]
     L.vqvs_guidance_mix.argtypes = [vp, vp, i32, i64, i32, f32, f32, vp]
+    L.vqvs_speaker_mix.argtypes = [vp, i32, i32, vp, vp, i32, vp, i32, vp]
     L.vqvs_randn.argtypes = [vp, i32, i32, u64, u64, u32, vp]
     L.vqvs_ddpm_noise.argtypes = [vp, i32, vp, vp, i32, vp, vp, i32, i32, u64, u64, vp]
     L.vqvs_ddpm_sqerr.argtypes = [vp, vp, i32, vp, vp, i32, i32, u64, u64, vp]

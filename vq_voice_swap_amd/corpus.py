@@ -47,8 +47,8 @@ def top_directory(rel_path: str) -> str:
 
 def read_label_map(path: str, directories: Optional[Sequence[str]] = None) -> Dict[str, int]:
     """`--label-map FILE`: lines `top-level-directory<TAB>label` (blank lines and lines starting with # are skipped) -> {directory:
-    label}.  ValueError for a line without exactly one tab, an empty directory, a label that is not a non-negative integer, a
-    directory named twice, and -- with `directories`, the top-level directories of the data -- a directory the file does not map."""
+    label}.  ValueError for a line without exactly one tab, an empty directory, a label that is neither a non-negative integer nor a voice spec
+    (speakers.parse_voice; kept as text), a directory named twice, and -- with `directories`, the top-level directories of the data -- a directory the file does not map."""
     mapping: Dict[str, int] = {}
     with open(path, "rt") as f:
         for number, line in enumerate(f, 1):
@@ -59,11 +59,16 @@ def read_label_map(path: str, directories: Optional[Sequence[str]] = None) -> Di
             if len(fields) != 2 or not fields[0].strip():
                 raise ValueError(f"{path}:{number}: expected `directory<TAB>label`, got {line!r}")
             name, text = fields[0].strip(), fields[1].strip()
-            if not text.isdigit():
-                raise ValueError(f"{path}:{number}: label {text!r} is not a non-negative integer")
+            if not text.isdigit():  # (not a label: a voice spec -- a blend, a vector file -- kept as text for speakers.voice_vectors)
+                from .speakers import parse_voice
+
+                try:
+                    parse_voice(text)
+                except ValueError as e:
+                    raise ValueError(f"{path}:{number}: label {text!r} is not a non-negative integer or a voice spec ({e})") from None
             if name in mapping:
                 raise ValueError(f"{path}:{number}: directory {name!r} is mapped twice")
-            mapping[name] = int(text)
+            mapping[name] = int(text) if text.isdigit() else text
     if directories is not None:
         missing = sorted(set(directories) - set(mapping))
         if missing:

@@ -193,6 +193,25 @@ int vqvs_unet_forward(vqvs_model* m, const float* d_x, const float* d_ts, const 
   return run_model(m, c);
 }
 
+int vqvs_unet_forward_vec(vqvs_model* m, const float* d_x, const float* d_ts, const float* d_cond, const float* d_vec, float* d_out, int B,
+                          int T, void* stream) {
+  if (m && m->cfg.kind != VQVS_KIND_PREDICTOR) VQVS_FAIL(VQVS_ERR_ARG, "handle kind %d: an explicit vector needs a predictor handle", m->cfg.kind);
+  if (int e = check_run(m, VQVS_KIND_PREDICTOR, B, T)) return e;
+  if (m->cfg.num_labels <= 0) VQVS_FAIL(VQVS_ERR_ARG, "an explicit vector stands in for a class embedding: the model has no labels");
+  if (!d_x || !d_ts || !d_vec || !d_out) VQVS_FAIL(VQVS_ERR_ARG, "x, ts, vec and out must be non-NULL");
+  if ((d_cond == nullptr) != (m->cfg.cond_channels == 0)) VQVS_FAIL(VQVS_ERR_ARG, "must provide cond sequence if and only if model is conditional");
+  RunCtx c;
+  c.B = B;
+  c.Lbase = T;
+  c.x = d_x;
+  c.ts = d_ts;
+  c.cond = d_cond;
+  c.class_vec = d_vec;  // (time_embed adds it where it adds class_embed[labels[b]]: the schedule is vqvs_unet_forward's otherwise)
+  c.out = d_out;
+  c.st = reinterpret_cast<hipStream_t>(stream);
+  return run_model(m, c);
+}
+
 int vqvs_unet_embed_grad(vqvs_model* m, const float* d_x_t, const float* d_ts, const float* d_cond, const float* d_vec, const float* d_eps,
                          float* d_mse, float* d_grad, float* d_pred, int B, int T, void* stream) {
   if (int e = check_run(m, VQVS_KIND_PREDICTOR_GRAD, B, T)) return e;
@@ -675,6 +694,17 @@ int vqvs_guidance_mix(const float* d_outs, float* d_eps, int rows, int64_t row_l
   if (d_eps != d_outs && bytes_overlap(d_eps, total * 4, d_outs, (int64_t)reps * total * 4))
     VQVS_FAIL(VQVS_ERR_ARG, "d_eps must be d_outs itself (in place over block 0) or not overlap d_outs at all");
   return run_guidance_mix(d_outs, d_eps, total, reps, s1, s2, reinterpret_cast<hipStream_t>(stream));
+}
+
+int vqvs_speaker_mix(const float* d_table, int K, int E, const int32_t* d_idx, const float* d_w, int J, float* d_out, int B, void* stream) {
+  if (!d_table || !d_idx || !d_w || !d_out) VQVS_FAIL(VQVS_ERR_ARG, "d_table, d_idx, d_w and d_out must be non-NULL");
+  if (K < 1 || E < 1 || B < 1) VQVS_FAIL(VQVS_ERR_ARG, "bad shape K=%d E=%d B=%d", K, E, B);
+  if (J < 1 || J > 16) VQVS_FAIL(VQVS_ERR_ARG, "J=%d outside 1..16", J);
+  const int64_t out_bytes = (int64_t)B * E * 4, slot_bytes = (int64_t)B * J * 4;
+  if (bytes_overlap(d_out, out_bytes, d_table, (int64_t)K * E * 4) || bytes_overlap(d_out, out_bytes, d_idx, slot_bytes) ||
+      bytes_overlap(d_out, out_bytes, d_w, slot_bytes))
+    VQVS_FAIL(VQVS_ERR_ARG, "d_out must not overlap d_table, d_idx or d_w");
+  return run_speaker_mix(d_table, K, E, d_idx, d_w, J, d_out, B, reinterpret_cast<hipStream_t>(stream));
 }
 
 int vqvs_randn(float* d_out, int B, int T, uint64_t seed, uint64_t clip_offset, uint32_t stream_id, void* stream) {

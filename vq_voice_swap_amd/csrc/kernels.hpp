@@ -384,6 +384,12 @@ int run_dtw_distance(const float* ca, const float* cb, const int* fa, const int*
                      long long* counts, double* sums, int B, int fa_max, int fb_max, int n_ceps, hipStream_t st);
 
 // ----------------------------------------------------------------------------------
+// Speaker mix (speaker_kernels.hip): out[b] = sum over the used slots j (idx >= 0), in slot order, of w[b][j] * table[idx[b][j]], every
+// product and sum rounded on its own; an index >= K reads row K - 1.
+// ----------------------------------------------------------------------------------
+int run_speaker_mix(const float* table, int K, int E, const int* idx, const float* w, int J, float* out, int B, hipStream_t st);
+
+// ----------------------------------------------------------------------------------
 // Pitch scores (pitch_kernels.hip): per-frame YIN periods of one or two waveform batches, per-clip voicing counts and sums of the
 // frame-wise pitch distance in semitones; scratch holds pitch_distance_scratch_bytes(B, T, hop) bytes of tile partials.  b may be
 // nullptr (then only period_a may be asked for); every output may be nullptr.

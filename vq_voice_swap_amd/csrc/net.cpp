@@ -1287,9 +1287,10 @@ int build_model(vqvs_model* m, const float* const* hp) {
       a.b1 = reinterpret_cast<const float*>(bp->wp(b1));
       a.w2 = reinterpret_cast<const float*>(bp->wp(w2));
       a.b2 = reinterpret_cast<const float*>(bp->wp(b2));
-      a.class_embed = NL > 0 && !gradk ? reinterpret_cast<const float*>(bp->wp(ce)) : nullptr;
+      // an explicit vector per clip (vqvs_unet_forward_vec, vqvs_unet_embed_grad) takes the table's place: the kernel adds one or the other
+      a.class_embed = NL > 0 && !gradk && !r.class_vec ? reinterpret_cast<const float*>(bp->wp(ce)) : nullptr;
       a.labels = r.labels;
-      a.class_vec = gradk ? r.class_vec : nullptr;
+      a.class_vec = gradk || NL > 0 ? r.class_vec : nullptr;
       a.num_labels = NL;
       a.emb = bp->miscp(emb_off);
       a.gemb = bp->miscp(gemb_off);

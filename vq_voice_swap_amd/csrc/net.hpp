@@ -53,7 +53,8 @@ struct RunCtx {
   float* feat = nullptr;
   float* probs = nullptr;
   // predictor-gradient handles (vqvs_unet_embed_grad): the conditioning vector of every clip [B][E] in place of class_embed[labels],
-  // the target noise [B][T], and the outputs mse [B] and egrad [B][E]; `out` (the prediction) may be nullptr
+  // the target noise [B][T], and the outputs mse [B] and egrad [B][E]; `out` (the prediction) may be nullptr.
+  // class_vec is honoured by class-conditional predictor handles as well (vqvs_unet_forward_vec): labels is then nullptr
   const float* class_vec = nullptr;
   const float* eps = nullptr;
   float* mse = nullptr;

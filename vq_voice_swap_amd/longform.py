@@ -380,9 +380,23 @@ def check_rate(model, window: int, hop: int) -> None:
         raise ValueError(f"window={window} and hop={hop} must be multiples of the model's downsample rate {rate}")
 
 
-def _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale, guidance=None):
+def _window_vectors(vectors: torch.Tensor, n: int, counts: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """Explicit conditioning vectors (speakers.py) in the place of a window batch's labels -> [n,E]: one [E] for every window, one
+    per window, or -- with the `counts` of a pack -- one per recording."""
+    v = vectors.reshape(-1, vectors.shape[-1])
+    if v.shape[0] == 1:
+        v = v.expand(n, -1)
+    elif counts is not None and v.shape[0] == len(counts) != n:
+        v = v.repeat_interleave(torch.tensor(list(counts), device=v.device), dim=0)
+    if v.shape[0] != n:
+        per = f", one per recording ({len(counts)})" if counts is not None else ""
+        raise ValueError(f"vectors must hold one vector{per} or one per window ({n}), got {v.shape[0]}")
+    return v.contiguous()
+
+
+def _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale, guidance=None, vectors=None):
     """(predictor, cond_fn) of a window batch: each slice of windows sees its own rows of the conditioning [n,C,T1], of `labels` [n]
-    (or None) and -- with `enc_pred` -- guidance towards its own codes (VQVAE.decode).  `guidance` (label_scale, vq_scale) makes the
+    or `vectors` [n,E] (or neither) and -- with `enc_pred` -- guidance towards its own codes (VQVAE.decode).  `guidance` (label_scale, vq_scale) makes the
     predictor the guided one of `VQVAE.decode_uncond_guidance` (vq_vae.guided_predictor): labels are then NOT offset by the caller."""
     cond_fn = None
     if enc_pred is not None:
@@ -396,11 +410,12 @@ def _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale, guidance=Non
     if guidance is not None:
         from .vq_vae import guided_predictor
 
-        return guided_predictor(model, cond_seq, labels, *guidance)[0], cond_fn
+        return guided_predictor(model, cond_seq, labels, *guidance, vectors=vectors)[0], cond_fn
 
     def predictor(xs, ts, first):
         sl = slice(first, first + xs.shape[0])
-        return model.predictor(xs, ts, cond=cond_seq[sl], labels=None if labels is None else labels[sl])
+        return model.predictor(xs, ts, cond=cond_seq[sl], labels=None if labels is None else labels[sl],
+                               vectors=None if vectors is None else vectors[sl])
 
     return predictor, cond_fn
 
@@ -409,15 +424,17 @@ def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = Non
                 steps: int = 100, progress: bool = False, constrain: bool = False, enc_pred=None, enc_pred_scale: float = 1.0,
                 seed: Optional[int] = None, clip_offset: int = 0, window_batch: int = 64, sampler: str = "ddpm", eta: float = 0.0,
                 source: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None, strength: float = 1.0,
-                guidance: Optional[Tuple[float, float]] = None, **kwargs) -> torch.Tensor:
+                guidance: Optional[Tuple[float, float]] = None, vectors: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
     """Window codes [n,T1] int or [n,C,T1] float (`encode_long`) -> [1,1,num_samples] waveform: `VQVAE.decode` on one long state.
-    x_T is ONE row of (n - 1) * hop + window samples keyed by `clip_offset`; `labels` is one label for every window, or [n].
+    x_T is ONE row of (n - 1) * hop + window samples keyed by `clip_offset`; `labels` is one label for every window, or [n];
+    `vectors` in their place is one conditioning vector [E] for every window, or [n,E] (a morph: speakers.morph_vectors).
     With one window the result is `decode`'s, bit for bit, at the same seed and clip_offset.  `sampler` "ddim" runs
     `ddim_sample_windows` with `eta` instead of `ddpm_sample_windows`, "dpmpp" `dpmpp_sample_windows`.  `source` [1,1,num_samples] (the recording itself), `keep`
     (bool / uint8, [1,1,num_samples]: samples that stay the source's) and `strength` in (0, 1] (below 1: start from the noised
     source, `strength_to_start_step`) are `VQVAE.decode`'s.  `guidance` (label_scale, vq_scale) is what
     `VQVAE.decode_long_uncond_guidance` passes: the guided window predictor of `_conditioned`, labels not offset by the caller."""
     from .diffusion import fresh_seed, pick_sampler, randn_clips, source_start_step
+    from .vq_vae import one_voice
 
     start_step = source_start_step(source, keep, strength, steps)
     cond_seq = model.cond_sequence(codes)
@@ -427,6 +444,9 @@ def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = Non
         raise ValueError(f"{num_samples} samples in windows of {window} every {hop} are {n} windows; codes hold {cond_seq.shape[0]}")
     if codes.shape[-1] * model.encoder.downsample_rate != window:
         raise ValueError(f"codes of length {codes.shape[-1]} describe {codes.shape[-1] * model.encoder.downsample_rate} samples, not window={window}")
+    one_voice(labels, vectors)
+    if vectors is not None:
+        vectors = _window_vectors(vectors, n)
     if labels is not None:
         labels = labels.reshape(-1)
         if labels.numel() == 1:
@@ -434,7 +454,7 @@ def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = Non
         if labels.shape != (n,):
             raise ValueError(f"labels must hold one label or one per window ({n}), got {labels.numel()}")
         labels = labels.contiguous()
-    predictor, cond_fn = _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale, guidance)
+    predictor, cond_fn = _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale, guidance, vectors)
     if seed is None:
         seed = fresh_seed()
     if source is not None:
@@ -451,15 +471,17 @@ def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = Non
 def decode_long_batch(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, *, counts: Sequence[int], num_samples: Sequence[int],
                       window: int, hop: int, steps: int = 100, progress: bool = False, constrain: bool = False, enc_pred=None,
                       enc_pred_scale: float = 1.0, seed: Optional[int] = None, clip_offset: int = 0, window_batch: int = 64,
-                      sampler: str = "ddpm", eta: float = 0.0, guidance: Optional[Tuple[float, float]] = None) -> List[torch.Tensor]:
+                      sampler: str = "ddpm", eta: float = 0.0, guidance: Optional[Tuple[float, float]] = None,
+                      vectors: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
     """`decode_long` for a pack of recordings (`encode_long_batch`): codes [N,T1] or [N,C,T1] of all their windows, `counts` windows and
     `num_samples` samples per recording -> one [1,1,num_samples[r]] waveform each.  The windows of all recordings fill the forwards
     together (`window_batch` at a time) and one packed step kernel follows, so many short recordings cost what one long one does.
-    `labels` is one label, one per recording, or one per window.  x_T is each recording's own row keyed clip_offset + r, and recording
+    `labels` is one label, one per recording, or one per window; `vectors` in their place one [E], [R,E] or [N,E].  x_T is each recording's own row keyed clip_offset + r, and recording
     r's result is what `decode_long` returns for it alone at clip_offset + r, bit for bit, whatever else is in the pack and whatever
     `window_batch` is.  `source`, `keep` and `strength` are not built for a pack.  `guidance` (label_scale, vq_scale) is `decode_long`'s,
     what `VQVAE.decode_long_batch_uncond_guidance` passes."""
     from .diffusion import fresh_seed, pick_sampler, randn_clips
+    from .vq_vae import one_voice
 
     cond_seq = model.cond_sequence(codes)
     check_rate(model, window, hop)
@@ -472,6 +494,9 @@ def decode_long_batch(model, codes: torch.Tensor, labels: Optional[torch.Tensor]
         raise ValueError(f"counts={counts} are {N} windows; codes hold {cond_seq.shape[0]}")
     if codes.shape[-1] * model.encoder.downsample_rate != window:
         raise ValueError(f"codes of length {codes.shape[-1]} describe {codes.shape[-1] * model.encoder.downsample_rate} samples, not window={window}")
+    one_voice(labels, vectors)
+    if vectors is not None:
+        vectors = _window_vectors(vectors, N, counts)
     if labels is not None:
         labels = labels.reshape(-1)
         if labels.numel() == 1:
@@ -481,7 +506,7 @@ def decode_long_batch(model, codes: torch.Tensor, labels: Optional[torch.Tensor]
         if labels.shape != (N,):
             raise ValueError(f"labels must hold one label, one per recording ({R}) or one per window ({N}), got {labels.numel()}")
         labels = labels.contiguous()
-    predictor, cond_fn = _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale, guidance)
+    predictor, cond_fn = _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale, guidance, vectors)
     if seed is None:
         seed = fresh_seed()
     padded = [(c - 1) * hop + window for c in counts]

@@ -431,10 +431,17 @@ class UNetPredictor(_NativeModule):
         return cfg
 
     def forward(self, x: torch.Tensor, ts: torch.Tensor, cond: Optional[torch.Tensor] = None,
-                labels: Optional[torch.Tensor] = None, use_checkpoint: bool = False) -> torch.Tensor:
-        assert (labels is None) == (self.num_labels is None), "must provide labels if and only if model is class conditional"
+                labels: Optional[torch.Tensor] = None, vectors: Optional[torch.Tensor] = None, use_checkpoint: bool = False) -> torch.Tensor:
+        """`vectors` [B, 4 * base_channels] (the real width) gives every clip's conditioning vector explicitly, in place of
+        `class_embed(labels)`: a class-conditional model takes exactly one of the two (`vqvs_unet_forward_vec`; speakers.py makes such
+        vectors).  With vectors = class_embed.weight[labels] the result is the labels call's, bit for bit, in every precision mode."""
+        if labels is not None and vectors is not None:
+            raise ValueError("give labels or vectors, not both: a vector stands in for class_embed(labels)")
+        if vectors is not None and self.num_labels is None:
+            raise ValueError("vectors stand in for a class embedding: this model is not class conditional")
+        assert (labels is None and vectors is None) == (self.num_labels is None), "must provide labels if and only if model is class conditional"
         assert (cond is None) == (self.cond_channels is None), "must provide cond sequence if and only if model is conditional"
-        _native.require_cuda(x, ts, cond, labels)
+        _native.require_cuda(x, ts, cond, labels, vectors)
         self._check_inference_only(x, cond)
         if x.dim() != 3 or x.shape[1] != self.in_channels:
             raise ValueError(f"expected x of shape [N, {self.in_channels}, T], got {tuple(x.shape)}")
@@ -460,12 +467,33 @@ class UNetPredictor(_NativeModule):
             if labels.shape != (B,):
                 raise ValueError(f"expected labels of shape [{B}], got {tuple(labels.shape)}")
             _native.check_index_range(labels, self.num_labels, "class labels")
+        if vectors is not None:
+            vectors = self.physical_vectors(vectors.detach().to(device=x.device, dtype=torch.float32), B)
         h = self.handle(x.device, B, T)
         out = torch.empty(B, self.out_channels, T, device=x.device, dtype=torch.float32)
         with torch.cuda.device(x.device):
+            if vectors is not None:
+                _native.check(_native.lib().vqvs_unet_forward_vec(
+                    h.ptr, x.data_ptr(), ts.data_ptr(), _native._ptr(cond), vectors.data_ptr(), out.data_ptr(), B, T,
+                    _native._stream_ptr()))
+                return out
             _native.check(_native.lib().vqvs_unet_forward(
                 h.ptr, x.data_ptr(), ts.data_ptr(), _native._ptr(cond), _native._ptr(labels), out.data_ptr(), B, T,
                 _native._stream_ptr()))
+        return out
+
+    def physical_vectors(self, vectors: torch.Tensor, B: int) -> torch.Tensor:
+        """Conditioning vectors [B, 4 * base_channels] at the real width -> contiguous [B, E] at the handle's width: on a padded
+        handle entry c goes to (c // q) * qp + c % q, where `pad_state` puts class_embed.weight's columns, and the rest is zero."""
+        E = 4 * self.base_channels
+        if tuple(vectors.shape) != (B, E):
+            raise ValueError(f"expected vectors of shape [{B}, {E}] (4 * base_channels), got {tuple(vectors.shape)}")
+        q, qp = pad_blocks(self.base_channels)
+        if q == qp:
+            return vectors.contiguous()
+        idx = torch.arange(E, device=vectors.device)
+        out = torch.zeros(B, E // q * qp, device=vectors.device, dtype=vectors.dtype)
+        out.index_copy_(1, (idx // q) * qp + idx % q, vectors)
         return out
 
     def condition(self, **kwargs) -> Callable:

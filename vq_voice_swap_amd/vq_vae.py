@@ -33,41 +33,57 @@ def make_encoder(enc_name: str, base_channels: int = 32, cond_mult: int = 16):
 
 
 def _guided(labels, label_scale: float, vq_scale: float) -> bool:
-    """Whether a guidance call extrapolates at all: a label scale counts only with labels."""
+    """Whether a guidance call extrapolates at all: a label scale counts only with labels (or vectors in their place)."""
     return bool(vq_scale) or (labels is not None and bool(label_scale))
 
 
-def guided_predictor(model, cond_seq: torch.Tensor, labels: Optional[torch.Tensor], label_scale: float, vq_scale: float):
+def one_voice(labels, vectors) -> None:
+    """A voice is named by labels or given as vectors (speakers.py), never both."""
+    if labels is not None and vectors is not None:
+        raise ValueError("give labels or vectors, not both: a vector stands in for class_embed(labels)")
+
+
+def guided_predictor(model, cond_seq: torch.Tensor, labels: Optional[torch.Tensor], label_scale: float, vq_scale: float,
+                     vectors: Optional[torch.Tensor] = None):
     """(predictor(xs, ts, first=0), guided) of classifier-free-style guidance on the rows of `cond_seq` [n,C,T1] and `labels` [n] (not
     offset; None: no labels).  A slice of m rows starting at `first` runs the decoder's predictor on the reps-fold batch
     [own cond, labels + 1 | zero cond, labels + 1 | own cond, label 0] -- a block only for a non-zero scale (reference
     vq_vae.py:188-214, whose always-tripled batch lines up only when both are) -- and `vqvs_guidance_mix` extrapolates in place over
-    block 0.  The batches of a slice are built once and kept: the sampling loop asks for the same slices at every step."""
+    block 0.  The batches of a slice are built once and kept: the sampling loop asks for the same slices at every step.
+    `vectors` [n,E] in place of labels (NOT offset: they are the voices themselves) run as [own cond, vectors | zero cond, vectors |
+    own cond, row 0 of the table as a vector]: with vectors = class_embed.weight[labels + 1] the labels run, bit for bit."""
+    one_voice(labels, vectors)
+    key = "labels" if vectors is None else "vectors"
+    voice = vectors if vectors is not None else (None if labels is None else labels + 1)
     use_vq = bool(vq_scale)
-    use_label = labels is not None and bool(label_scale)
+    use_label = voice is not None and bool(label_scale)
     reps = 1 + int(use_vq) + int(use_label)
     scales = [float(s) for flag, s in ((use_vq, vq_scale), (use_label, label_scale)) if flag] + [0.0, 0.0]
-    shifted = None if labels is None else labels + 1
     batches = {}
+
+    def null_voice(like):
+        if vectors is None:
+            return torch.zeros_like(like)
+        return model.predictor.class_embed.weight[0].detach().to(like).expand(like.shape[0], -1)
 
     def batch(first: int, m: int):
         if (first, m) not in batches:
             sl = slice(first, first + m)
             conds = [cond_seq[sl]]
-            labs = [shifted[sl]] if shifted is not None else None
+            voices = [voice[sl]] if voice is not None else None
             if use_vq:
                 conds.append(torch.zeros_like(cond_seq[sl]))
-                if labs is not None:
-                    labs.append(shifted[sl])
+                if voices is not None:
+                    voices.append(voice[sl])
             if use_label:
                 conds.append(cond_seq[sl])
-                labs.append(torch.zeros_like(shifted[sl]))
-            batches[first, m] = (torch.cat(conds, dim=0), torch.cat(labs, dim=0) if labs is not None else None)
+                voices.append(null_voice(voice[sl]))
+            batches[first, m] = (torch.cat(conds, dim=0), torch.cat(voices, dim=0) if voices is not None else None)
         return batches[first, m]
 
     def predictor(xs, ts, first: int = 0):
-        cond_batch, label_batch = batch(int(first), xs.shape[0])
-        outs = model.predictor(torch.cat([xs] * reps, dim=0), torch.cat([ts] * reps, dim=0), cond=cond_batch, labels=label_batch)
+        cond_batch, voice_batch = batch(int(first), xs.shape[0])
+        outs = model.predictor(torch.cat([xs] * reps, dim=0), torch.cat([ts] * reps, dim=0), cond=cond_batch, **{key: voice_batch})
         return guidance_mix(outs, reps, scales[0], scales[1])
 
     return predictor, reps > 1
@@ -160,13 +176,15 @@ class VQVAE(DiffusionModel):
     def decode(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, steps: int = 100, progress: bool = False,
                constrain: bool = False, enc_pred=None, enc_pred_scale: float = 1.0, x_T: Optional[torch.Tensor] = None,
                sampler: str = "ddpm", eta: float = 0.0, source: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
-               strength: float = 1.0, **kwargs) -> torch.Tensor:
-        """codes [N,T1] int or [N,C,T1] float -> [N,1,T1*256] waveform (vq_vae.py:92-145).  `sampler` "ddim" runs
+               strength: float = 1.0, vectors: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
+        """codes [N,T1] int or [N,C,T1] float -> [N,1,T1*256] waveform (vq_vae.py:92-145).  `vectors` [N,E] in place of `labels`
+        gives every clip's voice as an explicit conditioning vector (speakers.py).  `sampler` "ddim" runs
         `Diffusion.ddim_sample` with `eta` (0: the result depends on x_T alone) instead of `ddpm_sample`, "dpmpp" the deterministic
         second-order `Diffusion.dpmpp_sample`.
         `source` [N,1,T] is the waveform being converted: the samples `keep` marks (bool / uint8, [N,1,T]) stay the source's, bit for
         bit, and are shown to the predictor at every noise level; `strength` in (0, 1] below 1 starts from the source noised to step
         `strength_to_start_step(strength, steps)` instead of from x_T."""
+        one_voice(labels, vectors)
         start_step = source_start_step(source, keep, strength, steps)
         if source is not None:
             kwargs.update(source=source, keep=keep, start_step=start_step)
@@ -179,24 +197,25 @@ class VQVAE(DiffusionModel):
         seed, x_T = self._seed_and_x_T(codes, x_T, kwargs)
         sample, sampler_kw = pick_sampler(self.diffusion, sampler, eta)
         out = sample(
-            x_T, lambda xs, ts, **kw: self.predictor(xs, ts, cond=cond_seq, labels=labels, **kw),
+            x_T, lambda xs, ts, **kw: self.predictor(xs, ts, cond=cond_seq, labels=labels, vectors=vectors, **kw),
             steps=steps, progress=progress, constrain=constrain, cond_fn=cond_fn, seed=seed, **sampler_kw, **kwargs)
         self.predictor.check_status()  # range guard of the decoder's mode (once per sample)
         return out
 
     def invert(self, inputs: torch.Tensor, labels: Optional[torch.Tensor] = None, steps: int = 100, codes: Optional[torch.Tensor] = None,
-               **kwargs) -> torch.Tensor:
+               vectors: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
         """[N,1,T] waveform -> the x_T [N,1,T] that the DDIM sampler at eta = 0 maps back towards it under ITS OWN codes (encoded here
         unless `codes`, [N,T1] int or [N,C,T1] float, is given) and its own `labels`: `Diffusion.ddim_invert` with the decoder's
         predictor.  `decode(codes, other_labels, steps=steps, sampler="ddim", x_T=...)` then converts the voice from the source's
-        latent instead of a fresh draw."""
+        latent instead of a fresh draw.  `vectors` [N,E] in place of `labels`: the source's voice as explicit vectors."""
+        one_voice(labels, vectors)
         if codes is None:
             codes = self.encode(inputs)
         cond_seq = self.cond_sequence(codes)
         T = codes.shape[-1] * self.encoder.downsample_rate
         if inputs.dim() != 3 or inputs.shape[0] != cond_seq.shape[0] or inputs.shape[-1] != T:
             raise ValueError(f"inputs of shape {tuple(inputs.shape)} do not match codes for {cond_seq.shape[0]} clips of {T} samples")
-        out = self.diffusion.ddim_invert(inputs, lambda xs, ts: self.predictor(xs, ts, cond=cond_seq, labels=labels), steps, **kwargs)
+        out = self.diffusion.ddim_invert(inputs, lambda xs, ts: self.predictor(xs, ts, cond=cond_seq, labels=labels, vectors=vectors), steps, **kwargs)
         self.predictor.check_status()
         return out
 
@@ -206,13 +225,14 @@ class VQVAE(DiffusionModel):
 
         return encode_long(self, wave, window, hop, window_batch)
 
-    def decode_long(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
+    def decode_long(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, *, vectors: Optional[torch.Tensor] = None,
+                    **kwargs) -> torch.Tensor:
         """Window codes [n,T1] or [n,C,T1] -> [1,1,num_samples] waveform: `decode` on one long state whose windows are blended at
         every step (longform.decode_long; keywords num_samples, window, hop, steps, constrain, enc_pred, seed, window_batch, sampler,
-        eta, source, keep, strength ...)."""
+        eta, source, keep, strength ...).  `vectors` [n,E] (or one [E]) in place of `labels`: a voice per window, e.g. a morph."""
         from .longform import decode_long
 
-        return decode_long(self, codes, labels, **kwargs)
+        return decode_long(self, codes, labels, vectors=vectors, **kwargs)
 
     def encode_long_batch(self, waves, window: int, hop: int, window_batch: int = 64):
         """Several recordings [1,1,N_r] -> (codes [N, window / rate] of all their windows, counts per recording)
@@ -221,30 +241,33 @@ class VQVAE(DiffusionModel):
 
         return encode_long_batch(self, waves, window, hop, window_batch)
 
-    def decode_long_batch(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, **kwargs):
+    def decode_long_batch(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, *, vectors: Optional[torch.Tensor] = None,
+                          **kwargs):
         """The codes of a pack of recordings -> one [1,1,num_samples[r]] waveform each, the windows of all of them packed into the
         same forwards (longform.decode_long_batch; keywords counts, num_samples, window, hop, steps, sampler, eta, constrain, enc_pred,
-        enc_pred_scale, seed, clip_offset, window_batch, progress)."""
+        enc_pred_scale, seed, clip_offset, window_batch, progress).  `vectors` in place of `labels`: one [E], one per recording [R,E]
+        or one per window [N,E]."""
         from .longform import decode_long_batch
 
-        return decode_long_batch(self, codes, labels, **kwargs)
+        return decode_long_batch(self, codes, labels, vectors=vectors, **kwargs)
 
     def decode_uncond_guidance(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, steps: int = 100,
                                progress: bool = False, constrain: bool = False, label_scale: float = 0.0, vq_scale: float = 0.0,
                                x_T: Optional[torch.Tensor] = None, sampler: str = "ddpm", eta: float = 0.0,
                                source: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None, strength: float = 1.0,
-                               **kwargs) -> torch.Tensor:
+                               vectors: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
         """Decode with classifier-free-style guidance towards the VQ codes and/or the label (reference
         vq_vae.py:147-220): the predictor runs on a 1x-3x batch [conditional | codes dropped | label dropped] and the
         prediction is base + scale * (base - dropped), mixed by `vqvs_guidance_mix`.  Labels are NOT offset by the caller: label 0 is
         the unconditional label of such a model, so `labels + 1` is used as in the reference.  `source`, `keep` and `strength` are
-        `decode`'s."""
+        `decode`'s.  `vectors` [N,E] in place of `labels` are the voices themselves (not offset); the dropped label is row 0 of the table."""
+        one_voice(labels, vectors)
         start_step = source_start_step(source, keep, strength, steps)
         if source is not None:
             kwargs.update(source=source, keep=keep, start_step=start_step)
         cond_seq = self.cond_sequence(codes)
         seed, x_T = self._seed_and_x_T(codes, x_T, kwargs)
-        pred_fn, guided = guided_predictor(self, cond_seq, labels, label_scale, vq_scale)
+        pred_fn, guided = guided_predictor(self, cond_seq, labels, label_scale, vq_scale, vectors)
         sample, sampler_kw = pick_sampler(self.diffusion, sampler, eta)
         with self.guidance_precision(guided, "decode_uncond_guidance"):
             out = sample(x_T, pred_fn, steps=steps, progress=progress, constrain=constrain, seed=seed, **sampler_kw, **kwargs)
@@ -268,25 +291,27 @@ class VQVAE(DiffusionModel):
             yield
 
     def decode_long_uncond_guidance(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, *, label_scale: float = 0.0,
-                                    vq_scale: float = 0.0, **kwargs) -> torch.Tensor:
+                                    vq_scale: float = 0.0, vectors: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
         """`decode_uncond_guidance` on one long state: `decode_long` (its keywords: num_samples, window, hop, steps, constrain, seed,
         clip_offset, window_batch, sampler, eta, source, keep, strength ...) whose window predictor is the guided one -- each slice of
         windows runs as [own cond, labels + 1 | zero cond, labels + 1 | own cond, label 0] and is mixed by `vqvs_guidance_mix`.
         Labels are NOT offset by the caller.  With one window the result is `decode_uncond_guidance`'s, bit for bit."""
         from .longform import decode_long
 
-        with self.guidance_precision(_guided(labels, label_scale, vq_scale), "decode_long_uncond_guidance"):
-            return decode_long(self, codes, labels, guidance=(label_scale, vq_scale), **kwargs)
+        one_voice(labels, vectors)
+        with self.guidance_precision(_guided(vectors if labels is None else labels, label_scale, vq_scale), "decode_long_uncond_guidance"):
+            return decode_long(self, codes, labels, vectors=vectors, guidance=(label_scale, vq_scale), **kwargs)
 
     def decode_long_batch_uncond_guidance(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, *, label_scale: float = 0.0,
-                                          vq_scale: float = 0.0, **kwargs):
+                                          vq_scale: float = 0.0, vectors: Optional[torch.Tensor] = None, **kwargs):
         """`decode_long_uncond_guidance` for a pack of recordings: `decode_long_batch` (its keywords: counts, num_samples, window, hop
         ...) with the guided window predictor.  Recording r is what `decode_long_uncond_guidance` returns for it alone at
         clip_offset + r, bit for bit."""
         from .longform import decode_long_batch
 
-        with self.guidance_precision(_guided(labels, label_scale, vq_scale), "decode_long_batch_uncond_guidance"):
-            return decode_long_batch(self, codes, labels, guidance=(label_scale, vq_scale), **kwargs)
+        one_voice(labels, vectors)
+        with self.guidance_precision(_guided(vectors if labels is None else labels, label_scale, vq_scale), "decode_long_batch_uncond_guidance"):
+            return decode_long_batch(self, codes, labels, vectors=vectors, guidance=(label_scale, vq_scale), **kwargs)
 
     @property
     def downsample_rate(self) -> int:
