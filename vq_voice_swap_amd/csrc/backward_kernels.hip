@@ -1,6 +1,6 @@
 // Input-gradient kernels for classifier guidance (reference sample_diffusion.py:34-42 calls
 // torch.autograd.grad through models/classifier.py; here the backward pass with respect to the
-// waveform is an explicit schedule, see net.cpp "classifier").  The transposed convolutions reuse the
+// waveform is an explicit schedule, see net.cpp build_classifier).  The transposed convolutions reuse the
 // forward MFMA kernel; this file holds the bandwidth-bound element-wise pieces and the per-clip head.
 //
 // GroupNorm backward (per clip, group of n = channels_per_group * L elements), with the forward written as

@@ -237,6 +237,37 @@ int shiftL(int L, int lshift) {
 int ntiles_of(int L, int rows = STAT_TILE) { return (L + rows - 1) / rows; }
 constexpr int MIN_TILE_ROWS = 124;  // the smallest statistics tile any producer uses (128-row tiles, dilation 2)
 
+// Widths that are not multiples of 32 (vqvs_cfg.reserved[4] = the REAL base_channels of a predictor / encoder, 0 = base_channels itself):
+// the handle is built at the PHYSICAL width base_channels = padded_base(real), whose channels come in blocks of q_p of which the
+// first q carry the real channels and the rest are zero (weights, biases, affine parameters and FiLM rows of the pad channels are
+// zero: a pad channel is exactly 0 in every tensor).  real = 2^k * q with q odd; q_p = the next power of two >= q, widened until
+// 2^k * q_p is a multiple of 32.  Every real width m * real is a multiple of q and every GroupNorm group of the reference
+// (unet.py:345-349: 32 groups halved until they divide the width -- a power of two) is a whole number of blocks, so the reference's
+// groups are runs of physical channels too: the zero channels add nothing to a group's sums, and only the group COUNT and the number
+// of values per group (inv_count) have to come from the real width.
+struct PadMap {
+  int q = 1, qp = 1;
+  int phys(int c) const { return (c / q) * qp + c % q; }
+};
+PadMap pad_map(int real) {
+  PadMap m;
+  int k = 0;
+  while (((real >> k) & 1) == 0 && k < 5) ++k;
+  m.q = real >> k;
+  m.qp = 1;
+  while (m.qp < m.q) m.qp <<= 1;
+  while (((1 << k) * m.qp) % 32) m.qp <<= 1;
+  if (real % 32 == 0) m.qp = m.q;  // (nothing to pad)
+  return m;
+}
+
+// The guidance gradients d log p / d activation are O(1e-6 ... 1e-3): in fp16 storage they would sit in or below the
+// subnormal range (6e-5).  The backward schedule is linear in the gradient, so the fp16 mode carries it multiplied by 2^10
+// from the head (gscale) to the last kernel (in_conv_bw), which divides it out again in fp32.  bf16 / fp32 have the range.
+// The caller's guidance scale is NOT part of what the backward schedule carries (it is linear in it): in_conv_bw applies it in fp32,
+// so neither a very large --classifier-scale can overflow fp16 nor a very small one push the gradients into its subnormals.
+float grad_scale(int precision) { return precision == VQVS_PREC_F16 ? 1024.0f : 1.0f; }
+
 class Builder {
  public:
   Builder(vqvs_model* m, const float* const* hp) : m_(m), hp_(hp) {
@@ -333,8 +364,21 @@ class Builder {
   float* ssp(size_t foff) const { return reinterpret_cast<float*>(m_->d_arena + m_->ss_off) + foff; }
   float* miscp(size_t foff) const { return reinterpret_cast<float*>(m_->d_arena + m_->misc_off) + foff; }
   char* wp(size_t off) const { return m_->d_weights + off; }
+  const float* wf(size_t off) const { return reinterpret_cast<const float*>(wp(off)); }  // a float32 entry of the weight blob
+  float2* ssf2(size_t foff) const { return reinterpret_cast<float2*>(ssp(foff)); }       // a (scale, shift) / (mean, rstd) table
 
   // ---- ops ---------------------------------------------------------------------------
+  // The one place a schedule entry is made: its accounting row, its function and its phase go in together (run_model, vqvs_op_info and
+  // vqvs_profile_read index all three with one number).  `fn` itself becomes the std::function: nothing is wrapped around it.
+  // Phase 0 entries always run; phase 1 entries (a backward schedule) only when the call asks for them.
+  int phase = 0;
+  template <class F>
+  void op(const std::string& kind, const std::string& desc, double elems_T, double bytes_f32, double flops, F fn) {
+    m_->meta.push_back({kind, desc, elems_T, bytes_f32, flops});
+    m_->ops.emplace_back(std::move(fn));
+    m_->op_phase.push_back((uint8_t)phase);
+  }
+
   // A GroupNorm whose only consumer is the prologue of ONE convolution can be built by that convolution's producers (conv_ws.hip
   // WsGn): the link lets the two schedule entries agree at run time -- `fused` (set by add_conv) says whether the convolution
   // takes it for this batch / length, in which case the gn_prepare entry does nothing.
@@ -358,7 +402,6 @@ class Builder {
     for (auto& t : srcs) SR.push_back(stat_rows(t));
     const size_t st_off = status_off();
     const int guard = m_->cfg.precision == VQVS_PREC_F16 ? 1 : 0;
-    m_->meta.push_back({"gn_prepare", gn_name + " C=" + std::to_string(Ctot) + " L>>" + std::to_string(lshift), 0, 0, 0});
     auto link = std::make_shared<GnLink>();
     link->fill = [=](const RunCtx& c, GnArgs& a) {
       const int L = shiftL(c.Lbase, lshift);
@@ -367,17 +410,17 @@ class Builder {
       a.Ctot = Ctot;
       a.groups = groups;
       a.inv_count = 1.0 / ((double)(Creal / groups) * (double)L);
-      a.gamma = reinterpret_cast<const float*>(self->wp(g_off));
-      a.beta = reinterpret_cast<const float*>(self->wp(b_off));
+      a.gamma = self->wf(g_off);
+      a.beta = self->wf(b_off);
       a.film = film ? self->miscp(film_misc_off) : nullptr;
       a.film_stride = film_stride;
       a.film_off = film_off;
-      a.ss = reinterpret_cast<float2*>(self->ssp(ss_off));
-      a.mr = want_mr ? reinterpret_cast<float2*>(self->ssp(mr_off)) : nullptr;
+      a.ss = self->ssf2(ss_off);
+      a.mr = want_mr ? self->ssf2(mr_off) : nullptr;
       a.status = reinterpret_cast<unsigned*>(self->miscp(st_off));
       a.guard = guard;
     };
-    m_->add_op([=](const RunCtx& c) -> int {
+    op("gn_prepare", gn_name + " C=" + std::to_string(Ctot) + " L>>" + std::to_string(lshift), 0, 0, 0, [=](const RunCtx& c) -> int {
       if (link->fused && link->fused(c)) return 0;
       GnArgs a{};
       link->fill(c, a);
@@ -392,12 +435,11 @@ class Builder {
     Builder* self = this;
     const int prec = m_->cfg.precision;
     const TensorH S = src;
-    m_->meta.push_back({"xform", "C=" + std::to_string(src.C) + " L>>" + std::to_string(g.lshift) + (avg ? " avg" : ""),
-                        src.C * (lscale(src.lshift) + lscale(g.lshift)), 0, 0});
-    m_->add_op([=](const RunCtx& c) -> int {
+    op("xform", "C=" + std::to_string(src.C) + " L>>" + std::to_string(g.lshift) + (avg ? " avg" : ""),
+       src.C * (lscale(src.lshift) + lscale(g.lshift)), 0, 0, [=](const RunCtx& c) -> int {
       XformArgs a{};
       a.in = self->act(S.off);
-      a.ss = reinterpret_cast<const float2*>(self->ssp(ss_off));
+      a.ss = self->ssf2(ss_off);
       a.out = self->act(g.off);
       a.C = S.C;
       a.Lin = shiftL(c.Lbase, S.lshift);
@@ -494,7 +536,6 @@ class Builder {
     std::string desc;
     for (auto& s : segs) desc += (desc.empty() ? "" : "+") + std::to_string(s.C) + "x" + std::to_string(s.ntaps) + (s.resize == RESIZE_AVG2 ? "v" : s.resize == RESIZE_UP2 ? "^" : "") + (s.ntaps == 3 && s.dil > 1 ? "d" + std::to_string(s.dil) : "");
     desc += "->" + std::to_string(Cout) + " L>>" + std::to_string(out.lshift) + (skip ? " +id" : "");
-    m_->meta.push_back({"conv", desc, conv_elems, conv_f32, conv_flops});
     const int ws_f32 = ws_f32_kind ? 1 : 0;
     const int rev = (conv_seq_++) & 1;  // consecutive convolutions walk their tiles in opposite directions (ConvArgs.rev)
     auto build = [=](const RunCtx& c, ConvArgs& a) {
@@ -502,7 +543,7 @@ class Builder {
       for (int i = 0; i < a.nseg; ++i) {
         SegDesc& g = a.seg[i];
         g.src = self->act(S[i].t.off);
-        g.ss = S[i].xform ? reinterpret_cast<const float2*>(self->ssp(S[i].ss_off)) : nullptr;
+        g.ss = S[i].xform ? self->ssf2(S[i].ss_off) : nullptr;
         g.w_off = S[i].w_off;
         g.Csrc = S[i].t.C;
         g.c0 = S[i].c0;
@@ -523,7 +564,7 @@ class Builder {
       a.w_hi = reinterpret_cast<const bf16_t*>(self->wp(hi_off));
       a.w_lo = x3 ? reinterpret_cast<const bf16_t*>(self->wp(lo_off)) : nullptr;
       a.w_bytes = w_bytes;
-      a.bias = reinterpret_cast<const float*>(self->wp(bias_off));
+      a.bias = self->wf(bias_off);
       a.Cout = Cout;
       a.Lout = shiftL(c.Lbase, out_lshift == -1000 ? O.lshift : out_lshift);
       a.out_rows = shiftL(c.Lbase, O.lshift);
@@ -548,7 +589,7 @@ class Builder {
           a.bw[i] = BwActFuse{self->act(F.xf[i].off), F.xf[i].C, c0};
           c0 += F.xf[i].C;
         }
-        a.bw_ss = reinterpret_cast<const float2*>(self->ssp(F.ss_off));
+        a.bw_ss = self->ssf2(F.ss_off);
         a.bw_ss_stride = F.ss_stride;
         a.stats = self->statp(F.part_off);
       }
@@ -564,7 +605,7 @@ class Builder {
         return ws_fuses_gn(a, c.B, prec);
       };
     }
-    m_->add_op([=](const RunCtx& c) -> int {
+    op("conv", desc, conv_elems, conv_f32, conv_flops, [=](const RunCtx& c) -> int {
       ConvArgs a{};
       build(c, a);
       GnArgs g{};
@@ -678,14 +719,13 @@ class Builder {
     Builder* self = this;
     const int prec = m_->cfg.precision;
     if (Ctot == 0) Ctot = xf.C;
-    m_->meta.push_back({"bw_act", "C=" + std::to_string(xf.C) + " L>>" + std::to_string(xf.lshift) +
-                                      (resize == BW_FROM_HALF ? " from L/2" : resize == BW_FROM_DOUBLE ? " from 2L" : ""),
-                        xf.C * (2 * lscale(xf.lshift) + lscale(t.lshift)), 0, 0});
-    m_->add_op([=](const RunCtx& c) -> int {
+    op("bw_act", "C=" + std::to_string(xf.C) + " L>>" + std::to_string(xf.lshift) +
+                     (resize == BW_FROM_HALF ? " from L/2" : resize == BW_FROM_DOUBLE ? " from 2L" : ""),
+       xf.C * (2 * lscale(xf.lshift) + lscale(t.lshift)), 0, 0, [=](const RunCtx& c) -> int {
       BwActArgs a{};
       a.t = self->act(t.off);
       a.xf = self->act(xf.off);
-      a.ss = reinterpret_cast<const float2*>(self->ssp(ss_off));
+      a.ss = self->ssf2(ss_off);
       a.du = self->act(du.off);
       a.partials = self->statp(part_off);
       a.C = xf.C;
@@ -706,8 +746,7 @@ class Builder {
     const size_t coef = alloc_misc((size_t)maxB_ * C * 4);
     Builder* self = this;
     const int groups = gn_groups(C);
-    m_->meta.push_back({"gn_bw", "C=" + std::to_string(C) + " L>>" + std::to_string(lshift), 0, 0, 0});
-    m_->add_op([=](const RunCtx& c) -> int {
+    op("gn_bw", "C=" + std::to_string(C) + " L>>" + std::to_string(lshift), 0, 0, 0, [=](const RunCtx& c) -> int {
       GnBwArgs a{};
       const int L = shiftL(c.Lbase, lshift);
       a.partials = self->statp(part_off);
@@ -715,8 +754,8 @@ class Builder {
       a.C = C;
       a.groups = groups;
       a.inv_count = 1.0 / ((double)(C / groups) * (double)L);
-      a.ss = reinterpret_cast<const float2*>(self->ssp(ss_off));
-      a.mr = reinterpret_cast<const float2*>(self->ssp(mr_off));
+      a.ss = self->ssf2(ss_off);
+      a.mr = self->ssf2(mr_off);
       a.coef = reinterpret_cast<float4*>(self->miscp(coef));
       return launch_gn_bw(a, c.B, c.st);
     });
@@ -730,9 +769,8 @@ class Builder {
     if (Ctot == 0) Ctot = xf.C;
     const bool has_skip = skip != nullptr, has_extra = extra != nullptr;
     const TensorH K = skip ? *skip : TensorH{}, E = extra ? *extra : TensorH{};
-    m_->meta.push_back({"bw_affine", "C=" + std::to_string(xf.C) + " L>>" + std::to_string(xf.lshift),
-                        xf.C * lscale(xf.lshift) * (3 + (has_extra ? 1 : 0)) + (has_skip ? K.C * lscale(K.lshift) : 0.0), 0, 0});
-    m_->add_op([=](const RunCtx& c) -> int {
+    op("bw_affine", "C=" + std::to_string(xf.C) + " L>>" + std::to_string(xf.lshift),
+       xf.C * lscale(xf.lshift) * (3 + (has_extra ? 1 : 0)) + (has_skip ? K.C * lscale(K.lshift) : 0.0), 0, 0, [=](const RunCtx& c) -> int {
       BwAffineArgs a{};
       a.du = self->act(du.off);
       a.xf = self->act(xf.off);
@@ -755,8 +793,7 @@ class Builder {
   void add_bw_add(const TensorH& x, const TensorH& y, const TensorH& out) {  // out = x + y (same shape)
     Builder* self = this;
     const int prec = m_->cfg.precision;
-    m_->meta.push_back({"bw_add", "C=" + std::to_string(x.C) + " L>>" + std::to_string(x.lshift), 3 * x.C * lscale(x.lshift), 0, 0});
-    m_->add_op([=](const RunCtx& c) -> int {
+    op("bw_add", "C=" + std::to_string(x.C) + " L>>" + std::to_string(x.lshift), 3 * x.C * lscale(x.lshift), 0, 0, [=](const RunCtx& c) -> int {
       const long long n = (long long)c.B * shiftL(c.Lbase, x.lshift) * x.C;
       return launch_bw_add(self->act(x.off), self->act(y.off), self->act(out.off), n, prec, c.st);
     });
@@ -782,12 +819,12 @@ class Builder {
   //   out = skip(resize(x)) + conv2(gelu(GN2(conv1(resize(gelu(GN1(x)))))))       (unet.py:307-316)
   // x may be the concatenation [x, x2] (up path, unet.py:156).  Consumes `dout` (released); returns dx and sets
   // *dx2 to the gradient of the second input when the block concatenates.
-  // on_du2 (predictor-gradient handles): called once du2 = conv2^T(dout) * gelu'(u2) exists and before anything overwrites or
-  // releases it -- where the FiLM-coefficient gradient of the block is reduced.  input_grad = false: the block's input gradient is
-  // not wanted (the first block of such a handle): everything behind du2 is left out and an empty handle is returned.  A
-  // concatenating block called without dx2 leaves the second input's gradient out.
-  std::function<void(const BlockRec&, const TensorH&)> on_du2;
-  TensorH resblock_backward(const BlockRec& r, const TensorH& dout, TensorH* dx2 = nullptr, bool input_grad = true) {
+  // on_du2 (predictor-gradient handles; empty for the guidance schedules): called once du2 = conv2^T(dout) * gelu'(u2) exists and
+  // before anything overwrites or releases it -- where the FiLM-coefficient gradient of the block is reduced.  input_grad = false: the
+  // block's input gradient is not wanted (the first block of such a handle): everything behind du2 is left out and an empty handle
+  // is returned.  A concatenating block called without dx2 leaves the second input's gradient out.
+  using Du2Hook = std::function<void(const BlockRec&, const TensorH&)>;
+  TensorH resblock_backward(const BlockRec& r, const TensorH& dout, TensorH* dx2 = nullptr, bool input_grad = true, const Du2Hook& on_du2 = {}) {
     const BlockSpec& s = r.s;
     const std::string pre = s.prefix.empty() ? "" : s.prefix + ".";
     const int cin = s.cin, cout = s.cout;
@@ -866,7 +903,7 @@ class Builder {
   // The blocks of a whole UNet in reverse, from the gradient `g` of the last block's output.  Gradients of skip-stack tensors wait in
   // `pending` until the down path reaches their producer.  input_grad: return the gradient of recs[0].x (the in_conv output, which is
   // also the first skip-stack entry); otherwise neither it nor the skip gradient that would be added to it is computed.
-  TensorH unet_backward(const std::vector<BlockRec>& recs, TensorH g, bool input_grad = true) {
+  TensorH unet_backward(const std::vector<BlockRec>& recs, TensorH g, bool input_grad = true, const Du2Hook& on_du2 = {}) {
     std::map<int, TensorH> pending;
     auto add_pending = [&](const TensorH& produced) {  // produced = forward tensor whose gradient g currently is
       auto it = pending.find(produced.id);
@@ -880,11 +917,168 @@ class Builder {
       TensorH dsk{};
       const bool cat = recs[i].x2.id >= 0;
       const bool want_dsk = cat && (input_grad || recs[i].x2.id != recs[0].x.id);
-      g = resblock_backward(recs[i], g, cat && !want_dsk ? nullptr : &dsk, input_grad || i > 0);
+      g = resblock_backward(recs[i], g, cat && !want_dsk ? nullptr : &dsk, input_grad || i > 0, on_du2);
       if (want_dsk) pending[recs[i].x2.id] = dsk;
     }
     if (input_grad) add_pending(recs[0].x);
     return g;
+  }
+
+  // ---- stem and head pieces shared by the kinds -------------------------------------------------------
+  // (every piece allocates and uploads in a fixed order: blob offsets, arena offsets and the op list follow from it)
+  struct TimeEmb {
+    size_t emb_off, gemb_off;  // misc region: the conditioning vector [max_batch][E] and its GELU
+    int E;
+  };
+  // Time embedding under `px` (unet.py:132-136; the classifier stem's is the same module, classifier.py:111-114): frequency table,
+  // both linear layers, one kernel.  class_table: the kernel adds class_embed[labels] unless the call brings a vector per clip;
+  // class_vec: a call may bring one (RunCtx.class_vec).
+  TimeEmb time_embedding(const std::string& px, int num_labels, bool class_table, bool class_vec) {
+    const vqvs_cfg& c = m_->cfg;
+    const int E = 4 * c.base_channels;
+    // wavegrad.py:361-369 (float32 tensor math) at the REAL embedding width 4 * real base; a padded handle keeps the real entries at
+    // their physical positions (the halves of the embedding -- cos | sin -- are whole numbers of blocks), pad entries are 0 and meet
+    // zero weight rows
+    std::vector<float> freqs(E / 2, 0.0f);
+    const int Er = 4 * real_base(c);
+    const PadMap pm = pad_map(real_base(c));
+    for (int i = 0; i < Er / 2; ++i)
+      freqs[pm.phys(i)] = (float)(std::exp((double)(float)(-std::log(100.0 / 0.1)) * (double)i / (double)(Er / 2 - 1))) * 100.0f;
+    const size_t freq_off = blob.add(freqs.data(), freqs.size() * 4);
+    const size_t w1 = blob_f32_transposed(P(px + "time_embed.proj.weight"), E, E), b1 = blob_f32(px + "time_embed.proj.bias");
+    const size_t w2 = blob_f32_transposed(P(px + "time_embed_extra.1.weight"), E, E), b2 = blob_f32(px + "time_embed_extra.1.bias");
+    const size_t ce = class_table ? blob_f32(px + "class_embed.weight") : 0;
+    const size_t emb_off = alloc_misc((size_t)maxB_ * E);
+    const size_t gemb_off = alloc_misc((size_t)maxB_ * E);
+    m_->emb_misc_off = emb_off;
+    m_->emb_E = E;
+    Builder* self = this;
+    op("time_embed", "", 0, 0, 0, [=](const RunCtx& r) -> int {
+      TimeEmbedArgs a{};
+      a.ts = r.ts;
+      a.freqs = self->wf(freq_off);
+      a.w1 = self->wf(w1);
+      a.b1 = self->wf(b1);
+      a.w2 = self->wf(w2);
+      a.b2 = self->wf(b2);
+      // an explicit vector per clip (vqvs_unet_forward_vec, vqvs_unet_embed_grad) takes the table's place: the kernel adds one or the other
+      a.class_embed = class_table && !r.class_vec ? self->wf(ce) : nullptr;
+      a.labels = r.labels;  // (read beside class_embed only)
+      a.class_vec = class_vec ? r.class_vec : nullptr;
+      a.num_labels = num_labels;
+      a.emb = self->miscp(emb_off);
+      a.gemb = self->miscp(gemb_off);
+      a.E = E;
+      return launch_time_embed(a, r.B, r.st);
+    });
+    return {emb_off, gemb_off, E};
+  }
+
+  // The (a | b) rows of every block's cond_layers.1 stacked into one matrix: one kernel writes all blocks' FiLM rows [max_batch][R]
+  struct Film {
+    std::vector<int> row;  // first row of block i
+    int R = 0;
+    size_t wall_off = 0, film_off = 0;  // the stacked weights (transposed, weight blob) and the rows (misc region)
+  };
+  Film film_table(const std::vector<BlockSpec>& blocks, int E, size_t gemb_off) {
+    Film f;
+    std::vector<float> Wall, ball;
+    for (auto& s : blocks) {
+      f.row.push_back(f.R);
+      const float* W = P(s.prefix + ".cond_layers.1.weight");
+      const float* bb = P(s.prefix + ".cond_layers.1.bias");
+      const int rows = 2 * s.cout;
+      Wall.insert(Wall.end(), W, W + (size_t)rows * E);
+      ball.insert(ball.end(), bb, bb + rows);
+      f.R += rows;
+    }
+    const int R = f.R;
+    const size_t wall_off = f.wall_off = blob_f32_transposed(Wall.data(), R, E);
+    const size_t ball_off = blob.add(ball.data(), ball.size() * 4);
+    const size_t film_off = f.film_off = alloc_misc((size_t)maxB_ * R);
+    Builder* self = this;
+    op("film", "", 0, 0, 0, [=](const RunCtx& r) -> int {
+      FilmArgs a{self->miscp(gemb_off), self->wf(wall_off), self->wf(ball_off), self->miscp(film_off), E, R};
+      return launch_film(a, r.B, r.st);
+    });
+    return f;
+  }
+
+  // in_conv (unet.py:49, 137-139): Conv1d(Cin -> base, 3) over the NCT input [+ the nearest-upsampled conditioning projection].
+  // w_off: where the weights went in the blob, for a backward schedule's in_conv_bw.  row_cin: the input channels the accounting
+  // row shows and counts (the encoder's row has always said one, whatever in_channels is: kept, the tables are compared entry by entry).
+  TensorH in_conv(const std::string& px, int Cin, const TensorH* condp = nullptr, size_t* w_off = nullptr, int row_cin = 0) {
+    if (row_cin == 0) row_cin = Cin;
+    const int base = m_->cfg.base_channels, prec = m_->cfg.precision;
+    const TensorH h = new_tensor(base, 0, false, true);
+    const size_t w = blob_f32(px + "in_conv.weight"), bi = blob_f32(px + "in_conv.bias");
+    if (w_off) *w_off = w;
+    const bool has_cond = condp != nullptr;
+    const TensorH cp = condp ? *condp : TensorH{};
+    Builder* self = this;
+    op("in_conv", std::to_string(row_cin) + "->" + std::to_string(base), base + (has_cond ? base * lscale(cp.lshift) : 0.0), 4.0 * row_cin, 0,
+       [=](const RunCtx& r) -> int {
+      InConvArgs a{};
+      a.x = r.x;
+      a.Cin = Cin;
+      a.w = self->wf(w);
+      a.bias = self->wf(bi);
+      a.condp = has_cond ? self->act(cp.off) : nullptr;
+      a.cond_len = has_cond ? shiftL(r.Lbase, cp.lshift) : 0;
+      a.out = self->act(h.off);
+      a.stats = self->statp(h.stats_off);
+      a.C = base;
+      a.T = r.Lbase;
+      a.ntiles = ntiles_of(r.Lbase);
+      return launch_in_conv(a, r.B, prec, r.st);
+    });
+    return h;
+  }
+  // ... and its transpose, the last kernel of a guidance schedule: grad_out = (gscale / grad_scale) * in_conv^T(g)
+  void in_conv_bw(const TensorH& g, size_t w_off) {
+    const int base = m_->cfg.base_channels, prec = m_->cfg.precision;
+    Builder* self = this;
+    op("in_conv_bw", std::to_string(base) + "->1", (double)base, 4.0, 0, [=](const RunCtx& r) -> int {
+      InConvBwArgs a{};
+      a.dh = self->act(g.off);
+      a.w = self->wf(w_off);
+      a.out = r.grad_out;
+      a.C = base;
+      a.T = r.Lbase;
+      a.out_scale = r.gscale / grad_scale(prec);
+      return launch_in_conv_bw(a, r.B, prec, r.st);
+    });
+  }
+
+  // Output heads begin with GroupNorm + GELU over the last block's output (unet.py:113-116, classifier.py:94): its coefficient
+  // tables (mr: mean / rstd, kept for a backward schedule) and the gn_prepare entry
+  struct GnHead {
+    size_t ss = 0, mr = 0;
+  };
+  GnHead head_gn(const TensorH& h, const std::string& gn_name, bool want_mr) {
+    GnHead g;
+    g.ss = alloc_ss(h.C);
+    g.mr = want_mr ? alloc_ss(h.C) : 0;
+    add_gn({h}, gn_name, false, 0, 0, 0, g.ss, want_mr, g.mr);
+    return g;
+  }
+  // ... followed, in the UNets, by a 3-tap convolution into a float32 boundary tensor
+  TensorH head_conv(const TensorH& h, const GnHead& gh, const std::string& conv_name, int Cout, int out_lshift) {
+    TensorH o = new_tensor(Cout, out_lshift, true, false);
+    PackedConv pk(m_->cfg.precision);
+    SegSpec g{h, 0, h.C, 3, 1, RESIZE_NONE, true, gh.ss, h.C, 0, 0};
+    g.w_off = pk.append(P(conv_name + ".weight"), Cout, h.C, 3, 0, h.C);
+    const float* bb = P(conv_name + ".bias");
+    add_conv({g}, pk, std::vector<float>(bb, bb + Cout), Cout, o, nullptr, 0);
+    return o;
+  }
+  // the handle's output in the boundary's NCT layout
+  void to_nct(const TensorH& o) {
+    const int prec = o.f32 ? 0 : m_->cfg.precision;
+    Builder* self = this;
+    op("ntc_to_nct", "", 0, 0, 0, [=](const RunCtx& r) -> int {
+      return launch_ntc_to_nct(self->act(o.off), r.out, r.B, o.C, shiftL(r.Lbase, o.lshift), prec, r.st);
+    });
   }
 
   void tap(const std::string& name, const TensorH& t) { m_->taps.push_back({name, t}); }
@@ -940,13 +1134,6 @@ class Builder {
 
 int tensor_rows(int Lbase, int lshift) { return shiftL(Lbase, lshift); }
 
-// The guidance gradients d log p / d activation are O(1e-6 ... 1e-3): in fp16 storage they would sit in or below the
-// subnormal range (6e-5).  The backward schedule is linear in the gradient, so the fp16 mode carries it multiplied by 2^10
-// from the head (gscale) to the last kernel (in_conv_bw), which divides it out again in fp32.  bf16 / fp32 have the range.
-// The caller's guidance scale is NOT part of what the backward schedule carries (it is linear in it): in_conv_bw applies it in fp32,
-// so neither a very large --classifier-scale can overflow fp16 nor a very small one push the gradients into its subnormals.
-float grad_scale(int precision) { return precision == VQVS_PREC_F16 ? 1024.0f : 1.0f; }
-
 int unet_rate(const vqvs_cfg& c) {  // UNetPredictor / UNetEncoder.downsample_rate (unet.py:182-184, 243-245): 2^(len(channel_mult) - 1)
   return 1 << (topo_of(c).levels() - 1);
 }
@@ -957,29 +1144,6 @@ int gn_groups(int ch) {  // unet.py:345-349
   return g;
 }
 
-// Widths that are not multiples of 32 (vqvs_cfg.reserved[4] = the REAL base_channels of a predictor / encoder, 0 = base_channels itself):
-// the handle is built at the PHYSICAL width base_channels = padded_base(real), whose channels come in blocks of q_p of which the
-// first q carry the real channels and the rest are zero (weights, biases, affine parameters and FiLM rows of the pad channels are
-// zero: a pad channel is exactly 0 in every tensor).  real = 2^k * q with q odd; q_p = the next power of two >= q, widened until
-// 2^k * q_p is a multiple of 32.  Every real width m * real is a multiple of q and every GroupNorm group of the reference
-// (unet.py:345-349: 32 groups halved until they divide the width -- a power of two) is a whole number of blocks, so the reference's
-// groups are runs of physical channels too: the zero channels add nothing to a group's sums, and only the group COUNT and the number
-// of values per group (inv_count) have to come from the real width.
-struct PadMap {
-  int q = 1, qp = 1;
-  int phys(int c) const { return (c / q) * qp + c % q; }
-};
-PadMap pad_map(int real) {
-  PadMap m;
-  int k = 0;
-  while (((real >> k) & 1) == 0 && k < 5) ++k;
-  m.q = real >> k;
-  m.qp = 1;
-  while (m.qp < m.q) m.qp <<= 1;
-  while (((1 << k) * m.qp) % 32) m.qp <<= 1;
-  if (real % 32 == 0) m.qp = m.q;  // (nothing to pad)
-  return m;
-}
 int padded_base(int real) {
   const PadMap m = pad_map(real);
   return real / m.q * m.qp;
@@ -1198,706 +1362,512 @@ static int check_cfg(const vqvs_cfg& c) {
   return 0;
 }
 
+// ---- one schedule builder per kind -----------------------------------------------------------------------------------------------
+// (the ops capture the Builder by pointer for pointer resolution: build_model keeps it alive beside the handle)
+
+// A single ResBlock (unit-test granularity): NCT in, the external embedding through GELU + cond_layers.1, the block, NCT out
+static void build_resblock(vqvs_model* m, Builder& b) {
+  const vqvs_cfg& c = m->cfg;
+  Builder* bp = &b;
+  const int prec = c.precision, Cin = c.rb_cin, E = c.rb_emb_channels, R = 2 * c.rb_cout;
+  const BlockSpec s{"", c.rb_cin, c.rb_cout, c.rb_resize, c.rb_dilation, false};
+  TensorH x = b.new_tensor(Cin, 0, false, true);
+  b.op("nct_to_ntc", "", 0, 0, 0, [=](const RunCtx& r) -> int {
+    return launch_nct_to_ntc(r.x, bp->act(x.off), bp->statp(x.stats_off), r.B, Cin, r.Lbase, ntiles_of(r.Lbase), prec, r.st);
+  });
+  size_t film_misc = 0;
+  if (E) {
+    const size_t gemb = b.alloc_misc((size_t)c.max_batch * E);
+    film_misc = b.alloc_misc((size_t)c.max_batch * R);
+    const size_t w_off = b.blob_f32_transposed(b.P("cond_layers.1.weight"), R, E);
+    const size_t bias_off = b.blob_f32("cond_layers.1.bias");
+    b.op("film", "", 0, 0, 0, [=](const RunCtx& r) -> int {
+      if (!r.emb) VQVS_FAIL(VQVS_ERR_ARG, "resblock handle was built with an embedding; d_emb is NULL");
+      if (int e = launch_gelu_rows(r.emb, bp->miscp(gemb), r.B * E, r.st)) return e;
+      FilmArgs f{bp->miscp(gemb), bp->wf(w_off), bp->wf(bias_off), bp->miscp(film_misc), E, R};
+      return launch_film(f, r.B, r.st);
+    });
+  }
+  TensorH y = b.resblock("", s, {x}, E != 0, 0, R, film_misc);
+  b.to_nct(y);
+  b.tap("out", y);
+}
+
+// Predictor-gradient handles (speaker enrolment), behind the forward of build_unet: the loss head and the embedding-gradient schedule
+// (phase 1): d mse_b / d v_b for every clip b.  out_w: the output convolution's [3][base] weights; pred: where the prediction of a
+// call that does not ask for it goes.
+static void unet_embed_grad_tail(vqvs_model* m, Builder& b, const std::vector<Builder::BlockRec>& recs, const Builder::TimeEmb& te,
+                                 const Builder::Film& film, const TensorH& h, const Builder::GnHead& gh, size_t out_w, const TensorH& pred) {
+  const vqvs_cfg& c = m->cfg;
+  Builder* bp = &b;
+  const int base = c.base_channels, E = te.E, R = film.R;
+  const bool ws_f32_kind = b.ws_f32_kind;
+  b.ws_f32_kind = false;  // (the transposed convolutions run where the guidance schedules' run)
+  b.phase = 1;
+  TensorH dout = b.new_tensor(1, 0, true, false);
+  const size_t sq_off = b.alloc_misc(2 * (size_t)mse_head_scratch_doubles(c.max_batch, c.max_T));
+  b.op("mse_head", "", 0, 12.0, 0, [=](const RunCtx& r) -> int {
+    const float* p = r.out ? r.out : reinterpret_cast<const float*>(bp->act(pred.off));
+    return run_mse_head(p, r.eps, reinterpret_cast<float*>(bp->act(dout.off)), r.mse, reinterpret_cast<double*>(bp->miscp(sq_off)), r.B,
+                        r.Lbase, r.st);
+  });
+  // out.1 (3-tap conv base -> 1 over gelu(GN(h))) backwards: conv^T and gelu' in one kernel, then GroupNorm backward
+  TensorH t = b.new_tensor(base, 0, false, false);
+  const size_t po = b.alloc_stats(base, 0);
+  const size_t ss = gh.ss;
+  b.op("out_conv_bw", "1->" + std::to_string(base), 2.0 * base, 4.0, 0, [=](const RunCtx& r) -> int {
+    OutConvBwArgs a{};
+    a.dout = reinterpret_cast<const float*>(bp->act(dout.off));
+    a.xf = bp->act(h.off);
+    a.ss = bp->ssf2(ss);
+    a.w = bp->wf(out_w);
+    a.du = bp->act(t.off);
+    a.partials = bp->statp(po);
+    a.C = base;
+    a.L = r.Lbase;
+    return launch_out_conv_bw(a, r.B, r.st);
+  });
+  b.release(dout);
+  const size_t cfo = b.add_gn_bw(base, 0, po, gh.ss, gh.mr, STAT_TILE);
+  b.add_bw_affine(t, h, cfo, nullptr, BW_SAME, nullptr, t);
+  // per block, as soon as du2 exists: (d a | d b) into the block's rows of dfilm [B][R]
+  const size_t dfilm_off = b.alloc_misc((size_t)c.max_batch * R);
+  m->dfilm_misc_off = dfilm_off;
+  m->dfilm_R = R;
+  std::map<std::string, int> row_of;
+  for (size_t i = 0; i < recs.size(); ++i) row_of[recs[i].s.prefix] = film.row[i];
+  const Builder::Du2Hook film_grad = [&](const Builder::BlockRec& rec, const TensorH& du2) {
+    const int C = rec.s.cout, row = row_of.at(rec.s.prefix), ls = rec.out.lshift;
+    const size_t g_off = b.blob_f32(rec.s.prefix + ".pre_cond.3.weight"), be_off = b.blob_f32(rec.s.prefix + ".pre_cond.3.bias");
+    const size_t pf = b.alloc_stats(C, ls);
+    const TensorH D = du2, H1 = rec.h1;
+    const size_t mr2 = rec.mr2;
+    b.op("film_grad", "C=" + std::to_string(C) + " L>>" + std::to_string(ls), 2.0 * C * lscale(ls), 0, 0, [=](const RunCtx& r) -> int {
+      FilmGradArgs a{};
+      a.du = bp->act(D.off);
+      a.h1 = bp->act(H1.off);
+      a.mr = bp->ssf2(mr2);
+      a.gamma = bp->wf(g_off);
+      a.beta = bp->wf(be_off);
+      a.partials = bp->statp(pf);
+      a.dfilm = bp->miscp(dfilm_off);
+      a.film_stride = R;
+      a.film_off = row;
+      a.C = C;
+      a.L = shiftL(r.Lbase, ls);
+      a.ntiles = ntiles_of(a.L);
+      return launch_film_grad(a, r.B, r.st);
+    });
+  };
+  b.unet_backward(recs, t, false, film_grad);  // (the first block's input gradient and the skip path into in_conv are not needed)
+  // d v = gelu'(emb) * Wall^T dfilm
+  const size_t wall_off = film.wall_off, emb_off = te.emb_off;
+  b.op("film_bw", "", 0, 0, 0, [=](const RunCtx& r) -> int {
+    FilmBwArgs a{bp->miscp(dfilm_off), bp->wf(wall_off), bp->miscp(emb_off), r.egrad, E, R};
+    return launch_film_bw(a, r.B, r.st);
+  });
+  b.phase = 0;
+  b.ws_f32_kind = ws_f32_kind;
+}
+
+// EncoderPredictor (encoder_predictor.py:25-58), behind the forward of build_unet with a bottleneck output `o`: the 1x1 head with its
+// cross-entropy gradient (vq_vae.py:125-130: grads of the summed cross-entropy), then the backward schedule (phase 1) down to the input
+static void unet_encpred_tail(vqvs_model* m, Builder& b, const std::vector<Builder::BlockRec>& recs, const TensorH& h,
+                              const Builder::GnHead& gh, const TensorH& o) {
+  const vqvs_cfg& c = m->cfg;
+  Builder* bp = &b;
+  const int prec = c.precision, base = c.base_channels, OC = c.out_channels, D = c.reserved[2], rate = c.reserved[1];
+  const size_t hw = b.blob_f32("out.weight"), hb = b.blob_f32("out.bias");
+  TensorH dO = b.new_tensor(OC, 0, false, false);
+  const int es = b.es();
+  b.op("enc_head", "D=" + std::to_string(D), 0, 0, 0, [=](const RunCtx& r) -> int {
+    if (r.backward) VQVS_HIP(hipMemsetAsync(bp->act(dO.off), 0, (size_t)r.B * r.Lbase * OC * es, r.st));
+    EncHeadArgs a{};
+    a.o = reinterpret_cast<const float*>(bp->act(o.off));
+    a.w = bp->wf(hw);
+    a.bias = bp->wf(hb);
+    a.logits = r.out;
+    a.targets = r.backward ? r.labels : nullptr;
+    a.gscale = grad_scale(prec);  // (the caller's scale multiplies the finished gradient in fp32, in_conv_bw: the 2-byte gradient tensors never see it)
+    a.dO = bp->act(dO.off);
+    a.Cb = OC;
+    a.D = D;
+    a.T = r.Lbase;
+    a.T1 = r.Lbase / rate;
+    a.rate = rate;
+    return launch_enc_head(a, r.B, prec, r.st);
+  });
+  b.phase = 1;
+  // out.1 (3-tap conv base -> bottleneck over gelu(GN(h))) backwards: conv^T, gelu', GroupNorm backward
+  TensorH t = b.new_tensor(base, 0, false, false);
+  const size_t po = b.alloc_stats(base, 0);
+  const bool fuse = Builder::bw_fuse_enabled();
+  const Builder::BwFuse fo{{h}, gh.ss, base, po};
+  const int tro = b.add_conv_t(dO, b.P("unet.out.1.weight"), OC, base, 3, 1, t, fuse ? &fo : nullptr);
+  b.release(dO);
+  if (!fuse) b.add_bw_act(t, BW_SAME, h, gh.ss, t, po);
+  const size_t cfo = b.add_gn_bw(base, 0, po, gh.ss, gh.mr, fuse ? tro : STAT_TILE);
+  b.add_bw_affine(t, h, cfo, nullptr, BW_SAME, nullptr, t);
+  const TensorH gi = b.unet_backward(recs, t);  // blocks in reverse, down to the in_conv output
+  b.in_conv_bw(gi, b.blob_f32("unet.in_conv.weight"));
+  b.phase = 0;
+}
+
+// UNetPredictor.forward (unet.py:118-162) for three kinds of handle:
+//   predictor           the forward alone;
+//   EncoderPredictor    the same UNet under the "unet." prefix with a bottleneck output, every intermediate kept resident for the
+//                       backward schedule of unet_encpred_tail;
+//   predictor-gradient  the class-conditional predictor's own forward ops with the conditioning vector given per clip, every
+//                       intermediate kept resident too, and unet_embed_grad_tail behind the output convolution.
+static void build_unet(vqvs_model* m, Builder& b) {
+  const vqvs_cfg& c = m->cfg;
+  Builder* bp = &b;
+  const int prec = c.precision, base = c.base_channels, NL = c.num_labels;
+  const bool encpred = c.kind == VQVS_KIND_ENCPRED, gradk = c.kind == VQVS_KIND_PREDICTOR_GRAD;
+  const bool keep_bw = encpred || gradk;
+  const std::string px = encpred ? "unet." : "";
+  std::vector<BlockSpec> down, mid, up, all;
+  predictor_blocks(base, topo_of(c), down, mid, up);
+  for (auto* v : {&down, &mid, &up})
+    for (auto& s : *v) {
+      all.push_back(s);
+      all.back().prefix = px + s.prefix;
+    }
+  b.persist = keep_bw;  // (forward tensors of a handle with a backward schedule stay resident)
+  // ---- embedding + all blocks' FiLM rows (unet.py:132-136)
+  const Builder::TimeEmb te = b.time_embedding(px, NL, NL > 0 && !gradk, gradk || NL > 0);
+  const Builder::Film film = b.film_table(all, te.E, te.gemb_off);
+  // ---- conditioning projection (unet.py:46-47, 138-139)
+  TensorH condp{};
+  const bool has_cond = c.cond_channels > 0;
+  if (has_cond) {
+    // conditioning rows per clip: T / 256 behind a UNet encoder, (T / 160 + 1 - 2) / 2 + 1 = T / 320 behind the MFCC encoder
+    // or, reserved[3] = 1000 + rows, exactly that many rows for any T (nearest up-sampling to T with PyTorch's index formula, in_conv)
+    const int cond_ls = c.reserved[3] >= LEN_ABS ? c.reserved[3] : (c.reserved[3] == 1 ? LEN_HALF : 8);
+    const int CC = c.cond_channels;
+    TensorH ct = b.new_tensor(CC, cond_ls, false, false);
+    b.op("nct_to_ntc", "", 0, 0, 0, [=](const RunCtx& r) -> int {
+      return launch_nct_to_ntc(r.cond, bp->act(ct.off), nullptr, r.B, CC, shiftL(r.Lbase, cond_ls), 0, prec, r.st);
+    });
+    condp = b.new_tensor(base, cond_ls, false, false);
+    PackedConv pk(prec);
+    Builder::SegSpec g{ct, 0, CC, 3, 1, RESIZE_NONE, false, 0, 0, 0, 0};
+    g.w_off = pk.append(b.P(px + "cond_proj.weight"), base, CC, 3, 0, CC);
+    const float* bb = b.P(px + "cond_proj.bias");
+    b.add_conv({g}, pk, std::vector<float>(bb, bb + base), base, condp, nullptr, 0);
+    b.release(ct);
+  }
+  TensorH h = b.in_conv(px, c.in_channels, has_cond ? &condp : nullptr);
+  if (has_cond) b.release(condp);
+  b.tap("in_conv", h);
+  // ---- down / middle / up with the skip stack (unet.py:141-160)
+  std::vector<TensorH> skips{h};
+  b.retain(h);  // one reference held by `h`, one by the stack
+  std::vector<Builder::BlockRec> recs(all.size());
+  for (size_t i = 0; i < all.size(); ++i) {
+    const BlockSpec& s = all[i];
+    std::vector<TensorH> ins{h};
+    if (s.cat) {
+      ins.push_back(skips.back());
+      skips.pop_back();
+    }
+    TensorH o = b.resblock(s.prefix, s, ins, true, film.row[i], film.R, film.film_off, keep_bw ? &recs[i] : nullptr);
+    if (s.cat) b.release(ins[1]);
+    b.release(h);
+    h = o;
+    if (i < down.size()) {  // every down block's output waits on the stack for its up block
+      skips.push_back(h);
+      b.retain(h);
+    }
+    b.tap(s.prefix, h);
+  }
+  // ---- output head (unet.py:113-116, 162)
+  const Builder::GnHead gh = b.head_gn(h, px + "out.0.0", keep_bw);
+  // (persist is read by release() alone, and nothing between here and the tails releases -- new_tensor, blob entries and add_conv do
+  //  not -- so the forward ends here for every kind, although the tails allocate a little more before their first release)
+  b.persist = false;
+  if (c.out_channels != 1) {
+    TensorH o = b.head_conv(h, gh, px + "out.1", c.out_channels, 0);
+    if (encpred) unet_encpred_tail(m, b, recs, h, gh, o);
+    else b.to_nct(o);
+    return;
+  }
+  const float* W = b.P(px + "out.1.weight");  // [1][base][3] -> [3][base]
+  std::vector<float> wt(3 * base);
+  for (int k = 0; k < 3; ++k)
+    for (int ci = 0; ci < base; ++ci) wt[k * base + ci] = W[ci * 3 + k];
+  const size_t w = b.blob.add(wt.data(), wt.size() * 4);
+  const float bias = b.P(px + "out.1.bias")[0];
+  const TensorH pred = gradk ? b.new_tensor(1, 0, true, false) : TensorH{};  // (the prediction of a call that does not ask for it)
+  const size_t ss = gh.ss;
+  b.op("out_conv", std::to_string(base) + "->1", (double)base, 4.0, 0, [=](const RunCtx& r) -> int {
+    OutConvArgs a{};
+    a.in = bp->act(h.off);
+    a.ss = bp->ssf2(ss);
+    a.w = bp->wf(w);
+    a.bias = bias;
+    a.out = gradk && !r.out ? reinterpret_cast<float*>(bp->act(pred.off)) : r.out;
+    a.C = base;
+    a.L = r.Lbase;
+    return launch_out_conv(a, r.B, prec, r.st);
+  });
+  if (gradk) unet_embed_grad_tail(m, b, recs, te, film, h, gh, w, pred);
+}
+
+// Classifier.forward (classifier.py:31-36, 111-121) + the input gradient used by cond_fn (sample_diffusion.py:34-42)
+static void build_classifier(vqvs_model* m, Builder& b) {
+  const vqvs_cfg& c = m->cfg;
+  Builder* bp = &b;
+  const int prec = c.precision, base = c.base_channels, F = classifier_output_mult(c) * base, NL = c.num_labels;
+  std::vector<BlockSpec> blocks;
+  const int cur = classifier_blocks(base, topo_of(c), blocks);
+  b.persist = true;  // the backward pass re-reads every block input, h1 and their GroupNorm coefficients
+  const Builder::TimeEmb te = b.time_embedding("stem.", 0, false, false);
+  const Builder::Film film = b.film_table(blocks, te.E, te.gemb_off);
+  size_t inw = 0;
+  TensorH h = b.in_conv("stem.", 1, nullptr, &inw);
+  b.tap("stem.in_conv", h);
+  std::vector<Builder::BlockRec> recs(blocks.size());
+  for (size_t i = 0; i < blocks.size(); ++i) {
+    h = b.resblock(blocks[i].prefix, blocks[i], {h}, true, film.row[i], film.R, film.film_off, &recs[i]);
+    b.tap(blocks[i].prefix, h);
+  }
+  // ---- head: GroupNorm + GELU + attention pool (query token only) + c_proj + GELU + Linear, and its backward
+  const Builder::GnHead gh = b.head_gn(h, "stem.out.0.0", true);
+  const int ch = std::min(cur, 64), heads = cur / ch;
+  const float* Wqkv = b.P("stem.out.1.qkv_proj.weight");  // [3*cur][cur][1]: q rows, k rows, v rows
+  const float* bqkv = b.P("stem.out.1.qkv_proj.bias");
+  const double sc2 = 1.0 / std::sqrt((double)ch);  // both q and k carry ch^-1/4 (classifier.py:181-186)
+  std::vector<float> rvec((size_t)heads * cur), c0(heads);
+  for (int hd = 0; hd < heads; ++hd) {
+    double cc = 0.0;
+    for (int j = 0; j < ch; ++j) cc += (double)bqkv[hd * ch + j] * (double)bqkv[cur + hd * ch + j];
+    c0[hd] = (float)(cc * sc2);
+    for (int ci = 0; ci < cur; ++ci) {
+      double acc = 0.0;
+      for (int j = 0; j < ch; ++j) acc += (double)bqkv[hd * ch + j] * (double)Wqkv[(size_t)(cur + hd * ch + j) * cur + ci];
+      rvec[(size_t)hd * cur + ci] = (float)(acc * sc2);
+    }
+  }
+  const size_t r_off = b.blob.add(rvec.data(), rvec.size() * 4), c0_off = b.blob.add(c0.data(), c0.size() * 4);
+  const size_t wv_off = b.blob.add(Wqkv + (size_t)2 * cur * cur, (size_t)cur * cur * 4);
+  const size_t wvT_off = b.blob_f32_transposed(Wqkv + (size_t)2 * cur * cur, cur, cur);
+  const size_t wcT_off = b.blob_f32_transposed(b.P("stem.out.1.c_proj.weight"), F, cur);
+  const size_t wlT_off = b.blob_f32_transposed(b.P("out.1.weight"), NL, F);
+  const size_t bv_off = b.blob.add(bqkv + 2 * cur, (size_t)cur * 4);
+  const size_t wc_off = b.blob_f32("stem.out.1.c_proj.weight"), bc_off = b.blob_f32("stem.out.1.c_proj.bias");
+  const size_t wl_off = b.blob_f32("out.1.weight"), bl_off = b.blob_f32("out.1.bias");
+  b.persist = false;
+  TensorH dh = b.new_tensor(cur, h.lshift, false, false);
+  const int groups_h = gn_groups(cur);
+  b.op("cls_head", "C=" + std::to_string(cur), 0, 0, 0, [=](const RunCtx& r) -> int {
+    HeadArgs a{};
+    a.h = bp->act(h.off);
+    a.ss = bp->ssf2(gh.ss);
+    a.mr = bp->ssf2(gh.mr);
+    a.C = cur;
+    a.L = shiftL(r.Lbase, h.lshift);
+    a.heads = heads;
+    a.F = F;
+    a.NL = NL;
+    a.groups = groups_h;
+    a.inv_count = 1.0 / ((double)(cur / groups_h) * (double)a.L);
+    a.r = bp->wf(r_off);
+    a.c0 = bp->wf(c0_off);
+    a.wv = bp->wf(wv_off);
+    a.wvT = bp->wf(wvT_off);
+    a.wcT = bp->wf(wcT_off);
+    a.wlT = bp->wf(wlT_off);
+    a.bv = bp->wf(bv_off);
+    a.wc = bp->wf(wc_off);
+    a.bc = bp->wf(bc_off);
+    a.wl = bp->wf(wl_off);
+    a.bl = bp->wf(bl_off);
+    a.logits = r.out;
+    a.feat = r.feat;
+    a.probs = r.probs;
+    a.labels = r.backward ? r.labels : nullptr;
+    a.gscale = grad_scale(prec);  // (the caller's scale multiplies the finished gradient in fp32, in_conv_bw: the 2-byte gradient tensors never see it)
+    a.dh = bp->act(dh.off);
+    return launch_cls_head(a, r.B, prec, r.st);
+  });
+  // ---- backward schedule (phase 1): blocks in reverse, then the 1 -> base input convolution
+  b.phase = 1;
+  TensorH g = dh;
+  for (size_t i = blocks.size(); i-- > 0;) g = b.resblock_backward(recs[i], g);
+  b.in_conv_bw(g, inw);
+  b.phase = 0;
+}
+
+// ConvMFCCEncoder.forward (conv_encoder.py:90-110).  The convolution stack runs on the fused MFMA kernel in the fp32
+// mode: every layer is a raw segment with the GELU in the EPILOGUE (out = skip + gelu(conv(x)), conv_encoder.py:113-120);
+// Conv1d(k = 4, stride = 2, padding = 1) is a 3-tap stride-1 convolution over the input viewed as [pairs][2 * mid]:
+//   out[t] = W0 x[2t-1] + W1 x[2t] + W2 x[2t+1] + W3 x[2t+2]  =  sum over taps j = -1, 0, +1 of pair rows t + j with
+//   even half: (0, W1, W3), odd half: (W0, W2, 0).
+static void build_mfcc_encoder(vqvs_model* m, Builder& b) {
+  const vqvs_cfg& c = m->cfg;
+  Builder* bp = &b;
+  const int prec = c.precision, base = c.base_channels;
+  const int version = c.reserved[1], ulaw = c.reserved[2] ? 1 : 0;
+  const int n_fft = version == 2 ? 400 : 2 * MFCC_HOP, n_mels = version == 2 ? 80 : 40, n_freqs = n_fft / 2 + 1, mid = 12 * base;
+  const int OC = c.out_channels;
+  std::vector<double> tw(2 * (size_t)n_fft);
+  for (int n = 0; n < n_fft; ++n) {
+    tw[2 * n] = std::cos(2.0 * M_PI * n / n_fft);
+    tw[2 * n + 1] = -std::sin(2.0 * M_PI * n / n_fft);
+  }
+  const size_t tw_off = b.blob.add(tw.data(), tw.size() * 8);
+  const size_t win_off = b.blob_f32("mfcc.MelSpectrogram.spectrogram.window"), fb_off = b.blob_f32("mfcc.MelSpectrogram.mel_scale.fb");
+  const size_t dct_off = b.blob_f32("mfcc.dct_mat");
+  double wss = 0.0;
+  for (int n = 0; n < n_fft; ++n) wss += (double)b.P("mfcc.MelSpectrogram.spectrogram.window")[n] * (double)b.P("mfcc.MelSpectrogram.spectrogram.window")[n];
+  const double power_scale = version == 2 ? 1.0 / wss : 1.0;  // Spectrogram(normalized=True): spec / sqrt(sum w^2), then |.|^2
+  const int max_frames = c.max_T / MFCC_HOP + 1;
+  const size_t logmel_off = b.alloc_misc((size_t)c.max_batch * max_frames * n_mels);
+  const size_t wgmax_off = b.alloc_misc((size_t)c.max_batch * mfcc_groups(max_frames) + 64);
+  const bool db = version == 2;
+  TensorH feat = b.new_tensor(64, LEN_FRAMES, false, false);  // fp32 handle: the activation type is float
+  b.op("mfcc_logmel", "n_fft=" + std::to_string(n_fft) + " mels=" + std::to_string(n_mels), 0, 4.0, 0, [=](const RunCtx& r) -> int {
+    if (r.logmel != nullptr) {  // testing entry (vqvs_mfcc_encoder_forward_logmel): injected log-mel rows, the transform is skipped
+      if (db) VQVS_FAIL(-1, "the injected log-mel entry exists for the log_mels (version 1) front end only");
+      VQVS_HIP(hipMemcpyAsync(bp->miscp(logmel_off), r.logmel, (size_t)r.B * shiftL(r.Lbase, LEN_FRAMES) * n_mels * sizeof(float),
+                              hipMemcpyDeviceToDevice, r.st));
+      return 0;
+    }
+    MfccArgs a{};
+    a.x = r.x;
+    a.twiddle = reinterpret_cast<const double*>(bp->wp(tw_off));
+    a.window = bp->wf(win_off);
+    a.fb = bp->wf(fb_off);
+    a.logmel = bp->miscp(logmel_off);
+    a.wgmax = db ? bp->miscp(wgmax_off) + 64 : nullptr;
+    a.T = r.Lbase;
+    a.n_fft = n_fft;
+    a.hop = MFCC_HOP;
+    a.n_freqs = n_freqs;
+    a.n_mels = n_mels;
+    a.frames = shiftL(r.Lbase, LEN_FRAMES);
+    a.ulaw = ulaw;
+    a.log_mels = db ? 0 : 1;
+    a.power_scale = power_scale;
+    if (int e = launch_mfcc_logmel(a, r.B, r.st)) return e;
+    if (db) return launch_mfcc_batch_max(bp->miscp(wgmax_off) + 64, r.B * mfcc_groups(a.frames), bp->miscp(wgmax_off), r.st);
+    return 0;
+  });
+  b.op("mfcc_features", "13 x 3 -> 64 channels", 64.0 / MFCC_HOP, 0, 0, [=](const RunCtx& r) -> int {
+    MfccFeatArgs a{};
+    a.logmel = bp->miscp(logmel_off);
+    a.dct = bp->wf(dct_off);
+    a.batch_max = db ? bp->miscp(wgmax_off) : nullptr;
+    a.feat = reinterpret_cast<float*>(bp->act(feat.off));
+    a.frames = shiftL(r.Lbase, LEN_FRAMES);
+    a.rows_alloc = a.frames;
+    a.n_mels = n_mels;
+    return launch_mfcc_features(a, r.B, r.st);
+  });
+  b.tap("features", feat);
+  auto conv_layer = [&](const TensorH& in, int in_C, int in_lshift, const std::vector<float>& W, int cout, int cin, int ktaps,
+                        const float* bias, const TensorH& out, int out_lshift, const TensorH* skip, bool gelu) {
+    TensorH view = in;
+    view.C = in_C;
+    view.lshift = in_lshift;
+    PackedConv pk(prec);
+    Builder::SegSpec g{view, 0, in_C, ktaps, 1, RESIZE_NONE, false, 0, 0, 0, 0};
+    g.w_off = pk.append(W.data(), cout, cin, ktaps, 0, in_C);
+    b.add_conv({g}, pk, std::vector<float>(bias, bias + cout), cout, out, skip, RESIZE_NONE, out_lshift, gelu);
+  };
+  auto wvec = [&](const std::string& name, size_t n) { return std::vector<float>(b.P(name), b.P(name) + n); };
+  // blocks.0: Conv1d(39 -> mid, 3) + GELU over the zero-padded 64-channel feature rows
+  TensorH h0 = b.new_tensor(mid, LEN_FRAMES, false, false);
+  {
+    std::vector<float> W((size_t)mid * 64 * 3, 0.f);
+    const float* w = b.P("blocks.0.0.weight");
+    for (int co = 0; co < mid; ++co)
+      for (int ci = 0; ci < 39; ++ci)
+        for (int k = 0; k < 3; ++k) W[((size_t)co * 64 + ci) * 3 + k] = w[((size_t)co * 39 + ci) * 3 + k];
+    conv_layer(feat, 64, LEN_FRAMES, W, mid, 64, 3, b.P("blocks.0.0.bias"), h0, LEN_FRAMES, nullptr, true);
+  }
+  b.release(feat);
+  b.tap("blocks.0", h0);
+  // blocks.1: ResConv(3), written into an allocation with an even number of rows (last row zero: "pad_row")
+  TensorH h1 = b.new_tensor(mid, LEN_FRAMES_PAD, false, false);
+  b.op("pad_row", "", 0, 0, 0, [=](const RunCtx& r) -> int {
+    const int frames = shiftL(r.Lbase, LEN_FRAMES), rows = shiftL(r.Lbase, LEN_FRAMES_PAD);
+    if (rows == frames) return 0;
+    VQVS_HIP(hipMemset2DAsync(bp->act(h1.off) + (size_t)frames * mid * 4, (size_t)rows * mid * 4, 0, (size_t)mid * 4, r.B, r.st));
+    return 0;
+  });
+  conv_layer(h0, mid, LEN_FRAMES, wvec("blocks.1.conv.weight", (size_t)mid * mid * 3), mid, mid, 3, b.P("blocks.1.conv.bias"), h1,
+             LEN_FRAMES, &h0, true);
+  b.release(h0);
+  // blocks.2: Conv1d(mid -> mid, 4, stride 2, padding 1) + GELU as a 3-tap convolution over [pairs][2 * mid]
+  TensorH h2 = b.new_tensor(mid, LEN_HALF, false, false);
+  {
+    std::vector<float> W((size_t)mid * 2 * mid * 3, 0.f);
+    const float* w = b.P("blocks.2.0.weight");  // [mid][mid][4]
+    for (int co = 0; co < mid; ++co)
+      for (int ci = 0; ci < mid; ++ci) {
+        const float* wk = w + ((size_t)co * mid + ci) * 4;
+        float* even = &W[((size_t)co * 2 * mid + ci) * 3];
+        float* odd = &W[((size_t)co * 2 * mid + mid + ci) * 3];
+        even[1] = wk[1];  // x[2t]
+        even[2] = wk[3];  // x[2t+2] = even half of pair row t+1
+        odd[0] = wk[0];   // x[2t-1] = odd half of pair row t-1
+        odd[1] = wk[2];   // x[2t+1]
+      }
+    conv_layer(h1, 2 * mid, LEN_PAIRS, W, mid, 2 * mid, 3, b.P("blocks.2.0.bias"), h2, LEN_HALF, nullptr, true);
+  }
+  b.release(h1);
+  b.tap("blocks.2", h2);
+  TensorH h = h2;
+  for (int i = 3; i <= 8; ++i) {  // ResConv(3) x 2, ResConv(1) x 4
+    const int k = i <= 4 ? 3 : 1;
+    TensorH o = b.new_tensor(mid, LEN_HALF, false, false);
+    const std::string nm = "blocks." + std::to_string(i) + ".conv";
+    conv_layer(h, mid, LEN_HALF, wvec(nm + ".weight", (size_t)mid * mid * k), mid, mid, k, b.P(nm + ".bias"), o, LEN_HALF, &h, true);
+    b.release(h);
+    h = o;
+  }
+  b.tap("blocks.8", h);
+  TensorH o = b.new_tensor(OC, LEN_HALF, true, false);
+  conv_layer(h, mid, LEN_HALF, wvec("blocks.9.weight", (size_t)OC * mid), OC, mid, 1, b.P("blocks.9.bias"), o, LEN_HALF, nullptr, false);
+  b.release(h);
+  b.to_nct(o);
+}
+
+// UNetEncoder.forward (unet.py:229-241): the blocks without FiLM, the output has T / downsample_rate rows
+static void build_encoder(vqvs_model* m, Builder& b) {
+  const vqvs_cfg& c = m->cfg;
+  std::vector<BlockSpec> blocks;
+  encoder_blocks(c.base_channels, topo_of(c), blocks);
+  TensorH h = b.in_conv("", c.in_channels, nullptr, nullptr, 1);
+  b.tap("in_conv", h);
+  for (auto& s : blocks) {
+    TensorH o = b.resblock(s.prefix, s, {h}, false, 0, 0, 0);
+    b.release(h);
+    h = o;
+    b.tap(s.prefix, h);
+  }
+  const Builder::GnHead gh = b.head_gn(h, "out.0.0", false);
+  b.to_nct(b.head_conv(h, gh, "out.1", c.out_channels, topo_of(c).levels() - 1));
+}
+
 int build_model(vqvs_model* m, const float* const* hp) {
   const vqvs_cfg& c = m->cfg;
   if (int e = check_cfg(c)) return e;
   if (int e = enumerate_params(c, m->params)) return e;
-  const int prec = c.precision;
-  const int base = c.base_channels;
-  const int in_ch = c.in_channels;
   // NOTE: the builder object must outlive the ops (lambdas capture it for pointer resolution).
   auto keep = std::make_shared<Builder>(m, hp);
   m->keepalive = keep;
-  Builder* bp = keep.get();
-  Builder& b = *bp;
-
-  if (c.kind == VQVS_KIND_RESBLOCK) {
-    BlockSpec s{"", c.rb_cin, c.rb_cout, c.rb_resize, c.rb_dilation, false};
-    const int E = c.rb_emb_channels;
-    TensorH x = b.new_tensor(c.rb_cin, 0, false, true);
-    const int Cin = c.rb_cin;
-    m->meta.push_back({"nct_to_ntc", "", 0, 0, 0});
-    m->add_op([=](const RunCtx& r) -> int {
-      return launch_nct_to_ntc(r.x, bp->act(x.off), bp->statp(x.stats_off), r.B, Cin, r.Lbase, ntiles_of(r.Lbase), prec, r.st);
-    });
-    size_t film_misc = 0;
-    if (E) {
-      const size_t gemb = b.alloc_misc((size_t)c.max_batch * E);
-      film_misc = b.alloc_misc((size_t)c.max_batch * 2 * c.rb_cout);
-      const size_t w_off = b.blob_f32_transposed(b.P("cond_layers.1.weight"), 2 * c.rb_cout, E);
-      const size_t bias_off = b.blob_f32("cond_layers.1.bias");
-      const int R = 2 * c.rb_cout;
-      m->meta.push_back({"film", "", 0, 0, 0});
-      m->add_op([=](const RunCtx& r) -> int {
-        if (!r.emb) VQVS_FAIL(VQVS_ERR_ARG, "resblock handle was built with an embedding; d_emb is NULL");
-        if (int e = launch_gelu_rows(r.emb, bp->miscp(gemb), r.B * E, r.st)) return e;
-        FilmArgs f{bp->miscp(gemb), reinterpret_cast<const float*>(bp->wp(w_off)), reinterpret_cast<const float*>(bp->wp(bias_off)),
-                   bp->miscp(film_misc), E, R};
-        return launch_film(f, r.B, r.st);
-      });
-    }
-    TensorH y = b.resblock("", s, {x}, E != 0, 0, 2 * c.rb_cout, film_misc);
-    const int Cout = c.rb_cout;
-    m->meta.push_back({"ntc_to_nct", "", 0, 0, 0});
-    m->add_op([=](const RunCtx& r) -> int {
-      return launch_ntc_to_nct(bp->act(y.off), r.out, r.B, Cout, shiftL(r.Lbase, y.lshift), prec, r.st);
-    });
-    b.tap("out", y);
-  } else if (c.kind == VQVS_KIND_PREDICTOR || c.kind == VQVS_KIND_ENCPRED || c.kind == VQVS_KIND_PREDICTOR_GRAD) {
-    // ENCPRED (encoder_predictor.py:25-58): the same UNet under the "unet." prefix with a bottleneck output, every
-    // intermediate kept resident for the backward schedule appended below
-    // PREDICTOR_GRAD (speaker enrolment): the class-conditional predictor's own forward ops with the conditioning vector given per
-    // clip, every intermediate kept resident too, and the embedding-gradient schedule behind the output convolution
-    const bool encpred = c.kind == VQVS_KIND_ENCPRED;
-    const bool gradk = c.kind == VQVS_KIND_PREDICTOR_GRAD;
-    const bool keep_bw = encpred || gradk;
-    const std::string px = encpred ? "unet." : "";
-    b.persist = keep_bw;
-    const int E = 4 * base;
-    std::vector<BlockSpec> d, mdl, u;
-    predictor_blocks(base, topo_of(c), d, mdl, u);
-    for (auto* v : {&d, &mdl, &u})
-      for (auto& sp : *v) sp.prefix = px + sp.prefix;
-    // ---- embedding + all blocks' FiLM rows
-    std::vector<float> freqs(E / 2, 0.0f);
-    {
-      // wavegrad.py:361-369 (float32 tensor math) at the REAL embedding width 4 * real base; a padded handle keeps the real entries at
-      // their physical positions (the halves of the embedding -- cos | sin -- are whole numbers of blocks), pad entries are 0 and meet
-      // zero weight rows
-      const int Er = 4 * real_base(c);
-      const PadMap pm = pad_map(real_base(c));
-      for (int i = 0; i < Er / 2; ++i)
-        freqs[pm.phys(i)] = (float)(std::exp((double)(float)(-std::log(100.0 / 0.1)) * (double)i / (double)(Er / 2 - 1))) * 100.0f;
-    }
-    const size_t freq_off = b.blob.add(freqs.data(), freqs.size() * 4);
-    const size_t w1 = b.blob_f32_transposed(b.P(px + "time_embed.proj.weight"), E, E), b1 = b.blob_f32(px + "time_embed.proj.bias");
-    const size_t w2 = b.blob_f32_transposed(b.P(px + "time_embed_extra.1.weight"), E, E), b2 = b.blob_f32(px + "time_embed_extra.1.bias");
-    const size_t ce = c.num_labels > 0 && !gradk ? b.blob_f32(px + "class_embed.weight") : 0;
-    const size_t emb_off = b.alloc_misc((size_t)c.max_batch * E);
-    const size_t gemb_off = b.alloc_misc((size_t)c.max_batch * E);
-    m->emb_misc_off = emb_off;
-    m->emb_E = E;
-    const int NL = c.num_labels;
-    m->meta.push_back({"time_embed", "", 0, 0, 0});
-    m->add_op([=](const RunCtx& r) -> int {
-      TimeEmbedArgs a{};
-      a.ts = r.ts;
-      a.freqs = reinterpret_cast<const float*>(bp->wp(freq_off));
-      a.w1 = reinterpret_cast<const float*>(bp->wp(w1));
-      a.b1 = reinterpret_cast<const float*>(bp->wp(b1));
-      a.w2 = reinterpret_cast<const float*>(bp->wp(w2));
-      a.b2 = reinterpret_cast<const float*>(bp->wp(b2));
-      // an explicit vector per clip (vqvs_unet_forward_vec, vqvs_unet_embed_grad) takes the table's place: the kernel adds one or the other
-      a.class_embed = NL > 0 && !gradk && !r.class_vec ? reinterpret_cast<const float*>(bp->wp(ce)) : nullptr;
-      a.labels = r.labels;
-      a.class_vec = gradk || NL > 0 ? r.class_vec : nullptr;
-      a.num_labels = NL;
-      a.emb = bp->miscp(emb_off);
-      a.gemb = bp->miscp(gemb_off);
-      a.E = E;
-      return launch_time_embed(a, r.B, r.st);
-    });
-    std::vector<const BlockSpec*> all;
-    for (auto& s : d) all.push_back(&s);
-    for (auto& s : mdl) all.push_back(&s);
-    for (auto& s : u) all.push_back(&s);
-    std::vector<int> film_row(all.size());
-    int R = 0;
-    std::vector<float> Wall, ball;
-    for (size_t i = 0; i < all.size(); ++i) {
-      film_row[i] = R;
-      const float* W = b.P(all[i]->prefix + ".cond_layers.1.weight");
-      const float* bb = b.P(all[i]->prefix + ".cond_layers.1.bias");
-      const int rows = 2 * all[i]->cout;
-      Wall.insert(Wall.end(), W, W + (size_t)rows * E);
-      ball.insert(ball.end(), bb, bb + rows);
-      R += rows;
-    }
-    const size_t wall_off = b.blob_f32_transposed(Wall.data(), R, E);
-    const size_t ball_off = b.blob.add(ball.data(), ball.size() * 4);
-    const size_t film_off = b.alloc_misc((size_t)c.max_batch * R);
-    m->meta.push_back({"film", "", 0, 0, 0});
-    m->add_op([=](const RunCtx& r) -> int {
-      FilmArgs f{bp->miscp(gemb_off), reinterpret_cast<const float*>(bp->wp(wall_off)), reinterpret_cast<const float*>(bp->wp(ball_off)),
-                 bp->miscp(film_off), E, R};
-      return launch_film(f, r.B, r.st);
-    });
-    // ---- conditioning projection (unet.py:46-47, 138-139)
-    TensorH condp{};
-    const bool has_cond = c.cond_channels > 0;
-    if (has_cond) {
-      // conditioning rows per clip: T / 256 behind a UNet encoder, (T / 160 + 1 - 2) / 2 + 1 = T / 320 behind the MFCC encoder
-      // or, reserved[3] = 1000 + rows, exactly that many rows for any T (nearest up-sampling to T with PyTorch's index formula, in_conv)
-      const int cond_ls = c.reserved[3] >= LEN_ABS ? c.reserved[3] : (c.reserved[3] == 1 ? LEN_HALF : 8);
-      TensorH ct = b.new_tensor(c.cond_channels, cond_ls, false, false);
-      const int CC = c.cond_channels;
-      m->meta.push_back({"nct_to_ntc", "", 0, 0, 0});
-      m->add_op([=](const RunCtx& r) -> int {
-        return launch_nct_to_ntc(r.cond, bp->act(ct.off), nullptr, r.B, CC, shiftL(r.Lbase, cond_ls), 0, prec, r.st);
-      });
-      condp = b.new_tensor(base, cond_ls, false, false);
-      PackedConv pk(prec);
-      Builder::SegSpec g{ct, 0, CC, 3, 1, RESIZE_NONE, false, 0, 0, 0, 0};
-      g.w_off = pk.append(b.P(px + "cond_proj.weight"), base, CC, 3, 0, CC);
-      const float* bb = b.P(px + "cond_proj.bias");
-      b.add_conv({g}, pk, std::vector<float>(bb, bb + base), base, condp, nullptr, 0);
-      b.release(ct);
-    }
-    // ---- in_conv
-    TensorH h = b.new_tensor(base, 0, false, true);
-    {
-      const size_t w = b.blob_f32(px + "in_conv.weight"), bi = b.blob_f32(px + "in_conv.bias");
-      const TensorH cp = condp;
-      m->meta.push_back({"in_conv", std::to_string(in_ch) + "->" + std::to_string(base), base + (has_cond ? base * lscale(condp.lshift) : 0.0), 4.0 * in_ch, 0});
-      m->add_op([=](const RunCtx& r) -> int {
-        InConvArgs a{};
-        a.x = r.x;
-        a.Cin = in_ch;
-        a.w = reinterpret_cast<const float*>(bp->wp(w));
-        a.bias = reinterpret_cast<const float*>(bp->wp(bi));
-        a.condp = has_cond ? bp->act(cp.off) : nullptr;
-        a.cond_len = has_cond ? shiftL(r.Lbase, cp.lshift) : 0;
-        a.out = bp->act(h.off);
-        a.stats = bp->statp(h.stats_off);
-        a.C = base;
-        a.T = r.Lbase;
-        a.ntiles = ntiles_of(r.Lbase);
-        return launch_in_conv(a, r.B, prec, r.st);
-      });
-    }
-    if (has_cond) b.release(condp);
-    b.tap("in_conv", h);
-    // ---- down / middle / up with the skip stack (unet.py:141-160)
-    std::vector<TensorH> skips{h};
-    b.retain(h);  // one reference held by `h`, one by the stack
-    size_t bi = 0;
-    std::vector<Builder::BlockRec> recs(all.size());
-    auto recp = [&](size_t i) { return keep_bw ? &recs[i] : nullptr; };
-    for (auto& s : d) {
-      TensorH o = b.resblock(s.prefix, s, {h}, true, film_row[bi], R, film_off, recp(bi));
-      ++bi;
-      b.release(h);
-      h = o;
-      skips.push_back(h);
-      b.retain(h);
-      b.tap(s.prefix, h);
-    }
-    for (auto& s : mdl) {
-      TensorH o = b.resblock(s.prefix, s, {h}, true, film_row[bi], R, film_off, recp(bi));
-      ++bi;
-      b.release(h);
-      h = o;
-      b.tap(s.prefix, h);
-    }
-    for (auto& s : u) {
-      TensorH o;
-      if (s.cat) {
-        TensorH sk = skips.back();
-        skips.pop_back();
-        o = b.resblock(s.prefix, s, {h, sk}, true, film_row[bi], R, film_off, recp(bi));
-        b.release(sk);
-      } else {
-        o = b.resblock(s.prefix, s, {h}, true, film_row[bi], R, film_off, recp(bi));
-      }
-      ++bi;
-      b.release(h);
-      h = o;
-      b.tap(s.prefix, h);
-    }
-    // ---- output head (unet.py:113-116, 162)
-    const size_t ss = b.alloc_ss(base);
-    const size_t mr_out = keep_bw ? b.alloc_ss(base) : 0;
-    b.add_gn({h}, px + "out.0.0", false, 0, 0, 0, ss, keep_bw, mr_out);
-    if (c.out_channels == 1) {
-      const float* W = b.P(px + "out.1.weight");  // [1][base][3] -> [3][base]
-      std::vector<float> wt(3 * base);
-      for (int k = 0; k < 3; ++k)
-        for (int ci = 0; ci < base; ++ci) wt[k * base + ci] = W[ci * 3 + k];
-      const size_t w = b.blob.add(wt.data(), wt.size() * 4);
-      const float bias = b.P(px + "out.1.bias")[0];
-      const TensorH pred = gradk ? b.new_tensor(1, 0, true, false) : TensorH{};  // (the prediction of a call that does not ask for it)
-      m->meta.push_back({"out_conv", std::to_string(base) + "->1", (double)base, 4.0, 0});
-      m->add_op([=](const RunCtx& r) -> int {
-        OutConvArgs a{};
-        a.in = bp->act(h.off);
-        a.ss = reinterpret_cast<const float2*>(bp->ssp(ss));
-        a.w = reinterpret_cast<const float*>(bp->wp(w));
-        a.bias = bias;
-        a.out = gradk && !r.out ? reinterpret_cast<float*>(bp->act(pred.off)) : r.out;
-        a.C = base;
-        a.L = r.Lbase;
-        return launch_out_conv(a, r.B, prec, r.st);
-      });
-      if (gradk) {
-        // ---- loss head + the embedding-gradient schedule (phase 1): d mse_b / d v_b for every clip b
-        b.persist = false;
-        b.ws_f32_kind = false;  // (the transposed convolutions run where the guidance schedules' run)
-        m->cur_phase = 1;
-        TensorH dout = b.new_tensor(1, 0, true, false);
-        const size_t sq_off = b.alloc_misc(2 * (size_t)mse_head_scratch_doubles(c.max_batch, c.max_T));
-        m->meta.push_back({"mse_head", "", 0, 12.0, 0});
-        m->add_op([=](const RunCtx& r) -> int {
-          const float* p = r.out ? r.out : reinterpret_cast<const float*>(bp->act(pred.off));
-          return run_mse_head(p, r.eps, reinterpret_cast<float*>(bp->act(dout.off)), r.mse, reinterpret_cast<double*>(bp->miscp(sq_off)), r.B,
-                              r.Lbase, r.st);
-        });
-        // out.1 (3-tap conv base -> 1 over gelu(GN(h))) backwards: conv^T and gelu' in one kernel, then GroupNorm backward
-        TensorH t = b.new_tensor(base, 0, false, false);
-        const size_t po = b.alloc_stats(base, 0);
-        m->meta.push_back({"out_conv_bw", "1->" + std::to_string(base), 2.0 * base, 4.0, 0});
-        m->add_op([=](const RunCtx& r) -> int {
-          OutConvBwArgs a{};
-          a.dout = reinterpret_cast<const float*>(bp->act(dout.off));
-          a.xf = bp->act(h.off);
-          a.ss = reinterpret_cast<const float2*>(bp->ssp(ss));
-          a.w = reinterpret_cast<const float*>(bp->wp(w));
-          a.du = bp->act(t.off);
-          a.partials = bp->statp(po);
-          a.C = base;
-          a.L = r.Lbase;
-          return launch_out_conv_bw(a, r.B, r.st);
-        });
-        b.release(dout);
-        const size_t cfo = b.add_gn_bw(base, 0, po, ss, mr_out, STAT_TILE);
-        b.add_bw_affine(t, h, cfo, nullptr, BW_SAME, nullptr, t);
-        // per block, as soon as du2 exists: (d a | d b) into the block's rows of dfilm [B][R]
-        const size_t dfilm_off = b.alloc_misc((size_t)c.max_batch * R);
-        m->dfilm_misc_off = dfilm_off;
-        m->dfilm_R = R;
-        std::map<std::string, int> row_of;
-        for (size_t i = 0; i < all.size(); ++i) row_of[all[i]->prefix] = film_row[i];
-        b.on_du2 = [&](const Builder::BlockRec& rec, const TensorH& du2) {
-          const int C = rec.s.cout, row = row_of.at(rec.s.prefix), ls = rec.out.lshift;
-          const size_t g_off = b.blob_f32(rec.s.prefix + ".pre_cond.3.weight"), be_off = b.blob_f32(rec.s.prefix + ".pre_cond.3.bias");
-          const size_t pf = b.alloc_stats(C, ls);
-          const TensorH D = du2, H1 = rec.h1;
-          const size_t mr2 = rec.mr2;
-          m->meta.push_back({"film_grad", "C=" + std::to_string(C) + " L>>" + std::to_string(ls), 2.0 * C * lscale(ls), 0, 0});
-          m->add_op([=](const RunCtx& r) -> int {
-            FilmGradArgs a{};
-            a.du = bp->act(D.off);
-            a.h1 = bp->act(H1.off);
-            a.mr = reinterpret_cast<const float2*>(bp->ssp(mr2));
-            a.gamma = reinterpret_cast<const float*>(bp->wp(g_off));
-            a.beta = reinterpret_cast<const float*>(bp->wp(be_off));
-            a.partials = bp->statp(pf);
-            a.dfilm = bp->miscp(dfilm_off);
-            a.film_stride = R;
-            a.film_off = row;
-            a.C = C;
-            a.L = shiftL(r.Lbase, ls);
-            a.ntiles = ntiles_of(a.L);
-            return launch_film_grad(a, r.B, r.st);
-          });
-        };
-        b.unet_backward(recs, t, false);  // (the first block's input gradient and the skip path into in_conv are not needed)
-        b.on_du2 = nullptr;
-        // d v = gelu'(emb) * Wall^T dfilm
-        m->meta.push_back({"film_bw", "", 0, 0, 0});
-        m->add_op([=](const RunCtx& r) -> int {
-          FilmBwArgs a{bp->miscp(dfilm_off), reinterpret_cast<const float*>(bp->wp(wall_off)), bp->miscp(emb_off), r.egrad, E, R};
-          return launch_film_bw(a, r.B, r.st);
-        });
-        m->cur_phase = 0;
-      }
-    } else {
-      TensorH o = b.new_tensor(c.out_channels, 0, true, false);
-      PackedConv pk(prec);
-      Builder::SegSpec g{h, 0, base, 3, 1, RESIZE_NONE, true, ss, base, 0, 0};
-      g.w_off = pk.append(b.P(px + "out.1.weight"), c.out_channels, base, 3, 0, base);
-      const float* bb = b.P(px + "out.1.bias");
-      b.add_conv({g}, pk, std::vector<float>(bb, bb + c.out_channels), c.out_channels, o, nullptr, 0);
-      const int OC = c.out_channels;
-      if (!encpred) {
-        m->meta.push_back({"ntc_to_nct", "", 0, 0, 0});
-        m->add_op([=](const RunCtx& r) -> int { return launch_ntc_to_nct(bp->act(o.off), r.out, r.B, OC, r.Lbase, 0, r.st); });
-      } else {
-        // ---- EncoderPredictor head + backward schedule (vq_vae.py:125-130: grads of the summed cross-entropy)
-        const int D = c.reserved[2], rate = c.reserved[1];
-        const size_t hw = b.blob_f32("out.weight"), hb = b.blob_f32("out.bias");
-        b.persist = false;
-        TensorH dO = b.new_tensor(OC, 0, false, false);
-        const int es = b.es();
-        m->meta.push_back({"enc_head", "D=" + std::to_string(D), 0, 0, 0});
-        m->add_op([=](const RunCtx& r) -> int {
-          if (r.backward) VQVS_HIP(hipMemsetAsync(bp->act(dO.off), 0, (size_t)r.B * r.Lbase * OC * es, r.st));
-          EncHeadArgs a{};
-          a.o = reinterpret_cast<const float*>(bp->act(o.off));
-          a.w = reinterpret_cast<const float*>(bp->wp(hw));
-          a.bias = reinterpret_cast<const float*>(bp->wp(hb));
-          a.logits = r.out;
-          a.targets = r.backward ? r.labels : nullptr;
-          a.gscale = grad_scale(prec);  // (the caller's scale multiplies the finished gradient in fp32, in_conv_bw: the 2-byte gradient tensors never see it)
-          a.dO = bp->act(dO.off);
-          a.Cb = OC;
-          a.D = D;
-          a.T = r.Lbase;
-          a.T1 = r.Lbase / rate;
-          a.rate = rate;
-          return launch_enc_head(a, r.B, prec, r.st);
-        });
-        m->cur_phase = 1;
-        // out.1 (3-tap conv base -> bottleneck over gelu(GN(h))) backwards: conv^T, gelu', GroupNorm backward
-        TensorH t = b.new_tensor(base, 0, false, false);
-        const size_t po = b.alloc_stats(base, 0);
-        const bool fuse = Builder::bw_fuse_enabled();
-        const Builder::BwFuse fo{{h}, ss, base, po};
-        const int tro = b.add_conv_t(dO, b.P(px + "out.1.weight"), OC, base, 3, 1, t, fuse ? &fo : nullptr);
-        b.release(dO);
-        if (!fuse) b.add_bw_act(t, BW_SAME, h, ss, t, po);
-        const size_t cfo = b.add_gn_bw(base, 0, po, ss, mr_out, fuse ? tro : STAT_TILE);
-        b.add_bw_affine(t, h, cfo, nullptr, BW_SAME, nullptr, t);
-        const TensorH gi = b.unet_backward(recs, t);  // blocks in reverse, down to the in_conv output
-        const size_t inw = b.blob_f32(px + "in_conv.weight");
-        m->meta.push_back({"in_conv_bw", std::to_string(base) + "->1", (double)base, 4.0, 0});
-        m->add_op([=](const RunCtx& r) -> int {
-          InConvBwArgs a{};
-          a.dh = bp->act(gi.off);
-          a.w = reinterpret_cast<const float*>(bp->wp(inw));
-          a.out = r.grad_out;
-          a.C = base;
-          a.T = r.Lbase;
-          a.out_scale = r.gscale / grad_scale(prec);
-          return launch_in_conv_bw(a, r.B, prec, r.st);
-        });
-        m->cur_phase = 0;
-      }
-    }
-  } else if (c.kind == VQVS_KIND_CLASSIFIER) {
-    // Classifier.forward (classifier.py:31-36, 111-121) + the input gradient used by cond_fn (sample_diffusion.py:34-42)
-    const int E = 4 * base, F = classifier_output_mult(c) * base, NL = c.num_labels;
-    std::vector<BlockSpec> blocks;
-    const int cur = classifier_blocks(base, topo_of(c), blocks);
-    b.persist = true;  // the backward pass re-reads every block input, h1 and their GroupNorm coefficients
-    std::vector<float> freqs(E / 2);
-    for (int i = 0; i < E / 2; ++i)
-      freqs[i] = (float)(std::exp((double)(float)(-std::log(100.0 / 0.1)) * (double)i / (double)(E / 2 - 1))) * 100.0f;
-    const size_t freq_off = b.blob.add(freqs.data(), freqs.size() * 4);
-    const size_t w1 = b.blob_f32_transposed(b.P("stem.time_embed.proj.weight"), E, E), b1 = b.blob_f32("stem.time_embed.proj.bias");
-    const size_t w2 = b.blob_f32_transposed(b.P("stem.time_embed_extra.1.weight"), E, E), b2 = b.blob_f32("stem.time_embed_extra.1.bias");
-    const size_t emb_off = b.alloc_misc((size_t)c.max_batch * E);
-    const size_t gemb_off = b.alloc_misc((size_t)c.max_batch * E);
-    m->emb_misc_off = emb_off;
-    m->emb_E = E;
-    m->meta.push_back({"time_embed", "", 0, 0, 0});
-    m->add_op([=](const RunCtx& r) -> int {
-      TimeEmbedArgs a{};
-      a.ts = r.ts;
-      a.freqs = reinterpret_cast<const float*>(bp->wp(freq_off));
-      a.w1 = reinterpret_cast<const float*>(bp->wp(w1));
-      a.b1 = reinterpret_cast<const float*>(bp->wp(b1));
-      a.w2 = reinterpret_cast<const float*>(bp->wp(w2));
-      a.b2 = reinterpret_cast<const float*>(bp->wp(b2));
-      a.emb = bp->miscp(emb_off);
-      a.gemb = bp->miscp(gemb_off);
-      a.E = E;
-      return launch_time_embed(a, r.B, r.st);
-    });
-    std::vector<int> film_row(blocks.size());
-    int R = 0;
-    std::vector<float> Wall, ball;
-    for (size_t i = 0; i < blocks.size(); ++i) {
-      film_row[i] = R;
-      const float* W = b.P(blocks[i].prefix + ".cond_layers.1.weight");
-      const float* bb = b.P(blocks[i].prefix + ".cond_layers.1.bias");
-      const int rows = 2 * blocks[i].cout;
-      Wall.insert(Wall.end(), W, W + (size_t)rows * E);
-      ball.insert(ball.end(), bb, bb + rows);
-      R += rows;
-    }
-    const size_t wall_off = b.blob_f32_transposed(Wall.data(), R, E);
-    const size_t ball_off = b.blob.add(ball.data(), ball.size() * 4);
-    const size_t film_off = b.alloc_misc((size_t)c.max_batch * R);
-    m->meta.push_back({"film", "", 0, 0, 0});
-    m->add_op([=](const RunCtx& r) -> int {
-      FilmArgs f{bp->miscp(gemb_off), reinterpret_cast<const float*>(bp->wp(wall_off)), reinterpret_cast<const float*>(bp->wp(ball_off)),
-                 bp->miscp(film_off), E, R};
-      return launch_film(f, r.B, r.st);
-    });
-    TensorH h = b.new_tensor(base, 0, false, true);
-    const size_t inw = b.blob_f32("stem.in_conv.weight"), inb = b.blob_f32("stem.in_conv.bias");
-    m->meta.push_back({"in_conv", "1->" + std::to_string(base), (double)base, 4.0, 0});
-    m->add_op([=](const RunCtx& r) -> int {
-      InConvArgs a{};
-      a.x = r.x;
-      a.w = reinterpret_cast<const float*>(bp->wp(inw));
-      a.bias = reinterpret_cast<const float*>(bp->wp(inb));
-      a.condp = nullptr;
-      a.cond_len = 0;
-      a.out = bp->act(h.off);
-      a.stats = bp->statp(h.stats_off);
-      a.C = base;
-      a.T = r.Lbase;
-      a.ntiles = ntiles_of(r.Lbase);
-      return launch_in_conv(a, r.B, prec, r.st);
-    });
-    b.tap("stem.in_conv", h);
-    std::vector<Builder::BlockRec> recs(blocks.size());
-    for (size_t i = 0; i < blocks.size(); ++i) {
-      h = b.resblock(blocks[i].prefix, blocks[i], {h}, true, film_row[i], R, film_off, &recs[i]);
-      b.tap(blocks[i].prefix, h);
-    }
-    // ---- head: GroupNorm + GELU + attention pool (query token only) + c_proj + GELU + Linear, and its backward
-    const size_t ssh = b.alloc_ss(cur), mrh = b.alloc_ss(cur);
-    b.add_gn({h}, "stem.out.0.0", false, 0, 0, 0, ssh, true, mrh);
-    const int ch = std::min(cur, 64), heads = cur / ch;
-    const float* Wqkv = b.P("stem.out.1.qkv_proj.weight");  // [3*cur][cur][1]: q rows, k rows, v rows
-    const float* bqkv = b.P("stem.out.1.qkv_proj.bias");
-    const double sc2 = 1.0 / std::sqrt((double)ch);  // both q and k carry ch^-1/4 (classifier.py:181-186)
-    std::vector<float> rvec((size_t)heads * cur), c0(heads);
-    for (int hd = 0; hd < heads; ++hd) {
-      double cc = 0.0;
-      for (int j = 0; j < ch; ++j) cc += (double)bqkv[hd * ch + j] * (double)bqkv[cur + hd * ch + j];
-      c0[hd] = (float)(cc * sc2);
-      for (int ci = 0; ci < cur; ++ci) {
-        double acc = 0.0;
-        for (int j = 0; j < ch; ++j) acc += (double)bqkv[hd * ch + j] * (double)Wqkv[(size_t)(cur + hd * ch + j) * cur + ci];
-        rvec[(size_t)hd * cur + ci] = (float)(acc * sc2);
-      }
-    }
-    const size_t r_off = b.blob.add(rvec.data(), rvec.size() * 4), c0_off = b.blob.add(c0.data(), c0.size() * 4);
-    const size_t wv_off = b.blob.add(Wqkv + (size_t)2 * cur * cur, (size_t)cur * cur * 4);
-    const size_t wvT_off = b.blob_f32_transposed(Wqkv + (size_t)2 * cur * cur, cur, cur);
-    const size_t wcT_off = b.blob_f32_transposed(b.P("stem.out.1.c_proj.weight"), F, cur);
-    const size_t wlT_off = b.blob_f32_transposed(b.P("out.1.weight"), NL, F);
-    const size_t bv_off = b.blob.add(bqkv + 2 * cur, (size_t)cur * 4);
-    const size_t wc_off = b.blob_f32("stem.out.1.c_proj.weight"), bc_off = b.blob_f32("stem.out.1.c_proj.bias");
-    const size_t wl_off = b.blob_f32("out.1.weight"), bl_off = b.blob_f32("out.1.bias");
-    b.persist = false;
-    TensorH dh = b.new_tensor(cur, h.lshift, false, false);
-    const int groups_h = gn_groups(cur);
-    const TensorH hl = h;
-    m->meta.push_back({"cls_head", "C=" + std::to_string(cur), 0, 0, 0});
-    m->add_op([=](const RunCtx& r) -> int {
-      HeadArgs a{};
-      a.h = bp->act(hl.off);
-      a.ss = reinterpret_cast<const float2*>(bp->ssp(ssh));
-      a.mr = reinterpret_cast<const float2*>(bp->ssp(mrh));
-      a.C = cur;
-      a.L = shiftL(r.Lbase, hl.lshift);
-      a.heads = heads;
-      a.F = F;
-      a.NL = NL;
-      a.groups = groups_h;
-      a.inv_count = 1.0 / ((double)(cur / groups_h) * (double)a.L);
-      a.r = reinterpret_cast<const float*>(bp->wp(r_off));
-      a.c0 = reinterpret_cast<const float*>(bp->wp(c0_off));
-      a.wv = reinterpret_cast<const float*>(bp->wp(wv_off));
-      a.wvT = reinterpret_cast<const float*>(bp->wp(wvT_off));
-      a.wcT = reinterpret_cast<const float*>(bp->wp(wcT_off));
-      a.wlT = reinterpret_cast<const float*>(bp->wp(wlT_off));
-      a.bv = reinterpret_cast<const float*>(bp->wp(bv_off));
-      a.wc = reinterpret_cast<const float*>(bp->wp(wc_off));
-      a.bc = reinterpret_cast<const float*>(bp->wp(bc_off));
-      a.wl = reinterpret_cast<const float*>(bp->wp(wl_off));
-      a.bl = reinterpret_cast<const float*>(bp->wp(bl_off));
-      a.logits = r.out;
-      a.feat = r.feat;
-      a.probs = r.probs;
-      a.labels = r.backward ? r.labels : nullptr;
-      a.gscale = grad_scale(prec);  // (the caller's scale multiplies the finished gradient in fp32, in_conv_bw: the 2-byte gradient tensors never see it)
-      a.dh = bp->act(dh.off);
-      return launch_cls_head(a, r.B, prec, r.st);
-    });
-    // ---- backward schedule (phase 1): blocks in reverse, then the 1 -> base input convolution
-    m->cur_phase = 1;
-    TensorH g = dh;
-    for (size_t i = blocks.size(); i-- > 0;) g = b.resblock_backward(recs[i], g);
-    {
-      const TensorH gi = g;
-      m->meta.push_back({"in_conv_bw", std::to_string(base) + "->1", (double)base, 4.0, 0});
-      m->add_op([=](const RunCtx& r) -> int {
-        InConvBwArgs a{};
-        a.dh = bp->act(gi.off);
-        a.w = reinterpret_cast<const float*>(bp->wp(inw));
-        a.out = r.grad_out;
-        a.C = base;
-        a.T = r.Lbase;
-        a.out_scale = r.gscale / grad_scale(prec);
-        return launch_in_conv_bw(a, r.B, prec, r.st);
-      });
-    }
-    m->cur_phase = 0;
-  } else if (c.kind == VQVS_KIND_MFCC_ENCODER) {
-    // ConvMFCCEncoder.forward (conv_encoder.py:90-110).  The convolution stack runs on the fused MFMA kernel in the fp32
-    // mode: every layer is a raw segment with the GELU in the EPILOGUE (out = skip + gelu(conv(x)), conv_encoder.py:113-120);
-    // Conv1d(k = 4, stride = 2, padding = 1) is a 3-tap stride-1 convolution over the input viewed as [pairs][2 * mid]:
-    //   out[t] = W0 x[2t-1] + W1 x[2t] + W2 x[2t+1] + W3 x[2t+2]  =  sum over taps j = -1, 0, +1 of pair rows t + j with
-    //   even half: (0, W1, W3), odd half: (W0, W2, 0).
-    const int version = c.reserved[1], ulaw = c.reserved[2] ? 1 : 0;
-    const int n_fft = version == 2 ? 400 : 2 * MFCC_HOP, n_mels = version == 2 ? 80 : 40, n_freqs = n_fft / 2 + 1, mid = 12 * base;
-    const int OC = c.out_channels;
-    std::vector<double> tw(2 * (size_t)n_fft);
-    for (int n = 0; n < n_fft; ++n) {
-      tw[2 * n] = std::cos(2.0 * M_PI * n / n_fft);
-      tw[2 * n + 1] = -std::sin(2.0 * M_PI * n / n_fft);
-    }
-    const size_t tw_off = b.blob.add(tw.data(), tw.size() * 8);
-    const size_t win_off = b.blob_f32("mfcc.MelSpectrogram.spectrogram.window"), fb_off = b.blob_f32("mfcc.MelSpectrogram.mel_scale.fb");
-    const size_t dct_off = b.blob_f32("mfcc.dct_mat");
-    double wss = 0.0;
-    for (int n = 0; n < n_fft; ++n) wss += (double)b.P("mfcc.MelSpectrogram.spectrogram.window")[n] * (double)b.P("mfcc.MelSpectrogram.spectrogram.window")[n];
-    const double power_scale = version == 2 ? 1.0 / wss : 1.0;  // Spectrogram(normalized=True): spec / sqrt(sum w^2), then |.|^2
-    const int max_frames = c.max_T / MFCC_HOP + 1;
-    const size_t logmel_off = b.alloc_misc((size_t)c.max_batch * max_frames * n_mels);
-    const size_t wgmax_off = b.alloc_misc((size_t)c.max_batch * mfcc_groups(max_frames) + 64);
-    const bool db = version == 2;
-    TensorH feat = b.new_tensor(64, LEN_FRAMES, false, false);  // fp32 handle: the activation type is float
-    m->meta.push_back({"mfcc_logmel", "n_fft=" + std::to_string(n_fft) + " mels=" + std::to_string(n_mels), 0, 4.0, 0});
-    m->add_op([=](const RunCtx& r) -> int {
-      if (r.logmel != nullptr) {  // testing entry (vqvs_mfcc_encoder_forward_logmel): injected log-mel rows, the transform is skipped
-        if (db) VQVS_FAIL(-1, "the injected log-mel entry exists for the log_mels (version 1) front end only");
-        VQVS_HIP(hipMemcpyAsync(bp->miscp(logmel_off), r.logmel, (size_t)r.B * shiftL(r.Lbase, LEN_FRAMES) * n_mels * sizeof(float),
-                                hipMemcpyDeviceToDevice, r.st));
-        return 0;
-      }
-      MfccArgs a{};
-      a.x = r.x;
-      a.twiddle = reinterpret_cast<const double*>(bp->wp(tw_off));
-      a.window = reinterpret_cast<const float*>(bp->wp(win_off));
-      a.fb = reinterpret_cast<const float*>(bp->wp(fb_off));
-      a.logmel = bp->miscp(logmel_off);
-      a.wgmax = db ? bp->miscp(wgmax_off) + 64 : nullptr;
-      a.T = r.Lbase;
-      a.n_fft = n_fft;
-      a.hop = MFCC_HOP;
-      a.n_freqs = n_freqs;
-      a.n_mels = n_mels;
-      a.frames = shiftL(r.Lbase, LEN_FRAMES);
-      a.ulaw = ulaw;
-      a.log_mels = db ? 0 : 1;
-      a.power_scale = power_scale;
-      if (int e = launch_mfcc_logmel(a, r.B, r.st)) return e;
-      if (db) return launch_mfcc_batch_max(bp->miscp(wgmax_off) + 64, r.B * mfcc_groups(a.frames), bp->miscp(wgmax_off), r.st);
-      return 0;
-    });
-    m->meta.push_back({"mfcc_features", "13 x 3 -> 64 channels", 64.0 / MFCC_HOP, 0, 0});
-    m->add_op([=](const RunCtx& r) -> int {
-      MfccFeatArgs a{};
-      a.logmel = bp->miscp(logmel_off);
-      a.dct = reinterpret_cast<const float*>(bp->wp(dct_off));
-      a.batch_max = db ? bp->miscp(wgmax_off) : nullptr;
-      a.feat = reinterpret_cast<float*>(bp->act(feat.off));
-      a.frames = shiftL(r.Lbase, LEN_FRAMES);
-      a.rows_alloc = a.frames;
-      a.n_mels = n_mels;
-      return launch_mfcc_features(a, r.B, r.st);
-    });
-    b.tap("features", feat);
-    auto conv_layer = [&](const TensorH& in, int in_C, int in_lshift, const std::vector<float>& W, int cout, int cin, int ktaps,
-                          const float* bias, const TensorH& out, int out_lshift, const TensorH* skip, bool gelu) {
-      TensorH view = in;
-      view.C = in_C;
-      view.lshift = in_lshift;
-      PackedConv pk(prec);
-      Builder::SegSpec g{view, 0, in_C, ktaps, 1, RESIZE_NONE, false, 0, 0, 0, 0};
-      g.w_off = pk.append(W.data(), cout, cin, ktaps, 0, in_C);
-      b.add_conv({g}, pk, std::vector<float>(bias, bias + cout), cout, out, skip, RESIZE_NONE, out_lshift, gelu);
-    };
-    auto wvec = [&](const std::string& name, size_t n) { return std::vector<float>(b.P(name), b.P(name) + n); };
-    // blocks.0: Conv1d(39 -> mid, 3) + GELU over the zero-padded 64-channel feature rows
-    TensorH h0 = b.new_tensor(mid, LEN_FRAMES, false, false);
-    {
-      std::vector<float> W((size_t)mid * 64 * 3, 0.f);
-      const float* w = b.P("blocks.0.0.weight");
-      for (int co = 0; co < mid; ++co)
-        for (int ci = 0; ci < 39; ++ci)
-          for (int k = 0; k < 3; ++k) W[((size_t)co * 64 + ci) * 3 + k] = w[((size_t)co * 39 + ci) * 3 + k];
-      conv_layer(feat, 64, LEN_FRAMES, W, mid, 64, 3, b.P("blocks.0.0.bias"), h0, LEN_FRAMES, nullptr, true);
-    }
-    b.release(feat);
-    b.tap("blocks.0", h0);
-    // blocks.1: ResConv(3), written into an allocation with an even number of rows (last row zero)
-    TensorH h1 = b.new_tensor(mid, LEN_FRAMES_PAD, false, false);
-    {
-      const TensorH hp = h1;
-      m->meta.push_back({"pad_row", "", 0, 0, 0});
-      m->add_op([=](const RunCtx& r) -> int {
-        const int frames = shiftL(r.Lbase, LEN_FRAMES), rows = shiftL(r.Lbase, LEN_FRAMES_PAD);
-        if (rows == frames) return 0;
-        VQVS_HIP(hipMemset2DAsync(bp->act(hp.off) + (size_t)frames * mid * 4, (size_t)rows * mid * 4, 0, (size_t)mid * 4, r.B, r.st));
-        return 0;
-      });
-    }
-    conv_layer(h0, mid, LEN_FRAMES, wvec("blocks.1.conv.weight", (size_t)mid * mid * 3), mid, mid, 3, b.P("blocks.1.conv.bias"), h1,
-               LEN_FRAMES, &h0, true);
-    b.release(h0);
-    // blocks.2: Conv1d(mid -> mid, 4, stride 2, padding 1) + GELU as a 3-tap convolution over [pairs][2 * mid]
-    TensorH h2 = b.new_tensor(mid, LEN_HALF, false, false);
-    {
-      std::vector<float> W((size_t)mid * 2 * mid * 3, 0.f);
-      const float* w = b.P("blocks.2.0.weight");  // [mid][mid][4]
-      for (int co = 0; co < mid; ++co)
-        for (int ci = 0; ci < mid; ++ci) {
-          const float* wk = w + ((size_t)co * mid + ci) * 4;
-          float* even = &W[((size_t)co * 2 * mid + ci) * 3];
-          float* odd = &W[((size_t)co * 2 * mid + mid + ci) * 3];
-          even[1] = wk[1];  // x[2t]
-          even[2] = wk[3];  // x[2t+2] = even half of pair row t+1
-          odd[0] = wk[0];   // x[2t-1] = odd half of pair row t-1
-          odd[1] = wk[2];   // x[2t+1]
-        }
-      conv_layer(h1, 2 * mid, LEN_PAIRS, W, mid, 2 * mid, 3, b.P("blocks.2.0.bias"), h2, LEN_HALF, nullptr, true);
-    }
-    b.release(h1);
-    b.tap("blocks.2", h2);
-    TensorH h = h2;
-    for (int i = 3; i <= 8; ++i) {  // ResConv(3) x 2, ResConv(1) x 4
-      const int k = i <= 4 ? 3 : 1;
-      TensorH o = b.new_tensor(mid, LEN_HALF, false, false);
-      const std::string nm = "blocks." + std::to_string(i) + ".conv";
-      conv_layer(h, mid, LEN_HALF, wvec(nm + ".weight", (size_t)mid * mid * k), mid, mid, k, b.P(nm + ".bias"), o, LEN_HALF, &h, true);
-      b.release(h);
-      h = o;
-    }
-    b.tap("blocks.8", h);
-    TensorH o = b.new_tensor(OC, LEN_HALF, true, false);
-    conv_layer(h, mid, LEN_HALF, wvec("blocks.9.weight", (size_t)OC * mid), OC, mid, 1, b.P("blocks.9.bias"), o, LEN_HALF, nullptr, false);
-    b.release(h);
-    m->meta.push_back({"ntc_to_nct", "", 0, 0, 0});
-    m->add_op([=](const RunCtx& r) -> int { return launch_ntc_to_nct(bp->act(o.off), r.out, r.B, OC, shiftL(r.Lbase, LEN_HALF), 0, r.st); });
-  } else {  // encoder (unet.py:229-241)
-    std::vector<BlockSpec> blocks;
-    const int cur = encoder_blocks(base, topo_of(c), blocks);
-    const int out_ls = topo_of(c).levels() - 1;  // the output has T / downsample_rate rows
-    TensorH h = b.new_tensor(base, 0, false, true);
-    {
-      const size_t w = b.blob_f32("in_conv.weight"), bi = b.blob_f32("in_conv.bias");
-      m->meta.push_back({"in_conv", "1->" + std::to_string(base), (double)base, 4.0, 0});
-      m->add_op([=](const RunCtx& r) -> int {
-        InConvArgs a{};
-        a.x = r.x;
-        a.Cin = in_ch;
-        a.w = reinterpret_cast<const float*>(bp->wp(w));
-        a.bias = reinterpret_cast<const float*>(bp->wp(bi));
-        a.condp = nullptr;
-        a.cond_len = 0;
-        a.out = bp->act(h.off);
-        a.stats = bp->statp(h.stats_off);
-        a.C = base;
-        a.T = r.Lbase;
-        a.ntiles = ntiles_of(r.Lbase);
-        return launch_in_conv(a, r.B, prec, r.st);
-      });
-    }
-    b.tap("in_conv", h);
-    for (auto& s : blocks) {
-      TensorH o = b.resblock(s.prefix, s, {h}, false, 0, 0, 0);
-      b.release(h);
-      h = o;
-      b.tap(s.prefix, h);
-    }
-    const size_t ss = b.alloc_ss(cur);
-    b.add_gn({h}, "out.0.0", false, 0, 0, 0, ss);
-    TensorH o = b.new_tensor(c.out_channels, out_ls, true, false);
-    PackedConv pk(prec);
-    Builder::SegSpec g{h, 0, cur, 3, 1, RESIZE_NONE, true, ss, cur, 0, 0};
-    g.w_off = pk.append(b.P("out.1.weight"), c.out_channels, cur, 3, 0, cur);
-    const float* bb = b.P("out.1.bias");
-    b.add_conv({g}, pk, std::vector<float>(bb, bb + c.out_channels), c.out_channels, o, nullptr, 0);
-    const int OC = c.out_channels;
-    m->meta.push_back({"ntc_to_nct", "", 0, 0, 0});
-    m->add_op([=](const RunCtx& r) -> int { return launch_ntc_to_nct(bp->act(o.off), r.out, r.B, OC, r.Lbase >> out_ls, 0, r.st); });
+  Builder& b = *keep;
+  switch (c.kind) {
+    case VQVS_KIND_RESBLOCK: build_resblock(m, b); break;
+    case VQVS_KIND_PREDICTOR:
+    case VQVS_KIND_ENCPRED:
+    case VQVS_KIND_PREDICTOR_GRAD: build_unet(m, b); break;
+    case VQVS_KIND_CLASSIFIER: build_classifier(m, b); break;
+    case VQVS_KIND_MFCC_ENCODER: build_mfcc_encoder(m, b); break;
+    default: build_encoder(m, b); break;  // (enumerate_params has refused every unknown kind)
   }
 
   for (auto& mt : m->meta) {

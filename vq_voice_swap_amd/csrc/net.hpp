@@ -89,13 +89,9 @@ struct vqvs_model {
     double flops = 0;      // per clip per unit of base length
   };
   std::vector<OpMeta> meta;  // parallel to ops
-  // ops of phase 0 always run; phase 1 ops (the backward schedule of a classifier handle) only when asked for
+  // ops of phase 0 always run; phase 1 ops (a backward schedule) only when asked for.  Parallel to ops too: the three vectors are
+  // appended to together, by Builder::op in net.cpp and nowhere else
   std::vector<uint8_t> op_phase;
-  int cur_phase = 0;
-  void add_op(std::function<int(const vqvs::RunCtx&)> fn) {
-    ops.push_back(std::move(fn));
-    op_phase.push_back((uint8_t)cur_phase);
-  }
   bool profiling = false;
   std::vector<hipEvent_t> events;  // ops.size() + 1 when profiling
   std::vector<vqvs::TapDef> taps;
