@@ -143,7 +143,7 @@ assert st.n == 37
 assert rel(st.mean(), one.mean()) <= 1e-12 and rel(st.cov(), one.cov()) <= 1e-12, (rel(st.mean(), one.mean()), rel(st.cov(), one.cov()))
 assert np.array_equal(st.probs, one.probs.astype(np.float32))
 assert abs(st.class_score() - one.class_score()) <= 1e-12 * one.class_score()
-print("ALL_REDUCE_OK", rank)
+print(f"ALL_REDUCE_OK {{rank}}\n", end="", flush=True)  # one write: the two ranks share the pipe, and pieces of two prints can interleave
 dist.destroy_process_group()
 """
 

@@ -421,16 +421,32 @@ int vqvs_encpred_guidance(vqvs_model* m, const float* d_x, const float* d_ts, co
   return run_model(m, c);
 }
 
-// the x0-sum partials of a CONSTRAIN step over `rows` clips / windows of `len` samples; nothing is leased without the flag
-static int lease_x0sum(bool constrain, int rows, int len, void* stream, ScratchLease& lease) {
-  return constrain ? scratch_get((size_t)ddpm_scratch_doubles(rows, len) * 8, stream, lease) : 0;
-}
 // [a, a + na) against [b, b + nb) in bytes (NULL: absent)
 static bool bytes_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
   const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
   return pa && pb && pa < pb + nb && pb < pa + na;
 }
-// The window geometry of the three ..._windows entry points: n windows of W samples, one every H, span *Np = (n - 1) * H + W.
+// No output may overlap an input or another output (a NULL array is absent).  The one exception: an output marked `history` -- the
+// DPM-Solver++ x0_out -- may BE the input so marked -- x0_prev --, updated in place, though not overlap it in part.
+struct Span {
+  const char* name;
+  const void* p;
+  int64_t bytes;
+  bool history = false;
+};
+static int check_disjoint(std::initializer_list<Span> outs, std::initializer_list<Span> ins) {
+  for (const Span& out : outs) {
+    for (const Span& in : ins)
+      if (!(out.history && in.history && out.p == in.p) && bytes_overlap(out.p, out.bytes, in.p, in.bytes))
+        VQVS_FAIL(VQVS_ERR_ARG, "%s must not overlap %s%s", out.name, in.name, out.history && in.history ? " in part (it may be it)" : "");
+    for (const Span& other : outs)
+      if (&other != &out && bytes_overlap(out.p, out.bytes, other.p, other.bytes))
+        VQVS_FAIL(VQVS_ERR_ARG, "%s must not overlap %s", out.name, other.name);
+  }
+  return 0;
+}
+
+// The window geometry of the ..._windows entry points: n windows of W samples, one every H, span *Np = (n - 1) * H + W.
 static int check_window_geometry(int n, int W, int H, int64_t* Np) {
   if (n < 1 || n > 65535) VQVS_FAIL(VQVS_ERR_ARG, "window count n=%d outside 1..65535", n);
   if (W < 4 || H < 4 || W % 4 || H % 4) VQVS_FAIL(VQVS_ERR_ARG, "window W=%d and hop H=%d must be positive multiples of 4", W, H);
@@ -439,133 +455,6 @@ static int check_window_geometry(int n, int W, int H, int64_t* Np) {
   if (*Np >= ((int64_t)1 << 31)) VQVS_FAIL(VQVS_ERR_ARG, "n=%d windows every H=%d samples span %lld samples: 2^31 or more", n, H, (long long)*Np);
   return 0;
 }
-
-int vqvs_ddpm_step(const float* d_x_t, const float* d_eps, const float* d_noise, const float* d_alpha_t, const float* d_alpha_prev,
-                   float* d_x_prev, int B, int T, uint32_t flags, float noise_scale, uint64_t seed, uint64_t clip_offset,
-                   uint32_t step_index, void* stream) {
-  if (!d_x_t || !d_eps || !d_alpha_t || !d_alpha_prev || !d_x_prev) VQVS_FAIL(VQVS_ERR_ARG, "NULL argument");
-  if (B < 1 || T < 1) VQVS_FAIL(VQVS_ERR_ARG, "bad shape B=%d T=%d", B, T);
-  ScratchLease lease;
-  if (int e = lease_x0sum(flags & VQVS_DDPM_CONSTRAIN, B, T, stream, lease)) return e;
-  return run_ddpm_step(d_x_t, d_eps, d_noise, d_alpha_t, d_alpha_prev, d_x_prev, reinterpret_cast<double*>(lease.p), B, T, flags,
-                       noise_scale, seed, clip_offset, step_index, reinterpret_cast<hipStream_t>(stream));
-}
-
-int vqvs_ddpm_step_windows(const float* d_x, const float* d_eps, const float* d_noise, const float* d_alpha_t, const float* d_alpha_prev,
-                           float* d_x_prev, float* d_windows, int n, int W, int H, uint32_t flags, float noise_scale, uint64_t seed,
-                           uint64_t clip, uint32_t step_index, void* stream) {
-  if (!d_x || !d_eps || !d_alpha_t || !d_alpha_prev || !d_x_prev) VQVS_FAIL(VQVS_ERR_ARG, "x, eps, alpha_t, alpha_prev and x_prev must be non-NULL");
-  int64_t Np;
-  if (int e = check_window_geometry(n, W, H, &Np)) return e;
-  if (bytes_overlap(d_x_prev, Np * 4, d_x, Np * 4)) VQVS_FAIL(VQVS_ERR_ARG, "x_prev must not overlap x");
-  ScratchLease lease;
-  if (int e = lease_x0sum(flags & VQVS_DDPM_CONSTRAIN, n, W, stream, lease)) return e;
-  return run_ddpm_step_windows(d_x, d_eps, d_noise, d_alpha_t, d_alpha_prev, d_x_prev, d_windows, reinterpret_cast<double*>(lease.p), n, W, H,
-                               flags, noise_scale, seed, clip, step_index, reinterpret_cast<hipStream_t>(stream));
-}
-
-// shared argument rules of the two DDIM entry points
-static int check_ddim_args(uint32_t flags, float eta) {
-  if (!std::isfinite(eta) || eta < 0.f) VQVS_FAIL(VQVS_ERR_ARG, "eta %g must be finite and not negative", (double)eta);
-  if (flags & ~(VQVS_DDIM_CONSTRAIN | VQVS_DDIM_INVERT))
-    VQVS_FAIL(VQVS_ERR_ARG, "flags %#x: only VQVS_DDIM_CONSTRAIN and VQVS_DDIM_INVERT are defined for the DDIM step", flags);
-  if ((flags & VQVS_DDIM_INVERT) && (flags & VQVS_DDIM_CONSTRAIN)) VQVS_FAIL(VQVS_ERR_ARG, "INVERT cannot be combined with CONSTRAIN");
-  if ((flags & VQVS_DDIM_INVERT) && eta != 0.f) VQVS_FAIL(VQVS_ERR_ARG, "INVERT needs eta = 0 (got %g)", (double)eta);
-  return 0;
-}
-
-int vqvs_ddim_step(const float* d_x_t, const float* d_eps, const float* d_grad, const float* d_noise, const float* d_alpha_t,
-                   const float* d_alpha_to, float* d_x_to, int B, int T, uint32_t flags, float eta, float noise_scale, uint64_t seed,
-                   uint64_t clip_offset, uint32_t step_index, void* stream) {
-  if (!d_x_t || !d_eps || !d_alpha_t || !d_alpha_to || !d_x_to) VQVS_FAIL(VQVS_ERR_ARG, "x_t, eps, alpha_t, alpha_to and x_to must be non-NULL");
-  if (B < 1 || B > 65535) VQVS_FAIL(VQVS_ERR_ARG, "batch %d outside 1..65535", B);
-  if (T < 1 || T > (1 << 30)) VQVS_FAIL(VQVS_ERR_ARG, "row length %d outside 1..2^30", T);
-  if (int e = check_ddim_args(flags, eta)) return e;
-  const int64_t N = (int64_t)B * T;
-  for (const float* in : {d_x_t, d_eps, d_grad, d_noise})
-    if (bytes_overlap(d_x_to, N * 4, in, N * 4)) VQVS_FAIL(VQVS_ERR_ARG, "x_to must not overlap x_t, eps, grad or noise");
-  if (bytes_overlap(d_x_to, N * 4, d_alpha_t, B * 4) || bytes_overlap(d_x_to, N * 4, d_alpha_to, B * 4))
-    VQVS_FAIL(VQVS_ERR_ARG, "x_to must not overlap the alphas");
-  ScratchLease lease;
-  if (int e = lease_x0sum(flags & VQVS_DDIM_CONSTRAIN, B, T, stream, lease)) return e;
-  return run_ddim_step(d_x_t, d_eps, d_grad, d_noise, d_alpha_t, d_alpha_to, d_x_to, reinterpret_cast<double*>(lease.p), B, T, flags, eta,
-                       noise_scale, seed, clip_offset, step_index, reinterpret_cast<hipStream_t>(stream));
-}
-
-int vqvs_ddim_step_windows(const float* d_x, const float* d_eps, const float* d_grad, const float* d_noise, const float* d_alpha_t,
-                           const float* d_alpha_to, float* d_x_to, float* d_windows, int n, int W, int H, uint32_t flags, float eta,
-                           float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index, void* stream) {
-  if (!d_x || !d_eps || !d_alpha_t || !d_alpha_to || !d_x_to) VQVS_FAIL(VQVS_ERR_ARG, "x, eps, alpha_t, alpha_to and x_to must be non-NULL");
-  int64_t Np;
-  if (int e = check_window_geometry(n, W, H, &Np)) return e;
-  if (int e = check_ddim_args(flags, eta)) return e;
-  const int64_t NW = (int64_t)n * W;
-  const struct { const float* p; int64_t len; } ins[] = {{d_x, Np}, {d_eps, NW}, {d_grad, NW}, {d_noise, Np}, {d_alpha_t, 1}, {d_alpha_to, 1}};
-  for (const auto& in : ins)
-    if (bytes_overlap(d_x_to, Np * 4, in.p, in.len * 4) || bytes_overlap(d_windows, NW * 4, in.p, in.len * 4))
-      VQVS_FAIL(VQVS_ERR_ARG, "x_to and windows must not overlap x, eps, grad, noise or the alphas");
-  if (bytes_overlap(d_x_to, Np * 4, d_windows, NW * 4)) VQVS_FAIL(VQVS_ERR_ARG, "x_to must not overlap windows");
-  ScratchLease lease;
-  if (int e = lease_x0sum(flags & VQVS_DDIM_CONSTRAIN, n, W, stream, lease)) return e;
-  return run_ddim_step_windows(d_x, d_eps, d_grad, d_noise, d_alpha_t, d_alpha_to, d_x_to, d_windows, reinterpret_cast<double*>(lease.p), n, W, H,
-                               flags, eta, noise_scale, seed, clip, step_index, reinterpret_cast<hipStream_t>(stream));
-}
-
-// Shared argument rules of the two DPM-Solver++ entry points.  ins: every input but the history, with its length in floats (NULL:
-// absent); hist: x0_prev; outs: x_to, x0_out (FIRST) and -- the windows form -- windows.  An output may not overlap an input or another
-// output, except that x0_out may BE x0_prev.
-struct FloatSpan {
-  const float* p;
-  int64_t len;
-};
-static int check_dpmpp_args(uint32_t flags, FloatSpan hist, std::initializer_list<FloatSpan> ins, std::initializer_list<FloatSpan> outs) {
-  if (flags & ~VQVS_DDIM_CONSTRAIN) VQVS_FAIL(VQVS_ERR_ARG, "flags %#x: only VQVS_DDIM_CONSTRAIN is defined for the DPM-Solver++ step", flags);
-  for (const auto& out : outs) {
-    const bool in_place = &out == outs.begin() && out.p == hist.p;  // the history updated in place
-    if (!in_place && bytes_overlap(out.p, out.len * 4, hist.p, hist.len * 4))
-      VQVS_FAIL(VQVS_ERR_ARG, "x_to and windows must not overlap x0_prev, and x0_out may be x0_prev itself but not a part of it");
-    for (const auto& in : ins)
-      if (bytes_overlap(out.p, out.len * 4, in.p, in.len * 4))
-        VQVS_FAIL(VQVS_ERR_ARG, "x_to, x0_out and windows must not overlap x, eps, grad or the alphas");
-    for (const auto& other : outs)
-      if (&other != &out && bytes_overlap(out.p, out.len * 4, other.p, other.len * 4))
-        VQVS_FAIL(VQVS_ERR_ARG, "x_to, x0_out and windows must not overlap each other");
-  }
-  return 0;
-}
-
-int vqvs_dpmpp_step(const float* d_x_t, const float* d_eps, const float* d_grad, const float* d_x0_prev, const float* d_alpha_from,
-                    const float* d_alpha_t, const float* d_alpha_to, float* d_x_to, float* d_x0_out, int B, int T, uint32_t flags,
-                    void* stream) {
-  if (!d_x_t || !d_eps || !d_alpha_t || !d_alpha_to || !d_x_to) VQVS_FAIL(VQVS_ERR_ARG, "x_t, eps, alpha_t, alpha_to and x_to must be non-NULL");
-  if (B < 1 || B > 65535) VQVS_FAIL(VQVS_ERR_ARG, "batch %d outside 1..65535", B);
-  if (T < 1 || T > (1 << 30)) VQVS_FAIL(VQVS_ERR_ARG, "row length %d outside 1..2^30", T);
-  const int64_t N = (int64_t)B * T;
-  if (int e = check_dpmpp_args(flags, {d_x0_prev, N}, {{d_x_t, N}, {d_eps, N}, {d_grad, N}, {d_alpha_from, B}, {d_alpha_t, B}, {d_alpha_to, B}},
-                               {{d_x0_out, N}, {d_x_to, N}}))
-    return e;
-  ScratchLease lease;
-  if (int e = lease_x0sum(flags & VQVS_DDIM_CONSTRAIN, B, T, stream, lease)) return e;
-  return run_dpmpp_step(d_x_t, d_eps, d_grad, d_x0_prev, d_alpha_from, d_alpha_t, d_alpha_to, d_x_to, d_x0_out,
-                        reinterpret_cast<double*>(lease.p), B, T, flags, reinterpret_cast<hipStream_t>(stream));
-}
-
-int vqvs_dpmpp_step_windows(const float* d_x, const float* d_eps, const float* d_grad, const float* d_x0_prev, const float* d_alpha_from,
-                            const float* d_alpha_t, const float* d_alpha_to, float* d_x_to, float* d_x0_out, float* d_windows, int n, int W,
-                            int H, uint32_t flags, void* stream) {
-  if (!d_x || !d_eps || !d_alpha_t || !d_alpha_to || !d_x_to) VQVS_FAIL(VQVS_ERR_ARG, "x, eps, alpha_t, alpha_to and x_to must be non-NULL");
-  int64_t Np;
-  if (int e = check_window_geometry(n, W, H, &Np)) return e;
-  const int64_t NW = (int64_t)n * W;
-  if (int e = check_dpmpp_args(flags, {d_x0_prev, Np}, {{d_x, Np}, {d_eps, NW}, {d_grad, NW}, {d_alpha_from, 1}, {d_alpha_t, 1}, {d_alpha_to, 1}},
-                               {{d_x0_out, Np}, {d_x_to, Np}, {d_windows, NW}}))
-    return e;
-  ScratchLease lease;
-  if (int e = lease_x0sum(flags & VQVS_DDIM_CONSTRAIN, n, W, stream, lease)) return e;
-  return run_dpmpp_step_windows(d_x, d_eps, d_grad, d_x0_prev, d_alpha_from, d_alpha_t, d_alpha_to, d_x_to, d_x0_out, d_windows,
-                                reinterpret_cast<double*>(lease.p), n, W, H, flags, reinterpret_cast<hipStream_t>(stream));
-}
-
 // The geometry of the three ..._windows_packed entry points: R recordings in windows of W every H.  The window total is on the device;
 // *least = R * W is what every array of such a pack holds at the least, the extent the aliasing rules are checked over.
 static int check_pack_geometry(const int32_t* d_first, int R, int W, int H, int64_t* least) {
@@ -576,59 +465,155 @@ static int check_pack_geometry(const int32_t* d_first, int R, int W, int H, int6
   *least = (int64_t)R * W;
   return 0;
 }
+// the x0-sum partials of a CONSTRAIN step over `rows` clips / windows of `len` samples; nothing is leased without the flag
+static int lease_x0sum(bool constrain, int rows, int len, void* stream, ScratchLease& lease) {
+  return constrain ? scratch_get((size_t)ddpm_scratch_doubles(rows, len) * 8, stream, lease) : 0;
+}
 static int lease_x0sum_packed(bool constrain, int W, int H, void* stream, ScratchLease& lease) {
   return constrain ? scratch_get(packed_scratch_doubles(W, H) * 8, stream, lease) : 0;
+}
+
+// argument rules of the DDIM step
+static int check_ddim_args(uint32_t flags, float eta) {
+  if (!std::isfinite(eta) || eta < 0.f) VQVS_FAIL(VQVS_ERR_ARG, "eta %g must be finite and not negative", (double)eta);
+  if (flags & ~(VQVS_DDIM_CONSTRAIN | VQVS_DDIM_INVERT))
+    VQVS_FAIL(VQVS_ERR_ARG, "flags %#x: only VQVS_DDIM_CONSTRAIN and VQVS_DDIM_INVERT are defined for the DDIM step", flags);
+  if ((flags & VQVS_DDIM_INVERT) && (flags & VQVS_DDIM_CONSTRAIN)) VQVS_FAIL(VQVS_ERR_ARG, "INVERT cannot be combined with CONSTRAIN");
+  if ((flags & VQVS_DDIM_INVERT) && eta != 0.f) VQVS_FAIL(VQVS_ERR_ARG, "INVERT needs eta = 0 (got %g)", (double)eta);
+  return 0;
+}
+
+// What the nine step entry points share once each has filled a StepArgs and a StepLayout by name (designated initialisers, in the
+// order of the members): required pointers, the layout's geometry, the rule's own
+// argument rules, aliasing, the scratch of CONSTRAIN, the launch.  Aliasing is checked over what every array holds at the least:
+// long arrays (x, noise, x_to, the history) and window arrays (eps, grad, windows) are both B * T on clips and R * W on a pack.  The
+// DDPM step has always checked less than the others -- nothing on clips, where x_prev may be x_t itself, and x_prev against x alone
+// under windows -- and takes any flag word and, on clips, any positive B and T; callers rely on it.
+static int step(StepRule rule, StepArgs a, const StepLayout& l, void* stream) {
+  const bool ddpm = rule == StepRule::DDPM;
+  const char* to = ddpm ? "x_prev" : "x_to";
+  if (!a.x || !a.eps || !a.a_t || !a.a_to || !a.x_to) VQVS_FAIL(VQVS_ERR_ARG, "x, eps, alpha_t, alpha_%s and %s must be non-NULL", ddpm ? "prev" : "to", to);
+  int64_t n_long = 0, n_win = 0, n_alpha = 1;
+  switch (l.kind) {
+    case StepLayout::CLIPS:
+      if (ddpm && (l.n < 1 || l.W < 1)) VQVS_FAIL(VQVS_ERR_ARG, "bad shape B=%d T=%d", l.n, l.W);
+      if (!ddpm && (l.n < 1 || l.n > 65535)) VQVS_FAIL(VQVS_ERR_ARG, "batch %d outside 1..65535", l.n);
+      if (!ddpm && (l.W < 1 || l.W > (1 << 30))) VQVS_FAIL(VQVS_ERR_ARG, "row length %d outside 1..2^30", l.W);
+      n_long = n_win = (int64_t)l.n * l.W;
+      n_alpha = l.n;
+      break;
+    case StepLayout::WINDOWS:
+      if (int e = check_window_geometry(l.n, l.W, l.H, &n_long)) return e;
+      n_win = (int64_t)l.n * l.W;
+      break;
+    case StepLayout::PACK:
+      if (int e = check_pack_geometry(l.first, l.n, l.W, l.H, &n_long)) return e;
+      n_win = n_long;
+      break;
+  }
+  if (rule == StepRule::DDIM)
+    if (int e = check_ddim_args(a.flags, a.eta)) return e;
+  if (rule == StepRule::DPMPP && (a.flags & ~VQVS_DDIM_CONSTRAIN))
+    VQVS_FAIL(VQVS_ERR_ARG, "flags %#x: only VQVS_DDIM_CONSTRAIN is defined for the DPM-Solver++ step", a.flags);
+  const Span x{"x", a.x, n_long * 4}, eps{"eps", a.eps, n_win * 4}, grad{"grad", a.grad, n_win * 4}, noise{"noise", a.noise, n_long * 4},
+      x0_prev{"x0_prev", a.x0_prev, n_long * 4, true}, a_from{"alpha_from", a.a_from, n_alpha * 4}, a_t{"alpha_t", a.a_t, n_alpha * 4},
+      a_to{"alpha_to", a.a_to, n_alpha * 4}, first{"first", l.kind == StepLayout::PACK ? l.first : nullptr, ((int64_t)l.n + 1) * 4},
+      x_to{to, a.x_to, n_long * 4}, x0_out{"x0_out", a.x0_out, n_long * 4, true}, win{"windows", a.win, n_win * 4};
+  if (ddpm) {
+    if (l.kind != StepLayout::CLIPS)
+      if (int e = check_disjoint({x_to}, {x})) return e;
+  } else if (int e = check_disjoint({x0_out, x_to, win}, {x0_prev, x, eps, grad, noise, a_from, a_t, a_to, first})) {
+    return e;
+  }
+  ScratchLease lease;
+  const bool constrain = a.flags & VQVS_DDPM_CONSTRAIN;  // (VQVS_DDIM_CONSTRAIN is the same bit)
+  if (int e = l.kind == StepLayout::PACK ? lease_x0sum_packed(constrain, l.W, l.H, stream, lease) : lease_x0sum(constrain, l.n, l.W, stream, lease))
+    return e;
+  a.partial = reinterpret_cast<double*>(lease.p);
+  return run_step(rule, a, l, reinterpret_cast<hipStream_t>(stream));
+}
+
+int vqvs_ddpm_step(const float* d_x_t, const float* d_eps, const float* d_noise, const float* d_alpha_t, const float* d_alpha_prev,
+                   float* d_x_prev, int B, int T, uint32_t flags, float noise_scale, uint64_t seed, uint64_t clip_offset,
+                   uint32_t step_index, void* stream) {
+  return step(StepRule::DDPM,
+              {.x = d_x_t, .eps = d_eps, .noise = d_noise, .a_t = d_alpha_t, .a_to = d_alpha_prev, .x_to = d_x_prev, .flags = flags,
+               .noise_scale = noise_scale, .seed = seed, .clip = clip_offset, .step_index = step_index},
+              {StepLayout::CLIPS, B, T, 0, nullptr}, stream);
+}
+
+int vqvs_ddpm_step_windows(const float* d_x, const float* d_eps, const float* d_noise, const float* d_alpha_t, const float* d_alpha_prev,
+                           float* d_x_prev, float* d_windows, int n, int W, int H, uint32_t flags, float noise_scale, uint64_t seed,
+                           uint64_t clip, uint32_t step_index, void* stream) {
+  return step(StepRule::DDPM,
+              {.x = d_x, .eps = d_eps, .noise = d_noise, .a_t = d_alpha_t, .a_to = d_alpha_prev, .x_to = d_x_prev, .win = d_windows,
+               .flags = flags, .noise_scale = noise_scale, .seed = seed, .clip = clip, .step_index = step_index},
+              {StepLayout::WINDOWS, n, W, H, nullptr}, stream);
 }
 
 int vqvs_ddpm_step_windows_packed(const float* d_x, const float* d_eps, const float* d_noise, const float* d_alpha_t,
                                   const float* d_alpha_prev, float* d_x_prev, float* d_windows, const int32_t* d_first, int R, int W, int H,
                                   uint32_t flags, float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index, void* stream) {
-  if (!d_x || !d_eps || !d_alpha_t || !d_alpha_prev || !d_x_prev) VQVS_FAIL(VQVS_ERR_ARG, "x, eps, alpha_t, alpha_prev and x_prev must be non-NULL");
-  int64_t L;
-  if (int e = check_pack_geometry(d_first, R, W, H, &L)) return e;
-  if (bytes_overlap(d_x_prev, L * 4, d_x, L * 4)) VQVS_FAIL(VQVS_ERR_ARG, "x_prev must not overlap x");
-  ScratchLease lease;
-  if (int e = lease_x0sum_packed(flags & VQVS_DDPM_CONSTRAIN, W, H, stream, lease)) return e;
-  return run_ddpm_step_packed(d_x, d_eps, d_noise, d_alpha_t, d_alpha_prev, d_x_prev, d_windows, reinterpret_cast<double*>(lease.p), d_first, R,
-                              W, H, flags, noise_scale, seed, clip, step_index, reinterpret_cast<hipStream_t>(stream));
+  return step(StepRule::DDPM,
+              {.x = d_x, .eps = d_eps, .noise = d_noise, .a_t = d_alpha_t, .a_to = d_alpha_prev, .x_to = d_x_prev, .win = d_windows,
+               .flags = flags, .noise_scale = noise_scale, .seed = seed, .clip = clip, .step_index = step_index},
+              {StepLayout::PACK, R, W, H, d_first}, stream);
+}
+
+int vqvs_ddim_step(const float* d_x_t, const float* d_eps, const float* d_grad, const float* d_noise, const float* d_alpha_t,
+                   const float* d_alpha_to, float* d_x_to, int B, int T, uint32_t flags, float eta, float noise_scale, uint64_t seed,
+                   uint64_t clip_offset, uint32_t step_index, void* stream) {
+  return step(StepRule::DDIM,
+              {.x = d_x_t, .eps = d_eps, .grad = d_grad, .noise = d_noise, .a_t = d_alpha_t, .a_to = d_alpha_to, .x_to = d_x_to, .flags = flags,
+               .eta = eta, .noise_scale = noise_scale, .seed = seed, .clip = clip_offset, .step_index = step_index},
+              {StepLayout::CLIPS, B, T, 0, nullptr}, stream);
+}
+
+int vqvs_ddim_step_windows(const float* d_x, const float* d_eps, const float* d_grad, const float* d_noise, const float* d_alpha_t,
+                           const float* d_alpha_to, float* d_x_to, float* d_windows, int n, int W, int H, uint32_t flags, float eta,
+                           float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index, void* stream) {
+  return step(StepRule::DDIM,
+              {.x = d_x, .eps = d_eps, .grad = d_grad, .noise = d_noise, .a_t = d_alpha_t, .a_to = d_alpha_to, .x_to = d_x_to, .win = d_windows,
+               .flags = flags, .eta = eta, .noise_scale = noise_scale, .seed = seed, .clip = clip, .step_index = step_index},
+              {StepLayout::WINDOWS, n, W, H, nullptr}, stream);
 }
 
 int vqvs_ddim_step_windows_packed(const float* d_x, const float* d_eps, const float* d_grad, const float* d_noise, const float* d_alpha_t,
                                   const float* d_alpha_to, float* d_x_to, float* d_windows, const int32_t* d_first, int R, int W, int H,
                                   uint32_t flags, float eta, float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index,
                                   void* stream) {
-  if (!d_x || !d_eps || !d_alpha_t || !d_alpha_to || !d_x_to) VQVS_FAIL(VQVS_ERR_ARG, "x, eps, alpha_t, alpha_to and x_to must be non-NULL");
-  int64_t L;
-  if (int e = check_pack_geometry(d_first, R, W, H, &L)) return e;
-  if (int e = check_ddim_args(flags, eta)) return e;
-  const struct { const void* p; int64_t len; } ins[] = {{d_x, L}, {d_eps, L}, {d_grad, L}, {d_noise, L}, {d_alpha_t, 1}, {d_alpha_to, 1},
-                                                        {d_first, R + 1}};
-  for (const auto& in : ins)
-    if (bytes_overlap(d_x_to, L * 4, in.p, in.len * 4) || bytes_overlap(d_windows, L * 4, in.p, in.len * 4))
-      VQVS_FAIL(VQVS_ERR_ARG, "x_to and windows must not overlap x, eps, grad, noise, the alphas or first");
-  if (bytes_overlap(d_x_to, L * 4, d_windows, L * 4)) VQVS_FAIL(VQVS_ERR_ARG, "x_to must not overlap windows");
-  ScratchLease lease;
-  if (int e = lease_x0sum_packed(flags & VQVS_DDIM_CONSTRAIN, W, H, stream, lease)) return e;
-  return run_ddim_step_packed(d_x, d_eps, d_grad, d_noise, d_alpha_t, d_alpha_to, d_x_to, d_windows, reinterpret_cast<double*>(lease.p), d_first,
-                              R, W, H, flags, eta, noise_scale, seed, clip, step_index, reinterpret_cast<hipStream_t>(stream));
+  return step(StepRule::DDIM,
+              {.x = d_x, .eps = d_eps, .grad = d_grad, .noise = d_noise, .a_t = d_alpha_t, .a_to = d_alpha_to, .x_to = d_x_to, .win = d_windows,
+               .flags = flags, .eta = eta, .noise_scale = noise_scale, .seed = seed, .clip = clip, .step_index = step_index},
+              {StepLayout::PACK, R, W, H, d_first}, stream);
+}
+
+int vqvs_dpmpp_step(const float* d_x_t, const float* d_eps, const float* d_grad, const float* d_x0_prev, const float* d_alpha_from,
+                    const float* d_alpha_t, const float* d_alpha_to, float* d_x_to, float* d_x0_out, int B, int T, uint32_t flags,
+                    void* stream) {
+  return step(StepRule::DPMPP,
+              {.x = d_x_t, .eps = d_eps, .grad = d_grad, .x0_prev = d_x0_prev, .a_from = d_alpha_from, .a_t = d_alpha_t, .a_to = d_alpha_to,
+               .x_to = d_x_to, .x0_out = d_x0_out, .flags = flags},
+              {StepLayout::CLIPS, B, T, 0, nullptr}, stream);
+}
+
+int vqvs_dpmpp_step_windows(const float* d_x, const float* d_eps, const float* d_grad, const float* d_x0_prev, const float* d_alpha_from,
+                            const float* d_alpha_t, const float* d_alpha_to, float* d_x_to, float* d_x0_out, float* d_windows, int n, int W,
+                            int H, uint32_t flags, void* stream) {
+  return step(StepRule::DPMPP,
+              {.x = d_x, .eps = d_eps, .grad = d_grad, .x0_prev = d_x0_prev, .a_from = d_alpha_from, .a_t = d_alpha_t, .a_to = d_alpha_to,
+               .x_to = d_x_to, .x0_out = d_x0_out, .win = d_windows, .flags = flags},
+              {StepLayout::WINDOWS, n, W, H, nullptr}, stream);
 }
 
 int vqvs_dpmpp_step_windows_packed(const float* d_x, const float* d_eps, const float* d_grad, const float* d_x0_prev,
                                    const float* d_alpha_from, const float* d_alpha_t, const float* d_alpha_to, float* d_x_to,
                                    float* d_x0_out, float* d_windows, const int32_t* d_first, int R, int W, int H, uint32_t flags,
                                    void* stream) {
-  if (!d_x || !d_eps || !d_alpha_t || !d_alpha_to || !d_x_to) VQVS_FAIL(VQVS_ERR_ARG, "x, eps, alpha_t, alpha_to and x_to must be non-NULL");
-  int64_t L;
-  if (int e = check_pack_geometry(d_first, R, W, H, &L)) return e;
-  if (int e = check_dpmpp_args(flags, {d_x0_prev, L},
-                               {{d_x, L}, {d_eps, L}, {d_grad, L}, {d_alpha_from, 1}, {d_alpha_t, 1}, {d_alpha_to, 1},
-                                {reinterpret_cast<const float*>(d_first), R + 1}},
-                               {{d_x0_out, L}, {d_x_to, L}, {d_windows, L}}))
-    return e;
-  ScratchLease lease;
-  if (int e = lease_x0sum_packed(flags & VQVS_DDIM_CONSTRAIN, W, H, stream, lease)) return e;
-  return run_dpmpp_step_packed(d_x, d_eps, d_grad, d_x0_prev, d_alpha_from, d_alpha_t, d_alpha_to, d_x_to, d_x0_out, d_windows,
-                               reinterpret_cast<double*>(lease.p), d_first, R, W, H, flags, reinterpret_cast<hipStream_t>(stream));
+  return step(StepRule::DPMPP,
+              {.x = d_x, .eps = d_eps, .grad = d_grad, .x0_prev = d_x0_prev, .a_from = d_alpha_from, .a_t = d_alpha_t, .a_to = d_alpha_to,
+               .x_to = d_x_to, .x0_out = d_x0_out, .win = d_windows, .flags = flags},
+              {StepLayout::PACK, R, W, H, d_first}, stream);
 }
 
 // Shared argument rules of the two keep-region entry points.  N: samples of the state (and of x0, keep, noise); n_alpha: entries of
@@ -636,14 +621,8 @@ int vqvs_dpmpp_step_windows_packed(const float* d_x, const float* d_eps, const f
 static int check_keep_args(const float* d_x, const float* d_windows, const float* d_x0, const uint8_t* d_keep, const float* d_noise,
                            const float* d_alpha, int64_t N, int64_t n_alpha, int64_t NW, float noise_scale) {
   if (!std::isfinite(noise_scale)) VQVS_FAIL(VQVS_ERR_ARG, "noise_scale %g must be finite", (double)noise_scale);
-  const struct { const char* name; const void* p; int64_t bytes; } ins[] = {
-      {"d_x0", d_x0, N * 4}, {"d_keep", d_keep, N}, {"d_noise", d_noise, N * 4}, {"d_alpha", d_alpha, n_alpha * 4}};
-  for (const auto& in : ins) {
-    if (bytes_overlap(d_x, N * 4, in.p, in.bytes)) VQVS_FAIL(VQVS_ERR_ARG, "d_x must not overlap %s", in.name);
-    if (bytes_overlap(d_windows, NW * 4, in.p, in.bytes)) VQVS_FAIL(VQVS_ERR_ARG, "d_windows must not overlap %s", in.name);
-  }
-  if (bytes_overlap(d_windows, NW * 4, d_x, N * 4)) VQVS_FAIL(VQVS_ERR_ARG, "d_windows must not overlap d_x");
-  return 0;
+  return check_disjoint({{"d_x", d_x, N * 4}, {"d_windows", d_windows, NW * 4}},
+                        {{"d_x0", d_x0, N * 4}, {"d_keep", d_keep, N}, {"d_noise", d_noise, N * 4}, {"d_alpha", d_alpha, n_alpha * 4}});
 }
 
 int vqvs_keep_region(float* d_x, const float* d_x0, const uint8_t* d_keep, const float* d_noise, const float* d_alpha, int B, int T,
@@ -701,9 +680,8 @@ int vqvs_speaker_mix(const float* d_table, int K, int E, const int32_t* d_idx, c
   if (K < 1 || E < 1 || B < 1) VQVS_FAIL(VQVS_ERR_ARG, "bad shape K=%d E=%d B=%d", K, E, B);
   if (J < 1 || J > 16) VQVS_FAIL(VQVS_ERR_ARG, "J=%d outside 1..16", J);
   const int64_t out_bytes = (int64_t)B * E * 4, slot_bytes = (int64_t)B * J * 4;
-  if (bytes_overlap(d_out, out_bytes, d_table, (int64_t)K * E * 4) || bytes_overlap(d_out, out_bytes, d_idx, slot_bytes) ||
-      bytes_overlap(d_out, out_bytes, d_w, slot_bytes))
-    VQVS_FAIL(VQVS_ERR_ARG, "d_out must not overlap d_table, d_idx or d_w");
+  if (int e = check_disjoint({{"d_out", d_out, out_bytes}}, {{"d_table", d_table, (int64_t)K * E * 4}, {"d_idx", d_idx, slot_bytes}, {"d_w", d_w, slot_bytes}}))
+    return e;
   return run_speaker_mix(d_table, K, E, d_idx, d_w, J, d_out, B, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -791,14 +769,10 @@ int vqvs_spectral_distance(const float* d_a, const float* d_b, const float* d_wi
   if (n_ceps < 2 || n_ceps > (n_mels < 64 ? n_mels : 64)) VQVS_FAIL(VQVS_ERR_ARG, "n_ceps=%d outside 2..min(n_mels=%d, 64)", n_ceps, n_mels);
   if (!std::isfinite(eps) || !(eps > 0.f)) VQVS_FAIL(VQVS_ERR_ARG, "eps=%g must be finite and positive", (double)eps);
   const int64_t N = (int64_t)B * T;
-  const struct { const void* p; int64_t bytes; const char* name; } ins[] = {
-      {d_a, N * 4, "a"}, {d_b, N * 4, "b"}, {d_window, (int64_t)n_fft * 4, "window"}, {d_twiddle, (int64_t)n_fft * 16, "twiddle"},
-      {d_fb, (int64_t)(n_fft / 2 + 1) * n_mels * 4, "fb"}, {d_dct, (int64_t)n_mels * n_ceps * 4, "dct"}};
-  for (const auto& in : ins) {
-    if (bytes_overlap(d_mcd, (int64_t)B * 8, in.p, in.bytes)) VQVS_FAIL(VQVS_ERR_ARG, "d_mcd must not overlap %s", in.name);
-    if (bytes_overlap(d_lsd, (int64_t)B * 8, in.p, in.bytes)) VQVS_FAIL(VQVS_ERR_ARG, "d_lsd must not overlap %s", in.name);
-  }
-  if (bytes_overlap(d_mcd, (int64_t)B * 8, d_lsd, (int64_t)B * 8)) VQVS_FAIL(VQVS_ERR_ARG, "d_mcd must not overlap d_lsd");
+  if (int e = check_disjoint({{"mcd", d_mcd, (int64_t)B * 8}, {"lsd", d_lsd, (int64_t)B * 8}},
+                             {{"a", d_a, N * 4}, {"b", d_b, N * 4}, {"window", d_window, (int64_t)n_fft * 4}, {"twiddle", d_twiddle, (int64_t)n_fft * 16},
+                              {"fb", d_fb, (int64_t)(n_fft / 2 + 1) * n_mels * 4}, {"dct", d_dct, (int64_t)n_mels * n_ceps * 4}}))
+    return e;
   ScratchLease lease;
   if (int e = scratch_get(spectral_distance_scratch_bytes(B, T, hop), stream, lease)) return e;
   return run_spectral_distance(d_a, d_b, d_window, d_twiddle, d_fb, d_dct, lease.p, d_mcd, d_lsd, B, T, n_fft, hop, n_mels, n_ceps, eps,
@@ -820,18 +794,11 @@ int vqvs_mel_cepstra(const float* d_x, const int* d_len, const float* d_window, 
   if (n_ceps < 2 || n_ceps > (n_mels < 64 ? n_mels : 64)) VQVS_FAIL(VQVS_ERR_ARG, "n_ceps=%d outside 2..min(n_mels=%d, 64)", n_ceps, n_mels);
   if (!std::isfinite(eps) || !(eps > 0.f)) VQVS_FAIL(VQVS_ERR_ARG, "eps=%g must be finite and positive", (double)eps);
   const int64_t NF = (int64_t)B * (T / hop + 1);
-  const struct { const void* p; int64_t bytes; const char* name; } ins[] = {
-      {d_x, (int64_t)B * T * 4, "x"}, {d_len, (int64_t)B * 4, "len"}, {d_window, (int64_t)n_fft * 4, "window"},
-      {d_twiddle, (int64_t)n_fft * 16, "twiddle"}, {d_fb, (int64_t)(n_fft / 2 + 1) * n_mels * 4, "fb"}, {d_dct, (int64_t)n_mels * n_ceps * 4, "dct"}};
-  const struct { const void* p; int64_t bytes; const char* name; } outs[] = {
-      {d_ceps, NF * n_ceps * 4, "ceps"}, {d_logmel, NF * n_mels * 4, "logmel"}, {d_frames, (int64_t)B * 4, "frames"}};
-  for (const auto& out : outs) {
-    for (const auto& in : ins)
-      if (bytes_overlap(out.p, out.bytes, in.p, in.bytes)) VQVS_FAIL(VQVS_ERR_ARG, "%s must not overlap %s", out.name, in.name);
-    for (const auto& other : outs)
-      if (&other != &out && bytes_overlap(out.p, out.bytes, other.p, other.bytes))
-        VQVS_FAIL(VQVS_ERR_ARG, "%s must not overlap %s", out.name, other.name);
-  }
+  if (int e = check_disjoint({{"ceps", d_ceps, NF * n_ceps * 4}, {"logmel", d_logmel, NF * n_mels * 4}, {"frames", d_frames, (int64_t)B * 4}},
+                             {{"x", d_x, (int64_t)B * T * 4}, {"len", d_len, (int64_t)B * 4}, {"window", d_window, (int64_t)n_fft * 4},
+                              {"twiddle", d_twiddle, (int64_t)n_fft * 16}, {"fb", d_fb, (int64_t)(n_fft / 2 + 1) * n_mels * 4},
+                              {"dct", d_dct, (int64_t)n_mels * n_ceps * 4}}))
+    return e;
   return run_mel_cepstra(d_x, d_len, d_window, d_twiddle, d_fb, d_dct, d_ceps, d_logmel, d_frames, B, T, n_fft, hop, n_mels, n_ceps, eps,
                          reinterpret_cast<hipStream_t>(stream));
 }
@@ -849,19 +816,11 @@ int vqvs_dtw_distance(const float* d_ca, const float* d_cb, const int* d_fa, con
   if (Fb_max < 1 || Fb_max > 2048) VQVS_FAIL(VQVS_ERR_ARG, "Fb_max=%d outside 1..2048", Fb_max);
   if (n_ceps < 2 || n_ceps > 64) VQVS_FAIL(VQVS_ERR_ARG, "n_ceps=%d outside 2..64", n_ceps);
   const int64_t NA = (int64_t)B * Fa_max, NB = (int64_t)B * Fb_max;
-  const struct { const void* p; int64_t bytes; const char* name; } ins[] = {
-      {d_ca, NA * n_ceps * 4, "ca"}, {d_cb, NB * n_ceps * 4, "cb"}, {d_fa, (int64_t)B * 4, "fa"}, {d_fb, (int64_t)B * 4, "fb"},
-      {d_ta, NA * 8, "ta"}, {d_tb, NB * 8, "tb"}};
-  const struct { const void* p; int64_t bytes; const char* name; } outs[] = {
-      {d_cost, (int64_t)B * 8, "cost"}, {d_steps, (int64_t)B * 4, "steps"}, {d_track_counts, (int64_t)B * 16, "track_counts"},
-      {d_track_sums, (int64_t)B * 16, "track_sums"}};
-  for (const auto& out : outs) {
-    for (const auto& in : ins)
-      if (bytes_overlap(out.p, out.bytes, in.p, in.bytes)) VQVS_FAIL(VQVS_ERR_ARG, "%s must not overlap %s", out.name, in.name);
-    for (const auto& other : outs)
-      if (&other != &out && bytes_overlap(out.p, out.bytes, other.p, other.bytes))
-        VQVS_FAIL(VQVS_ERR_ARG, "%s must not overlap %s", out.name, other.name);
-  }
+  if (int e = check_disjoint({{"cost", d_cost, (int64_t)B * 8}, {"steps", d_steps, (int64_t)B * 4}, {"track_counts", d_track_counts, (int64_t)B * 16},
+                              {"track_sums", d_track_sums, (int64_t)B * 16}},
+                             {{"ca", d_ca, NA * n_ceps * 4}, {"cb", d_cb, NB * n_ceps * 4}, {"fa", d_fa, (int64_t)B * 4}, {"fb", d_fb, (int64_t)B * 4},
+                              {"ta", d_ta, NA * 8}, {"tb", d_tb, NB * 8}}))
+    return e;
   return run_dtw_distance(d_ca, d_cb, d_fa, d_fb, d_ta, d_tb, d_cost, d_steps, d_track_counts, d_track_sums, B, Fa_max, Fb_max, n_ceps,
                           reinterpret_cast<hipStream_t>(stream));
 }
@@ -883,15 +842,9 @@ int vqvs_pitch_distance(const float* a, const float* b, double* period_a, double
     VQVS_FAIL(VQVS_ERR_ARG, "window=%d times tau_max=%d is more than 2^20: the sums would not stay below 2^53", window, tau_max);
   if (!std::isfinite(threshold) || !(threshold > 0.0) || threshold > 1.0) VQVS_FAIL(VQVS_ERR_ARG, "threshold=%g must lie in (0, 1]", threshold);
   const int64_t N = (int64_t)B * T, NF = (int64_t)B * (T / hop + 1);
-  const struct { const void* p; int64_t bytes; const char* name; } outs[] = {
-      {period_a, NF * 8, "period_a"}, {period_b, NF * 8, "period_b"}, {counts, (int64_t)B * 32, "counts"}, {sums, (int64_t)B * 16, "sums"}};
-  for (const auto& out : outs) {
-    if (bytes_overlap(out.p, out.bytes, a, N * 4) || bytes_overlap(out.p, out.bytes, b, N * 4))
-      VQVS_FAIL(VQVS_ERR_ARG, "%s must not overlap a or b", out.name);
-    for (const auto& other : outs)
-      if (&other != &out && bytes_overlap(out.p, out.bytes, other.p, other.bytes))
-        VQVS_FAIL(VQVS_ERR_ARG, "%s must not overlap %s", out.name, other.name);
-  }
+  if (int e = check_disjoint({{"period_a", period_a, NF * 8}, {"period_b", period_b, NF * 8}, {"counts", counts, (int64_t)B * 32}, {"sums", sums, (int64_t)B * 16}},
+                             {{"a", a, N * 4}, {"b", b, N * 4}}))
+    return e;
   ScratchLease lease;
   if (counts || sums)
     if (int e = scratch_get(pitch_distance_scratch_bytes(B, T, hop), stream, lease)) return e;

@@ -1,7 +1,11 @@
 // DDPM, DDIM and DPM-Solver++(2M) reverse-step kernels, the keep region, the counter-based normal generator, and the VQ codebook search.
-// All of these are HBM-bound elementwise / small-reduction kernels.  The step and keep kernels come as a batch of clips [B, T] and as
-// ONE long row seen through overlapping windows; the forms share block_sum_256, step_noise_tail / _quad, quad_windows and store_quad.
-// The window steps also come PACKED: many such rows end to end, stepped by one launch through the same per-quad bodies.
+// All of these are HBM-bound elementwise / small-reduction kernels.  A reverse step is a RULE on a LAYOUT ("Rules and layouts" below):
+// DdpmRule, DdimRule<GUIDED> and DpmppRule<GUIDED> hold what is a sampler's own -- coefficients, x0-sum summand, noise, history and
+// the per-sample arithmetic, whose device functions spell out every rounding --, and three kernel templates hold where the samples
+// lie: step_clips_kernel (a batch of clips [B, T]), step_windows_kernel (ONE long row seen through overlapping windows) and
+// step_packed_kernel (many such rows end to end, stepped by one launch through the same per-quad body, windows_quad).  Every step
+// kernel takes one StepArgs by value; x0sum_kernel / x0sum_packed_kernel, which read five of its members, form the sums of CONSTRAIN.  The keep kernels come on clips
+// and on windows too and share quad_windows and store_quad with the steps.
 #include "kernels.hpp"
 #include "philox.hpp"
 #include "sampler_kernels.hpp"
@@ -46,6 +50,7 @@ __device__ __forceinline__ StepCoef step_coef(float a_t, float a_prev, bool sigm
 }
 
 constexpr int SUM_CHUNK = 4096;
+inline int sum_chunks(int len) { return (len + SUM_CHUNK - 1) / SUM_CHUNK; }
 
 // *out = the sum of `s` over the 256 threads of the workgroup, in fp64: the fixed tree whose stride halves from 128 to 1, thread 0 writes
 __device__ __forceinline__ void block_sum_256(double s, double* out) {
@@ -108,37 +113,18 @@ __device__ __forceinline__ void store_quad(float* x, float* win, int p, const Qu
   }
 }
 
-// sum over time of x0 = (x_t - sqrt(1-a_t) eps) rsqrt(a_t), per (clip, chunk); fp64 partials.  Row b of eps is [T] contiguous; row b of
-// x_t starts at b * x_stride and its alpha is a_t[b * a_stride]: (T, 1) for a batch of clips, (hop, 0) for the overlapping windows
-// of one long signal (ddpm_step_windows_kernel), which are then summed exactly as a clip is.
-// (the body, one chunk of one row: shared with the packed form below, which finds its rows in a table)
-__device__ __forceinline__ void ddpm_x0sum_chunk(const float* x_row, const float* eps_row, float at, double* out, int T, int chunk) {
-  const float sq = sqrtf(1.0f - at), rs = 1.0f / sqrtf(at);
-  const int beg = chunk * SUM_CHUNK, end = min(T, beg + SUM_CHUNK);
-  double s = 0.0;
-  for (int t = beg + threadIdx.x; t < end; t += 256) {
-    s += (double)((x_row[t] - sq * eps_row[t]) * rs);
-  }
-  block_sum_256(s, out);
-}
-__global__ __launch_bounds__(256) void ddpm_x0sum_kernel(const float* x_t, const float* eps, const float* a_t, double* partial, int T, int nchunk,
-                                                         int x_stride, int a_stride) {
-  const int b = blockIdx.y;
-  ddpm_x0sum_chunk(x_t + (size_t)b * x_stride, eps + (size_t)b * T, a_t[b * a_stride], partial + (size_t)b * nchunk + blockIdx.x, T, blockIdx.x);
-}
-
-// mean of x0 over one clip / window: the chunk partials of ddpm_x0sum_kernel added in chunk order
+// mean of x0 over one clip / window: the chunk partials of x0sum_kernel added in chunk order
 __device__ __forceinline__ float x0_mean(const double* partial, int nchunk, int T) {
   double s = 0.0;
   for (int i = 0; i < nchunk; ++i) s += partial[i];
   return (float)(s / (double)T);
 }
 
-// One sample of the reverse step, shared by ddpm_step_kernel and ddpm_step_windows_kernel (diffusion.py:84-90): with `constrain`
-// the prediction is re-derived from x0 clamped about the clip's (window's) own mean; BLEND cross-fades a left and a right window's
-// predictions, each re-derived with its own mean, with weight w on the right one.  Without BLEND the right-hand arguments are unused.
-// Every rounding is spelled out (contraction off, fmaf where the single-clip kernel has always fused), so that the two kernels --
-// and the two sides of BLEND -- round alike whatever surrounds the call: at one window the result is ddpm_step_kernel's to the bit.
+// One sample of the DDPM reverse step, on every layout (diffusion.py:84-90): with `constrain` the prediction is re-derived from x0
+// clamped about the clip's (window's) own mean; BLEND cross-fades a left and a right window's predictions, each re-derived with its
+// own mean, with weight w on the right one.  Without BLEND the right-hand arguments are unused.  Every rounding is spelled out
+// (contraction off, fmaf where the single-clip step has always fused), so that the layouts -- and the two sides of BLEND -- round
+// alike whatever surrounds the call: at one window the result is the clip's to the bit.
 __device__ __forceinline__ float constrained_eps(const StepCoef& k, float x, float e, float mean) {
 #pragma clang fp contract(off)
   float x0 = fmaf(fmaf(-k.sq1mat, e, x), k.rsat, -mean);
@@ -158,72 +144,6 @@ __device__ __forceinline__ float step_sample(const StepCoef& k, bool constrain, 
   return k.c1 * fmaf(-k.c2, e, x) + k.sig * nv;
 }
 
-__global__ __launch_bounds__(256) void ddpm_step_kernel(const float* x_t, const float* eps, const float* noise, const float* a_t,
-                                                        const float* a_prev, const double* partial, int nchunk, float* out, int T,
-                                                        uint32_t flags, float noise_scale, uint64_t seed, uint64_t clip_offset,
-                                                        uint32_t step_index) {
-  const int b = blockIdx.y;
-  const int q = blockIdx.x * 256 + threadIdx.x;
-  if (q * 4 >= T) return;
-  const StepCoef k = step_coef(a_t[b], a_prev[b], flags & 1u);
-  float mean = 0.f;
-  if (flags & 2u) mean = x0_mean(partial + (size_t)b * nchunk, nchunk, T);
-  const size_t base = (size_t)b * T + q * 4;
-  const int n = min(4, T - q * 4);
-  float xv[4], ev[4], nv[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int j = 0; j < n; ++j) {
-    xv[j] = x_t[base + j];
-    ev[j] = eps[base + j];
-  }
-  if (noise_scale != 0.f) step_noise_tail(nv, noise, base, n, noise_scale, seed, (uint32_t)q, clip_offset + b, step_index);
-  for (int j = 0; j < n; ++j) out[base + j] = step_sample<false>(k, flags & 2u, xv[j], nv[j], ev[j], mean);
-}
-
-// The reverse step of one long signal x [Np] whose predictions came from its n windows (eps [n, W]; quad_windows).  Where two windows
-// cover a quad their predictions are cross-faded with w = (u + 1/2) / V.  The noise is one draw per absolute position -- row 0 of a
-// [1, Np] batch at `clip`, as ddpm_step_kernel draws it -- so the overlapping windows share it, and the result goes to x_prev [Np]
-// and to win [n, W] (store_quad).  partial: n * nchunk chunk sums of ddpm_x0sum_kernel.
-// (the body: quad q < Np / 4 of ONE row, every pointer at that row's first sample / window / partial.  ddpm_step_windows_kernel runs it
-// on the only row there is, ddpm_step_packed_kernel on the row of a pack that PackRow finds.)
-__device__ __forceinline__ void ddpm_windows_quad(int q, const StepCoef& k, const float* x, const float* eps, const float* noise,
-                                                  const double* partial, int nchunk, float* x_prev, float* win, int n, int W, int H,
-                                                  uint32_t flags, float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index) {
-  const int V = W - H;
-  const int p = q * 4;
-  const bool constrain = flags & 2u;
-  const QuadWindows g = quad_windows(p, n, W, H);
-  const f32x4 xv = *reinterpret_cast<const f32x4*>(x + p);
-  const f32x4 er = *reinterpret_cast<const f32x4*>(eps + g.at_r);
-  f32x4 el = er;
-  if (g.two) el = *reinterpret_cast<const f32x4*>(eps + g.at_l);
-  float mean_r = 0.f, mean_l = 0.f;
-  if (constrain) {
-    mean_r = x0_mean(partial + (size_t)g.br * nchunk, nchunk, W);
-    if (g.two) mean_l = x0_mean(partial + (size_t)(g.br - 1) * nchunk, nchunk, W);
-  }
-  f32x4 nv = {0.f, 0.f, 0.f, 0.f};
-  if (noise_scale != 0.f) nv = step_noise_quad(noise, p, noise_scale, seed, (uint32_t)q, clip, step_index);
-  f32x4 o;
-  if (g.two) {
-    for (int j = 0; j < 4; ++j) {
-      const float w = ((float)(g.u + j) + 0.5f) / (float)V;
-      o[j] = step_sample<true>(k, constrain, xv[j], nv[j], el[j], mean_l, er[j], mean_r, w);
-    }
-  } else {
-    for (int j = 0; j < 4; ++j) o[j] = step_sample<false>(k, constrain, xv[j], nv[j], er[j], mean_r);
-  }
-  store_quad(x_prev, win, p, g, [&](float* dst) { *reinterpret_cast<f32x4*>(dst) = o; });
-}
-__global__ __launch_bounds__(256) void ddpm_step_windows_kernel(const float* x, const float* eps, const float* noise, const float* a_t,
-                                                                const float* a_prev, const double* partial, int nchunk, float* x_prev,
-                                                                float* win, int n, int W, int H, uint32_t flags, float noise_scale,
-                                                                uint64_t seed, uint64_t clip, uint32_t step_index) {
-  const int q = blockIdx.x * 256 + threadIdx.x;
-  if (q >= ((n - 1) * H + W) / 4) return;
-  ddpm_windows_quad(q, step_coef(a_t[0], a_prev[0], flags & 1u), x, eps, noise, partial, nchunk, x_prev, win, n, W, H, flags, noise_scale,
-                    seed, clip, step_index);
-}
-
 // mean = eps_to_prev(eps)
 __global__ __launch_bounds__(256) void ddpm_mean_kernel(const float* x_t, const float* eps, const float* a_t, const float* a_prev, float* out, int T) {
   const int b = blockIdx.y;
@@ -241,7 +161,7 @@ __global__ __launch_bounds__(256) void ddpm_guided_eps_kernel(const float* x_t, 
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= T) return;
   const float at = a_t[b], ap = a_prev[b];
-  const StepCoef k = step_coef(at, ap, flags & 1u);
+  const StepCoef k = step_coef(at, ap, flags & VQVS_DDPM_SIGMA_LARGE);
   const float alphas = at / ap;
   const float betas = 1.0f - alphas;
   const size_t i = (size_t)b * T + t;
@@ -262,7 +182,7 @@ struct DdimCoef {
   float sq1mat, rsat, sqat, rs1mat, sqto, sig, ce;
 };
 
-// the fp64 scalars of the x0 prediction: shared by the coefficients below and by ddim_x0sum_kernel
+// the fp64 scalars of the x0 prediction: shared by the coefficients below and by DdimSum
 struct DdimX0Coef {
   double sq1mat, rsat;
 };
@@ -287,28 +207,6 @@ __device__ __forceinline__ DdimCoef ddim_coef(float a_t, float a_to, float eta, 
   return k;
 }
 
-// ddpm_x0sum_kernel for the DDIM step: the clip's (window's) sum of x0 OF THE GUIDED PREDICTION, e = eps - sqrt(1 - a_t) grad (grad
-// NULL: e = eps).  Same rows, strides, chunks and partial layout; the summand is formed in fp64 from the fp32 inputs and the fp64
-// scalars, so the mean that x0_mean rounds to fp32 carries that one rounding.
-__device__ __forceinline__ void ddim_x0sum_chunk(const float* x_row, const float* eps_row, const float* grad_row, float at, double* out, int T,
-                                                 int chunk) {
-  const DdimX0Coef k = ddim_x0_coef(at);
-  const int beg = chunk * SUM_CHUNK, end = min(T, beg + SUM_CHUNK);
-  double s = 0.0;
-  for (int t = beg + threadIdx.x; t < end; t += 256) {
-    double e = (double)eps_row[t];
-    if (grad_row) e -= k.sq1mat * (double)grad_row[t];
-    s += ((double)x_row[t] - k.sq1mat * e) * k.rsat;
-  }
-  block_sum_256(s, out);
-}
-__global__ __launch_bounds__(256) void ddim_x0sum_kernel(const float* x_t, const float* eps, const float* grad, const float* a_t,
-                                                         double* partial, int T, int nchunk, int x_stride, int a_stride) {
-  const int b = blockIdx.y;
-  ddim_x0sum_chunk(x_t + (size_t)b * x_stride, eps + (size_t)b * T, grad ? grad + (size_t)b * T : nullptr, a_t[b * a_stride],
-                   partial + (size_t)b * nchunk + blockIdx.x, T, blockIdx.x);
-}
-
 // (x0, e') of one sample under one clip's / window's prediction e and gradient g (guided: e <- e - sqrt(1 - a_t) g)
 template <bool GUIDED>
 __device__ __forceinline__ void ddim_x0_eps(const DdimCoef& k, bool constrain, float x, float e, float g, float mean, float& x0, float& ep) {
@@ -324,9 +222,9 @@ __device__ __forceinline__ void ddim_x0_eps(const DdimCoef& k, bool constrain, f
   }
 }
 
-// One sample of the step, shared by ddim_step_kernel and ddim_step_windows_kernel.  BLEND cross-fades the (x0, e') of a left and a
-// right window, each guided and constrained on its own, with weight w on the right one; without BLEND the right-hand arguments are
-// unused.  Every rounding is spelled out, as in step_sample: at one window the result is ddim_step_kernel's to the bit.
+// One sample of the DDIM step, on every layout.  BLEND cross-fades the (x0, e') of a left and a right window, each guided and
+// constrained on its own, with weight w on the right one; without BLEND the right-hand arguments are unused.  Every rounding is
+// spelled out, as in step_sample: at one window the result is the clip's to the bit.
 template <bool BLEND, bool GUIDED>
 __device__ __forceinline__ float ddim_sample(const DdimCoef& k, bool constrain, float x, float nv, float e, float g, float mean,
                                              float e_r = 0.f, float g_r = 0.f, float mean_r = 0.f, float w = 0.f) {
@@ -342,86 +240,13 @@ __device__ __forceinline__ float ddim_sample(const DdimCoef& k, bool constrain, 
   return fmaf(k.sqto, x0, fmaf(k.ce, ep, k.sig * nv));
 }
 
-template <bool GUIDED>
-__global__ __launch_bounds__(256) void ddim_step_kernel(const float* x_t, const float* eps, const float* grad, const float* noise,
-                                                        const float* a_t, const float* a_to, const double* partial, int nchunk,
-                                                        float* out, int T, uint32_t flags, float eta, float noise_scale, uint64_t seed,
-                                                        uint64_t clip_offset, uint32_t step_index) {
-  const int b = blockIdx.y;
-  const int q = blockIdx.x * 256 + threadIdx.x;
-  if (q * 4 >= T) return;
-  const DdimCoef k = ddim_coef(a_t[b], a_to[b], eta, flags & 4u);
-  float mean = 0.f;
-  if (flags & 2u) mean = x0_mean(partial + (size_t)b * nchunk, nchunk, T);
-  const size_t base = (size_t)b * T + q * 4;
-  const int n = min(4, T - q * 4);
-  float xv[4], ev[4], gv[4] = {0.f, 0.f, 0.f, 0.f}, nv[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int j = 0; j < n; ++j) {
-    xv[j] = x_t[base + j];
-    ev[j] = eps[base + j];
-    if (GUIDED) gv[j] = grad[base + j];
-  }
-  if (noise_scale != 0.f && k.sig != 0.f)  // (eta = 0, INVERT, a_to = 1: nothing is drawn or read)
-    step_noise_tail(nv, noise, base, n, noise_scale, seed, (uint32_t)q, clip_offset + b, step_index);
-  for (int j = 0; j < n; ++j) out[base + j] = ddim_sample<false, GUIDED>(k, flags & 2u, xv[j], nv[j], ev[j], gv[j], mean);
-}
-
-// ddpm_step_windows_kernel's per-window means, shared noise and outputs, for the DDIM step; grad [n, W] enters per window, before
-// the blend.
-template <bool GUIDED>
-__device__ __forceinline__ void ddim_windows_quad(int q, const DdimCoef& k, const float* x, const float* eps, const float* grad,
-                                                  const float* noise, const double* partial, int nchunk, float* x_to, float* win, int n,
-                                                  int W, int H, uint32_t flags, float noise_scale, uint64_t seed, uint64_t clip,
-                                                  uint32_t step_index) {
-  const int V = W - H;
-  const int p = q * 4;
-  const bool constrain = flags & 2u;
-  const QuadWindows g = quad_windows(p, n, W, H);
-  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-  const f32x4 xv = *reinterpret_cast<const f32x4*>(x + p);
-  const f32x4 er = *reinterpret_cast<const f32x4*>(eps + g.at_r);
-  f32x4 el = er, gr = zero, gl = zero;
-  if (g.two) el = *reinterpret_cast<const f32x4*>(eps + g.at_l);
-  if (GUIDED) {
-    gr = *reinterpret_cast<const f32x4*>(grad + g.at_r);
-    if (g.two) gl = *reinterpret_cast<const f32x4*>(grad + g.at_l);
-  }
-  float mean_r = 0.f, mean_l = 0.f;
-  if (constrain) {
-    mean_r = x0_mean(partial + (size_t)g.br * nchunk, nchunk, W);
-    if (g.two) mean_l = x0_mean(partial + (size_t)(g.br - 1) * nchunk, nchunk, W);
-  }
-  f32x4 nv = zero;
-  if (noise_scale != 0.f && k.sig != 0.f) nv = step_noise_quad(noise, p, noise_scale, seed, (uint32_t)q, clip, step_index);
-  f32x4 o;
-  if (g.two) {
-    for (int j = 0; j < 4; ++j) {
-      const float w = ((float)(g.u + j) + 0.5f) / (float)V;
-      o[j] = ddim_sample<true, GUIDED>(k, constrain, xv[j], nv[j], el[j], gl[j], mean_l, er[j], gr[j], mean_r, w);
-    }
-  } else {
-    for (int j = 0; j < 4; ++j) o[j] = ddim_sample<false, GUIDED>(k, constrain, xv[j], nv[j], er[j], gr[j], mean_r);
-  }
-  store_quad(x_to, win, p, g, [&](float* dst) { *reinterpret_cast<f32x4*>(dst) = o; });
-}
-template <bool GUIDED>
-__global__ __launch_bounds__(256) void ddim_step_windows_kernel(const float* x, const float* eps, const float* grad, const float* noise,
-                                                                const float* a_t, const float* a_to, const double* partial, int nchunk,
-                                                                float* x_to, float* win, int n, int W, int H, uint32_t flags, float eta,
-                                                                float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index) {
-  const int q = blockIdx.x * 256 + threadIdx.x;
-  if (q >= ((n - 1) * H + W) / 4) return;
-  ddim_windows_quad<GUIDED>(q, ddim_coef(a_t[0], a_to[0], eta, flags & 4u), x, eps, grad, noise, partial, nchunk, x_to, win, n, W, H, flags,
-                            noise_scale, seed, clip, step_index);
-}
-
 // ---------------------------------------------------------------------------------
 // DPM-Solver++(2M) step (Lu et al. 2022, "DPM-Solver++", Algorithm 2; the reference has none), include/vqvs.h "DPM-Solver++(2M)
 // step".  The second-order multistep solver of the probability-flow ODE in data-prediction form: from alpha_bar a_t to a_to, with
 // alpha = sqrt(a), sigma = sqrt(1 - a), lambda(a) = (log a - log1p(-a)) / 2,
 //   x_to = (sigma_to / sigma_t) x + phi ((1 + q) x0 - q x0_prev),   phi = alpha_to - sigma_to alpha_t / sigma_t,   q = h / (2 h_prev)
 // h = lambda(a_to) - lambda(a_t), h_prev = lambda(a_t) - lambda(a_from); x0 is the DDIM step's guided, constrained prediction
-// (ddim_x0_coef, ddim_x0_eps, ddim_x0sum_kernel) and x0_prev the one the step before formed.  Without a usable history q = 0, and the
+// (ddim_x0_coef, ddim_x0_eps, DdimSum) and x0_prev the one the step before formed.  Without a usable history q = 0, and the
 // step is the eta = 0 DDIM step written in x0.  The scalars are formed in fp64 and rounded to fp32 once, as ddim_coef's are; the two
 // logarithms and log1p's cost a few hundred fp64 instructions, so ONE thread of a workgroup forms them and the rest read them from
 // LDS, instead of every wave repeating them in front of sixteen bytes of traffic per array.
@@ -466,10 +291,144 @@ __device__ __forceinline__ float dpmpp_x0(const DpmppCoef& k, bool constrain, fl
   return x0;
 }
 
-// the output line: every rounding spelled out, so that the clip and the windows kernel round alike
+// the output line: every rounding spelled out, so that every layout rounds alike
 __device__ __forceinline__ float dpmpp_out(const DpmppCoef& k, float x, float x0, float x0_prev) {
 #pragma clang fp contract(off)
   return fmaf(k.cx, x, k.second ? fmaf(k.c0, x0, k.c1 * x0_prev) : k.c0 * x0);
+}
+
+// ---------------------------------------------------------------------------------
+// Rules and layouts.  A step is a RULE -- what a sampler does to one sample -- run on a LAYOUT -- where the samples of a state lie:
+// step_clips_kernel (B rows of T), step_windows_kernel (one long row under n overlapping windows) and step_packed_kernel (R such
+// rows end to end) are each instantiated with DdpmRule, DdimRule<GUIDED> and DpmppRule<GUIDED>.  A layout finds a thread's quad,
+// loads what every rule reads of it (x, eps and, for a GUIDED rule, grad -- per covering window --, the x0 means, the noise, the
+// history), hands the values to the rule sample by sample and stores what comes back; it knows no sampler by name.  A rule holds
+//   Coef, coef(a, b)     the scalars of row b (b = 0 for the one alpha of a windowed state) and how they are formed; SHARED: by one
+//                        thread of the workgroup, the others reading them from LDS (workgroup_coef), else by every thread
+//   Sum                  the summand of the x0 sums that CONSTRAIN needs (x0sum_kernel)
+//   WIDE                 the clips layout may take 16-byte accesses where the arrays allow (else one sample at a time, as ever)
+//   draws_noise(k, a)    whether noise enters at all          HISTORY, reads_history(k)   whether x0_out is written / x0_prev read
+//   sample<BLEND>(...)   the arithmetic of one sample under one window's view of it (`one`), or blended from two (`left`, and `one` on the
+//                        right with weight w); x0 is set by a HISTORY rule alone
+// Members of StepArgs that a rule does not read may be NULL: a rule's code holds no access to them.
+// ---------------------------------------------------------------------------------
+constexpr uint32_t STEP_CONSTRAIN = VQVS_DDPM_CONSTRAIN;
+static_assert(VQVS_DDIM_CONSTRAIN == STEP_CONSTRAIN, "the rules share the CONSTRAIN bit");
+
+// one clip's / window's view of a sample: its prediction, its guidance gradient (0 unguided) and the mean of its x0 (0 unconstrained)
+struct View {
+  float e, g, mean;
+};
+
+// the x0 of CONSTRAIN, per sample of a row with alpha_bar `at`.  DDPM: fp32 arithmetic, accumulated in fp64
+struct DdpmSum {
+  float sq, rs;
+  __device__ __forceinline__ explicit DdpmSum(float at) : sq(sqrtf(1.0f - at)), rs(1.0f / sqrtf(at)) {}
+  __device__ __forceinline__ double operator()(const float* x_row, const float* eps_row, const float*, int t) const {
+    return (double)((x_row[t] - sq * eps_row[t]) * rs);
+  }
+};
+// DDIM and DPM-Solver++: x0 OF THE GUIDED PREDICTION, e = eps - sqrt(1 - a_t) grad (grad_row NULL: e = eps), formed in fp64 from the
+// fp32 inputs and the fp64 scalars, so the mean that x0_mean rounds to fp32 carries that one rounding
+struct DdimSum {
+  DdimX0Coef k;
+  __device__ __forceinline__ explicit DdimSum(float at) : k(ddim_x0_coef(at)) {}
+  __device__ __forceinline__ double operator()(const float* x_row, const float* eps_row, const float* grad_row, int t) const {
+    double e = (double)eps_row[t];
+    if (grad_row) e -= k.sq1mat * (double)grad_row[t];
+    return ((double)x_row[t] - k.sq1mat * e) * k.rsat;
+  }
+};
+
+struct DdpmRule {
+  using Coef = StepCoef;
+  using Sum = DdpmSum;
+  static constexpr bool GUIDED = false, SHARED = false, WIDE = false, HISTORY = false;
+  static __device__ __forceinline__ Coef coef(const StepArgs& a, int b) { return step_coef(a.a_t[b], a.a_to[b], a.flags & VQVS_DDPM_SIGMA_LARGE); }
+  static __device__ __forceinline__ bool draws_noise(const Coef&, const StepArgs& a) { return a.noise_scale != 0.f; }
+  static __device__ __forceinline__ bool reads_history(const Coef&) { return false; }
+  template <bool BLEND>
+  static __device__ __forceinline__ float sample(const Coef& k, bool constrain, float x, float nv, float, const View& one, const View& left,
+                                                 float w, float&) {
+    if constexpr (BLEND) return step_sample<true>(k, constrain, x, nv, left.e, left.mean, one.e, one.mean, w);
+    return step_sample<false>(k, constrain, x, nv, one.e, one.mean);
+  }
+};
+
+template <bool GUIDED_>
+struct DdimRule {
+  using Coef = DdimCoef;
+  using Sum = DdimSum;
+  static constexpr bool GUIDED = GUIDED_, SHARED = false, WIDE = false, HISTORY = false;
+  static __device__ __forceinline__ Coef coef(const StepArgs& a, int b) { return ddim_coef(a.a_t[b], a.a_to[b], a.eta, a.flags & VQVS_DDIM_INVERT); }
+  // (eta = 0, INVERT, a_to = 1: nothing is drawn or read)
+  static __device__ __forceinline__ bool draws_noise(const Coef& k, const StepArgs& a) { return a.noise_scale != 0.f && k.sig != 0.f; }
+  static __device__ __forceinline__ bool reads_history(const Coef&) { return false; }
+  template <bool BLEND>
+  static __device__ __forceinline__ float sample(const Coef& k, bool constrain, float x, float nv, float, const View& one, const View& left,
+                                                 float w, float&) {
+    if constexpr (BLEND) return ddim_sample<true, GUIDED>(k, constrain, x, nv, left.e, left.g, left.mean, one.e, one.g, one.mean, w);
+    return ddim_sample<false, GUIDED>(k, constrain, x, nv, one.e, one.g, one.mean);
+  }
+};
+
+// The history x0_prev / x0_out holds, per position, the x0 the step formed -- on a windowed state the BLENDED one.  x0_out may be
+// x0_prev itself: a layout reads a thread's quad of the history before it stores any.
+template <bool GUIDED_>
+struct DpmppRule {
+  using Coef = DpmppCoef;
+  using Sum = DdimSum;
+  static constexpr bool GUIDED = GUIDED_, SHARED = true, WIDE = true, HISTORY = true;
+  static __device__ __forceinline__ Coef coef(const StepArgs& a, int b) {
+    return dpmpp_coef(a.a_from ? a.a_from + b : nullptr, a.x0_prev != nullptr, a.a_t[b], a.a_to[b]);
+  }
+  static __device__ __forceinline__ bool draws_noise(const Coef&, const StepArgs&) { return false; }
+  static __device__ __forceinline__ bool reads_history(const Coef& k) { return k.second; }
+  template <bool BLEND>
+  static __device__ __forceinline__ float sample(const Coef& k, bool constrain, float x, float, float x0_prev, const View& one, const View& left,
+                                                 float w, float& x0) {
+#pragma clang fp contract(off)
+    x0 = dpmpp_x0<GUIDED>(k, constrain, x, one.e, one.g, one.mean);
+    if constexpr (BLEND) {
+      const float x0_l = dpmpp_x0<GUIDED>(k, constrain, x, left.e, left.g, left.mean);
+      x0 = fmaf(w, x0 - x0_l, x0_l);
+    }
+    return dpmpp_out(k, x, x0, x0_prev);
+  }
+};
+
+// Row b's coefficients in every thread of the workgroup, each of which calls this
+template <typename Rule>
+__device__ __forceinline__ typename Rule::Coef workgroup_coef(const StepArgs& a, int b) {
+  if constexpr (Rule::SHARED) {
+    __shared__ typename Rule::Coef ks;
+    if (threadIdx.x == 0) ks = Rule::coef(a, b);
+    __syncthreads();
+    return ks;
+  } else {
+    return Rule::coef(a, b);
+  }
+}
+
+// Sum over time of a rule's x0, per (row, chunk of SUM_CHUNK samples); fp64 partials [rows, nchunk], which x0_mean adds in chunk
+// order.  One chunk of one row:
+template <typename Sum>
+__device__ __forceinline__ void x0sum_chunk(const float* x_row, const float* eps_row, const float* grad_row, float at, double* out, int T,
+                                            int chunk) {
+  const Sum x0(at);
+  const int beg = chunk * SUM_CHUNK, end = min(T, beg + SUM_CHUNK);
+  double s = 0.0;
+  for (int t = beg + threadIdx.x; t < end; t += 256) s += x0(x_row, eps_row, grad_row, t);
+  block_sum_256(s, out);
+}
+// Row b of eps (and grad) is [T] contiguous; row b of x starts at b * x_stride and its alpha is a_t[b * a_stride]: (T, 1) for a
+// batch of clips, (H, 0) for the overlapping windows of one long signal, which are then summed exactly as a clip is.
+template <typename Sum>
+__global__ __launch_bounds__(256) void x0sum_kernel(const float* x, const float* eps, const float* grad, const float* a_t, double* partial,
+                                                    int T, int nchunk, int x_stride, int a_stride) {
+  const int b = blockIdx.y;
+  x0sum_chunk<Sum>(x + (size_t)b * x_stride, eps + (size_t)b * T, grad ? grad + (size_t)b * T : nullptr, a_t[b * a_stride],
+                   partial + (size_t)b * nchunk + blockIdx.x, T, blockIdx.x);
 }
 
 // `live` samples at p: one 16-byte access when `vec` (the quad is whole and aligned in every array), one by one otherwise
@@ -490,90 +449,106 @@ __device__ __forceinline__ void store_quad_at(float* p, const f32x4& v, int live
   }
 }
 
-// B rows of T; row b has its own alphas.  aligned: T % 4 == 0 and every base pointer is 16-byte aligned.  x0_out may be x0_prev
-// itself: a thread reads its quad of the history before it writes it.
-template <bool GUIDED>
-__global__ __launch_bounds__(256) void dpmpp_step_kernel(const float* x_t, const float* eps, const float* grad, const float* x0_prev,
-                                                         const float* a_from, const float* a_t, const float* a_to, const double* partial,
-                                                         int nchunk, float* x_to, float* x0_out, int T, uint32_t flags, bool aligned) {
-  __shared__ DpmppCoef ks;
-  __shared__ float means;
+// Clips: B rows of T, row b with its own alphas, mean and -- drawn as clip a.clip + b -- noise; a thread owns four consecutive
+// samples of a row.  aligned: T % 4 == 0 and every base pointer is 16-byte aligned; a rule that is not WIDE holds no 16-byte access.
+template <typename Rule>
+__global__ __launch_bounds__(256) void step_clips_kernel(StepArgs a, int T, bool aligned) {
+  const bool vec = Rule::WIDE && aligned;
   const int b = blockIdx.y;
-  if (threadIdx.x == 0) {
-    ks = dpmpp_coef(a_from ? a_from + b : nullptr, x0_prev != nullptr, a_t[b], a_to[b]);
-    means = (flags & 2u) ? x0_mean(partial + (size_t)b * nchunk, nchunk, T) : 0.f;
-  }
-  __syncthreads();
   const int q = blockIdx.x * 256 + threadIdx.x;
-  if (q * 4 >= T) return;
-  const DpmppCoef k = ks;
-  const float mean = means;
+  const bool constrain = a.flags & STEP_CONSTRAIN;
+  typename Rule::Coef k;
+  View v = {0.f, 0.f, 0.f};
+  if constexpr (Rule::SHARED) {  // (workgroup_coef, with the row's mean sharing its barrier)
+    __shared__ typename Rule::Coef ks;
+    __shared__ float means;
+    if (threadIdx.x == 0) {
+      ks = Rule::coef(a, b);
+      means = constrain ? x0_mean(a.partial + (size_t)b * a.nchunk, a.nchunk, T) : 0.f;
+    }
+    __syncthreads();
+    if (q * 4 >= T) return;
+    k = ks;
+    v.mean = means;
+  } else {
+    if (q * 4 >= T) return;
+    k = Rule::coef(a, b);
+    if (constrain) v.mean = x0_mean(a.partial + (size_t)b * a.nchunk, a.nchunk, T);
+  }
   const size_t base = (size_t)b * T + q * 4;
   const int n = min(4, T - q * 4);
-  const f32x4 xv = load_quad(x_t + base, n, aligned), ev = load_quad(eps + base, n, aligned);
-  f32x4 gv = {0.f, 0.f, 0.f, 0.f}, pv = gv;
-  if (GUIDED) gv = load_quad(grad + base, n, aligned);
-  if (k.second) pv = load_quad(x0_prev + base, n, aligned);
-  f32x4 x0, o;
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  const f32x4 xv = load_quad(a.x + base, n, vec), ev = load_quad(a.eps + base, n, vec);
+  f32x4 gv = zero, pv = zero;
+  if (Rule::GUIDED) gv = load_quad(a.grad + base, n, vec);
+  if (Rule::reads_history(k)) pv = load_quad(a.x0_prev + base, n, vec);
+  float nv[4] = {0.f, 0.f, 0.f, 0.f};
+  if (Rule::draws_noise(k, a)) step_noise_tail(nv, a.noise, base, n, a.noise_scale, a.seed, (uint32_t)q, a.clip + b, a.step_index);
+  f32x4 x0 = zero, o;
   for (int j = 0; j < 4; ++j) {
-    x0[j] = dpmpp_x0<GUIDED>(k, flags & 2u, xv[j], ev[j], gv[j], mean);
-    o[j] = dpmpp_out(k, xv[j], x0[j], pv[j]);
+    v.e = ev[j];
+    v.g = gv[j];
+    float x0j = 0.f;
+    o[j] = Rule::template sample<false>(k, constrain, xv[j], nv[j], pv[j], v, v, 0.f, x0j);
+    x0[j] = x0j;
   }
-  store_quad_at(x_to + base, o, n, aligned);
-  if (x0_out) store_quad_at(x0_out + base, x0, n, aligned);
+  store_quad_at(a.x_to + base, o, n, vec);
+  if constexpr (Rule::HISTORY)
+    if (a.x0_out) store_quad_at(a.x0_out + base, x0, n, vec);
 }
 
-// ddim_step_windows_kernel's geometry, per-window gradients and means and outputs, for the 2M step: the windows' x0 are blended, and
-// the history x0_prev / x0_out [Np] holds the BLENDED x0 per absolute position (x0_out may be x0_prev itself, as above).
-template <bool GUIDED>
-__device__ __forceinline__ void dpmpp_windows_quad(int q, const DpmppCoef& k, const float* x, const float* eps, const float* grad,
-                                                   const float* x0_prev, const double* partial, int nchunk, float* x_to, float* x0_out,
-                                                   float* win, int n, int W, int H, uint32_t flags) {
-#pragma clang fp contract(off)
+// Windows: one long signal x [Np] whose predictions came from its n windows (eps, grad [n, W]; quad_windows); partial holds n * nchunk
+// chunk sums, one mean per window.  Where two windows cover a quad, what they make of it is cross-faded with w = (u + 1/2) / V on
+// the later one.  The noise is one draw per absolute position -- row 0 of a [1, Np] batch at `clip`, as the clips layout draws it --
+// so the overlapping windows share it; the history is per absolute position too.  The result goes to x_to [Np] and to win [n, W]
+// (store_quad).
+// (the body: quad q < Np / 4 of ONE row, every pointer of `a` at that row's first sample / window / partial.  step_windows_kernel runs
+// it on the only row there is, step_packed_kernel on the row of a pack that PackRow finds.)
+template <typename Rule>
+__device__ __forceinline__ void windows_quad(int q, const typename Rule::Coef& k, const StepArgs& a, int n, int W, int H, uint64_t clip) {
   const int V = W - H;
   const int p = q * 4;
-  const bool constrain = flags & 2u;
+  const bool constrain = a.flags & STEP_CONSTRAIN;
   const QuadWindows g = quad_windows(p, n, W, H);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-  const f32x4 xv = *reinterpret_cast<const f32x4*>(x + p);
-  const f32x4 er = *reinterpret_cast<const f32x4*>(eps + g.at_r);
+  const f32x4 xv = *reinterpret_cast<const f32x4*>(a.x + p);
+  const f32x4 er = *reinterpret_cast<const f32x4*>(a.eps + g.at_r);
   f32x4 el = er, gr = zero, gl = zero, pv = zero;
-  if (g.two) el = *reinterpret_cast<const f32x4*>(eps + g.at_l);
-  if (GUIDED) {
-    gr = *reinterpret_cast<const f32x4*>(grad + g.at_r);
-    if (g.two) gl = *reinterpret_cast<const f32x4*>(grad + g.at_l);
+  if (g.two) el = *reinterpret_cast<const f32x4*>(a.eps + g.at_l);
+  if (Rule::GUIDED) {
+    gr = *reinterpret_cast<const f32x4*>(a.grad + g.at_r);
+    if (g.two) gl = *reinterpret_cast<const f32x4*>(a.grad + g.at_l);
   }
-  if (k.second) pv = *reinterpret_cast<const f32x4*>(x0_prev + p);
+  if (Rule::reads_history(k)) pv = *reinterpret_cast<const f32x4*>(a.x0_prev + p);
   float mean_r = 0.f, mean_l = 0.f;
   if (constrain) {
-    mean_r = x0_mean(partial + (size_t)g.br * nchunk, nchunk, W);
-    if (g.two) mean_l = x0_mean(partial + (size_t)(g.br - 1) * nchunk, nchunk, W);
+    mean_r = x0_mean(a.partial + (size_t)g.br * a.nchunk, a.nchunk, W);
+    if (g.two) mean_l = x0_mean(a.partial + (size_t)(g.br - 1) * a.nchunk, a.nchunk, W);
   }
-  f32x4 x0, o;
+  f32x4 nv = zero;
+  if (Rule::draws_noise(k, a)) nv = step_noise_quad(a.noise, p, a.noise_scale, a.seed, (uint32_t)q, clip, a.step_index);
+  f32x4 x0 = zero, o;
   for (int j = 0; j < 4; ++j) {
-    x0[j] = dpmpp_x0<GUIDED>(k, constrain, xv[j], er[j], gr[j], mean_r);
+    const View one = {er[j], gr[j], mean_r}, left = {el[j], gl[j], mean_l};
+    float x0j = 0.f;
     if (g.two) {
       const float w = ((float)(g.u + j) + 0.5f) / (float)V;
-      const float x0_l = dpmpp_x0<GUIDED>(k, constrain, xv[j], el[j], gl[j], mean_l);
-      x0[j] = fmaf(w, x0[j] - x0_l, x0_l);
+      o[j] = Rule::template sample<true>(k, constrain, xv[j], nv[j], pv[j], one, left, w, x0j);
+    } else {
+      o[j] = Rule::template sample<false>(k, constrain, xv[j], nv[j], pv[j], one, left, 0.f, x0j);
     }
-    o[j] = dpmpp_out(k, xv[j], x0[j], pv[j]);
+    x0[j] = x0j;
   }
-  store_quad(x_to, win, p, g, [&](float* dst) { *reinterpret_cast<f32x4*>(dst) = o; });
-  if (x0_out) *reinterpret_cast<f32x4*>(x0_out + p) = x0;
+  store_quad(a.x_to, a.win, p, g, [&](float* dst) { *reinterpret_cast<f32x4*>(dst) = o; });
+  if constexpr (Rule::HISTORY)
+    if (a.x0_out) *reinterpret_cast<f32x4*>(a.x0_out + p) = x0;
 }
-template <bool GUIDED>
-__global__ __launch_bounds__(256) void dpmpp_step_windows_kernel(const float* x, const float* eps, const float* grad, const float* x0_prev,
-                                                                 const float* a_from, const float* a_t, const float* a_to,
-                                                                 const double* partial, int nchunk, float* x_to, float* x0_out, float* win,
-                                                                 int n, int W, int H, uint32_t flags) {
-  __shared__ DpmppCoef ks;
-  if (threadIdx.x == 0) ks = dpmpp_coef(a_from, x0_prev != nullptr, a_t[0], a_to[0]);
-  __syncthreads();
+template <typename Rule>
+__global__ __launch_bounds__(256) void step_windows_kernel(StepArgs a, int n, int W, int H) {
+  const typename Rule::Coef k = workgroup_coef<Rule>(a, 0);
   const int q = blockIdx.x * 256 + threadIdx.x;
   if (q >= ((n - 1) * H + W) / 4) return;
-  const DpmppCoef k = ks;
-  dpmpp_windows_quad<GUIDED>(q, k, x, eps, grad, x0_prev, partial, nchunk, x_to, x0_out, win, n, W, H, flags);
+  windows_quad<Rule>(q, k, a, n, W, H, a.clip);
 }
 
 // ---------------------------------------------------------------------------------
@@ -581,7 +556,7 @@ __global__ __launch_bounds__(256) void dpmpp_step_windows_kernel(const float* x,
 // rows laid end to end and their windows stacked in [N, W] arrays, stepped by ONE launch.  `first` [R + 1] holds the prefix sums of
 // the window counts: recording r owns windows first[r] .. first[r + 1] - 1 and starts at sample first[r] * H + r * V of the long
 // arrays (every row is n_r * H + V long).  A quad is handed, with every pointer moved to its recording's first sample / window /
-// partial, to the ..._windows_quad body the single-recording kernels run, at clip + r: the arithmetic IS that kernel's on that
+// partial, to the windows_quad body the single-recording kernel runs, at clip + r: the arithmetic IS that kernel's on that
 // recording alone, and the last window of one recording never meets the first of the next.
 //
 // N = first[R] lives on the device, so the host cannot size a grid by it: a fixed grid walks the quads in strides of one grid.  A
@@ -644,72 +619,20 @@ __device__ __forceinline__ float* pack_shift(float* p, size_t by) { return p ? p
 
 // The x0 sums of every window of a pack, partial [N, nchunk]: window b starts at b * H + rec(b) * V of x.  One (window, chunk) per
 // workgroup and stride, summed by the body -- and so in the order -- of the single-recording launch.
-__global__ __launch_bounds__(256) void ddpm_x0sum_packed_kernel(const float* x, const float* eps, const float* a_t, double* partial,
-                                                                const int* first, int R, int W, int H, int nchunk) {
+template <typename Sum>
+__global__ __launch_bounds__(256) void x0sum_packed_kernel(const float* x, const float* eps, const float* grad, const float* a_t,
+                                                           double* partial, const int* first, int R, int W, int H, int nchunk) {
   const PackTable t = pack_table(first, R, W, H);
   for (int item = blockIdx.x; item < t.N * nchunk; item += gridDim.x) {
     const int b = item / nchunk;
     const size_t start = (size_t)t.off(pack_window_row(t, b), b);
-    ddpm_x0sum_chunk(x + start, eps + (size_t)b * W, a_t[0], partial + item, W, item - b * nchunk);
-  }
-}
-__global__ __launch_bounds__(256) void ddim_x0sum_packed_kernel(const float* x, const float* eps, const float* grad, const float* a_t,
-                                                                double* partial, const int* first, int R, int W, int H, int nchunk) {
-  const PackTable t = pack_table(first, R, W, H);
-  for (int item = blockIdx.x; item < t.N * nchunk; item += gridDim.x) {
-    const int b = item / nchunk;
-    const size_t start = (size_t)t.off(pack_window_row(t, b), b);
-    ddim_x0sum_chunk(x + start, eps + (size_t)b * W, pack_shift(grad, (size_t)b * W), a_t[0], partial + item, W, item - b * nchunk);
+    x0sum_chunk<Sum>(x + start, eps + (size_t)b * W, pack_shift(grad, (size_t)b * W), a_t[0], partial + item, W, item - b * nchunk);
   }
 }
 
-__global__ __launch_bounds__(256) void ddpm_step_packed_kernel(const float* x, const float* eps, const float* noise, const float* a_t,
-                                                               const float* a_prev, const double* partial, int nchunk, float* x_prev,
-                                                               float* win, const int* first, int R, int W, int H, uint32_t flags,
-                                                               float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index) {
-  const PackTable t = pack_table(first, R, W, H);
-  const StepCoef k = step_coef(a_t[0], a_prev[0], flags & 1u);
-  const int64_t total = t.total();
-  for (int64_t p0 = (int64_t)blockIdx.x * 1024; p0 < total; p0 += (int64_t)gridDim.x * 1024) {
-    const int64_t p = p0 + threadIdx.x * 4;
-    if (p >= total) continue;
-    const PackRow w = pack_row(t, p0, p);
-    if (!w.ok) continue;
-    const size_t wo = (size_t)w.fb * W;
-    ddpm_windows_quad(w.q, k, x + w.off, eps + wo, pack_shift(noise, w.off), partial + (size_t)w.fb * nchunk, nchunk, x_prev + w.off,
-                      pack_shift(win, wo), w.n, W, H, flags, noise_scale, seed, clip + w.r, step_index);
-  }
-}
-
-template <bool GUIDED>
-__global__ __launch_bounds__(256) void ddim_step_packed_kernel(const float* x, const float* eps, const float* grad, const float* noise,
-                                                               const float* a_t, const float* a_to, const double* partial, int nchunk,
-                                                               float* x_to, float* win, const int* first, int R, int W, int H,
-                                                               uint32_t flags, float eta, float noise_scale, uint64_t seed, uint64_t clip,
-                                                               uint32_t step_index) {
-  const PackTable t = pack_table(first, R, W, H);
-  const DdimCoef k = ddim_coef(a_t[0], a_to[0], eta, flags & 4u);
-  const int64_t total = t.total();
-  for (int64_t p0 = (int64_t)blockIdx.x * 1024; p0 < total; p0 += (int64_t)gridDim.x * 1024) {
-    const int64_t p = p0 + threadIdx.x * 4;
-    if (p >= total) continue;
-    const PackRow w = pack_row(t, p0, p);
-    if (!w.ok) continue;
-    const size_t wo = (size_t)w.fb * W;
-    ddim_windows_quad<GUIDED>(w.q, k, x + w.off, eps + wo, pack_shift(grad, wo), pack_shift(noise, w.off), partial + (size_t)w.fb * nchunk,
-                              nchunk, x_to + w.off, pack_shift(win, wo), w.n, W, H, flags, noise_scale, seed, clip + w.r, step_index);
-  }
-}
-
-template <bool GUIDED>
-__global__ __launch_bounds__(256) void dpmpp_step_packed_kernel(const float* x, const float* eps, const float* grad, const float* x0_prev,
-                                                                const float* a_from, const float* a_t, const float* a_to,
-                                                                const double* partial, int nchunk, float* x_to, float* x0_out, float* win,
-                                                                const int* first, int R, int W, int H, uint32_t flags) {
-  __shared__ DpmppCoef ks;
-  if (threadIdx.x == 0) ks = dpmpp_coef(a_from, x0_prev != nullptr, a_t[0], a_to[0]);
-  __syncthreads();
-  const DpmppCoef k = ks;
+template <typename Rule>
+__global__ __launch_bounds__(256) void step_packed_kernel(StepArgs a, const int* first, int R, int W, int H) {
+  const typename Rule::Coef k = workgroup_coef<Rule>(a, 0);
   const PackTable t = pack_table(first, R, W, H);
   const int64_t total = t.total();
   for (int64_t p0 = (int64_t)blockIdx.x * 1024; p0 < total; p0 += (int64_t)gridDim.x * 1024) {
@@ -718,9 +641,17 @@ __global__ __launch_bounds__(256) void dpmpp_step_packed_kernel(const float* x, 
     const PackRow w = pack_row(t, p0, p);
     if (!w.ok) continue;
     const size_t wo = (size_t)w.fb * W;
-    dpmpp_windows_quad<GUIDED>(w.q, k, x + w.off, eps + wo, pack_shift(grad, wo), pack_shift(x0_prev, w.off),
-                               partial + (size_t)w.fb * nchunk, nchunk, x_to + w.off, pack_shift(x0_out, w.off), pack_shift(win, wo), w.n, W,
-                               H, flags);
+    StepArgs row = a;  // the recording's own row: long arrays from its first sample, window arrays and partials from its first window
+    row.x = a.x + w.off;
+    row.noise = pack_shift(a.noise, w.off);
+    row.x0_prev = pack_shift(a.x0_prev, w.off);
+    row.x_to = a.x_to + w.off;
+    row.x0_out = pack_shift(a.x0_out, w.off);
+    row.eps = a.eps + wo;
+    row.grad = pack_shift(a.grad, wo);
+    row.win = pack_shift(a.win, wo);
+    row.partial = a.partial + (size_t)w.fb * a.nchunk;
+    windows_quad<Rule>(w.q, k, row, w.n, W, H, a.clip + w.r);
   }
 }
 // ---------------------------------------------------------------------------------
@@ -1047,148 +978,60 @@ int run_randn(float* out, int B, int T, uint64_t seed, uint64_t clip_offset, uin
   return 0;
 }
 
-int ddpm_scratch_doubles(int B, int T) { return B * ((T + SUM_CHUNK - 1) / SUM_CHUNK); }
-
-int run_ddpm_step(const float* x_t, const float* eps, const float* noise, const float* a_t, const float* a_prev, float* out,
-                  double* scratch, int B, int T, uint32_t flags, float noise_scale, uint64_t seed, uint64_t clip_offset,
-                  uint32_t step_index, hipStream_t st) {
-  const int nchunk = (T + SUM_CHUNK - 1) / SUM_CHUNK;
-  if (flags & 2u) {
-    hipLaunchKernelGGL(ddpm_x0sum_kernel, dim3(nchunk, B), dim3(256), 0, st, x_t, eps, a_t, scratch, T, nchunk, T, 1);
-  }
-  dim3 grid(((T + 3) / 4 + 255) / 256, B);
-  hipLaunchKernelGGL(ddpm_step_kernel, grid, dim3(256), 0, st, x_t, eps, noise, a_t, a_prev, scratch, nchunk, out, T, flags,
-                     noise_scale, seed, clip_offset, step_index);
-  VQVS_HIP(hipGetLastError());
-  return 0;
-}
-
-// scratch: ddpm_scratch_doubles(n, W) doubles when flags has CONSTRAIN (not read otherwise)
-int run_ddpm_step_windows(const float* x, const float* eps, const float* noise, const float* a_t, const float* a_prev, float* x_prev,
-                          float* windows, double* scratch, int n, int W, int H, uint32_t flags, float noise_scale, uint64_t seed,
-                          uint64_t clip, uint32_t step_index, hipStream_t st) {
-  const int nchunk = (W + SUM_CHUNK - 1) / SUM_CHUNK;
-  if (flags & 2u) {
-    hipLaunchKernelGGL(ddpm_x0sum_kernel, dim3(nchunk, n), dim3(256), 0, st, x, eps, a_t, scratch, W, nchunk, H, 0);
-  }
-  const int quads = ((n - 1) * H + W) / 4;
-  hipLaunchKernelGGL(ddpm_step_windows_kernel, dim3((quads + 255) / 256), dim3(256), 0, st, x, eps, noise, a_t, a_prev, scratch, nchunk,
-                     x_prev, windows, n, W, H, flags, noise_scale, seed, clip, step_index);
-  VQVS_HIP(hipGetLastError());
-  return 0;
-}
-
-// scratch: ddpm_scratch_doubles(B, T) doubles when flags has CONSTRAIN (not read otherwise)
-int run_ddim_step(const float* x_t, const float* eps, const float* grad, const float* noise, const float* a_t, const float* a_to, float* out,
-                  double* scratch, int B, int T, uint32_t flags, float eta, float noise_scale, uint64_t seed, uint64_t clip_offset,
-                  uint32_t step_index, hipStream_t st) {
-  const int nchunk = (T + SUM_CHUNK - 1) / SUM_CHUNK;
-  if (flags & 2u) {
-    hipLaunchKernelGGL(ddim_x0sum_kernel, dim3(nchunk, B), dim3(256), 0, st, x_t, eps, grad, a_t, scratch, T, nchunk, T, 1);
-  }
-  dim3 grid(((T + 3) / 4 + 255) / 256, B);
-  auto kernel = grad ? ddim_step_kernel<true> : ddim_step_kernel<false>;
-  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, x_t, eps, grad, noise, a_t, a_to, scratch, nchunk, out, T, flags, eta, noise_scale, seed,
-                     clip_offset, step_index);
-  VQVS_HIP(hipGetLastError());
-  return 0;
-}
-
-// scratch: ddpm_scratch_doubles(n, W) doubles when flags has CONSTRAIN (not read otherwise)
-int run_ddim_step_windows(const float* x, const float* eps, const float* grad, const float* noise, const float* a_t, const float* a_to,
-                          float* x_to, float* windows, double* scratch, int n, int W, int H, uint32_t flags, float eta, float noise_scale,
-                          uint64_t seed, uint64_t clip, uint32_t step_index, hipStream_t st) {
-  const int nchunk = (W + SUM_CHUNK - 1) / SUM_CHUNK;
-  if (flags & 2u) {
-    hipLaunchKernelGGL(ddim_x0sum_kernel, dim3(nchunk, n), dim3(256), 0, st, x, eps, grad, a_t, scratch, W, nchunk, H, 0);
-  }
-  const int quads = ((n - 1) * H + W) / 4;
-  auto kernel = grad ? ddim_step_windows_kernel<true> : ddim_step_windows_kernel<false>;
-  hipLaunchKernelGGL(kernel, dim3((quads + 255) / 256), dim3(256), 0, st, x, eps, grad, noise, a_t, a_to, scratch, nchunk, x_to, windows, n, W,
-                     H, flags, eta, noise_scale, seed, clip, step_index);
-  VQVS_HIP(hipGetLastError());
-  return 0;
-}
-
-// scratch: ddpm_scratch_doubles(B, T) doubles when flags has CONSTRAIN (not read otherwise)
-int run_dpmpp_step(const float* x_t, const float* eps, const float* grad, const float* x0_prev, const float* a_from, const float* a_t,
-                   const float* a_to, float* x_to, float* x0_out, double* scratch, int B, int T, uint32_t flags, hipStream_t st) {
-  const int nchunk = (T + SUM_CHUNK - 1) / SUM_CHUNK;
-  if (flags & 2u) {
-    hipLaunchKernelGGL(ddim_x0sum_kernel, dim3(nchunk, B), dim3(256), 0, st, x_t, eps, grad, a_t, scratch, T, nchunk, T, 1);
-  }
-  uintptr_t bits = 0;
-  for (const float* p : {x_t, eps, grad, x0_prev, (const float*)x_to, (const float*)x0_out}) bits |= reinterpret_cast<uintptr_t>(p);
-  const bool aligned = T % 4 == 0 && bits % 16 == 0;
-  dim3 grid(((T + 3) / 4 + 255) / 256, B);
-  auto kernel = grad ? dpmpp_step_kernel<true> : dpmpp_step_kernel<false>;
-  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, x_t, eps, grad, x0_prev, a_from, a_t, a_to, scratch, nchunk, x_to, x0_out, T, flags, aligned);
-  VQVS_HIP(hipGetLastError());
-  return 0;
-}
-
-// scratch: ddpm_scratch_doubles(n, W) doubles when flags has CONSTRAIN (not read otherwise)
-int run_dpmpp_step_windows(const float* x, const float* eps, const float* grad, const float* x0_prev, const float* a_from, const float* a_t,
-                           const float* a_to, float* x_to, float* x0_out, float* windows, double* scratch, int n, int W, int H, uint32_t flags,
-                           hipStream_t st) {
-  const int nchunk = (W + SUM_CHUNK - 1) / SUM_CHUNK;
-  if (flags & 2u) {
-    hipLaunchKernelGGL(ddim_x0sum_kernel, dim3(nchunk, n), dim3(256), 0, st, x, eps, grad, a_t, scratch, W, nchunk, H, 0);
-  }
-  const int quads = ((n - 1) * H + W) / 4;
-  auto kernel = grad ? dpmpp_step_windows_kernel<true> : dpmpp_step_windows_kernel<false>;
-  hipLaunchKernelGGL(kernel, dim3((quads + 255) / 256), dim3(256), 0, st, x, eps, grad, x0_prev, a_from, a_t, a_to, scratch, nchunk, x_to,
-                     x0_out, windows, n, W, H, flags);
-  VQVS_HIP(hipGetLastError());
-  return 0;
-}
+int ddpm_scratch_doubles(int B, int T) { return B * sum_chunks(T); }
 
 // The partials of a packed CONSTRAIN step: N * nchunk doubles, N on the device.  The host leases the most a pack of this geometry can
 // need: N <= 65535 and N * H + R * V < 2^31.
 size_t packed_scratch_doubles(int W, int H) {
   const int64_t most = std::min<int64_t>(65535, (((int64_t)1 << 31) - 1) / H);
-  return (size_t)most * ((W + SUM_CHUNK - 1) / SUM_CHUNK);
+  return (size_t)most * sum_chunks(W);
 }
 
-int run_ddpm_step_packed(const float* x, const float* eps, const float* noise, const float* a_t, const float* a_prev, float* x_prev,
-                         float* windows, double* scratch, const int* first, int R, int W, int H, uint32_t flags, float noise_scale,
-                         uint64_t seed, uint64_t clip, uint32_t step_index, hipStream_t st) {
-  const int nchunk = (W + SUM_CHUNK - 1) / SUM_CHUNK;
-  if (flags & 2u) {
-    hipLaunchKernelGGL(ddpm_x0sum_packed_kernel, dim3(PACK_GRID), dim3(256), 0, st, x, eps, a_t, scratch, first, R, W, H, nchunk);
+namespace {
+
+// One rule on one layout: the x0 sums when CONSTRAIN asks for them (a.partial: the scratch_doubles of the layout), then the step
+template <typename Rule>
+int launch_step(StepArgs a, const StepLayout& l, hipStream_t st) {
+  using Sum = typename Rule::Sum;
+  const bool constrain = a.flags & STEP_CONSTRAIN;
+  const dim3 wg(256);
+  a.nchunk = sum_chunks(l.W);
+  switch (l.kind) {
+    case StepLayout::CLIPS: {
+      const int B = l.n, T = l.W;
+      if (constrain) hipLaunchKernelGGL(x0sum_kernel<Sum>, dim3(a.nchunk, B), wg, 0, st, a.x, a.eps, a.grad, a.a_t, a.partial, T, a.nchunk, T, 1);
+      uintptr_t bits = 0;
+      for (const float* p : {a.x, a.eps, a.grad, a.x0_prev, (const float*)a.x_to, (const float*)a.x0_out}) bits |= reinterpret_cast<uintptr_t>(p);
+      const bool aligned = T % 4 == 0 && bits % 16 == 0;
+      hipLaunchKernelGGL(step_clips_kernel<Rule>, dim3(((T + 3) / 4 + 255) / 256, B), wg, 0, st, a, T, aligned);
+      break;
+    }
+    case StepLayout::WINDOWS: {
+      if (constrain) hipLaunchKernelGGL(x0sum_kernel<Sum>, dim3(a.nchunk, l.n), wg, 0, st, a.x, a.eps, a.grad, a.a_t, a.partial, l.W, a.nchunk, l.H, 0);
+      const int quads = ((l.n - 1) * l.H + l.W) / 4;
+      hipLaunchKernelGGL(step_windows_kernel<Rule>, dim3((quads + 255) / 256), wg, 0, st, a, l.n, l.W, l.H);
+      break;
+    }
+    case StepLayout::PACK:
+      if (constrain) hipLaunchKernelGGL(x0sum_packed_kernel<Sum>, dim3(PACK_GRID), wg, 0, st, a.x, a.eps, a.grad, a.a_t, a.partial, l.first, l.n, l.W, l.H,
+                                    a.nchunk);
+      hipLaunchKernelGGL(step_packed_kernel<Rule>, dim3(PACK_GRID), wg, 0, st, a, l.first, l.n, l.W, l.H);
+      break;
   }
-  hipLaunchKernelGGL(ddpm_step_packed_kernel, dim3(PACK_GRID), dim3(256), 0, st, x, eps, noise, a_t, a_prev, scratch, nchunk, x_prev, windows,
-                     first, R, W, H, flags, noise_scale, seed, clip, step_index);
   VQVS_HIP(hipGetLastError());
   return 0;
 }
 
-int run_ddim_step_packed(const float* x, const float* eps, const float* grad, const float* noise, const float* a_t, const float* a_to,
-                         float* x_to, float* windows, double* scratch, const int* first, int R, int W, int H, uint32_t flags, float eta,
-                         float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index, hipStream_t st) {
-  const int nchunk = (W + SUM_CHUNK - 1) / SUM_CHUNK;
-  if (flags & 2u) {
-    hipLaunchKernelGGL(ddim_x0sum_packed_kernel, dim3(PACK_GRID), dim3(256), 0, st, x, eps, grad, a_t, scratch, first, R, W, H, nchunk);
-  }
-  auto kernel = grad ? ddim_step_packed_kernel<true> : ddim_step_packed_kernel<false>;
-  hipLaunchKernelGGL(kernel, dim3(PACK_GRID), dim3(256), 0, st, x, eps, grad, noise, a_t, a_to, scratch, nchunk, x_to, windows, first, R, W, H,
-                     flags, eta, noise_scale, seed, clip, step_index);
-  VQVS_HIP(hipGetLastError());
-  return 0;
-}
+}  // namespace
 
-int run_dpmpp_step_packed(const float* x, const float* eps, const float* grad, const float* x0_prev, const float* a_from, const float* a_t,
-                          const float* a_to, float* x_to, float* x0_out, float* windows, double* scratch, const int* first, int R, int W,
-                          int H, uint32_t flags, hipStream_t st) {
-  const int nchunk = (W + SUM_CHUNK - 1) / SUM_CHUNK;
-  if (flags & 2u) {
-    hipLaunchKernelGGL(ddim_x0sum_packed_kernel, dim3(PACK_GRID), dim3(256), 0, st, x, eps, grad, a_t, scratch, first, R, W, H, nchunk);
+int run_step(StepRule rule, const StepArgs& a, const StepLayout& l, hipStream_t st) {
+  const bool guided = a.grad != nullptr;
+  switch (rule) {
+    case StepRule::DDPM: return launch_step<DdpmRule>(a, l, st);
+    case StepRule::DDIM: return guided ? launch_step<DdimRule<true>>(a, l, st) : launch_step<DdimRule<false>>(a, l, st);
+    case StepRule::DPMPP: return guided ? launch_step<DpmppRule<true>>(a, l, st) : launch_step<DpmppRule<false>>(a, l, st);
   }
-  auto kernel = grad ? dpmpp_step_packed_kernel<true> : dpmpp_step_packed_kernel<false>;
-  hipLaunchKernelGGL(kernel, dim3(PACK_GRID), dim3(256), 0, st, x, eps, grad, x0_prev, a_from, a_t, a_to, scratch, nchunk, x_to, x0_out,
-                     windows, first, R, W, H, flags);
-  VQVS_HIP(hipGetLastError());
-  return 0;
+  VQVS_FAIL(VQVS_ERR_ARG, "unknown step rule %d", (int)rule);
 }
 
 // 16-byte accesses need every array to start on a 16-byte boundary (the mask, read 4 bytes at a time, on a 4-byte one)

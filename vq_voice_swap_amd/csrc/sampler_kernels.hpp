@@ -1,44 +1,38 @@
 // Host launchers of the model-independent kernels (DDPM step, RNG, VQ).
 #pragma once
+#include "../../include/vqvs.h"
 #include "common.hpp"
 
 namespace vqvs {
 int run_randn(float* out, int B, int T, uint64_t seed, uint64_t clip_offset, uint32_t stream_id, hipStream_t st);
-int ddpm_scratch_doubles(int B, int T);
-int run_ddpm_step(const float* x_t, const float* eps, const float* noise, const float* a_t, const float* a_prev, float* out,
-                  double* scratch, int B, int T, uint32_t flags, float noise_scale, uint64_t seed, uint64_t clip_offset,
-                  uint32_t step_index, hipStream_t st);
-// the step of one long signal [(n - 1) * H + W] from the predictions of its n overlapping windows [n, W]; scratch as run_ddpm_step(n, W)
-int run_ddpm_step_windows(const float* x, const float* eps, const float* noise, const float* a_t, const float* a_prev, float* x_prev,
-                          float* windows, double* scratch, int n, int W, int H, uint32_t flags, float noise_scale, uint64_t seed,
-                          uint64_t clip, uint32_t step_index, hipStream_t st);
-// DDIM step from alpha_bar a_t to a_to, single clips and the windows of one long signal; grad NULL: unguided; scratch as the DDPM steps'
-int run_ddim_step(const float* x_t, const float* eps, const float* grad, const float* noise, const float* a_t, const float* a_to, float* out,
-                  double* scratch, int B, int T, uint32_t flags, float eta, float noise_scale, uint64_t seed, uint64_t clip_offset,
-                  uint32_t step_index, hipStream_t st);
-int run_ddim_step_windows(const float* x, const float* eps, const float* grad, const float* noise, const float* a_t, const float* a_to,
-                          float* x_to, float* windows, double* scratch, int n, int W, int H, uint32_t flags, float eta, float noise_scale,
-                          uint64_t seed, uint64_t clip, uint32_t step_index, hipStream_t st);
-// DPM-Solver++(2M) step from alpha_bar a_t to a_to with the previous step's x0 and alpha_bar (x0_prev / a_from NULL: first order),
-// single clips and the windows of one long signal; x0_out NULL: not wanted; scratch as the DDPM steps'
-int run_dpmpp_step(const float* x_t, const float* eps, const float* grad, const float* x0_prev, const float* a_from, const float* a_t,
-                   const float* a_to, float* x_to, float* x0_out, double* scratch, int B, int T, uint32_t flags, hipStream_t st);
-int run_dpmpp_step_windows(const float* x, const float* eps, const float* grad, const float* x0_prev, const float* a_from, const float* a_t,
-                           const float* a_to, float* x_to, float* x0_out, float* windows, double* scratch, int n, int W, int H, uint32_t flags,
-                           hipStream_t st);
-// The three window steps on a PACK of R recordings in one launch: first [R + 1] (device) holds the prefix sums of the recordings' window
-// counts, the long arrays hold the rows end to end, the window arrays the windows stacked; recording r is stepped as clip + r.
-// scratch: packed_scratch_doubles(W, H) doubles when flags has CONSTRAIN -- the window total is on the device, so this is its bound.
-size_t packed_scratch_doubles(int W, int H);
-int run_ddpm_step_packed(const float* x, const float* eps, const float* noise, const float* a_t, const float* a_prev, float* x_prev,
-                         float* windows, double* scratch, const int* first, int R, int W, int H, uint32_t flags, float noise_scale,
-                         uint64_t seed, uint64_t clip, uint32_t step_index, hipStream_t st);
-int run_ddim_step_packed(const float* x, const float* eps, const float* grad, const float* noise, const float* a_t, const float* a_to,
-                         float* x_to, float* windows, double* scratch, const int* first, int R, int W, int H, uint32_t flags, float eta,
-                         float noise_scale, uint64_t seed, uint64_t clip, uint32_t step_index, hipStream_t st);
-int run_dpmpp_step_packed(const float* x, const float* eps, const float* grad, const float* x0_prev, const float* a_from, const float* a_t,
-                          const float* a_to, float* x_to, float* x0_out, float* windows, double* scratch, const int* first, int R, int W,
-                          int H, uint32_t flags, hipStream_t st);
+// A reverse step is a RULE (the sampler) run on a LAYOUT (where the state's samples lie): sampler_kernels.hip "Rules and layouts".
+enum class StepRule { DDPM, DDIM, DPMPP };
+// Every array and scalar that any step takes (include/vqvs.h names them); what a rule or a layout has no use for stays NULL / 0.
+// The step goes from alpha_bar a_t to a_to (the DDPM step's alpha_prev), DPM-Solver++ with the step before's x0_prev and a_from
+// (NULL: first order); grad NULL: unguided; noise NULL: drawn from (seed, clip, step_index); win / x0_out NULL: not wanted.
+struct StepArgs {
+  const float *x = nullptr, *eps = nullptr, *grad = nullptr, *noise = nullptr, *x0_prev = nullptr;
+  const float *a_from = nullptr, *a_t = nullptr, *a_to = nullptr;
+  float *x_to = nullptr, *x0_out = nullptr, *win = nullptr;
+  double* partial = nullptr;  // the x0 sums of CONSTRAIN, nchunk per row: ddpm_scratch_doubles / packed_scratch_doubles of them (not read without the flag)
+  int nchunk = 0;             // (set by run_step)
+  uint32_t flags = 0;
+  float eta = 0.f, noise_scale = 0.f;
+  uint64_t seed = 0, clip = 0;
+  uint32_t step_index = 0;
+};
+// CLIPS: n rows of W samples, row b with its own alphas, stepped as clip + b.  WINDOWS: one long signal [(n - 1) * H + W] under its n
+// overlapping windows [n, W], one alpha.  PACK: n recordings of such windows in one launch; first [n + 1] (device) holds the prefix
+// sums of their window counts, the long arrays hold the rows end to end, the window arrays the windows stacked; recording r is
+// stepped as clip + r.
+struct StepLayout {
+  enum Kind { CLIPS, WINDOWS, PACK } kind;
+  int n, W, H;
+  const int* first;
+};
+int ddpm_scratch_doubles(int rows, int len);  // CLIPS (B, T), WINDOWS (n, W)
+size_t packed_scratch_doubles(int W, int H);  // PACK: the window total is on the device, so this is its bound
+int run_step(StepRule rule, const StepArgs& args, const StepLayout& layout, hipStream_t st);
 // kept samples of x (NULL keep: all) put back on the forward process of x0 at alpha, in place: B rows of T, and one long state with
 // its window copies
 int run_keep_region(float* x, const float* x0, const uint8_t* keep, const float* noise, const float* alpha, int B, int T, float noise_scale,
