@@ -711,6 +711,15 @@ int vqvs_debug_read_embedding(vqvs_model* m, int B, float* h_out);
 /* copies d mse_b / d (FiLM rows) of the LAST vqvs_unet_embed_grad -- per clip the (d a | d b) rows of every ResBlock in the order
  * down_blocks, middle_blocks, up_blocks, 2 * cout rows each -- to host as float32 [B][R]; returns R; synchronises */
 int vqvs_debug_read_dfilm(vqvs_model* m, int B, float* h_out);
+/* copies the FiLM rows of the LAST forward -- per clip the (a | b) rows bias + W . gelu(embedding) of every ResBlock's cond_layers in
+ * the order down_blocks, middle_blocks, up_blocks, 2 * cout rows each (physical widths on a padded handle) -- to host as float32
+ * [B][R]; returns R; synchronises.  VQVS_ERR_STATE on a model kind without a FiLM table */
+int vqvs_debug_read_film(vqvs_model* m, int B, float* h_out);
+/* handle-less: d_out[i] = one of the library's GELU device functions (csrc/common.hpp) of d_in[i], n float32 device values each.
+ * form 0: gelu_f; 1, 2, 3: gelu2 at GELU_EXACT, GELU_POLY6, GELU_POLY7 (the fp32, bf16 and fp16 modes' prologues), evaluated on the
+ * pairs (2i, 2i+1) as the prologues evaluate them, an odd tail paired with 0; 4: gelu_grad_f.  VQVS_ERR_ARG before the device is
+ * touched: NULL d_in or d_out; n < 1 or n > 2^30; form outside 0..4 */
+int vqvs_debug_gelu(const float* d_in, float* d_out, int n, int form, void* stream);
 /* number of kernels one forward enqueues, and the algorithmic activation bytes it moves (SURVEY 8d Model A) */
 int vqvs_forward_kernel_count(const vqvs_model* m);
 int64_t vqvs_forward_model_bytes(const vqvs_model* m, int B, int T);

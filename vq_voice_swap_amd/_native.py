@@ -77,6 +77,7 @@ EXPORTS = [
     "vqvs_forward_flops", "vqvs_set_profiling", "vqvs_op_info", "vqvs_op_desc", "vqvs_profile_read", "vqvs_last_error", "vqvs_version",
     "vqvs_unet_embed_grad", "vqvs_embed_adamw", "vqvs_debug_read_dfilm", "vqvs_head_xent_grad", "vqvs_head_adamw",
     "vqvs_mel_cepstra", "vqvs_dtw_distance", "vqvs_guidance_mix", "vqvs_unet_forward_vec", "vqvs_speaker_mix",
+    "vqvs_debug_read_film", "vqvs_debug_gelu",
 ]
 
 _lib = None
@@ -135,6 +136,8 @@ def lib():
     L.vqvs_unet_embed_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
     L.vqvs_embed_adamw.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp]
     L.vqvs_debug_read_dfilm.argtypes = [vp, i32, vp]
+    L.vqvs_debug_read_film.argtypes = [vp, i32, vp]
+    L.vqvs_debug_gelu.argtypes = [vp, vp, i32, i32, vp]
     L.vqvs_head_xent_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     L.vqvs_head_adamw.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp]
     L.vqvs_encoder_forward.argtypes = [vp, vp, vp, i32, i32, vp]
@@ -358,6 +361,19 @@ class Handle:
         assert r == R, (r, R)
         return out
 
+    def read_film(self, B: int):
+        """FiLM rows [B, R] of the last forward: per clip the (a | b) rows of every ResBlock in the order down, middle, up (the
+        handle's physical widths)."""
+        import torch
+
+        R = sum(shape[0] for name, shape in param_table(self.cfg) if name.endswith("cond_layers.1.bias"))  # 2 * cout rows per block
+        out = torch.empty(B, R, dtype=torch.float32)
+        r = lib().vqvs_debug_read_film(self._h, B, out.data_ptr())
+        if r < 0:
+            check(r)
+        assert r == R, (r, R)
+        return out
+
     def read_tap(self, i: int, B: int, T: int):
         import torch
 
@@ -368,6 +384,22 @@ class Handle:
         out = torch.empty(B, ch, Lx, dtype=torch.float32)
         check(lib().vqvs_debug_read_tap(self._h, i, B, T, out.data_ptr()))
         return out
+
+
+GELU_FORMS = {"gelu_f": 0, "exact": 1, "poly6": 2, "poly7": 3, "grad": 4}
+
+
+def debug_gelu(x, form: int):
+    """The library's GELU device function number `form` (vqvs_debug_gelu: 0 gelu_f, 1..3 gelu2 exact / degree 6 / degree 7 on pairs,
+    4 gelu_grad_f) of a float32 tensor on a ROCm device, element by element."""
+    import torch
+
+    require_cuda(x)
+    x = x.detach().to(torch.float32).contiguous()
+    out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        check(lib().vqvs_debug_gelu(x.data_ptr(), out.data_ptr(), x.numel(), int(form), _stream_ptr()))
+    return out
 
 
 _range_checked = {}

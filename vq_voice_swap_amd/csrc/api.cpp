@@ -919,6 +919,23 @@ int vqvs_debug_read_dfilm(vqvs_model* m, int B, float* h_out) {
   return m->dfilm_R;
 }
 
+int vqvs_debug_read_film(vqvs_model* m, int B, float* h_out) {
+  if (!m || !h_out || B < 1 || B > m->cfg.max_batch) VQVS_FAIL(VQVS_ERR_ARG, "bad argument");
+  if (!m->film_R) VQVS_FAIL(VQVS_ERR_STATE, "this model kind has no FiLM table");
+  VQVS_HIP(hipSetDevice(m->device));
+  VQVS_HIP(hipDeviceSynchronize());
+  const float* src = reinterpret_cast<const float*>(m->d_arena + m->misc_off) + m->film_misc_off;
+  VQVS_HIP(hipMemcpy(h_out, src, (size_t)B * m->film_R * sizeof(float), hipMemcpyDeviceToHost));
+  return m->film_R;
+}
+
+int vqvs_debug_gelu(const float* d_in, float* d_out, int n, int form, void* stream) {
+  if (!d_in || !d_out) VQVS_FAIL(VQVS_ERR_ARG, "d_in and d_out must be non-NULL");
+  if (n < 1 || n > (1 << 30)) VQVS_FAIL(VQVS_ERR_ARG, "n=%d outside 1..2^30", n);
+  if (form < 0 || form > 4) VQVS_FAIL(VQVS_ERR_ARG, "form=%d outside 0..4", form);
+  return launch_debug_gelu(d_in, d_out, n, form, reinterpret_cast<hipStream_t>(stream));
+}
+
 int vqvs_forward_kernel_count(const vqvs_model* m) { return m ? (int)m->ops.size() : 0; }
 
 int64_t vqvs_forward_model_bytes(const vqvs_model* m, int B, int T) {

@@ -41,7 +41,7 @@ constexpr int STAT_TILE = 256;
 // ---- device math ------------------------------------------------------------------
 // Exact-erf GELU (reference unet.py:341-342, nn.GELU() default) evaluated with the
 // Abramowitz-Stegun 7.1.28 rational form of erf: |erf error| <= 3e-7, no exp, one rcp.
-// Measured against float64: max |gelu error| = 8.7e-7 over [-8, 8] (tests/test_kernels_gpu.py).
+// Measured against float64: max |gelu error| = 8.7e-7 over [-8, 8] (tests/test_pointwise_gpu.py holds every form below, entry by entry).
 __device__ __forceinline__ float gelu_f(float v) {
   const float z = fabsf(v) * 0.70710678118654752440f;
   float p = fmaf(0.0000430638f, z, 0.0002765672f);

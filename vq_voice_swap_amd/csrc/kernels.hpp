@@ -164,6 +164,9 @@ struct TimeEmbedArgs {  // wavegrad.py:359-373 + unet.py:41-45, 133-135
 };
 int launch_time_embed(const TimeEmbedArgs& a, int B, hipStream_t st);
 int launch_gelu_rows(const float* in, float* out, int n, hipStream_t st);
+// debugging: out[i] = one of common.hpp's GELU device functions of in[i] (vqvs_debug_gelu; form 0 gelu_f, 1..3 gelu2<EXACT / POLY6 /
+// POLY7> on the pairs (2i, 2i+1), 4 gelu_grad_f)
+int launch_debug_gelu(const float* in, float* out, int n, int form, hipStream_t st);
 
 struct FilmArgs {  // all blocks' cond_layers Linear at once: film[b][r] = bias[r] + W[r] . gemb[b]
   const float* gemb;  // [B][E]

@@ -361,6 +361,23 @@ __global__ void gelu_rows_kernel(const float* in, float* out, int n) {
   if (i < n) out[i] = gelu_f(in[i]);
 }
 
+// vqvs_debug_gelu: the device functions of common.hpp themselves, one element (FORM 0, 4) or one pair (2i, 2i+1) (FORM 1..3, as the
+// fused prologues call gelu2) per thread; the partner of an odd tail is 0 and is not stored.
+template <int FORM>
+__global__ __launch_bounds__(256) void debug_gelu_kernel(const float* in, float* out, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if constexpr (FORM == 0 || FORM == 4) {
+    if (i < n) out[i] = FORM == 0 ? gelu_f(in[i]) : gelu_grad_f(in[i]);
+  } else {
+    const long long j = 2ll * i;
+    if (j >= n) return;
+    const bool pair = j + 1 < n;
+    const f32x2 g = gelu2<FORM - 1>(f32x2{in[j], pair ? in[j + 1] : 0.f});
+    out[j] = g[0];
+    if (pair) out[j + 1] = g[1];
+  }
+}
+
 // film[b][r] = bias[r] + W[r] . gemb[b].  W is stored TRANSPOSED ([E][R]): a workgroup owns 64 output rows r (lane = row: coalesced
 // weight reads) of 32 clips; its four waves split E, each accumulating 32 clips in registers against gemb staged in LDS as
 // [e][32 clips], and the four partial sums are added in wave order through LDS (deterministic).  Grid: (R / 64, B / 32).
@@ -559,6 +576,21 @@ int launch_time_embed(const TimeEmbedArgs& a, int B, hipStream_t st) {
 
 int launch_gelu_rows(const float* in, float* out, int n, hipStream_t st) {
   hipLaunchKernelGGL(gelu_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, st, in, out, n);
+  VQVS_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_debug_gelu(const float* in, float* out, int n, int form, hipStream_t st) {
+  const int items = form == 0 || form == 4 ? n : (n + 1) / 2;
+  const dim3 grid((items + 255) / 256), block(256);
+  switch (form) {
+    case 0: hipLaunchKernelGGL(debug_gelu_kernel<0>, grid, block, 0, st, in, out, n); break;
+    case 1: hipLaunchKernelGGL(debug_gelu_kernel<1>, grid, block, 0, st, in, out, n); break;
+    case 2: hipLaunchKernelGGL(debug_gelu_kernel<2>, grid, block, 0, st, in, out, n); break;
+    case 3: hipLaunchKernelGGL(debug_gelu_kernel<3>, grid, block, 0, st, in, out, n); break;
+    case 4: hipLaunchKernelGGL(debug_gelu_kernel<4>, grid, block, 0, st, in, out, n); break;
+    default: VQVS_FAIL(-1, "debug_gelu: form=%d outside 0..4", form);
+  }
   VQVS_HIP(hipGetLastError());
   return 0;
 }

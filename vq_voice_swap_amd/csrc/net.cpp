@@ -996,6 +996,8 @@ class Builder {
     const size_t wall_off = f.wall_off = blob_f32_transposed(Wall.data(), R, E);
     const size_t ball_off = blob.add(ball.data(), ball.size() * 4);
     const size_t film_off = f.film_off = alloc_misc((size_t)maxB_ * R);
+    m_->film_misc_off = film_off;
+    m_->film_R = R;
     Builder* self = this;
     op("film", "", 0, 0, 0, [=](const RunCtx& r) -> int {
       FilmArgs a{self->miscp(gemb_off), self->wf(wall_off), self->wf(ball_off), self->miscp(film_off), E, R};
@@ -1379,6 +1381,8 @@ static void build_resblock(vqvs_model* m, Builder& b) {
   if (E) {
     const size_t gemb = b.alloc_misc((size_t)c.max_batch * E);
     film_misc = b.alloc_misc((size_t)c.max_batch * R);
+    m->film_misc_off = film_misc;
+    m->film_R = R;
     const size_t w_off = b.blob_f32_transposed(b.P("cond_layers.1.weight"), R, E);
     const size_t bias_off = b.blob_f32("cond_layers.1.bias");
     b.op("film", "", 0, 0, 0, [=](const RunCtx& r) -> int {

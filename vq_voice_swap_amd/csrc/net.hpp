@@ -107,6 +107,8 @@ struct vqvs_model {
   int emb_E = 0;
   size_t dfilm_misc_off = 0;  // predictor-gradient handles: d loss / d FiLM rows [max_batch][dfilm_R] of the last call (misc region, floats)
   int dfilm_R = 0;
+  size_t film_misc_off = 0;  // FiLM rows [max_batch][film_R] of the last forward, the `film` op's output (misc region, floats); film_R = 0: none
+  int film_R = 0;
   std::shared_ptr<void> keepalive;  // schedule builder (resolves arena/weight offsets for the ops)
 };
 
