@@ -28,6 +28,11 @@ output is then what `sample_vqvae_uncond.py --whole-file` writes for the file wi
 of K speakers that depends on the seed and the directory's name alone; the mapping goes to `out_dir/pseudo_voices.tsv` (a label map this
 script reads back).  A file's output then depends on (checkpoint, flags, --seed, its directory's name, its global id) only, and is what
 `sample_vqvae.py --whole-file --voice <the spec>` writes for the file with id 0.
+
+`--strength S` and `--keep-pauses DB` (with `--min-pause`, `--pause-guard`, `--no-skip-kept`) are sample_vqvae.py's: the conversion
+starts from the noised input, and the pauses of every recording -- runs of 10 ms frames at or below DB dBFS -- come out as they went
+in, bit for bit.  Windows that lie in a pause whole are left out of the forwards, which changes no output
+bit; the final line then also reports the seconds kept and the windows skipped.
 """
 import argparse
 import os
@@ -42,7 +47,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from vq_voice_swap_amd import VQVAE, EncoderPredictor  # noqa: E402
 from vq_voice_swap_amd.audio import ChunkReader, ChunkWriter  # noqa: E402
-from vq_voice_swap_amd.corpus import add_guidance_flags, deal_packs, guided, list_files, make_packs, read_label_map, top_directory  # noqa: E402
+from vq_voice_swap_amd.corpus import (add_guidance_flags, add_pause_flags, check_pause_flags, deal_packs, guided, list_files, make_packs,  # noqa: E402
+                                      pause_settings, read_label_map, skip_kept, top_directory)
 from vq_voice_swap_amd.dataset import build_file_index  # noqa: E402
 from vq_voice_swap_amd.eval_pass import close_ranks, local_device, open_ranks  # noqa: E402
 from vq_voice_swap_amd.longform import plan_windows  # noqa: E402
@@ -87,7 +93,14 @@ def parse_args(argv=None):
                         help="the voice every file is converted to: a label, a blend `3:0.7,251:0.3`, a vector file `@voice.npy`")
     target.add_argument("--anonymize", type=int, default=argparse.SUPPRESS, metavar="K",
                         help="every top-level directory gets a pseudo-voice blended of K speakers, listed in out_dir/pseudo_voices.tsv")
+    # ... and --strength and the pause flags, likewise
+    parser.add_argument("--strength", type=float, default=argparse.SUPPRESS,
+                        help="in (0, 1]: below 1 the conversion starts from the noised input and runs the last ceil(S * steps) steps")
+    add_pause_flags(parser)
     args = parser.parse_args(argv)
+    if not 0.0 < strength_of(args) <= 1.0:
+        parser.error("--strength must lie in (0, 1]")
+    check_pause_flags(parser, args)
     if voice_of(args) is not None:
         try:
             parse_voice(args.voice)
@@ -112,6 +125,24 @@ def voice_of(args):
 
 def anonymize_of(args):
     return getattr(args, "anonymize", None)
+
+
+def strength_of(args) -> float:
+    return getattr(args, "strength", 1.0)
+
+
+def keeps_source(args) -> bool:
+    """Whether the run hands the recordings themselves to the decoder: --strength below 1 or --keep-pauses."""
+    return strength_of(args) < 1.0 or getattr(args, "keep_pauses", None) is not None
+
+
+def summary(args, totals, seconds: float) -> str:
+    """The final line; with --strength or the pause flags it also says what was kept and skipped."""
+    line = (f"{int(totals[0])} files written, {int(totals[1])} skipped: {totals[2] / SAMPLE_RATE:.1f} s of audio, {int(totals[3])} windows, "
+            f"{int(totals[4])} packs in {seconds:.1f} s")
+    if keeps_source(args) or hasattr(args, "no_skip_kept"):
+        line += f", kept {totals[5] / SAMPLE_RATE:.1f} s, skipped {int(totals[6])} of {int(totals[3])} windows"
+    return line
 
 
 def out_path(out_dir: str, rel: str) -> str:
@@ -159,11 +190,12 @@ def read_wave(path: str, encoding: str):
 
 
 def convert_pack(args, model, enc_pred, device, files, labels, pack, window: int, hop: int):
-    """One pack of consecutive ids -> (files written, files skipped, samples, windows, decode calls).  A file that cannot be read
-    leaves a gap in the ids, so the rest of the pack is decoded as runs of consecutive ids (`make_packs` on what was read)."""
+    """One pack of consecutive ids -> (files written, files skipped, samples, windows, decode calls, samples kept, windows skipped).
+    A file that cannot be read leaves a gap in the ids, so the rest of the pack is decoded as runs of consecutive ids (`make_packs` on
+    what was read)."""
     waves = {i: w for i in pack if (w := read_wave(os.path.join(args.data_dir, files[i][0]), args.encoding)) is not None}
     got = sorted(waves)
-    written = samples = windows = calls = 0
+    written = samples = windows = calls = kept = skipped = 0
     counts = [plan_windows(waves[i].size, window, hop)[0] for i in got]
     for run in make_packs(counts, max(args.pack_windows, max(counts, default=1)), got):
         batch = [torch.from_numpy(waves[i][None, None]).to(device) for i in run]
@@ -176,6 +208,10 @@ def convert_pack(args, model, enc_pred, device, files, labels, pack, window: int
         else:  # voice specs: one vector per recording, made on the device (specs name speakers without the null label's offset)
             target = None
             guide_kw["vectors"] = voice_vectors(model.predictor, [labels[i] for i in run], label_offset=1 if guided(args) else 0)
+        stats = {}
+        if keeps_source(args):
+            guide_kw.update(sources=batch, strength=strength_of(args), keep_pauses=pause_settings(args, SAMPLE_RATE), skip_kept=skip_kept(args),
+                            stats=stats)
         outs = decode(codes, target, counts=run_counts, num_samples=[b.shape[-1] for b in batch], window=window, hop=hop,
                       steps=args.sample_steps, constrain=True, seed=args.seed, clip_offset=run[0], enc_pred=enc_pred,
                       enc_pred_scale=args.enc_pred_scale, window_batch=args.window_batch, sampler=args.sampler, eta=args.eta, **guide_kw)
@@ -192,7 +228,9 @@ def convert_pack(args, model, enc_pred, device, files, labels, pack, window: int
             samples += out.shape[-1]
         windows += sum(run_counts)
         calls += 1
-    return written, len(pack) - len(got), samples, windows, calls
+        kept += stats.get("kept_samples", 0)
+        skipped += stats.get("skipped_windows", 0)
+    return written, len(pack) - len(got), samples, windows, calls, kept, skipped
 
 
 def main(argv=None):
@@ -233,9 +271,10 @@ def main(argv=None):
         enc_pred.set_precision(args.precision)
 
     start = time.time()
-    totals = np.zeros(5, dtype=np.int64)  # written, skipped, samples, windows, packs
+    totals = np.zeros(7, dtype=np.int64)  # written, skipped, samples, windows, packs, samples kept, windows skipped
     for pack in deal_packs(packs, rank, world):
-        totals += np.array(convert_pack(args, model, enc_pred, device, files, labels, pack, window, hop), dtype=np.int64)
+        done = np.array(convert_pack(args, model, enc_pred, device, files, labels, pack, window, hop), dtype=np.int64)
+        totals[:len(done)] += done
     if world > 1:
         import torch.distributed as dist
 
@@ -244,8 +283,7 @@ def main(argv=None):
         if rank == 0:
             totals = np.sum(gathered, axis=0)
     if rank == 0:
-        print(f"{int(totals[0])} files written, {int(totals[1])} skipped: {totals[2] / SAMPLE_RATE:.1f} s of audio, {int(totals[3])} windows, "
-              f"{int(totals[4])} packs in {time.time() - start:.1f} s")
+        print(summary(args, totals, time.time() - start))
     close_ranks(world)
     return totals
 

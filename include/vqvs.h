@@ -522,6 +522,43 @@ int vqvs_keep_region(float* d_x, const float* d_x0, const uint8_t* d_keep, const
 int vqvs_keep_region_windows(float* d_x, float* d_windows, const float* d_x0, const uint8_t* d_keep, const float* d_noise,
                              const float* d_alpha, int n, int W, int H, float noise_scale, uint64_t seed, uint64_t clip, uint32_t index,
                              void* stream);
+/* The same on a PACK of R such states in the geometry of "Packed window steps": d_first [R + 1]; the long arrays d_x, d_x0, d_keep (or
+ * NULL) and d_noise (or NULL) hold the rows end to end, recording r at off_r = first[r] * H + r * V; d_windows [N,W] or NULL; ONE
+ * d_alpha.  Recording r's slices of d_x and d_windows are EXACTLY what vqvs_keep_region_windows writes for (n = n_r, clip = clip + r)
+ * on recording r's slices, bit for bit: the same coefficients, drawn noise philox_normal4(seed, quad = (p - off_r) / 4, clip + r,
+ * index, stream 3).  A kept sample is written to d_x and to each window copy that covers it inside its own recording only -- the last
+ * window of recording r and the first of r + 1 are not an overlap --, and a sample outside the mask is not written.  N is read on the
+ * device; the grid is fixed and strides over the pack, and the table is clamped as the packed steps clamp it: a table that is not one
+ * of prefix sums gives wrong samples, never an access outside N * H + R * V samples or N windows.
+ * VQVS_ERR_ARG before the device is touched: every rule of vqvs_keep_region_windows on (W, H, noise_scale, NULL pointers); R outside
+ * 1..65535; NULL d_first; and its aliasing rules (d_first among the inputs), checked over the R * W samples a pack holds at the least. */
+int vqvs_keep_region_windows_packed(float* d_x, float* d_windows, const float* d_x0, const uint8_t* d_keep, const float* d_noise,
+                                    const float* d_alpha, const int32_t* d_first, int R, int W, int H, float noise_scale, uint64_t seed,
+                                    uint64_t clip, uint32_t index, void* stream);
+/* ---- Pauses (handle-less; the reference has no counterpart) ----
+ * The mask of the samples of a pack's source rows that lie in a pause, for vqvs_keep_region_windows_packed.  Integer arithmetic
+ * throughout, as in vqvs_pitch_distance: the mask equals its definition bit for bit, and a recording's mask does not depend on R,
+ * on its place in the pack or on the run.
+ *   d_x [N * H + R * V] f32: the padded source rows in the layout of "Packed window steps" (the zero padding is part of a row)
+ *   d_keep, same layout, uint8: fully written with 0 or 1.   d_counts [R,2] int64 or NULL: kept samples and pauses per recording
+ *   frame: samples per frame, a multiple of 4 in 4..4096; thr: energy per sample, 0..2^30; min_frames 1..2^20; guard_frames 0..2^20
+ * Per recording row of L = n_r * H + V samples: q[n] = clamp(rint(x[n] * 32768), -32768, 32767), NaN -> 0 (the sample rule of
+ * vqvs_pitch_distance).  Frame f covers [f * frame, min((f + 1) * frame, L)) and holds c_f samples; E_f = sum q^2; the frame is
+ * QUIET iff E_f <= thr * c_f.  A PAUSE is a maximal run of quiet frames at least min_frames long; its kept part is the run less
+ * guard_frames at each end that touches a loud frame (an end at the row's start or end is not trimmed); keep[n] = 1 iff n's frame
+ * lies in a kept part.  Equivalently, with left(f) the last loud frame <= f or -1 and right(f) the first loud frame >= f or F, frame
+ * f is kept iff it is quiet, right - left - 1 >= min_frames, (left < 0 or f - left > guard) and (right >= F or right - f > guard).
+ * N is read on the device and the table clamped as above; the per-(device, stream) scratch buffer is leased at
+ * 8 * (min(65535 H + R V, 2^31) / (256 frame) + R + 1) bytes.  No floating-point atomics.
+ * VQVS_ERR_ARG before the device is touched: NULL d_x, d_keep or d_first; R outside 1..65535; the rules on (W, H) above; frame, thr,
+ * min_frames or guard_frames outside their ranges; d_keep or d_counts overlapping d_x, d_first or each other (over R * W samples). */
+int vqvs_pause_mask(const float* d_x, uint8_t* d_keep, int64_t* d_counts, const int32_t* d_first, int R, int W, int H, int frame,
+                    int64_t thr, int min_frames, int guard_frames, void* stream);
+/* d_out [N] uint8: out[b] = 1 iff all W bytes of window b of the mask d_keep (any mask in the layout above) are non-zero -- a window
+ * whose every sample the keep region overwrites after every step, so that its forward cannot reach the result.
+ * VQVS_ERR_ARG before the device is touched: NULL d_keep, d_out or d_first; R outside 1..65535; the rules on (W, H); d_out overlapping
+ * d_keep or d_first. */
+int vqvs_windows_kept(const uint8_t* d_keep, uint8_t* d_out, const int32_t* d_first, int R, int W, int H, void* stream);
 /* x_T ~ N(0,1) from the same counter-based generator (replaces torch.randn, sample_diffusion.py:86) */
 int vqvs_randn(float* d_out, int B, int T, uint64_t seed, uint64_t clip_offset, uint32_t stream_id, void* stream);
 

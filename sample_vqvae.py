@@ -8,6 +8,9 @@ sample_vqvae.py (same flags and positionals; reference sample_vqvae.py:76-92): r
 `--source-label L` it starts from `VQVAE.invert` of the input under its own codes and label L instead of from a fresh draw.
 `--keep START:END` (seconds, repeatable) leaves those ranges of the input as they are and converts the rest around them;
 `--strength S` below 1 starts from the noised input instead of from pure noise.  Both work with either sampler and with `--whole-file`.
+`--keep-pauses DB` leaves the pauses of the input as they are as well: runs of at least `--min-pause` seconds of 10 ms frames at or
+below DB dBFS, less `--pause-guard` seconds at each end that touches speech (vq_voice_swap_amd/pauses.py).  With `--whole-file` the
+windows that lie in a kept region whole are left out of the forwards (`--no-skip-kept` runs them; the output is the same).
 `--voice SPEC` in place of `--label` names the target as a voice spec (vq_voice_swap_amd/speakers.py): "3:0.7,251:0.3" blends speakers,
 "@voice.npy" is a vector fitted to a recording by `enroll_speaker.py --input-file`.  `--voice-at SEC:SPEC` (two or more, with
 `--whole-file`) moves the voice along the file: each window takes the voice at its centre, interpolated between the points.
@@ -27,6 +30,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from vq_voice_swap_amd import VQVAE, EncoderPredictor  # noqa: E402
 from vq_voice_swap_amd.audio import ChunkReader, ChunkWriter, keep_mask, parse_keep_range  # noqa: E402
+from vq_voice_swap_amd.corpus import add_pause_flags, check_pause_flags, pause_settings, skip_kept  # noqa: E402
+from vq_voice_swap_amd.pauses import pause_mask  # noqa: E402
 from vq_voice_swap_amd.speakers import as_entries, morph_vectors, parse_voice, voice_vectors  # noqa: E402
 
 
@@ -130,8 +135,10 @@ def target_kwargs(args, model, device, label_offset: int = 0, windows=None):
 def parse_args(argv=None):
     parser = arg_parser(sampler_flags=True, keep_flags=True)
     add_voice_flags(parser)
+    add_pause_flags(parser)  # (--keep-pauses / --min-pause / --pause-guard / --no-skip-kept join here, as the voice flags do)
     args = parser.parse_args(argv)
     check_voice_flags(parser, args)
+    check_pause_flags(parser, args)
     if args.sampler != "ddim" and args.eta:
         parser.error("--eta belongs to --sampler ddim (ddpm has its own variance, dpmpp is deterministic)")
     if args.eta < 0:
@@ -142,8 +149,8 @@ def parse_args(argv=None):
         parser.error(str(e))
     if not 0.0 < args.strength <= 1.0:
         parser.error("--strength must lie in (0, 1]")
-    if args.source_label is not None and (args.keep or args.strength < 1):
-        parser.error("--source-label starts from the inverted input: it cannot be combined with --keep or --strength")
+    if args.source_label is not None and (args.keep or args.strength < 1 or hasattr(args, "keep_pauses")):
+        parser.error("--source-label starts from the inverted input: it cannot be combined with --keep, --keep-pauses or --strength")
     if args.source_label is not None:
         if args.sampler != "ddim":
             parser.error("--source-label needs --sampler ddim (the inversion is the DDIM step run backwards)")
@@ -155,14 +162,23 @@ def parse_args(argv=None):
 
 
 def source_kwargs(args, wave: torch.Tensor):
-    """decode's source / keep / strength keywords for the input `wave` [1,1,N]: nothing unless --keep or --strength asks."""
-    if not args.keep and args.strength == 1.0:
+    """decode's source / keep / strength keywords for the input `wave` [1,1,N]: nothing unless --keep, --keep-pauses or --strength
+    asks.  With --whole-file the pauses are `decode_long`'s to find (keep_pauses= / skip_kept=, on the padded row); a clip's are found
+    here -- a pack of one recording of one window, without overlap -- and OR-ed into the mask."""
+    pauses = pause_settings(args, args.sample_rate)
+    if not args.keep and args.strength == 1.0 and pauses is None:
         return {}
     kw = dict(source=wave, strength=args.strength)
     if args.keep:
         mask = keep_mask(args.keep, wave.shape[-1], args.sample_rate)
         print(f"keeping {mask.mean():.1%} of the input ({int(mask.sum())} of {mask.size} samples)")
         kw["keep"] = torch.from_numpy(mask[None, None]).to(wave.device)
+    if pauses is not None and args.whole_file:
+        kw.update(keep_pauses=pauses, skip_kept=skip_kept(args))
+    elif pauses is not None:
+        found = pause_mask(wave, [1], wave.shape[-1], wave.shape[-1], **pauses)
+        print(f"keeping {float(found.float().mean()):.1%} of the input as pauses")
+        kw["keep"] = found if "keep" not in kw else torch.bitwise_or(kw["keep"].to(torch.uint8), found)
     return kw
 
 

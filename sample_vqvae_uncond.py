@@ -10,7 +10,8 @@ batch only lines up when both are non-zero, vq_vae.py:188-203).  `--whole-file`,
 `--window-batch`, `--keep` and `--strength` are sample_vqvae.py's, with its meanings and defaults: the whole input through
 `encode_long` / `decode_long_uncond_guidance`, regions of the input left as they are, a start from the noised input.  `--schedule`
 works with all of them (every sampling loop takes it).  `--voice SPEC` and `--voice-at SEC:SPEC` are sample_vqvae.py's too; their
-specs name speakers as `--label` does here, without the null label's offset.
+specs name speakers as `--label` does here, without the null label's offset.  `--keep-pauses`, `--min-pause`, `--pause-guard` and
+`--no-skip-kept` are sample_vqvae.py's as well.
 """
 import argparse
 import os
@@ -25,6 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from sample_vqvae import add_voice_flags, check_voice_flags, check_voice_labels, source_kwargs, target_kwargs  # noqa: E402
 from vq_voice_swap_amd import VQVAE  # noqa: E402
 from vq_voice_swap_amd.audio import ChunkReader, ChunkWriter, parse_keep_range, parse_time_schedule  # noqa: E402
+from vq_voice_swap_amd.corpus import add_pause_flags, check_pause_flags  # noqa: E402
 
 
 def arg_parser():
@@ -61,8 +63,10 @@ def arg_parser():
 def parse_args(argv=None):
     parser = arg_parser()
     add_voice_flags(parser)
+    add_pause_flags(parser)  # (sample_vqvae.py's --keep-pauses / --min-pause / --pause-guard / --no-skip-kept)
     args = parser.parse_args(argv)
     check_voice_flags(parser, args)
+    check_pause_flags(parser, args)
     if args.sampler != "ddim" and args.eta:
         parser.error("--eta belongs to --sampler ddim (ddpm has its own variance, dpmpp is deterministic)")
     if args.eta < 0:

@@ -18,6 +18,7 @@ from .encoder_predictor import EncoderPredictor
 from .enroll import ClassifierEnroller, NullLabelEnroller, SpeakerEnroller
 from .longform import plan_pack, plan_windows
 from .losses import LossTracker, classification_scores, speaker_search_losses
+from .pauses import pause_mask, threshold_energy, windows_kept
 from .pitch import PitchDistance
 from .speakers import load_voice, morph_vectors, parse_voice, pseudo_voice, save_voice, speaker_mix, voice_vectors
 from .spectral import SpectralDistance, spectral_constants
@@ -34,4 +35,5 @@ __all__ = [
     "SpectralDistance", "spectral_constants", "PitchDistance", "SpeakerEnroller", "ClassifierEnroller",
     "AlignedDistance", "dtw_distance", "NullLabelEnroller", "guidance_mix",
     "parse_voice", "voice_vectors", "morph_vectors", "pseudo_voice", "save_voice", "load_voice", "speaker_mix",
+    "pause_mask", "threshold_energy", "windows_kept",
 ]

@@ -78,6 +78,7 @@ EXPORTS = [
     "vqvs_unet_embed_grad", "vqvs_embed_adamw", "vqvs_debug_read_dfilm", "vqvs_head_xent_grad", "vqvs_head_adamw",
     "vqvs_mel_cepstra", "vqvs_dtw_distance", "vqvs_guidance_mix", "vqvs_unet_forward_vec", "vqvs_speaker_mix",
     "vqvs_debug_read_film", "vqvs_debug_gelu",
+    "vqvs_keep_region_windows_packed", "vqvs_pause_mask", "vqvs_windows_kept",
 ]
 
 _lib = None
@@ -162,6 +163,9 @@ def lib():
     L.vqvs_dpmpp_step_windows_packed.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, u32, vp]
     L.vqvs_keep_region.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, u64, u64, u32, vp]
     L.vqvs_keep_region_windows.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, u64, u64, u32, vp]
+    L.vqvs_keep_region_windows_packed.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, u64, u64, u32, vp]
+    L.vqvs_pause_mask.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i64, i32, i32, vp]
+    L.vqvs_windows_kept.argtypes = [vp, vp, vp, i32, i32, i32, vp]
     L.vqvs_ddpm_mean.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
     L.vqvs_ddpm_guided_eps.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, u32, vp]
     L.vqvs_guidance_mix.argtypes = [vp, vp, i32, i64, i32, f32, f32, vp]

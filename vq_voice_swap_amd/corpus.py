@@ -41,6 +41,58 @@ def guided(args) -> bool:
     return bool(getattr(args, "guide_label_scale", 0.0)) or bool(getattr(args, "guide_vq_scale", 0.0))
 
 
+PAUSE_FRAME_SECONDS = 0.01  # the detector's frame on the command line: 10 ms
+
+
+def add_pause_flags(parser) -> None:
+    """`--keep-pauses` / `--min-pause` / `--pause-guard` / `--no-skip-kept` of convert_dataset.py and the sample_vqvae scripts.  A flag
+    that is not given leaves no attribute behind (`pause_settings` and `skip_kept` read them), so the namespace of a run without
+    them is what it was."""
+    import argparse
+
+    parser.add_argument("--keep-pauses", type=float, default=argparse.SUPPRESS, metavar="DB",
+                        help="leave the pauses of the input as they are: runs of 10 ms frames at or below this level in dBFS (e.g. -50)")
+    parser.add_argument("--min-pause", type=float, default=argparse.SUPPRESS, metavar="SECONDS", help="the shortest pause that is kept (default 0.3)")
+    parser.add_argument("--pause-guard", type=float, default=argparse.SUPPRESS, metavar="SECONDS",
+                        help="converted anyway at each end of a pause that touches speech (default 0.05)")
+    parser.add_argument("--no-skip-kept", action="store_true", default=argparse.SUPPRESS,
+                        help="run the predictor on windows that are kept whole as well (the output is the same bit for bit)")
+
+
+def check_pause_flags(parser, args) -> None:
+    """The pause flags of a parsed command line: the level, the two lengths, and -- the detector is defined on linear samples -- no
+    --keep-pauses with --encoding ulaw."""
+    import math
+
+    db = getattr(args, "keep_pauses", None)
+    if db is None:
+        if hasattr(args, "min_pause") or hasattr(args, "pause_guard"):
+            parser.error("--min-pause and --pause-guard belong to --keep-pauses")
+        return
+    if not math.isfinite(db) or db > 0:
+        parser.error("--keep-pauses takes a level in dBFS, at or below 0")
+    if getattr(args, "encoding", "linear") == "ulaw":
+        parser.error("--keep-pauses is defined on linear samples: it cannot be combined with --encoding ulaw")
+    if not 0 < getattr(args, "min_pause", 0.3) <= 3600 or not 0 <= getattr(args, "pause_guard", 0.05) <= 3600:
+        parser.error("--min-pause must be positive and --pause-guard not negative (seconds, an hour at the most)")
+
+
+def pause_settings(args, sample_rate: int) -> Optional[dict]:
+    """The detector's settings (`pauses.pause_mask`'s keywords) of a parsed command line, or None without --keep-pauses."""
+    db = getattr(args, "keep_pauses", None)
+    if db is None:
+        return None
+    frame = round(PAUSE_FRAME_SECONDS * sample_rate)
+    if frame < 4 or frame % 4:
+        raise SystemExit(f"--keep-pauses: a 10 ms frame at {sample_rate} Hz is {frame} samples, not a multiple of 4")
+    return dict(threshold_db=float(db), frame=frame, min_pause_frames=max(1, round(getattr(args, "min_pause", 0.3) / PAUSE_FRAME_SECONDS)),
+                guard_frames=round(getattr(args, "pause_guard", 0.05) / PAUSE_FRAME_SECONDS))
+
+
+def skip_kept(args) -> bool:
+    return not getattr(args, "no_skip_kept", False)
+
+
 def top_directory(rel_path: str) -> str:
     return rel_path.replace("\\", "/").split("/", 1)[0]
 

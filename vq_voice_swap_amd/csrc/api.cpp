@@ -649,6 +649,48 @@ int vqvs_keep_region_windows(float* d_x, float* d_windows, const float* d_x0, co
                                  reinterpret_cast<hipStream_t>(stream));
 }
 
+int vqvs_keep_region_windows_packed(float* d_x, float* d_windows, const float* d_x0, const uint8_t* d_keep, const float* d_noise,
+                                    const float* d_alpha, const int32_t* d_first, int R, int W, int H, float noise_scale, uint64_t seed,
+                                    uint64_t clip, uint32_t index, void* stream) {
+  if (!d_x) VQVS_FAIL(VQVS_ERR_ARG, "d_x must be non-NULL");
+  if (!d_x0) VQVS_FAIL(VQVS_ERR_ARG, "d_x0 must be non-NULL");
+  if (!d_alpha) VQVS_FAIL(VQVS_ERR_ARG, "d_alpha must be non-NULL");
+  int64_t least;
+  if (int e = check_pack_geometry(d_first, R, W, H, &least)) return e;
+  if (int e = check_keep_args(d_x, d_windows, d_x0, d_keep, d_noise, d_alpha, least, 1, least, noise_scale)) return e;
+  if (int e = check_disjoint({{"d_x", d_x, least * 4}, {"d_windows", d_windows, least * 4}}, {{"d_first", d_first, ((int64_t)R + 1) * 4}})) return e;
+  return run_keep_region_packed(d_x, d_windows, d_x0, d_keep, d_noise, d_alpha, d_first, R, W, H, noise_scale, seed, clip, index,
+                                reinterpret_cast<hipStream_t>(stream));
+}
+
+int vqvs_pause_mask(const float* d_x, uint8_t* d_keep, int64_t* d_counts, const int32_t* d_first, int R, int W, int H, int frame,
+                    int64_t thr, int min_frames, int guard_frames, void* stream) {
+  if (!d_x) VQVS_FAIL(VQVS_ERR_ARG, "d_x must be non-NULL");
+  if (!d_keep) VQVS_FAIL(VQVS_ERR_ARG, "d_keep must be non-NULL");
+  int64_t least;
+  if (int e = check_pack_geometry(d_first, R, W, H, &least)) return e;
+  if (frame < 4 || frame > 4096 || frame % 4) VQVS_FAIL(VQVS_ERR_ARG, "frame=%d must be a multiple of 4 in 4..4096", frame);
+  if (thr < 0 || thr > ((int64_t)1 << 30)) VQVS_FAIL(VQVS_ERR_ARG, "thr=%lld outside 0..2^30", (long long)thr);
+  if (min_frames < 1 || min_frames > (1 << 20)) VQVS_FAIL(VQVS_ERR_ARG, "min_frames=%d outside 1..2^20", min_frames);
+  if (guard_frames < 0 || guard_frames > (1 << 20)) VQVS_FAIL(VQVS_ERR_ARG, "guard_frames=%d outside 0..2^20", guard_frames);
+  if (int e = check_disjoint({{"d_keep", d_keep, least}, {"d_counts", d_counts, (int64_t)R * 16}},
+                             {{"d_x", d_x, least * 4}, {"d_first", d_first, ((int64_t)R + 1) * 4}}))
+    return e;
+  ScratchLease lease;
+  if (int e = scratch_get(pause_mask_scratch_bytes(R, W, H, frame), stream, lease)) return e;
+  return run_pause_mask(d_x, d_keep, reinterpret_cast<long long*>(d_counts), d_first, lease.p, R, W, H, frame, (long long)thr, min_frames,
+                        guard_frames, reinterpret_cast<hipStream_t>(stream));
+}
+
+int vqvs_windows_kept(const uint8_t* d_keep, uint8_t* d_out, const int32_t* d_first, int R, int W, int H, void* stream) {
+  if (!d_keep) VQVS_FAIL(VQVS_ERR_ARG, "d_keep must be non-NULL");
+  if (!d_out) VQVS_FAIL(VQVS_ERR_ARG, "d_out must be non-NULL");
+  int64_t least;
+  if (int e = check_pack_geometry(d_first, R, W, H, &least)) return e;
+  if (int e = check_disjoint({{"d_out", d_out, R}}, {{"d_keep", d_keep, least}, {"d_first", d_first, ((int64_t)R + 1) * 4}})) return e;
+  return run_windows_kept(d_keep, d_out, d_first, R, W, H, reinterpret_cast<hipStream_t>(stream));
+}
+
 int vqvs_ddpm_mean(const float* d_x_t, const float* d_eps, const float* d_alpha_t, const float* d_alpha_prev, float* d_mean, int B, int T,
                    void* stream) {
   if (!d_x_t || !d_eps || !d_alpha_t || !d_alpha_prev || !d_mean) VQVS_FAIL(VQVS_ERR_ARG, "NULL argument");

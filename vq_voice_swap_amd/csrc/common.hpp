@@ -79,6 +79,14 @@ __device__ __forceinline__ float gelu_grad_f(float v) {
 // Packed-math variants (v_pk_fma_f32 / v_pk_mul_f32 process two floats per lane per issue; a plain
 // wave64 VALU instruction occupies the SIMD for 4 cycles on gfx950, so the prologue is written on
 // float2 throughout).
+// A float sample as the 16 bits a WAV would hold: clamp(rint(x * 32768), -32768, 32767), NaN -> 0 (the sample rule of
+// vqvs_pitch_distance and vqvs_pause_mask)
+__device__ __forceinline__ int quantise(float x) {
+  const float p = x * 32768.0f;  // exact (a power of two); +-inf stays +-inf and saturates below
+  if (!(p == p)) return 0;       // NaN
+  return (int)fminf(fmaxf(rintf(p), -32768.0f), 32767.0f);
+}
+
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 splat2(float x) { return f32x2{x, x}; }
 __device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }

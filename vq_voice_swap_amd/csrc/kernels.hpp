@@ -401,6 +401,16 @@ size_t pitch_distance_scratch_bytes(int B, int T, int hop);
 int run_pitch_distance(const float* a, const float* b, double* period_a, double* period_b, long long* counts, double* sums, void* scratch,
                        int B, int T, int window, int hop, int tau_min, int tau_max, double threshold, hipStream_t st);
 
+// ----------------------------------------------------------------------------------
+// Pauses (pause_kernels.hip): the uint8 mask of the samples of a pack's source rows that lie in a pause, per-recording counts (kept
+// samples, pauses; may be nullptr), and the windows a mask covers whole.  The pack is that of StepLayout::PACK; scratch holds
+// pause_mask_scratch_bytes(R, W, H, frame) bytes of per-chunk carries.
+// ----------------------------------------------------------------------------------
+size_t pause_mask_scratch_bytes(int R, int W, int H, int frame);
+int run_pause_mask(const float* x, uint8_t* keep, long long* counts, const int* first, void* scratch, int R, int W, int H, int frame,
+                   long long thr, int min_frames, int guard_frames, hipStream_t st);
+int run_windows_kept(const uint8_t* keep, uint8_t* out, const int* first, int R, int W, int H, hipStream_t st);
+
 // layout changes at the library boundary (reference tensors are NCT float32)
 int launch_nct_to_ntc(const float* in, void* out, float* stats, int B, int C, int L, int ntiles, int precision, hipStream_t st);
 int launch_ntc_to_nct(const void* in, float* out, int B, int C, int L, int in_precision, hipStream_t st);

@@ -41,12 +41,7 @@ struct PitchArgs {
   double threshold;
 };
 
-__device__ __forceinline__ int quantise(float x) {
-  const float p = x * 32768.0f;  // exact (a power of two); +-inf stays +-inf and saturates below
-  if (!(p == p)) return 0;       // NaN
-  return (int)fminf(fmaxf(rintf(p), -32768.0f), 32767.0f);
-}
-
+// (quantise: common.hpp, the sample rule shared with pause_kernels.hip)
 // Steps 5 and 6 for one row: y[tau] holds the bits of d'(tau), t the first lag under the threshold.  Every operation is one float64
 // operation.
 __device__ __forceinline__ double walk_and_refine(const unsigned long long* y, int t, int tau_max) {

@@ -7,6 +7,7 @@
 // kernel takes one StepArgs by value; x0sum_kernel / x0sum_packed_kernel, which read five of its members, form the sums of CONSTRAIN.  The keep kernels come on clips
 // and on windows too and share quad_windows and store_quad with the steps.
 #include "kernels.hpp"
+#include "pack_table.hpp"
 #include "philox.hpp"
 #include "sampler_kernels.hpp"
 
@@ -567,53 +568,7 @@ __global__ __launch_bounds__(256) void step_windows_kernel(StepArgs a, int n, in
 // ---------------------------------------------------------------------------------
 constexpr int PACK_GRID = 2048;  // 256 CUs x 8 workgroups of 256: every CU full, the rest of a long pack in further strides
 
-struct PackRow {
-  int r, fb, n, q;  // recording, its first window, its window count, the quad's index in the recording's own row
-  bool ok;          // the quad lies in that row: a quad that a malformed table puts nowhere is left alone
-  size_t off;       // the recording's first sample in the long arrays
-};
-struct PackTable {
-  const int* first;
-  int R, N, H, V;
-  __device__ __forceinline__ int at(int i) const { return i <= 0 ? 0 : i >= R ? N : min(max(first[i], 0), N); }
-  __device__ __forceinline__ int64_t off(int i, int f) const { return (int64_t)f * H + (int64_t)i * V; }
-  __device__ __forceinline__ int64_t total() const { return min(off(R, N), ((int64_t)1 << 31) - 4); }
-};
-__device__ __forceinline__ PackTable pack_table(const int* first, int R, int W, int H) {
-  return PackTable{first, R, min(max(first[R], 1), 65535), H, W - H};
-}
-// p0: a position at or before p that is uniform over the workgroup (its first thread's)
-__device__ __forceinline__ PackRow pack_row(const PackTable& t, int64_t p0, int64_t p) {
-  int lo = 0, hi = t.R;  // off(lo) <= p0 < off(hi)
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (t.off(mid, t.at(mid)) <= p0) lo = mid; else hi = mid;
-  }
-  int r = lo, f0 = t.at(r), f1 = t.at(r + 1);
-  while (r + 1 < t.R && t.off(r + 1, f1) <= p) {
-    ++r;
-    f0 = f1;
-    f1 = t.at(r + 1);
-  }
-  PackRow w;
-  w.r = r;
-  w.n = f1 - f0;
-  w.fb = f0;
-  w.off = (size_t)t.off(r, f0);
-  const int64_t u = p - t.off(r, f0);
-  w.ok = w.n >= 1 && u >= 0 && u < (int64_t)w.n * t.H + t.V;  // (always, unless the table is not one of prefix sums)
-  w.q = (int)(u / 4);
-  return w;
-}
-// window b's recording: the last r with first[r] <= b (b uniform over the workgroup: scalar loads again)
-__device__ __forceinline__ int pack_window_row(const PackTable& t, int b) {
-  int lo = 0, hi = t.R;  // at(lo) <= b < at(hi)
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (t.at(mid) <= b) lo = mid; else hi = mid;
-  }
-  return lo;
-}
+// (PackTable, pack_row and pack_window_row: pack_table.hpp, shared with pause_kernels.hip)
 __device__ __forceinline__ const float* pack_shift(const float* p, size_t by) { return p ? p + by : nullptr; }
 __device__ __forceinline__ float* pack_shift(float* p, size_t by) { return p ? p + by : nullptr; }
 
@@ -752,6 +707,29 @@ __global__ __launch_bounds__(256) void keep_region_windows_kernel(float* x, floa
   const uint32_t mask = keep_quad(x0, keep, noise, (size_t)p, 4, aligned, k, noise_scale, seed, (uint32_t)q, clip, index, o);
   if (!mask) return;
   store_quad(x, win, p, quad_windows(p, n, W, H), [&](float* dst) { keep_store(dst, o, mask, aligned); });
+}
+
+// ... and on a PACK of such states (the walk of step_packed_kernel: a fixed grid strides over the pack, pack_row finds the quad's
+// recording).  x0, keep and noise are read at the quad's position in the pack; the noise is drawn at the quad's index in its own
+// row and at clip + r, and the quad goes to the row's own windows alone, so recording r's slices are what
+// keep_region_windows_kernel writes for (n_r, clip + r) on them.
+__global__ __launch_bounds__(256) void keep_region_packed_kernel(float* x, float* win, const float* x0, const uint8_t* keep,
+                                                                 const float* noise, const float* alpha, const int* first, int R, int W, int H,
+                                                                 bool aligned, float noise_scale, uint64_t seed, uint64_t clip, uint32_t index) {
+  const KeepCoef k = keep_coef(alpha[0]);
+  const PackTable t = pack_table(first, R, W, H);
+  const int64_t total = t.total();
+  for (int64_t p0 = (int64_t)blockIdx.x * 1024; p0 < total; p0 += (int64_t)gridDim.x * 1024) {
+    const int64_t p = p0 + threadIdx.x * 4;
+    if (p >= total) continue;
+    const PackRow w = pack_row(t, p0, p);
+    if (!w.ok) continue;
+    f32x4 o;
+    const uint32_t mask = keep_quad(x0, keep, noise, (size_t)p, 4, aligned, k, noise_scale, seed, (uint32_t)w.q, clip + w.r, index, o);
+    if (!mask) continue;
+    const int u = w.q * 4;
+    store_quad(x + w.off, pack_shift(win, (size_t)w.fb * W), u, quad_windows(u, w.n, W, H), [&](float* dst) { keep_store(dst, o, mask, aligned); });
+  }
 }
 
 // ---------------------------------------------------------------------------------
@@ -1056,6 +1034,16 @@ int run_keep_region_windows(float* x, float* windows, const float* x0, const uin
   const int quads = ((n - 1) * H + W) / 4;
   hipLaunchKernelGGL(keep_region_windows_kernel, dim3((quads + 255) / 256), dim3(256), 0, st, x, windows, x0, keep, noise, alpha, n, W, H,
                      aligned, noise_scale, seed, clip, index);
+  VQVS_HIP(hipGetLastError());
+  return 0;
+}
+
+int run_keep_region_packed(float* x, float* windows, const float* x0, const uint8_t* keep, const float* noise, const float* alpha,
+                           const int* first, int R, int W, int H, float noise_scale, uint64_t seed, uint64_t clip, uint32_t index,
+                           hipStream_t st) {
+  const bool aligned = keep_aligned(x, windows, x0, keep, noise);  // (every row starts a multiple of 4 samples into the pack)
+  hipLaunchKernelGGL(keep_region_packed_kernel, dim3(PACK_GRID), dim3(256), 0, st, x, windows, x0, keep, noise, alpha, first, R, W, H, aligned,
+                     noise_scale, seed, clip, index);
   VQVS_HIP(hipGetLastError());
   return 0;
 }

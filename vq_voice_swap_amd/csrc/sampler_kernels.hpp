@@ -39,6 +39,10 @@ int run_keep_region(float* x, const float* x0, const uint8_t* keep, const float*
                     uint64_t seed, uint64_t clip_offset, uint32_t index, hipStream_t st);
 int run_keep_region_windows(float* x, float* windows, const float* x0, const uint8_t* keep, const float* noise, const float* alpha, int n,
                             int W, int H, float noise_scale, uint64_t seed, uint64_t clip, uint32_t index, hipStream_t st);
+// ... and a pack of such states (first [R + 1] on the device, as in StepLayout::PACK): recording r at clip + r
+int run_keep_region_packed(float* x, float* windows, const float* x0, const uint8_t* keep, const float* noise, const float* alpha,
+                           const int* first, int R, int W, int H, float noise_scale, uint64_t seed, uint64_t clip, uint32_t index,
+                           hipStream_t st);
 int run_ddpm_mean(const float* x_t, const float* eps, const float* a_t, const float* a_prev, float* out, int B, int T, hipStream_t st);
 int run_ddpm_guided_eps(const float* x_t, const float* mean, const float* grad, const float* a_t, const float* a_prev, float* out,
                         int B, int T, uint32_t flags, hipStream_t st);

@@ -12,6 +12,9 @@ step and the step has the variance a single clip's has.
 is the same walk with the DDIM step `vqvs_ddim_step_windows`, `Diffusion.dpmpp_sample_windows` with the
 DPM-Solver++(2M) step `vqvs_dpmpp_step_windows` (section 3.12).
 
+Pauses (section 3.21): `pack_source=` / `pack_keep=` / `pack_start_step=` are the keep region of a pack, `skip=` leaves the windows that a
+mask covers whole out of the forwards, and `decode_long(_batch)(keep_pauses=, skip_kept=)` find the pauses (pauses.py) and do both.
+
 A corpus is converted in PACKS (section 3.17): with `counts=` the three loops run several recordings' rows laid end to end, their
 windows in one batch that fills the forwards, and the step is the `..._packed` entry point, which keeps the recordings apart.
 `VQVAE.encode_long_batch` / `decode_long_batch` are below as well; recording r of a pack is, bit for bit, what `decode_long` returns
@@ -87,6 +90,15 @@ def keep_windows_(x: torch.Tensor, windows: Optional[torch.Tensor], source: torc
     _native.check(_native.lib().vqvs_keep_region_windows(x.data_ptr(), _native._ptr(windows), source.data_ptr(), _native._ptr(keep), None,
                                                          alpha.data_ptr(), n, window, hop, 1.0, int(seed), int(clip_offset), int(index),
                                                          _native._stream_ptr()))
+
+
+def keep_pack_(x: torch.Tensor, windows: Optional[torch.Tensor], source: torch.Tensor, keep: Optional[torch.Tensor], alpha: torch.Tensor, *,
+               first: torch.Tensor, R: int, window: int, hop: int, seed: int, clip_offset: int, index: int) -> None:
+    """`vqvs_keep_region_windows_packed` IN PLACE on the rows x [total] of a pack and (unless None) on its window batch [N,1,window]:
+    `keep_windows_` on every recording's own slices, recording r keyed clip_offset + r, in one launch."""
+    _native.check(_native.lib().vqvs_keep_region_windows_packed(x.data_ptr(), _native._ptr(windows), source.data_ptr(), _native._ptr(keep), None,
+                                                                alpha.data_ptr(), first.data_ptr(), R, window, hop, 1.0, int(seed),
+                                                                int(clip_offset), int(index), _native._stream_ptr()))
 
 
 def start_windows(x_T_long: torch.Tensor, source, keep, alpha, *, start_step: int, n: int, window: int, hop: int, seed: int, clip_offset: int):
@@ -187,11 +199,26 @@ def _dpmpp_step_windows(rule, x, eps, grad, nz, a_t, a_to, x_to, next_windows, n
 class _Windows:
     """The state layout of the window loops for `Diffusion._sample`: the long row [Np], with its window batch [n,1,window] kept
     beside it.  The predictor and cond_fn see slices of at most `window_batch` windows, with `first=`; `fill` and `step` are the
-    rule's window forms above."""
+    rule's window forms above.  `skip` (bool [n], checked by `_check_skip`) names windows that are not predicted: the slices then
+    run over the ACTIVE windows, gathered, with `first=idx[0], rows=idx`, and the skipped rows of eps and grad stay zero."""
 
-    def __init__(self, rule, predictor: Callable, cond_fn: Optional[Callable], window: int, hop: int, window_batch: int, fill, step):
+    def __init__(self, rule, predictor: Callable, cond_fn: Optional[Callable], window: int, hop: int, window_batch: int, fill, step,
+                 skip: Optional[torch.Tensor] = None):
         self.rule, self.predictor, self.cond_fn, self.fill, self.step_windows = rule, predictor, cond_fn, fill, step
         self.window, self.hop, self.window_batch = window, hop, window_batch
+        self.skip, self.active = skip, None
+
+    def plan_skip(self, device) -> None:
+        """The slices of active windows as (first index, index tensor [m]); the tensors stay the same objects for the whole run (a
+        callee may key a cache by them).  None when no window is skipped."""
+        if self.skip is None:
+            return
+        if self.skip.numel() != self.n:
+            raise ValueError(f"skip must hold one entry per window ({self.n}), got {self.skip.numel()}")
+        idx = (~self.skip.to(device)).nonzero().reshape(-1)  # (one synchronisation per run)
+        if idx.numel() < self.n:
+            firsts = idx[::self.mb].tolist()
+            self.active = [(firsts[k], idx[a0:a0 + self.mb].contiguous()) for k, a0 in enumerate(range(0, idx.numel(), self.mb))]
 
     def rows(self, x_T_long) -> int:
         """The input checks; the tables hold one row per window of a slice."""
@@ -205,12 +232,14 @@ class _Windows:
             raise ValueError(f"window_batch={self.window_batch} must be at least 1")
         self.geom = self.n  # (what the step's entry point is told: `_entry`)
         self.mb = min(self.n, int(self.window_batch))
+        self.plan_skip(x_T_long.device)
         return self.mb
 
     def start(self, x_T_long, source, keep, alpha, **kw):
         x, self.windows = self.gather(x_T_long, source, keep, alpha, **kw)
-        self.eps = torch.empty_like(self.windows)
-        self.grad = torch.empty_like(self.windows) if self.cond_fn is not None and self.rule.name != "ddpm" else None
+        fresh = torch.empty_like if self.active is None else torch.zeros_like  # (rows of skipped windows: zero, filled once)
+        self.eps = fresh(self.windows)
+        self.grad = fresh(self.windows) if self.cond_fn is not None and self.rule.name != "ddpm" else None
         return x
 
     def gather(self, x_T_long, source, keep, alpha, **kw):
@@ -218,6 +247,8 @@ class _Windows:
 
     def predict(self, x, tables, i) -> None:
         self.st = _native._stream_ptr()  # (of this step: the slices' kernels and the step kernel)
+        if self.active is not None:
+            return self.predict_active(tables, i)
         for b0 in range(0, self.n, self.mb):
             m = min(self.mb, self.n - b0)
             xw = self.windows[b0:b0 + m]
@@ -226,6 +257,27 @@ class _Windows:
             if tuple(e.shape) != tuple(xw.shape):
                 raise ValueError(f"the predictor returned shape {tuple(e.shape)} for windows of shape {tuple(xw.shape)}")
             self.fill(self.rule, xw, e, tables, i, b0, self.cond_fn, self.eps, self.grad, self.st)
+
+    def predict_active(self, tables, i) -> None:
+        """`predict` under a skip list: each slice of active windows is gathered, predicted with `first=idx[0], rows=idx`, filled as a
+        batch of its own (the rule's `fill` at row 0 of [m,1,window] buffers, cond_fn bound to the slice), and its eps and grad rows
+        scattered back."""
+        for first, idx in self.active:
+            m = idx.numel()
+            xw = self.windows.index_select(0, idx)
+            e = self.predictor(xw, tables[0][i, :m], first=first, rows=idx)
+            _native.require_cuda(e)
+            if tuple(e.shape) != tuple(xw.shape):
+                raise ValueError(f"the predictor returned shape {tuple(e.shape)} for windows of shape {tuple(xw.shape)}")
+            cond = None
+            if self.cond_fn is not None:
+                def cond(x_, ts_, first=0, at=first, idx=idx):  # (`first` is the row in the slice's own buffers: 0)
+                    return self.cond_fn(x_, ts_, first=at, rows=idx)
+            eps, grad = torch.empty_like(xw), None if self.grad is None else torch.empty_like(xw)
+            self.fill(self.rule, xw, e, tables, i, 0, cond, eps, grad, self.st)
+            self.eps.index_copy_(0, idx, eps)
+            if grad is not None:
+                self.grad.index_copy_(0, idx, grad)
 
     def step(self, x, _, nz, tables, i, *, noise_scale, seed, clip_offset):
         if nz is not None:
@@ -249,8 +301,8 @@ class _Pack(_Windows):
     entry point (`_entry`), which keys recording r by clip_offset + r and blends nothing across recordings.  Only the geometry
     differs: the table instead of n, and the gather that starts the run."""
 
-    def __init__(self, counts: Sequence[int], *args):
-        super().__init__(*args)
+    def __init__(self, counts: Sequence[int], *args, **kwargs):
+        super().__init__(*args, **kwargs)
         self.counts = counts
 
     def rows(self, x_T_long) -> int:
@@ -265,29 +317,72 @@ class _Pack(_Windows):
         self.n, self.R, self.geom = first[-1], len(first) - 1, self
         self.first = torch.tensor(first, dtype=torch.int32, device=x_T_long.device)
         self.mb = min(self.n, int(self.window_batch))
+        self.plan_skip(x_T_long.device)
         return self.mb
 
-    def gather(self, x_T_long, source, keep, alpha, **kw):
+    def gather(self, x_T_long, source, keep, alpha, *, start_step, seed, clip_offset):
+        """`start_windows` on the pack's rows: x_T as it is, with the kept samples replaced, or the source noised to `start_step`."""
         x = x_T_long.detach().to(torch.float32).contiguous()
+        if source is not None and (start_step > 0 or keep is not None):
+            x = torch.empty_like(x) if start_step > 0 else x.clone()
+            with torch.cuda.device(x.device):
+                keep_pack_(x, None, source, None if start_step > 0 else keep, alpha, first=self.first, R=self.R, window=self.window,
+                           hop=self.hop, seed=seed, clip_offset=clip_offset, index=start_step)
         rows = [x[..., o:o + (c - 1) * self.hop + self.window] for o, c in zip(self.offsets, self.counts)]
         return x, torch.cat([gather_windows(r, self.window, self.hop) for r in rows])
 
+    def keep(self, x, source, keep, alpha, **kw) -> None:
+        keep_pack_(x, self.windows, source, keep, alpha, first=self.first, R=self.R, window=self.window, hop=self.hop, **kw)
 
-def _layout(counts, source, keep, start_step, *args):
-    """`_Windows` for one recording; with `counts` the `_Pack` of several, for which `source`, `keep` and `start_step` are not built
-    (vqvs_keep_region_windows has no packed form)."""
+
+def _check_skip(skip, keep, counts, window: int, hop: int):
+    """The `skip=` keyword of the window loops as a bool [n] tensor.  A window may be skipped only when the keep mask covers it
+    whole -- then every sample it covers is overwritten after every step, and its forward cannot reach the result.  One reduction
+    over the mask's windows, once per run, on whatever device the mask is on."""
+    if skip is None:
+        return None
+    if not torch.is_tensor(skip) or skip.dtype not in (torch.bool, torch.uint8) or skip.dim() != 1:
+        raise ValueError("skip must be a bool or uint8 tensor [n]: the windows not to predict")
+    if keep is None:
+        raise ValueError("skip= needs a keep mask: only a window whose every sample is kept may be skipped")
+    if keep.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"keep must be a bool or uint8 tensor, got {keep.dtype}")
+    flat = keep.detach().reshape(-1)
+    counts = [plan_windows(flat.numel(), window, hop)[0]] if counts is None else list(counts)
+    first, offsets, total = pack_layout(counts, window, hop)
+    if flat.numel() != total or skip.numel() != first[-1]:
+        raise ValueError(f"skip of {skip.numel()} windows and a keep mask of {flat.numel()} samples do not match {first[-1]} windows of {window} "
+                         f"every {hop} spanning {total} samples")
+    whole = torch.cat([flat[o:o + (c - 1) * hop + window].unfold(0, window, hop).ne(0).all(dim=1) for o, c in zip(offsets, counts)])
+    skip = skip.detach().ne(0).to(whole.device)
+    if bool((skip & ~whole).any()):
+        raise ValueError("skip= names a window that the keep mask does not cover whole: its forward would be missed")
+    return skip
+
+
+def _layout(counts, source, keep, start_step, pack, skip, *args):
+    """(layout, source, keep, start_step) of a window loop: `_Windows` for one recording with its `source`, `keep` and `start_step`; with
+    `counts` the `_Pack` of several, which takes them in pack layout as pack = (`pack_source`, `pack_keep`, `pack_start_step`) and
+    refuses the single-recording keywords.  `skip` is checked against the mask of either (`_check_skip`)."""
+    window, hop = args[3], args[4]
     if counts is None:
-        return _Windows(*args)
+        if pack[0] is not None or pack[1] is not None or pack[2]:
+            raise ValueError("pack_source, pack_keep and pack_start_step belong to a pack of recordings (counts=): one recording takes source, "
+                             "keep and start_step")
+        return _Windows(*args, skip=_check_skip(skip, keep, None, window, hop)), source, keep, start_step
     if source is not None or keep is not None or start_step:
-        raise ValueError("source, keep and start_step are not built for a pack of recordings (counts=): convert such a recording on its own")
-    return _Pack(counts, *args)
+        raise ValueError("source, keep and start_step are one recording's: a pack of recordings (counts=) takes pack_source, pack_keep and "
+                         "pack_start_step, the same in pack layout [1,1,total]")
+    return _Pack(counts, *args, skip=_check_skip(skip, pack[1], counts, window, hop)), pack[0], pack[1], pack[2]
 
 
 def ddpm_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, steps: int, *, window: int, hop: int,
                         window_batch: int = 64, constrain: bool = False, sigma_large: bool = False, cond_fn: Optional[Callable] = None,
                         schedule: Optional[Callable] = None, noise=None, seed: Optional[int] = None, clip_offset: int = 0,
                         progress: bool = False, source: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
-                        start_step: int = 0, counts: Optional[Sequence[int]] = None) -> torch.Tensor:
+                        start_step: int = 0, counts: Optional[Sequence[int]] = None, pack_source: Optional[torch.Tensor] = None,
+                        pack_keep: Optional[torch.Tensor] = None, pack_start_step: int = 0,
+                        skip: Optional[torch.Tensor] = None) -> torch.Tensor:
     """`Diffusion.ddpm_sample` for one long state x_T_long [1,1,Np], Np = (n - 1) * hop + window (`plan_windows`): the same
     host-side tables of t and alpha_bar(t), the same step numbering, zero noise on the last step.
 
@@ -302,10 +397,19 @@ def ddpm_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, 
     `counts` makes the run a PACK of recordings of that many windows each: x_T_long (and `noise` per step) is their rows end to end,
     [1,1,total] (`plan_pack`), recording r is keyed clip_offset + r, and the predictor's and cond_fn's slices run across recordings
     (`first` indexes the pack's window batch).  Recording r's slice of the result is what the run of that recording alone returns at
-    clip_offset + r, bit for bit.  `source`, `keep` and `start_step` are not built for a pack and raise ValueError."""
+    clip_offset + r, bit for bit.  A pack takes `pack_source`, `pack_keep` ([1,1,total], the rows end to end) and `pack_start_step` in
+    the place of `source`, `keep` and `start_step`, which raise ValueError with `counts`; they are applied by
+    `vqvs_keep_region_windows_packed`, recording r at clip_offset + r.
+
+    `skip` (bool or uint8 [n], with or without `counts`) names windows that are NOT predicted.  It is refused unless the keep mask
+    covers every skipped window whole: such a window's samples are all overwritten after every step, so the result is the same bit
+    for bit and only the forwards are saved.  The predictor and cond_fn are then called on gathered slices of the active windows as
+    `predictor(windows [m,1,window], ts [m], first=idx[0], rows=idx)`, idx the int64 [m] indices of the slice's windows; without
+    `skip` (or with nothing skipped) `first=` alone is passed, as ever."""
     from .diffusion import _Ddpm
 
-    layout = _layout(counts, source, keep, start_step, _Ddpm(sigma_large, constrain), predictor, cond_fn, window, hop, window_batch, _ddpm_fill, _ddpm_step_windows)
+    layout, source, keep, start_step = _layout(counts, source, keep, start_step, (pack_source, pack_keep, pack_start_step), skip, _Ddpm(sigma_large, constrain),
+                                               predictor, cond_fn, window, hop, window_batch, _ddpm_fill, _ddpm_step_windows)
     return diffusion._sample("ddpm_sample_windows", layout, x_T_long, steps, schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset,
                              progress=progress, source=source, keep=keep, start_step=start_step)
 
@@ -314,15 +418,19 @@ def ddim_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, 
                         window_batch: int = 64, eta: float = 0.0, constrain: bool = False, cond_fn: Optional[Callable] = None,
                         schedule: Optional[Callable] = None, noise=None, seed: Optional[int] = None, clip_offset: int = 0,
                         progress: bool = False, source: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
-                        start_step: int = 0, counts: Optional[Sequence[int]] = None) -> torch.Tensor:
+                        start_step: int = 0, counts: Optional[Sequence[int]] = None, pack_source: Optional[torch.Tensor] = None,
+                        pack_keep: Optional[torch.Tensor] = None, pack_start_step: int = 0,
+                        skip: Optional[torch.Tensor] = None) -> torch.Tensor:
     """`Diffusion.ddim_sample` for one long state x_T_long [1,1,Np]: `ddpm_sample_windows` with `vqvs_ddim_step_windows` as the step.
     `predictor` and `noise` are as there.  `cond_fn(x [m,1,window], ts [m], first=b0)` is evaluated on each slice of windows AT the
     windows the predictor saw and at their t; its gradients fill a [n, window] batch that the step kernel applies per window, before
     the windows' predictions are blended -- one kernel after the forwards, no half-steps.  `source`, `keep` and `start_step` are as
-    there, the kept samples replaced at the alpha_bar stepped TO; `counts` (a pack of recordings) is as there."""
+    there, the kept samples replaced at the alpha_bar stepped TO; `counts` (a pack of recordings), the `pack_...` keywords and `skip` are
+    as there."""
     from .diffusion import _Ddim
 
-    layout = _layout(counts, source, keep, start_step, _Ddim(eta, constrain), predictor, cond_fn, window, hop, window_batch, _ddim_fill, _ddim_step_windows)
+    layout, source, keep, start_step = _layout(counts, source, keep, start_step, (pack_source, pack_keep, pack_start_step), skip, _Ddim(eta, constrain),
+                                               predictor, cond_fn, window, hop, window_batch, _ddim_fill, _ddim_step_windows)
     return diffusion._sample("ddim_sample_windows", layout, x_T_long, steps, schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset,
                              progress=progress, source=source, keep=keep, start_step=start_step)
 
@@ -331,15 +439,19 @@ def dpmpp_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable,
                          window_batch: int = 64, constrain: bool = False, cond_fn: Optional[Callable] = None,
                          schedule: Optional[Callable] = None, noise=None, seed: Optional[int] = None, clip_offset: int = 0,
                          progress: bool = False, source: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
-                         start_step: int = 0, counts: Optional[Sequence[int]] = None) -> torch.Tensor:
+                         start_step: int = 0, counts: Optional[Sequence[int]] = None, pack_source: Optional[torch.Tensor] = None,
+                         pack_keep: Optional[torch.Tensor] = None, pack_start_step: int = 0,
+                         skip: Optional[torch.Tensor] = None) -> torch.Tensor:
     """`Diffusion.dpmpp_sample` for one long state x_T_long [1,1,Np]: `ddim_sample_windows` at eta = 0 with `vqvs_dpmpp_step_windows` as
     the step.  `predictor` and `cond_fn` are as there (the gradient is taken at the windows the predictor saw and applied per window,
     before the blend); the history is the BLENDED x0 of the long row, one value per absolute position, kept by the rule.  `noise` is
     accepted and never asked for anything; `source`, `keep` and `start_step` are as there and leave the history alone; `counts` (a
-    pack of recordings) is as there, the history the pack's rows end to end."""
+    pack of recordings) is as there, the history the pack's rows end to end; the `pack_...` keywords and `skip` are as there (a kept
+    position of the history never reaches a sample that is not kept)."""
     from .diffusion import _Dpmpp
 
-    layout = _layout(counts, source, keep, start_step, _Dpmpp(constrain), predictor, cond_fn, window, hop, window_batch, _ddim_fill, _dpmpp_step_windows)
+    layout, source, keep, start_step = _layout(counts, source, keep, start_step, (pack_source, pack_keep, pack_start_step), skip, _Dpmpp(constrain),
+                                               predictor, cond_fn, window, hop, window_batch, _ddim_fill, _dpmpp_step_windows)
     return diffusion._sample("dpmpp_sample_windows", layout, x_T_long, steps, schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset,
                              progress=progress, source=source, keep=keep, start_step=start_step)
 
@@ -395,15 +507,16 @@ def _window_vectors(vectors: torch.Tensor, n: int, counts: Optional[Sequence[int
 
 
 def _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale, guidance=None, vectors=None):
-    """(predictor, cond_fn) of a window batch: each slice of windows sees its own rows of the conditioning [n,C,T1], of `labels` [n]
+    """(predictor, cond_fn) of a window batch: each slice of windows (`first=`, or the gathered `rows=` of a run that skips windows)
+    sees its own rows of the conditioning [n,C,T1], of `labels` [n]
     or `vectors` [n,E] (or neither) and -- with `enc_pred` -- guidance towards its own codes (VQVAE.decode).  `guidance` (label_scale, vq_scale) makes the
     predictor the guided one of `VQVAE.decode_uncond_guidance` (vq_vae.guided_predictor): labels are then NOT offset by the caller."""
     cond_fn = None
     if enc_pred is not None:
         targets = model.vq.encode(cond_seq)
 
-        def cond_fn(x, ts, first):
-            return enc_pred.guidance_grad(x, ts, targets[first:first + x.shape[0]], enc_pred_scale)
+        def cond_fn(x, ts, first, rows=None):
+            return enc_pred.guidance_grad(x, ts, targets[first:first + x.shape[0]] if rows is None else targets[rows], enc_pred_scale)
 
         cond_fn.native_modules = (enc_pred,)
 
@@ -412,19 +525,45 @@ def _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale, guidance=Non
 
         return guided_predictor(model, cond_seq, labels, *guidance, vectors=vectors)[0], cond_fn
 
-    def predictor(xs, ts, first):
-        sl = slice(first, first + xs.shape[0])
+    def predictor(xs, ts, first, rows=None):
+        sl = slice(first, first + xs.shape[0]) if rows is None else rows  # (rows: the windows of a gathered slice, `_Windows.predict_active`)
         return model.predictor(xs, ts, cond=cond_seq[sl], labels=None if labels is None else labels[sl],
                                vectors=None if vectors is None else vectors[sl])
 
     return predictor, cond_fn
 
 
+def _pause_keep_and_skip(source, keep, counts, window, hop, keep_pauses, skip_kept, num_samples, stats):
+    """(mask, skip list) of a pack's padded rows `source` [1,1,total]: the user's mask `keep` (uint8 or None) OR-ed, once, on the device,
+    with the pause mask of the rows when `keep_pauses` holds the detector's settings; the windows the result covers whole when
+    `skip_kept` (None when there are none).  `stats` (a dict or None) receives kept_samples (of the un-padded recordings), windows and
+    skipped_windows."""
+    from .pauses import pause_mask, windows_kept
+
+    if keep_pauses is not None:
+        _native.require_cuda(source)
+        found = pause_mask(source, counts, window, hop, **keep_pauses)
+        keep = found if keep is None else torch.bitwise_or(keep.ne(0).to(torch.uint8), found)
+    skip = None
+    if skip_kept and keep is not None and keep.is_cuda:
+        skip = windows_kept(keep, counts, window, hop)
+    if stats is not None or skip is not None:
+        skipped = 0 if skip is None else int(skip.sum())  # (one synchronisation per pack)
+        if skip is not None and skipped == 0:
+            skip = None
+        if stats is not None:
+            _, offsets, _ = pack_layout(counts, window, hop)
+            kept = 0 if keep is None else sum(int(keep[..., o:o + n].ne(0).sum()) for o, n in zip(offsets, num_samples))
+            stats.update(kept_samples=kept, windows=sum(counts), skipped_windows=skipped)
+    return keep, skip
+
+
 def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, *, num_samples: int, window: int, hop: int,
                 steps: int = 100, progress: bool = False, constrain: bool = False, enc_pred=None, enc_pred_scale: float = 1.0,
                 seed: Optional[int] = None, clip_offset: int = 0, window_batch: int = 64, sampler: str = "ddpm", eta: float = 0.0,
                 source: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None, strength: float = 1.0,
-                guidance: Optional[Tuple[float, float]] = None, vectors: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
+                guidance: Optional[Tuple[float, float]] = None, vectors: Optional[torch.Tensor] = None,
+                keep_pauses: Optional[dict] = None, skip_kept: bool = True, stats: Optional[dict] = None, **kwargs) -> torch.Tensor:
     """Window codes [n,T1] int or [n,C,T1] float (`encode_long`) -> [1,1,num_samples] waveform: `VQVAE.decode` on one long state.
     x_T is ONE row of (n - 1) * hop + window samples keyed by `clip_offset`; `labels` is one label for every window, or [n];
     `vectors` in their place is one conditioning vector [E] for every window, or [n,E] (a morph: speakers.morph_vectors).
@@ -432,10 +571,15 @@ def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = Non
     `ddim_sample_windows` with `eta` instead of `ddpm_sample_windows`, "dpmpp" `dpmpp_sample_windows`.  `source` [1,1,num_samples] (the recording itself), `keep`
     (bool / uint8, [1,1,num_samples]: samples that stay the source's) and `strength` in (0, 1] (below 1: start from the noised
     source, `strength_to_start_step`) are `VQVAE.decode`'s.  `guidance` (label_scale, vq_scale) is what
-    `VQVAE.decode_long_uncond_guidance` passes: the guided window predictor of `_conditioned`, labels not offset by the caller."""
+    `VQVAE.decode_long_uncond_guidance` passes: the guided window predictor of `_conditioned`, labels not offset by the caller.
+    `keep_pauses` (the detector's settings: `pauses.pause_mask`'s keywords, at least threshold_db) also keeps the pauses of `source`,
+    found on the zero-padded row and OR-ed with `keep`; `skip_kept` leaves the windows that the mask covers whole out of the
+    forwards, which changes no bit of the result; `stats` (a dict) receives kept_samples, windows and skipped_windows."""
     from .diffusion import fresh_seed, pick_sampler, randn_clips, source_start_step
     from .vq_vae import one_voice
 
+    if keep_pauses is not None and source is None:
+        raise ValueError("keep_pauses= needs source=, the waveform whose pauses are kept")
     start_step = source_start_step(source, keep, strength, steps)
     cond_seq = model.cond_sequence(codes)
     check_rate(model, window, hop)
@@ -459,7 +603,8 @@ def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = Non
         seed = fresh_seed()
     if source is not None:
         source, keep = pad_source_keep(source, keep, num_samples, padded)
-        kwargs.update(source=source, keep=keep, start_step=start_step)
+        keep, skip = _pause_keep_and_skip(source, keep, [n], window, hop, keep_pauses, skip_kept, [num_samples], stats)
+        kwargs.update(source=source, keep=keep, start_step=start_step, skip=skip)
     x_T = randn_clips(1, padded, codes.device, seed, clip_offset)
     sample, sampler_kw = pick_sampler(model.diffusion, sampler, eta, windows=True)
     out = sample(x_T, predictor, steps, window=window, hop=hop, window_batch=window_batch, constrain=constrain, cond_fn=cond_fn, seed=seed,
@@ -472,17 +617,24 @@ def decode_long_batch(model, codes: torch.Tensor, labels: Optional[torch.Tensor]
                       window: int, hop: int, steps: int = 100, progress: bool = False, constrain: bool = False, enc_pred=None,
                       enc_pred_scale: float = 1.0, seed: Optional[int] = None, clip_offset: int = 0, window_batch: int = 64,
                       sampler: str = "ddpm", eta: float = 0.0, guidance: Optional[Tuple[float, float]] = None,
-                      vectors: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+                      vectors: Optional[torch.Tensor] = None, sources: Optional[Sequence[torch.Tensor]] = None,
+                      keeps: Optional[Sequence[Optional[torch.Tensor]]] = None, strength: float = 1.0, keep_pauses: Optional[dict] = None,
+                      skip_kept: bool = True, stats: Optional[dict] = None) -> List[torch.Tensor]:
     """`decode_long` for a pack of recordings (`encode_long_batch`): codes [N,T1] or [N,C,T1] of all their windows, `counts` windows and
     `num_samples` samples per recording -> one [1,1,num_samples[r]] waveform each.  The windows of all recordings fill the forwards
     together (`window_batch` at a time) and one packed step kernel follows, so many short recordings cost what one long one does.
     `labels` is one label, one per recording, or one per window; `vectors` in their place one [E], [R,E] or [N,E].  x_T is each recording's own row keyed clip_offset + r, and recording
     r's result is what `decode_long` returns for it alone at clip_offset + r, bit for bit, whatever else is in the pack and whatever
-    `window_batch` is.  `source`, `keep` and `strength` are not built for a pack.  `guidance` (label_scale, vq_scale) is `decode_long`'s,
-    what `VQVAE.decode_long_batch_uncond_guidance` passes."""
-    from .diffusion import fresh_seed, pick_sampler, randn_clips
+    `window_batch` is.  `sources` and `keeps` are `decode_long`'s `source` and `keep`, one per recording ([1,1,num_samples[r]]; an entry
+    of `keeps` may be None), `strength`, `keep_pauses`, `skip_kept` and `stats` are `decode_long`'s: rows are zero-padded as there, the
+    detector sees the padded rows, and the kept samples are replaced by `vqvs_keep_region_windows_packed`.  `guidance` (label_scale,
+    vq_scale) is `decode_long`'s, what `VQVAE.decode_long_batch_uncond_guidance` passes."""
+    from .diffusion import fresh_seed, pick_sampler, randn_clips, strength_to_start_step
     from .vq_vae import one_voice
 
+    start_step = strength_to_start_step(strength, steps)
+    if sources is None and (keeps is not None or start_step or keep_pauses is not None):
+        raise ValueError("keeps=, strength < 1 and keep_pauses= need sources=, the waveforms whose samples are kept or noised")
     cond_seq = model.cond_sequence(codes)
     check_rate(model, window, hop)
     counts, num_samples = [int(c) for c in counts], [int(n) for n in num_samples]
@@ -510,9 +662,21 @@ def decode_long_batch(model, codes: torch.Tensor, labels: Optional[torch.Tensor]
     if seed is None:
         seed = fresh_seed()
     padded = [(c - 1) * hop + window for c in counts]
+    pack_kw = {}
+    if sources is not None:
+        if len(sources) != R or (keeps is not None and len(keeps) != R):
+            raise ValueError(f"sources (and keeps) must hold one entry per recording ({R})")
+        rows = [pad_source_keep(sources[r], None if keeps is None else keeps[r], num_samples[r], padded[r]) for r in range(R)]
+        source = torch.cat([s for s, _ in rows], dim=-1)
+        keep = None
+        if any(k is not None for _, k in rows):
+            keep = torch.cat([torch.zeros(1, 1, padded[r], dtype=torch.uint8, device=source.device) if k is None else k
+                              for r, (_, k) in enumerate(rows)], dim=-1)
+        keep, skip = _pause_keep_and_skip(source, keep, counts, window, hop, keep_pauses, skip_kept, num_samples, stats)
+        pack_kw = dict(pack_source=source, pack_keep=keep, pack_start_step=start_step, skip=skip)
     x_T = torch.cat([randn_clips(1, padded[r], codes.device, seed, clip_offset + r) for r in range(R)], dim=-1)
     sample, sampler_kw = pick_sampler(model.diffusion, sampler, eta, windows=True)
     out = sample(x_T, predictor, steps, window=window, hop=hop, window_batch=window_batch, constrain=constrain, cond_fn=cond_fn, seed=seed,
-                 clip_offset=clip_offset, progress=progress, counts=counts, **sampler_kw)
+                 clip_offset=clip_offset, progress=progress, counts=counts, **sampler_kw, **pack_kw)
     model.predictor.check_status()  # range guard of the decoder's mode (once per sample)
     return [out[..., o:o + n].clone() for o, n in zip(offsets, num_samples)]

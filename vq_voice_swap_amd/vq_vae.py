@@ -49,7 +49,9 @@ def guided_predictor(model, cond_seq: torch.Tensor, labels: Optional[torch.Tenso
     offset; None: no labels).  A slice of m rows starting at `first` runs the decoder's predictor on the reps-fold batch
     [own cond, labels + 1 | zero cond, labels + 1 | own cond, label 0] -- a block only for a non-zero scale (reference
     vq_vae.py:188-214, whose always-tripled batch lines up only when both are) -- and `vqvs_guidance_mix` extrapolates in place over
-    block 0.  The batches of a slice are built once and kept: the sampling loop asks for the same slices at every step.
+    block 0.  The batches of a slice are built once and kept: the sampling loop asks for the same slices at every step.  `rows=` (an
+    int64 [m] index tensor, what a window loop that skips windows passes) names the slice's rows in the place of first .. first + m;
+    its batch is keyed by the tensor itself, which the loop keeps for the whole run.
     `vectors` [n,E] in place of labels (NOT offset: they are the voices themselves) run as [own cond, vectors | zero cond, vectors |
     own cond, row 0 of the table as a vector]: with vectors = class_embed.weight[labels + 1] the labels run, bit for bit."""
     one_voice(labels, vectors)
@@ -66,9 +68,10 @@ def guided_predictor(model, cond_seq: torch.Tensor, labels: Optional[torch.Tenso
             return torch.zeros_like(like)
         return model.predictor.class_embed.weight[0].detach().to(like).expand(like.shape[0], -1)
 
-    def batch(first: int, m: int):
-        if (first, m) not in batches:
-            sl = slice(first, first + m)
+    def batch(first: int, m: int, rows=None):
+        key_ = (first, m) if rows is None else ("rows", id(rows))  # (a gathered slice: the run passes the same index tensor every step)
+        if key_ not in batches:
+            sl = slice(first, first + m) if rows is None else rows
             conds = [cond_seq[sl]]
             voices = [voice[sl]] if voice is not None else None
             if use_vq:
@@ -78,11 +81,11 @@ def guided_predictor(model, cond_seq: torch.Tensor, labels: Optional[torch.Tenso
             if use_label:
                 conds.append(cond_seq[sl])
                 voices.append(null_voice(voice[sl]))
-            batches[first, m] = (torch.cat(conds, dim=0), torch.cat(voices, dim=0) if voices is not None else None)
-        return batches[first, m]
+            batches[key_] = (torch.cat(conds, dim=0), torch.cat(voices, dim=0) if voices is not None else None, rows)
+        return batches[key_][:2]
 
-    def predictor(xs, ts, first: int = 0):
-        cond_batch, voice_batch = batch(int(first), xs.shape[0])
+    def predictor(xs, ts, first: int = 0, rows=None):
+        cond_batch, voice_batch = batch(int(first), xs.shape[0], rows)
         outs = model.predictor(torch.cat([xs] * reps, dim=0), torch.cat([ts] * reps, dim=0), cond=cond_batch, **{key: voice_batch})
         return guidance_mix(outs, reps, scales[0], scales[1])
 
