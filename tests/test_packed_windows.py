@@ -12,7 +12,7 @@ import torch
 from vq_voice_swap_amd import _native
 from vq_voice_swap_amd.corpus import deal_packs, list_files, make_packs, read_label_map
 from vq_voice_swap_amd.diffusion import Diffusion, make_schedule
-from vq_voice_swap_amd.longform import MAX_WINDOWS, plan_pack, plan_windows
+from vq_voice_swap_amd.longform import MAX_WINDOWS, pack_layout, plan_pack, plan_windows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -276,3 +276,71 @@ def test_counts_refuses_source_keep_and_start_step(method):
                 dict(source=x, start_step=1), dict(start_step=1)):
         with pytest.raises(ValueError, match="pack"):
             sample(x, predictor, 4, window=W, hop=H, counts=counts, **bad)
+
+
+# ---------------------------------------------------------------- 6. one layout: what the kernels are told, and a pack of one
+class RecordingLib:
+    """Stands in for the library: every entry point is there, records (name, arguments) and reports success."""
+
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        return lambda *args: self.calls.append((name, args)) or 0
+
+
+GEOMETRY_AT = {"ddpm": 7, "ddim": 8, "dpmpp": 10, "keep": 6}  # the index of the first geometry argument (include/vqvs.h)
+
+
+@pytest.mark.parametrize("counts", [None, (2, 1), (3,)])
+def test_the_layout_picks_the_entry_point_and_its_geometry(counts, monkeypatch):
+    """One step and one keep call of each rule through `_Windows`, the library replaced by a recorder: one recording (no `counts`) is
+    told to the `..._windows` entry points as n, a pack -- of one recording too -- to the `..._windows_packed` ones as (d_first, R)."""
+    from vq_voice_swap_amd import _native, longform
+    from vq_voice_swap_amd.diffusion import _Ddim, _Ddpm, _Dpmpp
+
+    lib = RecordingLib()
+    monkeypatch.setattr(_native, "lib", lambda: lib)
+    monkeypatch.setattr(_native, "_stream_ptr", lambda: 0)
+    W, H, n = 16, 12, 3
+    _, _, total = pack_layout(counts or [n], W, H)
+    d = Diffusion(make_schedule("exp"))
+    x = torch.zeros(1, 1, total)
+    source, keep = torch.ones_like(x), torch.ones_like(x, dtype=torch.uint8)
+    for name, rule, fill, step in (("ddpm", _Ddpm(False, False), longform._ddpm_fill, longform._ddpm_step_windows),
+                                   ("ddim", _Ddim(0.5, False), longform._ddim_fill, longform._ddim_step_windows),
+                                   ("dpmpp", _Dpmpp(False), longform._ddim_fill, longform._dpmpp_step_windows)):
+        del lib.calls[:]
+        layout = longform._Windows(rule, None, None, W, H, 2, fill, step, counts=counts)
+        tables = d.step_tables(2, layout.rows(x), None, x.device)
+        assert (layout.n, layout.Np, layout.mb) == (n, total, 2)
+        state = layout.start(x, None, None, tables[1][0], start_step=0, seed=7, clip_offset=3)
+        layout.st = 0  # (what `predict` leaves: the step's stream)
+        state = layout.step(state, None, None, tables, 0, noise_scale=1.0, seed=7, clip_offset=3)
+        layout.keep(state, source, keep, tables[2][0], index=1, seed=7, clip_offset=3)
+        (step_name, step_args), (keep_name, keep_args) = lib.calls
+        suffix, geom = ("", (n,)) if counts is None else ("_packed", (layout.first.data_ptr(), len(counts)))
+        assert step_name == f"vqvs_{name}_step_windows{suffix}" and keep_name == f"vqvs_keep_region_windows{suffix}"
+        for args, at in ((step_args, GEOMETRY_AT[name]), (keep_args, GEOMETRY_AT["keep"])):
+            assert args[at:at + len(geom) + 2] == geom + (W, H), (name, args)
+        if counts is not None:
+            assert layout.first.dtype == torch.int32 and layout.first.tolist() == pack_layout(counts, W, H)[0]
+
+
+def test_a_pack_of_one_is_the_single_layout(monkeypatch):
+    """`_Windows` without `counts` and with `counts=(n,)`: the same n, Np, offsets and slice size, and the same window batch gathered
+    from the same x_T (only the entry points differ, above)."""
+    from vq_voice_swap_amd import _native, longform
+
+    monkeypatch.setattr(_native, "require_cuda", lambda *tensors: None)
+    W, H, n = 16, 12, 3
+    x = torch.arange((n - 1) * H + W, dtype=torch.float32).view(1, 1, -1)
+    layouts = [longform._Windows(type("Rule", (), dict(name="ddim", flags=0))(), None, None, W, H, 2, None, None, counts=counts) for counts in (None, (n,))]
+    states = []
+    for layout in layouts:
+        assert layout.rows(x) == 2 == layout.mb
+        assert (layout.n, layout.Np, layout.offsets, list(layout.counts)) == (n, x.shape[2], [0], [n])
+        states.append(layout.start(x, None, None, None, start_step=0, seed=0, clip_offset=0))
+    assert isinstance(layouts[0].geom, int) and layouts[0].geom == n and layouts[1].geom is layouts[1] and layouts[1].R == 1
+    assert torch.equal(layouts[0].windows, layouts[1].windows) and torch.equal(states[0], states[1])
+    assert torch.equal(layouts[0].windows, longform.gather_windows(x, W, H))

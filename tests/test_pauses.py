@@ -287,7 +287,7 @@ def test_old_and_new_keywords_keep_to_their_layouts(method):
 
 @pytest.mark.parametrize("method", METHODS)
 def test_new_keywords_reach_the_layout(method, monkeypatch):
-    """`pack_source` / `pack_keep` / `pack_start_step` / `skip` arrive at a stubbed `_Pack` and at `Diffusion._sample` as the source,
+    """`pack_source` / `pack_keep` / `pack_start_step` / `skip` arrive at a stubbed `_Windows` and at `Diffusion._sample` as the source,
     mask and first step of the run."""
     d = Diffusion(make_schedule("exp"))
     W, H, counts = 16, 12, (2, 1)
@@ -298,10 +298,10 @@ def test_new_keywords_reach_the_layout(method, monkeypatch):
     seen = {}
 
     class Stub:
-        def __init__(self, counts_, *args, skip=None):
-            seen.update(counts=counts_, skip=skip, window=args[3], hop=args[4])
+        def __init__(self, *args, skip=None, counts=None):
+            seen.update(counts=counts, skip=skip, window=args[3], hop=args[4])
 
-    monkeypatch.setattr(longform, "_Pack", Stub)
+    monkeypatch.setattr(longform, "_Windows", Stub)
     monkeypatch.setattr(d, "_sample", lambda what, layout, x_T, steps, **kw: seen.update(what=what, layout=layout, **kw))
     getattr(d, method)(x, never, 4, window=W, hop=H, counts=counts, pack_source=x, pack_keep=keep, pack_start_step=2,
                        skip=torch.tensor([0, 1, 1], dtype=torch.uint8), seed=3)

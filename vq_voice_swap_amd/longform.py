@@ -19,10 +19,17 @@ A corpus is converted in PACKS (section 3.17): with `counts=` the three loops ru
 windows in one batch that fills the forwards, and the step is the `..._packed` entry point, which keeps the recordings apart.
 `VQVAE.encode_long_batch` / `decode_long_batch` are below as well; recording r of a pack is, bit for bit, what `decode_long` returns
 for it alone at clip_offset + r.
+
+So on the host ONE recording is the pack of one -- `pack_layout([n], W, H)` is offsets [0] and `plan_windows`' length -- and everything
+here is written once, over (offsets, counts): the layout `_Windows`, the gather that starts a run, the body of the three loops
+(`_window_run`), `encode_long` as `encode_long_batch` of one, `decode_long` and `decode_long_batch` over `_decode`.  The two forms
+differ in what the kernels are told alone (`_entry`): n and the `..._windows` entry points without `counts=`, the table and the
+`..._windows_packed` ones with it.
 """
 
 from __future__ import annotations
 
+import functools
 from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
@@ -78,39 +85,59 @@ def plan_pack(num_samples_list: Sequence[int], window: int, hop: int) -> Tuple[L
     return counts, offsets, total
 
 
+def pack_table(counts: Sequence[int], window: int, hop: int, device) -> Tuple[torch.Tensor, int, int, List[int], int]:
+    """(d_first, R, N, offsets, total) of a pack (`pack_layout`): the prefix sums `first` uploaded as the int32 [R + 1] table that every
+    packed entry point reads, the numbers of recordings and of windows, each recording's first sample and the samples in all."""
+    first, offsets, total = pack_layout(counts, window, hop)
+    return torch.tensor(first, dtype=torch.int32, device=device), len(first) - 1, first[-1], offsets, total
+
+
+def pack_rows(t: torch.Tensor, offsets: Sequence[int], counts: Sequence[int], window: int, hop: int):
+    """Each recording's padded row t[..., o : o + (c - 1) * hop + window] of a tensor in pack layout, as views."""
+    for o, c in zip(offsets, counts):
+        yield t[..., o:o + (c - 1) * hop + window]
+
+
+def _cat(tensors: List[torch.Tensor], dim: int = 0) -> torch.Tensor:
+    """`torch.cat`, without its copy where there is one tensor (one recording)."""
+    return tensors[0] if len(tensors) == 1 else torch.cat(tensors, dim=dim)
+
+
 def gather_windows(x: torch.Tensor, window: int, hop: int) -> torch.Tensor:
     """[1,1,Np] -> the contiguous window batch [n,1,window] (a copy; the step kernel writes the later ones itself)."""
     return x.reshape(-1).unfold(0, window, hop).unsqueeze(1).contiguous()
 
 
+def _entry(name: str, geom):
+    """The C entry point of a window kernel and its geometry arguments: `geom` is the window count n of one recording, or the `_Windows`
+    of a pack -- the packed form takes (d_first, R) where the single one takes n."""
+    if isinstance(geom, int):
+        return getattr(_native.lib(), name), (geom,)
+    return getattr(_native.lib(), name + "_packed"), (geom.first.data_ptr(), geom.R)
+
+
 def keep_windows_(x: torch.Tensor, windows: Optional[torch.Tensor], source: torch.Tensor, keep: Optional[torch.Tensor], alpha: torch.Tensor, *,
-                  n: int, window: int, hop: int, seed: int, clip_offset: int, index: int) -> None:
+                  geom, window: int, hop: int, seed: int, clip_offset: int, index: int) -> None:
     """`vqvs_keep_region_windows` IN PLACE on the long state x [Np] and (unless None) on the window batch [n,1,window] gathered from
-    it: the kept samples (keep None: all) are put back on the source's forward process at alpha[0]."""
-    _native.check(_native.lib().vqvs_keep_region_windows(x.data_ptr(), _native._ptr(windows), source.data_ptr(), _native._ptr(keep), None,
-                                                         alpha.data_ptr(), n, window, hop, 1.0, int(seed), int(clip_offset), int(index),
-                                                         _native._stream_ptr()))
+    it: the kept samples (keep None: all) are put back on the source's forward process at alpha[0].  For a pack (`_entry`) the
+    packed form: the same on every recording's own slices, recording r keyed clip_offset + r, in one launch."""
+    fn, geom = _entry("vqvs_keep_region_windows", geom)
+    _native.check(fn(x.data_ptr(), _native._ptr(windows), source.data_ptr(), _native._ptr(keep), None, alpha.data_ptr(), *geom, window, hop, 1.0,
+                     int(seed), int(clip_offset), int(index), _native._stream_ptr()))
 
 
-def keep_pack_(x: torch.Tensor, windows: Optional[torch.Tensor], source: torch.Tensor, keep: Optional[torch.Tensor], alpha: torch.Tensor, *,
-               first: torch.Tensor, R: int, window: int, hop: int, seed: int, clip_offset: int, index: int) -> None:
-    """`vqvs_keep_region_windows_packed` IN PLACE on the rows x [total] of a pack and (unless None) on its window batch [N,1,window]:
-    `keep_windows_` on every recording's own slices, recording r keyed clip_offset + r, in one launch."""
-    _native.check(_native.lib().vqvs_keep_region_windows_packed(x.data_ptr(), _native._ptr(windows), source.data_ptr(), _native._ptr(keep), None,
-                                                                alpha.data_ptr(), first.data_ptr(), R, window, hop, 1.0, int(seed),
-                                                                int(clip_offset), int(index), _native._stream_ptr()))
-
-
-def start_windows(x_T_long: torch.Tensor, source, keep, alpha, *, start_step: int, n: int, window: int, hop: int, seed: int, clip_offset: int):
+def start_windows(x_T_long: torch.Tensor, source, keep, alpha, *, start_step: int, geom, offsets: Sequence[int], counts: Sequence[int],
+                  window: int, hop: int, seed: int, clip_offset: int):
     """(long state, window batch) a windowed run starts from: x_T as it is, x_T with the kept samples replaced, or -- `start_step` > 0
-    -- the source noised to that step's alpha_bar (Diffusion._keep_start, on the long state)."""
+    -- the source noised to that step's alpha_bar (Diffusion._keep_start, on the long state).  The batch is gathered recording by
+    recording: no window spans two."""
     x = x_T_long.detach().to(torch.float32).contiguous()
     if source is not None and (start_step > 0 or keep is not None):
         x = torch.empty_like(x) if start_step > 0 else x.clone()
         with torch.cuda.device(x.device):
-            keep_windows_(x, None, source, None if start_step > 0 else keep, alpha, n=n, window=window, hop=hop, seed=seed,
+            keep_windows_(x, None, source, None if start_step > 0 else keep, alpha, geom=geom, window=window, hop=hop, seed=seed,
                           clip_offset=clip_offset, index=start_step)
-    return x, gather_windows(x, window, hop)
+    return x, _cat([gather_windows(row, window, hop) for row in pack_rows(x, offsets, counts, window, hop)])
 
 
 def pad_source_keep(source: Optional[torch.Tensor], keep: Optional[torch.Tensor], num_samples: int, padded_len: int):
@@ -159,14 +186,6 @@ def _ddim_fill(rule, xw, e, tables, i, b0, cond_fn, eps, grad, st) -> None:
         grad[b0:b0 + m].copy_(g.detach())
 
 
-def _entry(name: str, geom):
-    """The C entry point of a window step and its geometry arguments: `geom` is the window count n of one recording, or the `_Pack`
-    of several -- the packed form takes (d_first, R) where the single one takes n."""
-    if isinstance(geom, int):
-        return getattr(_native.lib(), name), (geom,)
-    return getattr(_native.lib(), name + "_packed"), (geom.first.data_ptr(), geom.R)
-
-
 def _ddpm_step_windows(rule, x, eps, grad, nz, a_t, a_to, x_to, next_windows, n, window, hop, noise_scale, seed, clip_offset, step_index, st) -> None:
     fn, geom = _entry("vqvs_ddpm_step_windows", n)
     _native.check(fn(x.data_ptr(), eps.data_ptr(), _native._ptr(nz), a_t.data_ptr(), a_to.data_ptr(), x_to.data_ptr(), next_windows.data_ptr(),
@@ -182,7 +201,7 @@ def _ddim_step_windows(rule, x, eps, grad, nz, a_t, a_to, x_to, next_windows, n,
 
 def dpmpp_step_windows_(x, eps, grad, x0_prev, a_from, a_t, a_to, x_to, x0_out, next_windows, n, window, hop, flags, st) -> None:
     """`vqvs_dpmpp_step_windows` on the long state x [Np] and the window batches eps / grad [n,1,window]: x_to and x0_out [Np] and the
-    next forward's windows are written; x0_prev / a_from None: no history.  (n a `_Pack`: the packed form, `_entry`.)"""
+    next forward's windows are written; x0_prev / a_from None: no history.  (n the layout of a pack: the packed form, `_entry`.)"""
     fn, geom = _entry("vqvs_dpmpp_step_windows", n)
     _native.check(fn(x.data_ptr(), eps.data_ptr(), _native._ptr(grad), _native._ptr(x0_prev), _native._ptr(a_from), a_t.data_ptr(), a_to.data_ptr(),
                      x_to.data_ptr(), x0_out.data_ptr(), next_windows.data_ptr(), *geom, window, hop, flags, st))
@@ -200,13 +219,18 @@ class _Windows:
     """The state layout of the window loops for `Diffusion._sample`: the long row [Np], with its window batch [n,1,window] kept
     beside it.  The predictor and cond_fn see slices of at most `window_batch` windows, with `first=`; `fill` and `step` are the
     rule's window forms above.  `skip` (bool [n], checked by `_check_skip`) names windows that are not predicted: the slices then
-    run over the ACTIVE windows, gathered, with `first=idx[0], rows=idx`, and the skipped rows of eps and grad stay zero."""
+    run over the ACTIVE windows, gathered, with `first=idx[0], rows=idx`, and the skipped rows of eps and grad stay zero.
+
+    `counts` makes it a pack of recordings of that many windows each (`pack_layout`): the long rows end to end in one [total] state,
+    the windows of all of them in one batch, so the predictor's slices run across recordings.  One recording is the pack of one, rows
+    (0, n) of the same walk; only what the kernels are told differs (`geom`): n and the single entry points, or the table `first` and
+    the packed ones, which key recording r by clip_offset + r and blend nothing across recordings."""
 
     def __init__(self, rule, predictor: Callable, cond_fn: Optional[Callable], window: int, hop: int, window_batch: int, fill, step,
-                 skip: Optional[torch.Tensor] = None):
+                 skip: Optional[torch.Tensor] = None, counts: Optional[Sequence[int]] = None):
         self.rule, self.predictor, self.cond_fn, self.fill, self.step_windows = rule, predictor, cond_fn, fill, step
         self.window, self.hop, self.window_batch = window, hop, window_batch
-        self.skip, self.active = skip, None
+        self.skip, self.active, self.pack = skip, None, counts
 
     def plan_skip(self, device) -> None:
         """The slices of active windows as (first index, index tensor [m]); the tensors stay the same objects for the whole run (a
@@ -221,16 +245,22 @@ class _Windows:
             self.active = [(firsts[k], idx[a0:a0 + self.mb].contiguous()) for k, a0 in enumerate(range(0, idx.numel(), self.mb))]
 
     def rows(self, x_T_long) -> int:
-        """The input checks; the tables hold one row per window of a slice."""
+        """The input checks and the geometry; the tables hold one row per window of a slice."""
         if x_T_long.dim() != 3 or x_T_long.shape[0] != 1 or x_T_long.shape[1] != 1:
             raise ValueError(f"x_T_long must be [1, 1, Np], got {tuple(x_T_long.shape)}")
-        self.Np = x_T_long.shape[2]
-        self.n, padded = plan_windows(self.Np, self.window, self.hop)
-        if padded != self.Np:
-            raise ValueError(f"x_T_long has {self.Np} samples: {self.n} windows of {self.window} every {self.hop} span {padded} (see plan_windows)")
+        got, W, H = x_T_long.shape[2], self.window, self.hop
+        if self.pack is None:
+            self.n, self.Np = plan_windows(got, W, H)
+            self.counts, self.offsets, self.geom = [self.n], [0], self.n  # (geom: what the entry points are told, `_entry`)
+            laid = f"{self.n} windows of {W} every {H} span {self.Np} (see plan_windows)"
+        else:
+            self.first, self.R, self.n, self.offsets, self.Np = pack_table(self.pack, W, H, x_T_long.device)
+            self.counts, self.geom = list(self.pack), self
+            laid = f"recordings of {self.counts} windows of {W} every {H} are {self.Np} laid end to end (see plan_pack)"
+        if got != self.Np:
+            raise ValueError(f"x_T_long has {got} samples: {laid}")
         if self.window_batch < 1:
             raise ValueError(f"window_batch={self.window_batch} must be at least 1")
-        self.geom = self.n  # (what the step's entry point is told: `_entry`)
         self.mb = min(self.n, int(self.window_batch))
         self.plan_skip(x_T_long.device)
         return self.mb
@@ -243,7 +273,8 @@ class _Windows:
         return x
 
     def gather(self, x_T_long, source, keep, alpha, **kw):
-        return start_windows(x_T_long, source, keep, alpha, n=self.n, window=self.window, hop=self.hop, **kw)
+        return start_windows(x_T_long, source, keep, alpha, geom=self.geom, offsets=self.offsets, counts=self.counts, window=self.window,
+                             hop=self.hop, **kw)
 
     def predict(self, x, tables, i) -> None:
         self.st = _native._stream_ptr()  # (of this step: the slices' kernels and the step kernel)
@@ -292,47 +323,7 @@ class _Windows:
         return x_to
 
     def keep(self, x, source, keep, alpha, **kw) -> None:
-        keep_windows_(x, self.windows, source, keep, alpha, n=self.n, window=self.window, hop=self.hop, **kw)
-
-
-class _Pack(_Windows):
-    """`_Windows` for a pack of recordings of `counts` windows each (`pack_layout`): the long rows end to end in one [total] state,
-    the windows of all of them in one [N,1,window] batch, so the predictor's slices run across recordings; the step is the packed
-    entry point (`_entry`), which keys recording r by clip_offset + r and blends nothing across recordings.  Only the geometry
-    differs: the table instead of n, and the gather that starts the run."""
-
-    def __init__(self, counts: Sequence[int], *args, **kwargs):
-        super().__init__(*args, **kwargs)
-        self.counts = counts
-
-    def rows(self, x_T_long) -> int:
-        if x_T_long.dim() != 3 or x_T_long.shape[0] != 1 or x_T_long.shape[1] != 1:
-            raise ValueError(f"x_T_long must be [1, 1, total], got {tuple(x_T_long.shape)}")
-        first, self.offsets, self.Np = pack_layout(self.counts, self.window, self.hop)
-        if x_T_long.shape[2] != self.Np:
-            raise ValueError(f"x_T_long has {x_T_long.shape[2]} samples: recordings of {list(self.counts)} windows of {self.window} every "
-                             f"{self.hop} are {self.Np} laid end to end (see plan_pack)")
-        if self.window_batch < 1:
-            raise ValueError(f"window_batch={self.window_batch} must be at least 1")
-        self.n, self.R, self.geom = first[-1], len(first) - 1, self
-        self.first = torch.tensor(first, dtype=torch.int32, device=x_T_long.device)
-        self.mb = min(self.n, int(self.window_batch))
-        self.plan_skip(x_T_long.device)
-        return self.mb
-
-    def gather(self, x_T_long, source, keep, alpha, *, start_step, seed, clip_offset):
-        """`start_windows` on the pack's rows: x_T as it is, with the kept samples replaced, or the source noised to `start_step`."""
-        x = x_T_long.detach().to(torch.float32).contiguous()
-        if source is not None and (start_step > 0 or keep is not None):
-            x = torch.empty_like(x) if start_step > 0 else x.clone()
-            with torch.cuda.device(x.device):
-                keep_pack_(x, None, source, None if start_step > 0 else keep, alpha, first=self.first, R=self.R, window=self.window,
-                           hop=self.hop, seed=seed, clip_offset=clip_offset, index=start_step)
-        rows = [x[..., o:o + (c - 1) * self.hop + self.window] for o, c in zip(self.offsets, self.counts)]
-        return x, torch.cat([gather_windows(r, self.window, self.hop) for r in rows])
-
-    def keep(self, x, source, keep, alpha, **kw) -> None:
-        keep_pack_(x, self.windows, source, keep, alpha, first=self.first, R=self.R, window=self.window, hop=self.hop, **kw)
+        keep_windows_(x, self.windows, source, keep, alpha, geom=self.geom, window=self.window, hop=self.hop, **kw)
 
 
 def _check_skip(skip, keep, counts, window: int, hop: int):
@@ -353,27 +344,31 @@ def _check_skip(skip, keep, counts, window: int, hop: int):
     if flat.numel() != total or skip.numel() != first[-1]:
         raise ValueError(f"skip of {skip.numel()} windows and a keep mask of {flat.numel()} samples do not match {first[-1]} windows of {window} "
                          f"every {hop} spanning {total} samples")
-    whole = torch.cat([flat[o:o + (c - 1) * hop + window].unfold(0, window, hop).ne(0).all(dim=1) for o, c in zip(offsets, counts)])
+    whole = torch.cat([row.unfold(0, window, hop).ne(0).all(dim=1) for row in pack_rows(flat, offsets, counts, window, hop)])
     skip = skip.detach().ne(0).to(whole.device)
     if bool((skip & ~whole).any()):
         raise ValueError("skip= names a window that the keep mask does not cover whole: its forward would be missed")
     return skip
 
 
-def _layout(counts, source, keep, start_step, pack, skip, *args):
-    """(layout, source, keep, start_step) of a window loop: `_Windows` for one recording with its `source`, `keep` and `start_step`; with
-    `counts` the `_Pack` of several, which takes them in pack layout as pack = (`pack_source`, `pack_keep`, `pack_start_step`) and
-    refuses the single-recording keywords.  `skip` is checked against the mask of either (`_check_skip`)."""
-    window, hop = args[3], args[4]
+def _window_run(diffusion, what: str, x_T_long, steps, counts, skip, one, pack, *layout, **run):
+    """The body of the three `..._sample_windows` functions, as the `Diffusion._sample` call for its caller to make (it is made
+    there because `_sample` addresses its warnings by stack depth, to the caller of the public function).  `layout` is `_Windows`'
+    arguments, the rule first.  One recording takes one = (`source`, `keep`, `start_step`); with `counts` a pack takes them in pack
+    layout as pack = (`pack_source`, `pack_keep`, `pack_start_step`); each refuses the other's.  `skip` is checked against the mask of
+    either (`_check_skip`)."""
     if counts is None:
         if pack[0] is not None or pack[1] is not None or pack[2]:
             raise ValueError("pack_source, pack_keep and pack_start_step belong to a pack of recordings (counts=): one recording takes source, "
                              "keep and start_step")
-        return _Windows(*args, skip=_check_skip(skip, keep, None, window, hop)), source, keep, start_step
-    if source is not None or keep is not None or start_step:
-        raise ValueError("source, keep and start_step are one recording's: a pack of recordings (counts=) takes pack_source, pack_keep and "
-                         "pack_start_step, the same in pack layout [1,1,total]")
-    return _Pack(counts, *args, skip=_check_skip(skip, pack[1], counts, window, hop)), pack[0], pack[1], pack[2]
+        source, keep, start_step = one
+    else:
+        if one[0] is not None or one[1] is not None or one[2]:
+            raise ValueError("source, keep and start_step are one recording's: a pack of recordings (counts=) takes pack_source, pack_keep and "
+                             "pack_start_step, the same in pack layout [1,1,total]")
+        source, keep, start_step = pack
+    windows = _Windows(*layout, skip=_check_skip(skip, keep, counts, layout[3], layout[4]), counts=counts)
+    return functools.partial(diffusion._sample, what, windows, x_T_long, steps, source=source, keep=keep, start_step=start_step, **run)
 
 
 def ddpm_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, steps: int, *, window: int, hop: int,
@@ -408,10 +403,9 @@ def ddpm_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, 
     `skip` (or with nothing skipped) `first=` alone is passed, as ever."""
     from .diffusion import _Ddpm
 
-    layout, source, keep, start_step = _layout(counts, source, keep, start_step, (pack_source, pack_keep, pack_start_step), skip, _Ddpm(sigma_large, constrain),
-                                               predictor, cond_fn, window, hop, window_batch, _ddpm_fill, _ddpm_step_windows)
-    return diffusion._sample("ddpm_sample_windows", layout, x_T_long, steps, schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset,
-                             progress=progress, source=source, keep=keep, start_step=start_step)
+    return _window_run(diffusion, "ddpm_sample_windows", x_T_long, steps, counts, skip, (source, keep, start_step), (pack_source, pack_keep, pack_start_step),
+                       _Ddpm(sigma_large, constrain), predictor, cond_fn, window, hop, window_batch, _ddpm_fill, _ddpm_step_windows,
+                       schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset, progress=progress)()
 
 
 def ddim_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, steps: int, *, window: int, hop: int,
@@ -429,10 +423,9 @@ def ddim_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, 
     as there."""
     from .diffusion import _Ddim
 
-    layout, source, keep, start_step = _layout(counts, source, keep, start_step, (pack_source, pack_keep, pack_start_step), skip, _Ddim(eta, constrain),
-                                               predictor, cond_fn, window, hop, window_batch, _ddim_fill, _ddim_step_windows)
-    return diffusion._sample("ddim_sample_windows", layout, x_T_long, steps, schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset,
-                             progress=progress, source=source, keep=keep, start_step=start_step)
+    return _window_run(diffusion, "ddim_sample_windows", x_T_long, steps, counts, skip, (source, keep, start_step), (pack_source, pack_keep, pack_start_step),
+                       _Ddim(eta, constrain), predictor, cond_fn, window, hop, window_batch, _ddim_fill, _ddim_step_windows,
+                       schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset, progress=progress)()
 
 
 def dpmpp_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable, steps: int, *, window: int, hop: int,
@@ -450,29 +443,24 @@ def dpmpp_sample_windows(diffusion, x_T_long: torch.Tensor, predictor: Callable,
     position of the history never reaches a sample that is not kept)."""
     from .diffusion import _Dpmpp
 
-    layout, source, keep, start_step = _layout(counts, source, keep, start_step, (pack_source, pack_keep, pack_start_step), skip, _Dpmpp(constrain),
-                                               predictor, cond_fn, window, hop, window_batch, _ddim_fill, _dpmpp_step_windows)
-    return diffusion._sample("dpmpp_sample_windows", layout, x_T_long, steps, schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset,
-                             progress=progress, source=source, keep=keep, start_step=start_step)
+    return _window_run(diffusion, "dpmpp_sample_windows", x_T_long, steps, counts, skip, (source, keep, start_step), (pack_source, pack_keep, pack_start_step),
+                       _Dpmpp(constrain), predictor, cond_fn, window, hop, window_batch, _ddim_fill, _dpmpp_step_windows,
+                       schedule=schedule, noise=noise, seed=seed, clip_offset=clip_offset, progress=progress)()
 
 
 def encode_long(model, wave: torch.Tensor, window: int, hop: int, window_batch: int = 64) -> torch.Tensor:
-    """[1,1,N] waveform -> codes [n, window / rate] of its n windows (`plan_windows`), the tail zero-padded.  Windows are encoded in
-    slices of `window_batch`; behind the version-2 (dB) MFCC front end, which floors at the maximum over the BATCH, one at a time, so
-    that the codes do not depend on `window_batch`."""
+    """[1,1,N] waveform -> codes [n, window / rate] of its n windows (`plan_windows`), the tail zero-padded: `encode_long_batch` of the
+    one recording, without the counts."""
     if wave.dim() != 3 or wave.shape[0] != 1 or wave.shape[1] != 1:
         raise ValueError(f"wave must be [1, 1, N], got {tuple(wave.shape)}")
-    check_rate(model, window, hop)
-    n, padded = plan_windows(wave.shape[2], window, hop)
-    windows = gather_windows(torch.nn.functional.pad(wave, (0, padded - wave.shape[2])), window, hop)
-    mb = 1 if getattr(model.encoder, "version", 1) == 2 else max(1, int(window_batch))
-    return torch.cat([model.encode(windows[b0:b0 + mb]) for b0 in range(0, n, mb)])
+    return encode_long_batch(model, [wave], window, hop, window_batch)[0]
 
 
 def encode_long_batch(model, waves: Sequence[torch.Tensor], window: int, hop: int, window_batch: int = 64) -> Tuple[torch.Tensor, List[int]]:
-    """`encode_long` for several recordings [1,1,N_r]: (codes [N, window / rate], counts), the windows of recording r -- zero-padded to
-    its own `plan_windows` length -- at rows sum(counts[:r]) ... of the codes.  Windows are encoded in slices of `window_batch` that run
-    across recordings (one at a time behind the version-2 front end, as there), so the codes are `encode_long`'s of each recording."""
+    """Several recordings [1,1,N_r] -> (codes [N, window / rate], counts), the windows of recording r -- zero-padded to its own
+    `plan_windows` length -- at rows sum(counts[:r]) ... of the codes.  Windows are encoded in slices of `window_batch` that run across
+    recordings; behind the version-2 (dB) MFCC front end, which floors at the maximum over the BATCH, one at a time, so that the codes
+    depend neither on `window_batch` nor on the pack: they are `encode_long`'s of each recording."""
     if not len(waves):
         raise ValueError("waves must hold at least one recording")
     for w in waves:
@@ -480,8 +468,8 @@ def encode_long_batch(model, waves: Sequence[torch.Tensor], window: int, hop: in
             raise ValueError(f"every wave must be [1, 1, N], got {tuple(w.shape)}")
     check_rate(model, window, hop)
     counts, _, _ = plan_pack([w.shape[2] for w in waves], window, hop)
-    windows = torch.cat([gather_windows(torch.nn.functional.pad(w, (0, (c - 1) * hop + window - w.shape[2])), window, hop)
-                         for w, c in zip(waves, counts)])
+    windows = _cat([gather_windows(torch.nn.functional.pad(w, (0, (c - 1) * hop + window - w.shape[2])), window, hop)
+                    for w, c in zip(waves, counts)])
     mb = 1 if getattr(model.encoder, "version", 1) == 2 else max(1, int(window_batch))
     return torch.cat([model.encode(windows[b0:b0 + mb]) for b0 in range(0, windows.shape[0], mb)]), counts
 
@@ -492,18 +480,17 @@ def check_rate(model, window: int, hop: int) -> None:
         raise ValueError(f"window={window} and hop={hop} must be multiples of the model's downsample rate {rate}")
 
 
-def _window_vectors(vectors: torch.Tensor, n: int, counts: Optional[Sequence[int]] = None) -> torch.Tensor:
-    """Explicit conditioning vectors (speakers.py) in the place of a window batch's labels -> [n,E]: one [E] for every window, one
-    per window, or -- with the `counts` of a pack -- one per recording."""
-    v = vectors.reshape(-1, vectors.shape[-1])
-    if v.shape[0] == 1:
-        v = v.expand(n, -1)
-    elif counts is not None and v.shape[0] == len(counts) != n:
-        v = v.repeat_interleave(torch.tensor(list(counts), device=v.device), dim=0)
-    if v.shape[0] != n:
+def _per_window(rows: torch.Tensor, n: int, counts: Optional[Sequence[int]], what: str) -> torch.Tensor:
+    """The `labels` [k] or the explicit conditioning vectors [k,E] (speakers.py) of a window batch -> one row per window [n, ...]: one
+    for every window, one per window, or -- with the `counts` of a pack -- one per recording."""
+    if rows.shape[0] == 1:
+        rows = rows.expand(n, *rows.shape[1:])
+    elif counts is not None and rows.shape[0] == len(counts) != n:
+        rows = rows.repeat_interleave(torch.tensor(list(counts), device=rows.device), dim=0)
+    if rows.shape[0] != n:
         per = f", one per recording ({len(counts)})" if counts is not None else ""
-        raise ValueError(f"vectors must hold one vector{per} or one per window ({n}), got {v.shape[0]}")
-    return v.contiguous()
+        raise ValueError(f"{what}s must hold one {what}{per} or one per window ({n}), got {rows.shape[0]}")
+    return rows.contiguous()
 
 
 def _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale, guidance=None, vectors=None):
@@ -552,10 +539,60 @@ def _pause_keep_and_skip(source, keep, counts, window, hop, keep_pauses, skip_ke
         if skip is not None and skipped == 0:
             skip = None
         if stats is not None:
-            _, offsets, _ = pack_layout(counts, window, hop)
-            kept = 0 if keep is None else sum(int(keep[..., o:o + n].ne(0).sum()) for o, n in zip(offsets, num_samples))
+            rows = () if keep is None else pack_rows(keep, pack_layout(counts, window, hop)[1], counts, window, hop)
+            kept = sum(int(row[..., :n].ne(0).sum()) for row, n in zip(rows, num_samples))
             stats.update(kept_samples=kept, windows=sum(counts), skipped_windows=skipped)
     return keep, skip
+
+
+def _decode(model, codes, labels, counts, num_samples, single, sources, keeps, start_step, sampler_kwargs, *, window, hop, steps, progress,
+            constrain, enc_pred, enc_pred_scale, seed, clip_offset, window_batch, sampler, eta, guidance, vectors, keep_pauses, skip_kept, stats):
+    """`decode_long` (`single`: the pack of one recording, `counts` None, run on the single entry points with `sampler_kwargs` passed
+    through, the result a view) and `decode_long_batch` (the result one clone per recording).  `sources` / `keeps` are None or hold one
+    entry per recording; `start_step` is what the caller made of `strength`."""
+    from .diffusion import fresh_seed, pick_sampler, randn_clips
+    from .vq_vae import one_voice
+
+    cond_seq = model.cond_sequence(codes)
+    check_rate(model, window, hop)
+    num_samples = [int(n) for n in num_samples]
+    planned, offsets, _ = plan_pack(num_samples, window, hop)
+    if not single and planned != [int(c) for c in counts]:
+        raise ValueError(f"recordings of {num_samples} samples in windows of {window} every {hop} are {planned} windows, not counts={list(counts)}")
+    counts, N, R = planned, sum(planned), len(planned)
+    if cond_seq.shape[0] != N:
+        raise ValueError(f"{num_samples} samples in windows of {window} every {hop} are {counts} windows; codes hold {cond_seq.shape[0]}")
+    if codes.shape[-1] * model.encoder.downsample_rate != window:
+        raise ValueError(f"codes of length {codes.shape[-1]} describe {codes.shape[-1] * model.encoder.downsample_rate} samples, not window={window}")
+    one_voice(labels, vectors)
+    if vectors is not None:
+        vectors = _per_window(vectors.reshape(-1, vectors.shape[-1]), N, None if single else counts, "vector")
+    if labels is not None:
+        labels = _per_window(labels.reshape(-1), N, None if single else counts, "label")
+    predictor, cond_fn = _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale, guidance, vectors)
+    if seed is None:
+        seed = fresh_seed()
+    padded = [(c - 1) * hop + window for c in counts]
+    run = dict(sampler_kwargs) if single else dict(counts=counts)
+    if sources is not None:
+        if len(sources) != R or (keeps is not None and len(keeps) != R):
+            raise ValueError(f"sources (and keeps) must hold one entry per recording ({R})")
+        rows = [pad_source_keep(sources[r], None if keeps is None else keeps[r], num_samples[r], padded[r]) for r in range(R)]
+        source = _cat([s for s, _ in rows], dim=-1)
+        keep = None
+        if any(k is not None for _, k in rows):
+            keep = _cat([torch.zeros(1, 1, padded[r], dtype=torch.uint8, device=source.device) if k is None else k
+                         for r, (_, k) in enumerate(rows)], dim=-1)
+        keep, skip = _pause_keep_and_skip(source, keep, counts, window, hop, keep_pauses, skip_kept, num_samples, stats)
+        names = ("source", "keep", "start_step") if single else ("pack_source", "pack_keep", "pack_start_step")
+        run.update(zip(names, (source, keep, start_step)), skip=skip)
+    x_T = _cat([randn_clips(1, padded[r], codes.device, seed, clip_offset + r) for r in range(R)], dim=-1)
+    sample, sampler_kw = pick_sampler(model.diffusion, sampler, eta, windows=True)
+    out = sample(x_T, predictor, steps, window=window, hop=hop, window_batch=window_batch, constrain=constrain, cond_fn=cond_fn, seed=seed,
+                 clip_offset=clip_offset, progress=progress, **sampler_kw, **run)
+    model.predictor.check_status()  # range guard of the decoder's mode (once per sample)
+    outs = [row[..., :n] for row, n in zip(pack_rows(out, offsets, counts, window, hop), num_samples)]
+    return outs[0] if single else [o.clone() for o in outs]
 
 
 def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, *, num_samples: int, window: int, hop: int,
@@ -574,43 +611,17 @@ def decode_long(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = Non
     `VQVAE.decode_long_uncond_guidance` passes: the guided window predictor of `_conditioned`, labels not offset by the caller.
     `keep_pauses` (the detector's settings: `pauses.pause_mask`'s keywords, at least threshold_db) also keeps the pauses of `source`,
     found on the zero-padded row and OR-ed with `keep`; `skip_kept` leaves the windows that the mask covers whole out of the
-    forwards, which changes no bit of the result; `stats` (a dict) receives kept_samples, windows and skipped_windows."""
-    from .diffusion import fresh_seed, pick_sampler, randn_clips, source_start_step
-    from .vq_vae import one_voice
+    forwards, which changes no bit of the result; `stats` (a dict) receives kept_samples, windows and skipped_windows.  Further
+    keywords (`schedule=` ...) go to the sampler."""
+    from .diffusion import source_start_step
 
     if keep_pauses is not None and source is None:
         raise ValueError("keep_pauses= needs source=, the waveform whose pauses are kept")
     start_step = source_start_step(source, keep, strength, steps)
-    cond_seq = model.cond_sequence(codes)
-    check_rate(model, window, hop)
-    n, padded = plan_windows(num_samples, window, hop)
-    if cond_seq.shape[0] != n:
-        raise ValueError(f"{num_samples} samples in windows of {window} every {hop} are {n} windows; codes hold {cond_seq.shape[0]}")
-    if codes.shape[-1] * model.encoder.downsample_rate != window:
-        raise ValueError(f"codes of length {codes.shape[-1]} describe {codes.shape[-1] * model.encoder.downsample_rate} samples, not window={window}")
-    one_voice(labels, vectors)
-    if vectors is not None:
-        vectors = _window_vectors(vectors, n)
-    if labels is not None:
-        labels = labels.reshape(-1)
-        if labels.numel() == 1:
-            labels = labels.expand(n)
-        if labels.shape != (n,):
-            raise ValueError(f"labels must hold one label or one per window ({n}), got {labels.numel()}")
-        labels = labels.contiguous()
-    predictor, cond_fn = _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale, guidance, vectors)
-    if seed is None:
-        seed = fresh_seed()
-    if source is not None:
-        source, keep = pad_source_keep(source, keep, num_samples, padded)
-        keep, skip = _pause_keep_and_skip(source, keep, [n], window, hop, keep_pauses, skip_kept, [num_samples], stats)
-        kwargs.update(source=source, keep=keep, start_step=start_step, skip=skip)
-    x_T = randn_clips(1, padded, codes.device, seed, clip_offset)
-    sample, sampler_kw = pick_sampler(model.diffusion, sampler, eta, windows=True)
-    out = sample(x_T, predictor, steps, window=window, hop=hop, window_batch=window_batch, constrain=constrain, cond_fn=cond_fn, seed=seed,
-                 clip_offset=clip_offset, progress=progress, **sampler_kw, **kwargs)
-    model.predictor.check_status()  # range guard of the decoder's mode (once per sample)
-    return out[..., :num_samples]
+    return _decode(model, codes, labels, None, [num_samples], True, None if source is None else [source], [keep], start_step, kwargs,
+                   window=window, hop=hop, steps=steps, progress=progress, constrain=constrain, enc_pred=enc_pred, enc_pred_scale=enc_pred_scale,
+                   seed=seed, clip_offset=clip_offset, window_batch=window_batch, sampler=sampler, eta=eta, guidance=guidance, vectors=vectors,
+                   keep_pauses=keep_pauses, skip_kept=skip_kept, stats=stats)
 
 
 def decode_long_batch(model, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, *, counts: Sequence[int], num_samples: Sequence[int],
@@ -629,54 +640,12 @@ def decode_long_batch(model, codes: torch.Tensor, labels: Optional[torch.Tensor]
     of `keeps` may be None), `strength`, `keep_pauses`, `skip_kept` and `stats` are `decode_long`'s: rows are zero-padded as there, the
     detector sees the padded rows, and the kept samples are replaced by `vqvs_keep_region_windows_packed`.  `guidance` (label_scale,
     vq_scale) is `decode_long`'s, what `VQVAE.decode_long_batch_uncond_guidance` passes."""
-    from .diffusion import fresh_seed, pick_sampler, randn_clips, strength_to_start_step
-    from .vq_vae import one_voice
+    from .diffusion import strength_to_start_step
 
     start_step = strength_to_start_step(strength, steps)
     if sources is None and (keeps is not None or start_step or keep_pauses is not None):
         raise ValueError("keeps=, strength < 1 and keep_pauses= need sources=, the waveforms whose samples are kept or noised")
-    cond_seq = model.cond_sequence(codes)
-    check_rate(model, window, hop)
-    counts, num_samples = [int(c) for c in counts], [int(n) for n in num_samples]
-    planned, offsets, total = plan_pack(num_samples, window, hop)
-    if planned != counts:
-        raise ValueError(f"recordings of {num_samples} samples in windows of {window} every {hop} are {planned} windows, not counts={counts}")
-    N, R = sum(counts), len(counts)
-    if cond_seq.shape[0] != N:
-        raise ValueError(f"counts={counts} are {N} windows; codes hold {cond_seq.shape[0]}")
-    if codes.shape[-1] * model.encoder.downsample_rate != window:
-        raise ValueError(f"codes of length {codes.shape[-1]} describe {codes.shape[-1] * model.encoder.downsample_rate} samples, not window={window}")
-    one_voice(labels, vectors)
-    if vectors is not None:
-        vectors = _window_vectors(vectors, N, counts)
-    if labels is not None:
-        labels = labels.reshape(-1)
-        if labels.numel() == 1:
-            labels = labels.expand(N)
-        elif labels.numel() == R:
-            labels = labels.repeat_interleave(torch.tensor(counts, device=labels.device))
-        if labels.shape != (N,):
-            raise ValueError(f"labels must hold one label, one per recording ({R}) or one per window ({N}), got {labels.numel()}")
-        labels = labels.contiguous()
-    predictor, cond_fn = _conditioned(model, cond_seq, labels, enc_pred, enc_pred_scale, guidance, vectors)
-    if seed is None:
-        seed = fresh_seed()
-    padded = [(c - 1) * hop + window for c in counts]
-    pack_kw = {}
-    if sources is not None:
-        if len(sources) != R or (keeps is not None and len(keeps) != R):
-            raise ValueError(f"sources (and keeps) must hold one entry per recording ({R})")
-        rows = [pad_source_keep(sources[r], None if keeps is None else keeps[r], num_samples[r], padded[r]) for r in range(R)]
-        source = torch.cat([s for s, _ in rows], dim=-1)
-        keep = None
-        if any(k is not None for _, k in rows):
-            keep = torch.cat([torch.zeros(1, 1, padded[r], dtype=torch.uint8, device=source.device) if k is None else k
-                              for r, (_, k) in enumerate(rows)], dim=-1)
-        keep, skip = _pause_keep_and_skip(source, keep, counts, window, hop, keep_pauses, skip_kept, num_samples, stats)
-        pack_kw = dict(pack_source=source, pack_keep=keep, pack_start_step=start_step, skip=skip)
-    x_T = torch.cat([randn_clips(1, padded[r], codes.device, seed, clip_offset + r) for r in range(R)], dim=-1)
-    sample, sampler_kw = pick_sampler(model.diffusion, sampler, eta, windows=True)
-    out = sample(x_T, predictor, steps, window=window, hop=hop, window_batch=window_batch, constrain=constrain, cond_fn=cond_fn, seed=seed,
-                 clip_offset=clip_offset, progress=progress, counts=counts, **sampler_kw, **pack_kw)
-    model.predictor.check_status()  # range guard of the decoder's mode (once per sample)
-    return [out[..., o:o + n].clone() for o, n in zip(offsets, num_samples)]
+    return _decode(model, codes, labels, counts, num_samples, False, sources, keeps, start_step, {},
+                   window=window, hop=hop, steps=steps, progress=progress, constrain=constrain, enc_pred=enc_pred, enc_pred_scale=enc_pred_scale,
+                   seed=seed, clip_offset=clip_offset, window_batch=window_batch, sampler=sampler, eta=eta, guidance=guidance, vectors=vectors,
+                   keep_pauses=keep_pauses, skip_kept=skip_kept, stats=stats)

@@ -12,11 +12,12 @@ recording's mask does not depend on the pack it is in.
 from __future__ import annotations
 
 import math
-from typing import Optional, Sequence, Tuple
+from typing import Sequence
 
 import torch
 
 from . import _native
+from .longform import pack_table
 
 FULL_SCALE_ENERGY = 1 << 30  # the energy per sample of a full-scale square wave: 32768^2
 
@@ -29,20 +30,13 @@ def threshold_energy(db: float) -> int:
     return int(math.floor(FULL_SCALE_ENERGY * 10.0 ** (db / 10.0)))
 
 
-def _pack(counts: Sequence[int], window: int, hop: int, device) -> Tuple[torch.Tensor, int, int, int]:
-    from .longform import pack_layout
-
-    first, _, total = pack_layout(counts, window, hop)
-    return torch.tensor(first, dtype=torch.int32, device=device), len(first) - 1, first[-1], total
-
-
 def pause_mask(rows: torch.Tensor, counts: Sequence[int], window: int, hop: int, *, threshold_db: float, frame: int = 160,
                min_pause_frames: int = 30, guard_frames: int = 5, return_counts: bool = False):
     """rows [1,1,total] float32: the padded source rows of a pack of recordings of `counts` windows each, end to end (`plan_pack`) ->
     the uint8 mask [1,1,total] of the samples that lie in a pause.  With `return_counts` also an int64 [R,2] tensor: kept samples
     and pauses per recording."""
     _native.require_cuda(rows)
-    first, R, _, total = _pack(counts, window, hop, rows.device)
+    first, R, _, _, total = pack_table(counts, window, hop, rows.device)
     if rows.dim() != 3 or rows.shape[0] != 1 or rows.shape[1] != 1 or rows.shape[2] != total:
         raise ValueError(f"rows must be [1, 1, {total}] (recordings of {list(counts)} windows of {window} every {hop}), got {tuple(rows.shape)}")
     x = rows.detach().to(torch.float32).contiguous()
@@ -58,7 +52,7 @@ def pause_mask(rows: torch.Tensor, counts: Sequence[int], window: int, hop: int,
 def windows_kept(keep: torch.Tensor, counts: Sequence[int], window: int, hop: int) -> torch.Tensor:
     """keep [1,1,total] bool or uint8 in pack layout -> uint8 [N]: 1 for a window whose every sample is kept."""
     _native.require_cuda(keep)
-    first, R, N, total = _pack(counts, window, hop, keep.device)
+    first, R, N, _, total = pack_table(counts, window, hop, keep.device)
     if keep.dtype not in (torch.bool, torch.uint8):
         raise ValueError(f"keep must be a bool or uint8 tensor, got {keep.dtype}")
     if keep.numel() != total:

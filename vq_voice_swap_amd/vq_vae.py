@@ -301,9 +301,7 @@ class VQVAE(DiffusionModel):
         Labels are NOT offset by the caller.  With one window the result is `decode_uncond_guidance`'s, bit for bit."""
         from .longform import decode_long
 
-        one_voice(labels, vectors)
-        with self.guidance_precision(_guided(vectors if labels is None else labels, label_scale, vq_scale), "decode_long_uncond_guidance"):
-            return decode_long(self, codes, labels, vectors=vectors, guidance=(label_scale, vq_scale), **kwargs)
+        return self._decode_long_guided(decode_long, "decode_long_uncond_guidance", codes, labels, label_scale, vq_scale, vectors, kwargs)
 
     def decode_long_batch_uncond_guidance(self, codes: torch.Tensor, labels: Optional[torch.Tensor] = None, *, label_scale: float = 0.0,
                                           vq_scale: float = 0.0, vectors: Optional[torch.Tensor] = None, **kwargs):
@@ -312,9 +310,14 @@ class VQVAE(DiffusionModel):
         clip_offset + r, bit for bit."""
         from .longform import decode_long_batch
 
+        return self._decode_long_guided(decode_long_batch, "decode_long_batch_uncond_guidance", codes, labels, label_scale, vq_scale, vectors, kwargs)
+
+    def _decode_long_guided(self, decode, what: str, codes, labels, label_scale, vq_scale, vectors, kwargs):
+        """`decode` (longform.decode_long or decode_long_batch) with the guided window predictor, in the precision a guided call takes;
+        `what` names the caller in the precision warning (stacklevel 5: addressed to that caller's caller)."""
         one_voice(labels, vectors)
-        with self.guidance_precision(_guided(vectors if labels is None else labels, label_scale, vq_scale), "decode_long_batch_uncond_guidance"):
-            return decode_long_batch(self, codes, labels, vectors=vectors, guidance=(label_scale, vq_scale), **kwargs)
+        with self.guidance_precision(_guided(vectors if labels is None else labels, label_scale, vq_scale), what, stacklevel=5):
+            return decode(self, codes, labels, vectors=vectors, guidance=(label_scale, vq_scale), **kwargs)
 
     @property
     def downsample_rate(self) -> int:
