@@ -752,6 +752,26 @@ int vqvs_debug_read_dfilm(vqvs_model* m, int B, float* h_out);
  * the order down_blocks, middle_blocks, up_blocks, 2 * cout rows each (physical widths on a padded handle) -- to host as float32
  * [B][R]; returns R; synchronises.  VQVS_ERR_STATE on a model kind without a FiLM table */
 int vqvs_debug_read_film(vqvs_model* m, int B, float* h_out);
+/* GroupNorm i (schedule order, 0..count-1) of a handle created with debug_taps = 1 -- other handles count 0 and every entry below
+ * returns VQVS_ERR_STATE -- as the LAST forward at (B, T) ran it.  Read-only: no entry changes the arena or the status word.
+ * info (24 x int64): [0] Ctot, [1] groups, [2] values per group behind inv_count = (real channels per group) * rows, [3] FiLM applies,
+ * [4] its offset into a clip's FiLM rows (a at [4] .. [4] + Ctot, b behind them), [5] sources (1, or 2 for a GroupNorm over a
+ * concatenation), [6] the schedule keeps a (mean, rstd) table, [7] the consuming convolution built the (scale, shift) table itself
+ * at this (B, T) -- then the global table was not written --, and per source s at [8 + 4 s ..]: C, rows per clip, rows per
+ * statistics tile of its producer, tiles per clip; at [16 + s]: its producer summed the values as STORED (0: the float32 values before
+ * they were rounded to a 2-byte storage type -- in_conv_kernel and conv_mfma_kernel in the bf16 / fp16 modes). */
+int vqvs_debug_gn_count(const vqvs_model* m);
+int vqvs_debug_gn_info(vqvs_model* m, int i, int B, int T, char* name_out, int name_cap, int64_t* info);
+/* what 0: source `src` as stored, float32 NCT [B][C][rows];  1: its tile partials (sum x, sum x^2) [B][tiles][C][2];
+ * 2: the (scale, shift) table [B][Ctot][2] -- where info[7] is set, what the schedule's gn_prepare launch makes of the resident
+ * partials, written to a scratch table --;  3: the (mean, rstd) table [B][Ctot][2] (VQVS_ERR_STATE without one).  Synchronises. */
+int vqvs_debug_gn_read(vqvs_model* m, int i, int B, int T, int what, int src, float* h_out);
+/* xform entry i (the stand-alone gelu(scale * x + shift) [+ avg_pool(2)] pass in front of some convolutions), same rules.
+ * info (8 x int64): [0] GroupNorm whose table it reads, [1] C, [2] input rows, [3] output rows, [4] avg, [5] the table's row stride,
+ * [6] its first column.  vqvs_debug_xform_read: the input (output = 0) or output (1) tensor as float32 NCT. */
+int vqvs_debug_xform_count(const vqvs_model* m);
+int vqvs_debug_xform_info(vqvs_model* m, int i, int B, int T, int64_t* info);
+int vqvs_debug_xform_read(vqvs_model* m, int i, int B, int T, int output, float* h_out);
 /* handle-less: d_out[i] = one of the library's GELU device functions (csrc/common.hpp) of d_in[i], n float32 device values each.
  * form 0: gelu_f; 1, 2, 3: gelu2 at GELU_EXACT, GELU_POLY6, GELU_POLY7 (the fp32, bf16 and fp16 modes' prologues), evaluated on the
  * pairs (2i, 2i+1) as the prologues evaluate them, an odd tail paired with 0; 4: gelu_grad_f.  VQVS_ERR_ARG before the device is

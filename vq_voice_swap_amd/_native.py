@@ -78,6 +78,7 @@ EXPORTS = [
     "vqvs_unet_embed_grad", "vqvs_embed_adamw", "vqvs_debug_read_dfilm", "vqvs_head_xent_grad", "vqvs_head_adamw",
     "vqvs_mel_cepstra", "vqvs_dtw_distance", "vqvs_guidance_mix", "vqvs_unet_forward_vec", "vqvs_speaker_mix",
     "vqvs_debug_read_film", "vqvs_debug_gelu",
+    "vqvs_debug_gn_count", "vqvs_debug_gn_info", "vqvs_debug_gn_read", "vqvs_debug_xform_count", "vqvs_debug_xform_info", "vqvs_debug_xform_read",
     "vqvs_keep_region_windows_packed", "vqvs_pause_mask", "vqvs_windows_kept",
 ]
 
@@ -139,6 +140,12 @@ def lib():
     L.vqvs_debug_read_dfilm.argtypes = [vp, i32, vp]
     L.vqvs_debug_read_film.argtypes = [vp, i32, vp]
     L.vqvs_debug_gelu.argtypes = [vp, vp, i32, i32, vp]
+    L.vqvs_debug_gn_count.argtypes = [vp]
+    L.vqvs_debug_gn_info.argtypes = [vp, i32, i32, i32, C.c_char_p, i32, C.POINTER(i64)]
+    L.vqvs_debug_gn_read.argtypes = [vp, i32, i32, i32, i32, i32, vp]
+    L.vqvs_debug_xform_count.argtypes = [vp]
+    L.vqvs_debug_xform_info.argtypes = [vp, i32, i32, i32, C.POINTER(i64)]
+    L.vqvs_debug_xform_read.argtypes = [vp, i32, i32, i32, i32, vp]
     L.vqvs_head_xent_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     L.vqvs_head_adamw.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp]
     L.vqvs_encoder_forward.argtypes = [vp, vp, vp, i32, i32, vp]
@@ -376,6 +383,56 @@ class Handle:
         if r < 0:
             check(r)
         assert r == R, (r, R)
+        return out
+
+    # ---- GroupNorm / xform entries of a debug_taps handle, as the last forward at (B, T) ran them (include/vqvs.h)
+    def gn_count(self) -> int:
+        return int(lib().vqvs_debug_gn_count(self._h))
+
+    def gn_info(self, i: int, B: int, T: int) -> dict:
+        name = C.create_string_buffer(256)
+        v = (C.c_int64 * 24)()
+        check(lib().vqvs_debug_gn_info(self._h, i, B, T, name, 256, v))
+        srcs = [dict(C=int(v[8 + 4 * s]), rows=int(v[9 + 4 * s]), tile_rows=int(v[10 + 4 * s]), ntiles=int(v[11 + 4 * s]), sums_stored=bool(v[16 + s]))
+                for s in range(int(v[5]))]
+        return dict(name=name.value.decode(), Ctot=int(v[0]), groups=int(v[1]), count=int(v[2]), film=bool(v[3]), film_off=int(v[4]),
+                    has_mr=bool(v[6]), fused=bool(v[7]), srcs=srcs)
+
+    def _gn_read(self, i: int, B: int, T: int, what: int, src: int, shape):
+        import torch
+
+        out = torch.empty(*shape, dtype=torch.float32)
+        check(lib().vqvs_debug_gn_read(self._h, i, B, T, what, src, out.data_ptr()))
+        return out
+
+    def gn_source(self, i: int, B: int, T: int, src: int = 0):
+        """Source `src` of GroupNorm i as stored, float32 [B, C, rows]."""
+        s = self.gn_info(i, B, T)["srcs"][src]
+        return self._gn_read(i, B, T, 0, src, (B, s["C"], s["rows"]))
+
+    def gn_partials(self, i: int, B: int, T: int, src: int = 0):
+        """Its tile partials (sum x, sum x^2), float32 [B, ntiles, C, 2]."""
+        s = self.gn_info(i, B, T)["srcs"][src]
+        return self._gn_read(i, B, T, 1, src, (B, s["ntiles"], s["C"], 2))
+
+    def gn_table(self, i: int, B: int, T: int, mean_rstd: bool = False):
+        """(scale, shift) -- or (mean, rstd) -- of GroupNorm i, float32 [B, Ctot, 2]."""
+        return self._gn_read(i, B, T, 3 if mean_rstd else 2, 0, (B, self.gn_info(i, B, T)["Ctot"], 2))
+
+    def xform_count(self) -> int:
+        return int(lib().vqvs_debug_xform_count(self._h))
+
+    def xform_info(self, i: int, B: int, T: int) -> dict:
+        v = (C.c_int64 * 8)()
+        check(lib().vqvs_debug_xform_info(self._h, i, B, T, v))
+        return dict(gn=int(v[0]), C=int(v[1]), Lin=int(v[2]), Lout=int(v[3]), avg=bool(v[4]), ss_stride=int(v[5]), ss_c0=int(v[6]))
+
+    def xform_tensor(self, i: int, B: int, T: int, output: bool):
+        import torch
+
+        x = self.xform_info(i, B, T)
+        out = torch.empty(B, x["C"], x["Lout"] if output else x["Lin"], dtype=torch.float32)
+        check(lib().vqvs_debug_xform_read(self._h, i, B, T, 1 if output else 0, out.data_ptr()))
         return out
 
     def read_tap(self, i: int, B: int, T: int):

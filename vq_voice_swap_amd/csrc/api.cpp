@@ -971,6 +971,134 @@ int vqvs_debug_read_film(vqvs_model* m, int B, float* h_out) {
   return m->film_R;
 }
 
+// ---- GroupNorm / xform debug entries (tests/test_groupnorm_gpu.py) -----------------------------------------------------------
+namespace {
+int debug_shape_ok(const vqvs_model* m, int B, int T) {
+  if (!m) VQVS_FAIL(VQVS_ERR_ARG, "model is NULL");
+  if (!m->cfg.debug_taps) VQVS_FAIL(VQVS_ERR_STATE, "model was not created with debug_taps=1");
+  if (B < 1 || B > m->cfg.max_batch || T < 1 || T > m->cfg.max_T) VQVS_FAIL(VQVS_ERR_ARG, "B=%d T=%d outside the handle's 1..%d x 1..%d", B, T, m->cfg.max_batch, m->cfg.max_T);
+  return 0;
+}
+RunCtx debug_ctx(int B, int T) {
+  RunCtx c;
+  c.B = B;
+  c.Lbase = T;
+  return c;
+}
+// an arena tensor [B][L][C] of the handle's storage type -> host float32 NCT [B][C][L]
+int debug_read_tensor(vqvs_model* m, const TensorH& t, int B, int T, float* h_out) {
+  const int L = tensor_rows(T, t.lshift);
+  const size_t n = (size_t)B * t.C * L;
+  float* d_tmp = nullptr;
+  VQVS_HIP(hipSetDevice(m->device));
+  VQVS_HIP(hipMalloc(reinterpret_cast<void**>(&d_tmp), n * 4));
+  int e = launch_ntc_to_nct(m->d_arena + t.off, d_tmp, B, t.C, L, t.f32 ? 0 : m->cfg.precision, nullptr);
+  if (!e && hipMemcpy(h_out, d_tmp, n * 4, hipMemcpyDeviceToHost) != hipSuccess) {
+    set_error("hipMemcpy failed");
+    e = VQVS_ERR_HIP;
+  }
+  (void)hipFree(d_tmp);
+  return e;
+}
+}  // namespace
+
+int vqvs_debug_gn_count(const vqvs_model* m) { return m ? (int)m->gns.size() : 0; }
+
+int vqvs_debug_gn_info(vqvs_model* m, int i, int B, int T, char* name_out, int name_cap, int64_t* info) {
+  if (int e = debug_shape_ok(m, B, T)) return e;
+  if (i < 0 || i >= (int)m->gns.size() || !info) VQVS_FAIL(VQVS_ERR_ARG, "bad GroupNorm index or NULL info");
+  const GnDef& g = m->gns[i];
+  if (name_out && name_cap > 0) {
+    strncpy(name_out, g.name.c_str(), name_cap - 1);
+    name_out[name_cap - 1] = 0;
+  }
+  const int L = tensor_rows(T, g.lshift);
+  info[0] = g.Ctot;
+  info[1] = g.groups;
+  info[2] = (int64_t)g.cpg_real * L;
+  info[3] = g.film ? 1 : 0;
+  info[4] = g.film_off;
+  info[5] = (int64_t)g.srcs.size();
+  info[6] = g.has_mr ? 1 : 0;
+  info[7] = g.fused(debug_ctx(B, T)) ? 1 : 0;
+  for (size_t s = 0; s < 2; ++s) {
+    const bool on = s < g.srcs.size();
+    const int rows = on ? tensor_rows(T, g.srcs[s].lshift) : 0;
+    info[8 + 4 * s] = on ? g.srcs[s].C : 0;
+    info[9 + 4 * s] = rows;
+    info[10 + 4 * s] = on ? g.tile_rows[s] : 0;
+    info[11 + 4 * s] = on ? (rows + g.tile_rows[s] - 1) / g.tile_rows[s] : 0;
+    info[16 + s] = on && g.sums_stored[s](debug_ctx(B, T)) ? 1 : 0;
+  }
+  return 0;
+}
+
+int vqvs_debug_gn_read(vqvs_model* m, int i, int B, int T, int what, int src, float* h_out) {
+  if (int e = debug_shape_ok(m, B, T)) return e;
+  if (i < 0 || i >= (int)m->gns.size() || !h_out) VQVS_FAIL(VQVS_ERR_ARG, "bad GroupNorm index or NULL h_out");
+  const GnDef& g = m->gns[i];
+  if (what < 0 || what > 3) VQVS_FAIL(VQVS_ERR_ARG, "what=%d outside 0..3", what);
+  if (what <= 1 && (src < 0 || src >= (int)g.srcs.size())) VQVS_FAIL(VQVS_ERR_ARG, "source %d of a GroupNorm over %d", src, (int)g.srcs.size());
+  VQVS_HIP(hipSetDevice(m->device));
+  VQVS_HIP(hipDeviceSynchronize());
+  if (what == 0) return debug_read_tensor(m, g.srcs[src], B, T, h_out);
+  if (what == 1) {
+    const TensorH& t = g.srcs[src];
+    const int rows = tensor_rows(T, t.lshift), nt = (rows + g.tile_rows[src] - 1) / g.tile_rows[src];
+    const float* p = reinterpret_cast<const float*>(m->d_arena + m->stats_off) + t.stats_off;
+    VQVS_HIP(hipMemcpy(h_out, p, (size_t)B * nt * t.C * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+  }
+  if (what == 3 && !g.has_mr) VQVS_FAIL(VQVS_ERR_STATE, "the schedule keeps no (mean, rstd) table for this GroupNorm");
+  const size_t bytes = (size_t)B * g.Ctot * 2 * sizeof(float);
+  const RunCtx c = debug_ctx(B, T);
+  if (what == 2 && g.fused(c)) {
+    // the consuming convolution built this call's table in LDS: the schedule's own gn_prepare launch, on the resident partials, into
+    // a scratch table (the status word is left alone: reading does not change what vqvs_model_status reports)
+    GnArgs a{};
+    g.fill(c, a);
+    float2* d_tmp = nullptr;
+    VQVS_HIP(hipMalloc(reinterpret_cast<void**>(&d_tmp), bytes));
+    a.ss = d_tmp;
+    a.mr = nullptr;
+    a.status = nullptr;
+    int e = launch_gn_prepare(a, B, nullptr);
+    if (!e && hipMemcpy(h_out, d_tmp, bytes, hipMemcpyDeviceToHost) != hipSuccess) {
+      set_error("hipMemcpy failed");
+      e = VQVS_ERR_HIP;
+    }
+    (void)hipFree(d_tmp);
+    return e;
+  }
+  const float* p = reinterpret_cast<const float*>(m->d_arena + m->ss_off) + (what == 2 ? g.ss_off : g.mr_off);
+  VQVS_HIP(hipMemcpy(h_out, p, bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int vqvs_debug_xform_count(const vqvs_model* m) { return m ? (int)m->xforms.size() : 0; }
+
+int vqvs_debug_xform_info(vqvs_model* m, int i, int B, int T, int64_t* info) {
+  if (int e = debug_shape_ok(m, B, T)) return e;
+  if (i < 0 || i >= (int)m->xforms.size() || !info) VQVS_FAIL(VQVS_ERR_ARG, "bad xform index or NULL info");
+  const XformDef& x = m->xforms[i];
+  info[0] = x.gn;
+  info[1] = x.in.C;
+  info[2] = tensor_rows(T, x.in.lshift);
+  info[3] = tensor_rows(T, x.out.lshift);
+  info[4] = x.avg ? 1 : 0;
+  info[5] = x.ss_stride;
+  info[6] = x.ss_c0;
+  return 0;
+}
+
+int vqvs_debug_xform_read(vqvs_model* m, int i, int B, int T, int output, float* h_out) {
+  if (int e = debug_shape_ok(m, B, T)) return e;
+  if (i < 0 || i >= (int)m->xforms.size() || !h_out) VQVS_FAIL(VQVS_ERR_ARG, "bad xform index or NULL h_out");
+  VQVS_HIP(hipSetDevice(m->device));
+  VQVS_HIP(hipDeviceSynchronize());
+  return debug_read_tensor(m, output ? m->xforms[i].out : m->xforms[i].in, B, T, h_out);
+}
+
 int vqvs_debug_gelu(const float* d_in, float* d_out, int n, int form, void* stream) {
   if (!d_in || !d_out) VQVS_FAIL(VQVS_ERR_ARG, "d_in and d_out must be non-NULL");
   if (n < 1 || n > (1 << 30)) VQVS_FAIL(VQVS_ERR_ARG, "n=%d outside 1..2^30", n);

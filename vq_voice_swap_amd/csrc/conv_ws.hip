@@ -1491,6 +1491,11 @@ bool ws_fuses_gn(const ConvArgs& a, int B, int precision) {
   return a.gn != nullptr && ws_plan(a, B, precision, plan) && plan.gn;
 }
 
+bool ws_takes(const ConvArgs& a, int B, int precision) {  // (host-side query for the debug entries: plans, launches nothing)
+  WsPlan plan;
+  return ws_plan(a, B, precision, plan) && !(a.gn != nullptr && !plan.gn);
+}
+
 int launch_conv_ws(const ConvArgs& a, int B, int precision, hipStream_t st) {
   WsPlan plan;
   if (!ws_plan(a, B, precision, plan)) return 0;

@@ -242,7 +242,9 @@ __global__ __launch_bounds__(256) void gn_prepare_kernel(const GnArgs a) {
         for (int k = 0; k < 8; ++k) {
           s1 += (double)q[k].x;
           s2 += (double)q[k].y;
-          // range guard (the statistics are fp32 sums of the stored values): a non-finite partial means an activation overflowed
+          // range guard.  The statistics are fp32 sums of the stored values where conv_ws_kernel or ntc_stats_kernel made them; the
+          // stem (in_conv_kernel) and conv_mfma_kernel sum their float32 values BEFORE store8 rounds them to a 2-byte type (at most
+          // 2^-11 per value off the stored ones: tests/groupnorm_ref.py bounds it).  A non-finite partial means an activation overflowed
           // the storage type; in the fp16 mode a tile whose sum of squares reaches 9e8 may hold an element beyond 3e4 (of 65504)
           if (!(fabsf(q[k].x) <= 3.0e38f) || !(q[k].y <= 3.0e38f)) bad |= 1u;
           if (a.guard && q[k].y >= 9.0e8f) bad |= 2u;

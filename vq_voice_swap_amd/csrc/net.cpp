@@ -420,6 +420,30 @@ class Builder {
       a.status = reinterpret_cast<unsigned*>(self->miscp(st_off));
       a.guard = guard;
     };
+    if (m_->cfg.debug_taps) {  // (read-only record for vqvs_debug_gn_*: nothing the schedule runs depends on it)
+      GnDef d;
+      d.name = gn_name;
+      d.srcs = S;
+      d.tile_rows = SR;
+      for (auto& t : srcs) {
+        std::function<bool(const RunCtx&)> f = [](const RunCtx&) { return true; };  // (ntc_stats_kernel reads the tensor back)
+        if (sums_stored_.count(t.id)) f = sums_stored_.at(t.id);
+        d.sums_stored.push_back(f);
+      }
+      d.Ctot = Ctot;
+      d.groups = groups;
+      d.cpg_real = Creal / groups;
+      d.lshift = lshift;
+      d.film = film;
+      d.film_off = film_off;
+      d.film_stride = film_stride;
+      d.ss_off = ss_off;
+      d.mr_off = mr_off;
+      d.has_mr = want_mr;
+      d.fused = [link](const RunCtx& c) { return link->fused && link->fused(c); };
+      d.fill = [link](const RunCtx& c, GnArgs& a) { link->fill(c, a); };
+      m_->gns.push_back(std::move(d));
+    }
     op("gn_prepare", gn_name + " C=" + std::to_string(Ctot) + " L>>" + std::to_string(lshift), 0, 0, 0, [=](const RunCtx& c) -> int {
       if (link->fused && link->fused(c)) return 0;
       GnArgs a{};
@@ -435,6 +459,17 @@ class Builder {
     Builder* self = this;
     const int prec = m_->cfg.precision;
     const TensorH S = src;
+    if (m_->cfg.debug_taps) {
+      XformDef d;
+      d.in = src;
+      d.out = g;
+      d.avg = avg;
+      d.ss_stride = ss_stride;
+      d.ss_c0 = ss_c0;
+      for (size_t i = 0; i < m_->gns.size(); ++i)
+        if (m_->gns[i].ss_off == ss_off) d.gn = (int)i;
+      m_->xforms.push_back(d);
+    }
     op("xform", "C=" + std::to_string(src.C) + " L>>" + std::to_string(g.lshift) + (avg ? " avg" : ""),
        src.C * (lscale(src.lshift) + lscale(g.lshift)), 0, 0, [=](const RunCtx& c) -> int {
       XformArgs a{};
@@ -605,6 +640,19 @@ class Builder {
         return ws_fuses_gn(a, c.B, prec);
       };
     }
+    if (m_->cfg.debug_taps && out.has_stats)  // (for vqvs_debug_gn_info: which kernel this launch's statistics come from)
+      sums_stored_[out.id] = [=](const RunCtx& c) -> bool {
+        if (x3) return true;  // (float32 storage: the accumulators are what is stored)
+        ConvArgs a{};
+        build(c, a);
+        GnArgs g{};
+        if (gn) {
+          gn->fill(c, g);
+          a.gn = &g;
+          if (!ws_fuses_gn(a, c.B, prec)) a.gn = nullptr;
+        }
+        return ws_takes(a, c.B, prec);
+      };
     op("conv", desc, conv_elems, conv_f32, conv_flops, [=](const RunCtx& c) -> int {
       ConvArgs a{};
       build(c, a);
@@ -1018,6 +1066,7 @@ class Builder {
     const bool has_cond = condp != nullptr;
     const TensorH cp = condp ? *condp : TensorH{};
     Builder* self = this;
+    if (m_->cfg.debug_taps) sums_stored_[h.id] = [prec](const RunCtx&) { return prec == VQVS_PREC_F32; };
     op("in_conv", std::to_string(row_cin) + "->" + std::to_string(base), base + (has_cond ? base * lscale(cp.lshift) : 0.0), 4.0 * row_cin, 0,
        [=](const RunCtx& r) -> int {
       InConvArgs a{};
@@ -1084,6 +1133,7 @@ class Builder {
   }
 
   void tap(const std::string& name, const TensorH& t) { m_->taps.push_back({name, t}); }
+  std::map<int, std::function<bool(const RunCtx&)>> sums_stored_;  // debug_taps handles: by tensor id (GnDef.sums_stored)
 
   // region sizes after planning
   size_t act_high = 0, stats_floats = 0, ss_floats = 0, misc_floats = 0;

@@ -67,6 +67,30 @@ struct TapDef {
   TensorH t;
 };
 
+// What the debug entries of include/vqvs.h (vqvs_debug_gn_*, vqvs_debug_xform_*) need to know about one GroupNorm / one xform entry of
+// the schedule; recorded by Builder::add_gn / add_xform on handles created with debug_taps = 1, in schedule order.
+struct GnDef {
+  std::string name;
+  std::vector<TensorH> srcs;   // 1 tensor, or 2 for a GroupNorm over torch.cat
+  std::vector<int> tile_rows;  // rows per statistics tile of each source's producer
+  // per source: did its producer sum the values as STORED at this (B, L)?  (false: the float32 values before they were rounded to a
+  // 2-byte storage type -- in_conv_kernel and conv_mfma_kernel; conv_ws_kernel and ntc_stats_kernel sum what they store)
+  std::vector<std::function<bool(const RunCtx&)>> sums_stored;
+  int Ctot = 0, groups = 0, cpg_real = 0, lshift = 0;  // cpg_real: channels per group at the REAL width (inv_count = 1 / (cpg_real * L))
+  bool film = false;
+  int film_off = 0, film_stride = 0;
+  size_t ss_off = 0, mr_off = 0;  // float offsets in the ss region
+  bool has_mr = false;
+  std::function<bool(const RunCtx&)> fused;            // did the consuming convolution build the table itself at this (B, L)?
+  std::function<void(const RunCtx&, GnArgs&)> fill;    // the arguments the schedule's gn_prepare entry launches with
+};
+struct XformDef {
+  TensorH in, out;
+  bool avg = false;
+  int gn = -1;  // index of the GroupNorm whose table it reads
+  int ss_stride = 0, ss_c0 = 0;
+};
+
 }  // namespace vqvs
 
 struct vqvs_model {
@@ -95,6 +119,8 @@ struct vqvs_model {
   bool profiling = false;
   std::vector<hipEvent_t> events;  // ops.size() + 1 when profiling
   std::vector<vqvs::TapDef> taps;
+  std::vector<vqvs::GnDef> gns;        // debug_taps handles only
+  std::vector<vqvs::XformDef> xforms;  // debug_taps handles only
   // accounting (per clip, per unit of base length): elements moved / flops, as (coefficient, lshift) lists
   struct Cost {
     double elems_T = 0;    // activation elements of type T moved per clip at Lbase = 1 (scaled by L)
