@@ -112,6 +112,11 @@ typedef struct vqvs_cfg {
 } vqvs_cfg;
 #define VQVS_MAX_LEVELS 12
 
+/* The padded-width rule of reserved[4], for callers that lay parameters out: *q and *q_p of a REAL base_channels (q_p == q for a multiple
+ * of 32: nothing is padded); the physical width is real / q * q_p.  Host arithmetic only, no device is touched.  VQVS_ERR_ARG:
+ * real_base_channels < 1 or a NULL output. */
+int vqvs_pad_blocks(int real_base_channels, int* q, int* q_p);
+
 /* ---- parameters -----------------------------------------------------------
  * The library owns the topology.  It enumerates the parameters it needs under
  * the reference's own state-dict key names (checkpoint format = reference
@@ -789,6 +794,15 @@ int vqvs_set_profiling(vqvs_model* m, int on);
 int vqvs_op_info(const vqvs_model* m, int i, char* kind_out, int kind_cap, int64_t* bytes_out, int64_t* flops_out, int B, int T);
 int vqvs_op_desc(const vqvs_model* m, int i, char* out, int cap);
 int vqvs_profile_read(vqvs_model* m, float* h_ms, int cap);
+/* In-kernel phase counters of the instrumented build (`make -C vq_voice_swap_amd/csrc timing`, -DVQVS_TIMING: libvqvs_timing.so), summed
+ * over the sampled waves of every launch since the last reset and copied to host; reset != 0 clears them; synchronises the device.
+ * Every other build exports the two entries and returns VQVS_ERR_STATE.
+ * conv_timing (conv_mfma.hip): 24 x uint64 -- [0..17] shader-clock ticks per phase (tools/conv_phases.py names them), [18..21] spread
+ * of the workgroups' starts and ends in 100 MHz ticks, [23] sampled waves.
+ * ws_timing (conv_ws.hip): 32 x uint64 -- [0..4] producer phases, [8..14] consumer phases (tools/ws_phases.py), [16] / [17] sampled
+ * producer / consumer waves, [18] steps, [19] tiles, [20] / [21] shader-clock and 100 MHz ticks per workgroup, [22..25] startup. */
+int vqvs_debug_conv_timing(unsigned long long* h_counters, int reset);
+int vqvs_debug_ws_timing(unsigned long long* h_counters, int reset);
 
 const char* vqvs_last_error(void);
 const char* vqvs_version(void);

@@ -100,7 +100,7 @@ def test_schedule_parser():
         parse_time_schedule("__import__('os').system('true')")
 
 
-def test_import_shim_paths():
+def test_import_shim_paths(lib_built):
     sys.path.insert(0, ROOT)
     from vq_voice_swap.dataset import ChunkWriter as W  # noqa: F401
     from vq_voice_swap.diffusion_model import DiffusionModel  # noqa: F401

@@ -15,7 +15,7 @@ REF_TOL = 2e-5
 
 
 @pytest.fixture(scope="module")
-def f64():
+def f64(lib_built):
     return {c["id"]: R.oracle(c, torch.float64) for c in R.CASES}
 
 

@@ -59,7 +59,7 @@ def test_native_classifier_vs_golden(golden, precision, tol_logit, tol_grad):
     assert torch.equal(clf.log_prob_grad(x, ts, labels, 1.0), grad)
 
 
-def test_load_from_predictor_copies_the_shared_stem():
+def test_load_from_predictor_copies_the_shared_stem(lib_built):
     """classifier.py:123-131: in_conv, the time embedding and the blocks that line up with the predictor's down path."""
     m = DiffusionModel("unet", 32)
     det_init_(m.state_dict().items())

@@ -37,7 +37,7 @@ def test_oracle_front_end_matches_independent_restatement(version):
     assert np.abs(got - want).max() <= 2e-3 * max(1.0, np.abs(want).max()), np.abs(got - want).max()
 
 
-def test_parameter_container_layout():
+def test_parameter_container_layout(lib_built):
     """State-dict keys and shapes a reference checkpoint of `VQVAE(enc_name="conv-mfcc-ulaw")` carries for its encoder
     (conv_encoder.py:42-88 plus the persistent buffers of torchaudio.transforms.MFCC)."""
     e = ConvMFCCEncoder(32, out_channels=512)

@@ -278,6 +278,8 @@ def test_clip_loop_hands_each_step_the_previous_x0(monkeypatch, host_loops):
         return x_t + 1, x0
 
     def keep_stub(x, source, keep, alpha, **kw):
+        if keep is None:  # the start at a later step: the call writes EVERY sample of a state that is uninitialised memory until then
+            x.copy_(source)
         log.append(dict(kind="keep", index=kw["index"], alpha=alpha, seed=kw["seed"], clip_offset=kw["clip_offset"]))
 
     def noise(i):
@@ -329,6 +331,8 @@ def test_window_loop_keeps_the_history_in_the_long_layout(monkeypatch, host_loop
         next_windows.copy_(longform.gather_windows(x_to, W, H))
 
     def keep_stub(*args, **kw):
+        if args[3] is None:  # the start at a later step: the call writes EVERY sample of a state that is uninitialised memory until then
+            args[0].copy_(args[2])
         log.append(dict(kind="keep", index=kw["index"], alpha=args[-1]))
 
     monkeypatch.setattr(longform, "dpmpp_step_windows_", stub)

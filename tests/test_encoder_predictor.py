@@ -19,7 +19,7 @@ def make_encpred(num_latents=96):
     return ep
 
 
-def test_encpred_oracle_matches_reference_golden(golden, tmp_path):
+def test_encpred_oracle_matches_reference_golden(golden, tmp_path, lib_built):
     z = golden("f10_encpred32")
     ep = make_encpred()
     sd = {k: v.detach() for k, v in ep.state_dict().items()}

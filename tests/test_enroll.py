@@ -40,7 +40,7 @@ def test_numpy_adamw_is_torch_adamw(wd):
     assert (ref[0][2] == rows0.numpy()[2]).all() == (wd == 0.0)  # the unnamed row moves by weight decay alone
 
 
-def test_reference_gradient_of_an_unnamed_row_is_zero():
+def test_reference_gradient_of_an_unnamed_row_is_zero(lib_built):
     case = R.CASE["pg_ragged"]
     r = R.reference(case)
     named = set(case["labels"])
@@ -61,7 +61,7 @@ def test_reference_gradient_of_an_unnamed_row_is_zero():
     assert bool(torch.isfinite(r["dfilm"][:, row + c]).all()) and r["dfilm"][:, row + c].abs().min() > 0
 
 
-def test_cases_are_the_shapes_they_claim():
+def test_cases_are_the_shapes_they_claim(lib_built):
     for cid, (B, T, blocks, E) in {"pg32": (3, 1792, 65, 128), "pg_ragged": (2, 592, 14, 128), "pg96": (2, 592, 14, 384)}.items():
         case = R.CASE[cid]
         x_t, ts, eps, cond, labels = R.inputs(case)
@@ -148,8 +148,9 @@ class _StubLib:
 
 
 @pytest.fixture
-def stubbed(monkeypatch):
+def stubbed(monkeypatch, lib_built):
     lib = _StubLib()
+    lib.vqvs_pad_blocks = lib_built.vqvs_pad_blocks  # (host arithmetic that constructing a model asks the library for)
     monkeypatch.setattr(_native, "lib", lambda: lib)
     monkeypatch.setattr(_native, "require_cuda", lambda *t: None)
     monkeypatch.setattr(_native, "_stream_ptr", lambda: None)
@@ -164,7 +165,7 @@ def _model(num_labels=4):
     return model.eval()
 
 
-def test_init_modes():
+def test_init_modes(lib_built):
     model = _model()
     old = model.predictor.class_embed.weight.detach().clone()
     a = enroll.SpeakerEnroller(model, 3, init="normal", seed=7).rows
@@ -225,7 +226,7 @@ def test_step_calls_and_resume_round_trip(stubbed, monkeypatch):
         enroll.SpeakerEnroller(_model(5), 3).load_state_dict(state)
 
 
-def test_finish_and_checkpoint_leave_the_old_rows_bitwise():
+def test_finish_and_checkpoint_leave_the_old_rows_bitwise(lib_built):
     model = _model()
     old = model.predictor.class_embed.weight.detach().clone()
     others = {k: v.clone() for k, v in model.state_dict().items() if k != "predictor.class_embed.weight"}

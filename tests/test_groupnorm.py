@@ -101,7 +101,7 @@ def test_reference_is_the_oracles_group_norm_in_float64(C, L):
     assert ((x * cf["scale"][:, :, None] + cf["shift"][:, :, None]) - wantf).abs().max().item() < 1e-11
 
 
-def test_reference_at_a_padded_width_and_over_a_concatenation():
+def test_reference_at_a_padded_width_and_over_a_concatenation(lib_built):
     """Physical channels in blocks of 4 of which 3 are real (base 48 -> 64): groups and count from the REAL width; two sources."""
     B, L, real = 2, 300, 96  # 2 x 48
     xr = pw.wave((B, real, L), 52).double()
@@ -217,7 +217,7 @@ GEOM = [  # (id, C per source, L, rows per tile per source, real base / physical
 
 @pytest.mark.parametrize("form", gr.FORMS)
 @pytest.mark.parametrize("geom", GEOM, ids=[g[0] for g in GEOM])
-def test_coefficient_bounds_hold_for_an_emulated_library_and_cover_every_input_form(geom, form):
+def test_coefficient_bounds_hold_for_an_emulated_library_and_cover_every_input_form(geom, form, lib_built):
     _id, Cs, L, rows, pad = geom
     B, Ctot = 2, sum(Cs)
     xs = [form_of(pw.wave((B, C, L), 80 + i), form).half().float() for i, C in enumerate(Cs)]
@@ -310,7 +310,7 @@ def test_defect_a_miscounted_row(geom):
     assert defect_factor(f"{geom[0]}: one halo row twice", *coef(s, twice), *s["want"]) >= FACTOR
 
 
-def test_defect_inv_count_from_the_padded_width():
+def test_defect_inv_count_from_the_padded_width(lib_built):
     s = setup((64, 64), 512, (254, 256), pad=(48, 64))
     assert s["groups"] == 32 and s["count"] == 3 * 512
     assert defect_factor("unet48 cat: inv_count from the padded width", *coef(s, count=4 * 512), *s["want"]) >= FACTOR
@@ -325,7 +325,7 @@ def test_defect_group_boundaries_off_by_one_at_cpg_3():
     assert defect_factor("c96_L300: group boundaries off by one channel", *coef(s, group_shift=1), *s["want"]) >= FACTOR
 
 
-def test_defects_of_the_second_source():
+def test_defects_of_the_second_source(lib_built):
     for name, Cs, L, rows, pad in (("unet32_cat_T1024", (32, 32), 1024, (254, 256), None), ("unet48_cat_T512", (64, 64), 512, (254, 256), (48, 64))):
         s = setup(Cs, L, rows, pad=pad)
         B, C0, C1 = s["B"], Cs[0], Cs[1]

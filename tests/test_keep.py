@@ -228,7 +228,7 @@ def test_samplers_refuse_bad_keyword_combinations():
         d.keep_region(torch.zeros(2, 1, 64), torch.zeros(2, 1, 64), 0.5, torch.zeros(2, 1, 60, dtype=torch.bool), seed=0, index=0)
 
 
-def test_decode_refuses_bad_keyword_combinations():
+def test_decode_refuses_bad_keyword_combinations(lib_built):
     from vq_voice_swap_amd import VQVAE
     from vq_voice_swap_amd.longform import decode_long
 

@@ -133,7 +133,7 @@ def models():
     return get
 
 
-def test_clip_inputs_are_the_cases_the_issue_sets():
+def test_clip_inputs_are_the_cases_the_issue_sets(lib_built):
     ts, labels, vec = pw.clip_inputs(33, 32)
     assert ts[:13].tolist() == [float(np.float32(v)) for v in pw.TS_HEAD] and ts[13].item() == float(np.float32(27 / 40)) and len(set(ts.tolist())) == 33
     assert labels.tolist() == [i % 4 for i in range(33)] and vec.shape == (33, 128) and 0.25 < vec.std().item() < 0.35
@@ -144,7 +144,7 @@ def test_clip_inputs_are_the_cases_the_issue_sets():
 
 @pytest.mark.parametrize("path", ["labels", "vectors", "none"])
 @pytest.mark.parametrize("base", pw.EMB_BASES)
-def test_embedding_reference_and_bound(models, base, path):
+def test_embedding_reference_and_bound(models, base, path, lib_built):
     m = models(base, labels=path != "none")
     c = pw.emb_case(m, 33, path)
     print(f"[emb] base {base} {path}: E_ref {c['eref']:.2e}, max |want| {c['want'].abs().max():.3f}, bound {c['bound'].min():.2e} .. {c['bound'].max():.2e}")
@@ -167,7 +167,7 @@ def test_embedding_reference_and_bound(models, base, path):
 
 # ------------------------------------------------------------------------------------------------------------------ Stage C
 @pytest.mark.parametrize("base", (32, 96, 40))
-def test_film_reference_bound_and_planted_defects(models, base):
+def test_film_reference_bound_and_planted_defects(models, base, lib_built):
     m = models(base)
     ts, labels, _ = pw.clip_inputs(33)
     sd32 = pw.state(m, torch.float32)
@@ -200,7 +200,7 @@ def _stem32(m, x, cond=None):
 
 
 @pytest.mark.parametrize("key", [32, 96, "in3", "cond"])
-def test_stem_reference_bound_and_planted_defects(models, key):
+def test_stem_reference_bound_and_planted_defects(models, key, lib_built):
     kw = dict(pw.EXTRA[key]) if key in pw.EXTRA else dict(base=key)
     m = models(kw.pop("base"), **kw)
     B, T = 3, 770
@@ -223,7 +223,7 @@ def test_stem_reference_bound_and_planted_defects(models, key):
             assert share > 50 and t == (256 if defect == "left256" else T - 1), (key, defect, mode, share)
 
 
-def test_single_row_defects_pass_todays_fp16_gate(models):
+def test_single_row_defects_pass_todays_fp16_gate(models, lib_built):
     """At the shape of today's tap test (base 32, T = 64000, B = 2) a single wrong row is invisible to rel_rms < 4e-3."""
     m = models(32)
     B, T = 2, 64000
@@ -244,7 +244,7 @@ def test_single_row_defects_pass_todays_fp16_gate(models):
 
 
 @pytest.mark.parametrize("key", [32, 96])
-def test_head_reference_bound_and_planted_defects(models, key):
+def test_head_reference_bound_and_planted_defects(models, key, lib_built):
     m = models(key)
     B, T = 3, 770
     tap = 0.3 + 1.5 * pw.wave((B, key, T), 31)
@@ -265,7 +265,7 @@ def test_head_reference_bound_and_planted_defects(models, key):
                 assert int(np.unravel_index(i, tuple(bad.shape))[2]) == (256 if defect == "left256" else T - 1)
 
 
-def test_head_bound_follows_the_taps_that_exist_and_the_clamp(models):
+def test_head_bound_follows_the_taps_that_exist_and_the_clamp(models, lib_built):
     m = models(32)
     tap = pw.wave((1, 32, 258), 41)
     tap[0, 3, 100] = 40.0  # one |u| beyond the polynomial forms' clamp

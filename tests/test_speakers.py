@@ -87,7 +87,7 @@ def test_morph_entries():
         S.morph_entries([(0.0, "x")], 2, W, H, SR_HZ)
 
 
-def test_morph_and_voice_vectors_call_the_mix_once(monkeypatch, tmp_path):
+def test_morph_and_voice_vectors_call_the_mix_once(monkeypatch, tmp_path, lib_built):
     """The native call stubbed: what it is handed -- the table with the vector files behind it, idx and w."""
     pred = UNetPredictor(32, num_labels=4)
     E = 128

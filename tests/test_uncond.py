@@ -129,7 +129,7 @@ def cpu_model(num_labels=3):
     return m.eval()
 
 
-def test_checkpoint_puts_the_row_in_front():
+def test_checkpoint_puts_the_row_in_front(lib_built):
     model = cpu_model()
     old = model.predictor.class_embed.weight.detach().clone()
     en = NullLabelEnroller(model, init="mean", seed=3)
@@ -156,7 +156,7 @@ def test_checkpoint_puts_the_row_in_front():
         en.finish()
 
 
-def test_checkpoint_loads_as_a_vqvae(tmp_path):
+def test_checkpoint_loads_as_a_vqvae(tmp_path, lib_built):
     model = VQVAE(base_channels=32, pred_name="unet", num_labels=3)
     det_init_(("uncond.vq." + k, v) for k, v in model.state_dict().items())
     model.eval()
@@ -170,7 +170,7 @@ def test_checkpoint_loads_as_a_vqvae(tmp_path):
     assert grown.num_labels == grown.predictor.num_labels == 4 and torch.equal(w[1:], old) and torch.equal(w[0], old[1])
 
 
-def test_a_resume_of_the_other_kind_is_refused():
+def test_a_resume_of_the_other_kind_is_refused(lib_built):
     front, back = NullLabelEnroller(cpu_model(), init="mean"), SpeakerEnroller(cpu_model(), 1, init="mean")
     fs, bs = front.state_dict(), back.state_dict()
     assert fs["front"] is True and "front" not in bs  # the marker; a back state is the dict it always was

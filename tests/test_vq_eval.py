@@ -83,7 +83,7 @@ def test_standard_vq_loss_forms_agree(commitment):
     assert not loss(inputs.clone().requires_grad_(), embedded, None).requires_grad
 
 
-def test_losses_refuses_training_only_arguments_before_a_device():
+def test_losses_refuses_training_only_arguments_before_a_device(lib_built):
     model = VQVAE(base_channels=32, pred_name="unet", num_labels=5, dictionary_size=16).eval()
     x = torch.zeros(2, 1, 4096)  # a CPU tensor: a device would be demanded next
     for kw in (dict(jitter=0.1), dict(no_vq_prob=0.5), dict(jitter=1.0, no_vq_prob=0.1)):

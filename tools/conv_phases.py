@@ -17,7 +17,6 @@ from vq_voice_swap_amd.det_init import det_init_
 PH = ["setup", "issue/loop", "wait loads", "prologue+LDS wr", "barrier", "LDS rd+MFMA", "epi barrier", "acc->LDS", "epi barrier2",
       "row phase", "stats reduce", "  issue: ss loads", "  issue: act loads", "  issue: weight loads", "  loop/geom", "-", "back-edge", "matrix-pipe drain"]
 L = _native.lib()
-L.vqvs_debug_conv_timing.argtypes = [C.c_void_p, C.c_int]
 dev = torch.device("cuda:0")
 
 

@@ -18,7 +18,6 @@ P_PH = ["wait loads (vmcnt)", "prologue + ds_write", "load cursor (prepare)", "l
 C_PH = ["tile start: store + bias", "weight DMA issue", "ds_read + MFMA", "tile end: stats/round/LDS", "vmcnt + barrier", "last tile's store (after the loop)",
         "look-ahead GroupNorm table"]
 L = _native.lib()
-L.vqvs_debug_ws_timing.argtypes = [C.c_void_p, C.c_int]
 dev = torch.device("cuda:0")
 
 

@@ -13,50 +13,25 @@ import os
 import subprocess
 from typing import Dict, List, Optional, Sequence, Tuple
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VQVS_LIB_PATH") or os.path.join(_HERE, "libvqvs_hip.so")  # override: instrumented builds (tools/)
 CSRC = os.path.join(_HERE, "csrc")
+HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "vqvs.h"))  # the tree travels whole (csrc/Makefile depends on this path too)
 
-KIND_PREDICTOR, KIND_ENCODER, KIND_RESBLOCK, KIND_CLASSIFIER, KIND_ENCPRED, KIND_MFCC_ENCODER, KIND_PREDICTOR_GRAD = 0, 1, 2, 3, 4, 5, 6
-PREC_F32, PREC_BF16, PREC_F16 = 0, 1, 2
-DDPM_SIGMA_LARGE, DDPM_CONSTRAIN = 1, 2
-DDIM_CONSTRAIN, DDIM_INVERT = 2, 4
-STREAM_STEP, STREAM_XT, STREAM_LOSS, STREAM_KEEP = 0, 1, 2, 3  # stream ids of the noise generator (csrc/philox.hpp)
-PRECISIONS = {"fp32": PREC_F32, "f32": PREC_F32, "float32": PREC_F32, "bf16": PREC_BF16, "bfloat16": PREC_BF16,
-              "fp16": PREC_F16, "f16": PREC_F16, "float16": PREC_F16, "half": PREC_F16}
+
+class NativeError(RuntimeError):
+    pass
 
 
 class Cfg(C.Structure):
-    _fields_ = [
-        ("kind", C.c_int32),
-        ("base_channels", C.c_int32),
-        ("in_channels", C.c_int32),
-        ("out_channels", C.c_int32),
-        ("cond_channels", C.c_int32),
-        ("num_labels", C.c_int32),
-        ("precision", C.c_int32),
-        ("max_batch", C.c_int32),
-        ("max_T", C.c_int32),
-        ("debug_taps", C.c_int32),
-        ("rb_cin", C.c_int32),
-        ("rb_cout", C.c_int32),
-        ("rb_resize", C.c_int32),
-        ("rb_dilation", C.c_int32),
-        ("rb_emb_channels", C.c_int32),
-        ("reserved", C.c_int32 * 5),  # reserved[0] = 1: checkpoints trained with dropout (conv is post_cond.2)
-        # topology of predictor / encoder handles (include/vqvs.h); topology_set = 0: the reference's defaults
-        ("topology_set", C.c_int32),
-        ("n_levels", C.c_int32),
-        ("channel_mult", C.c_int32 * 12),
-        ("depth_mult", C.c_int32),
-        ("n_dilations", C.c_int32),
-        ("dilations", C.c_int32 * 12),
-    ]
+    """vqvs_cfg; its fields are the header's (set below)."""
 
     def set_topology(self, channel_mult, depth_mult, dilations):
         """Describe a UNet other than the reference's default one (unet.py:17-30, 188-196)."""
-        if len(channel_mult) > 12 or len(dilations) > 12:
-            raise ValueError("the gfx950 library builds at most 12 levels and 12 middle / output dilations")
+        if len(channel_mult) > MAX_LEVELS or len(dilations) > MAX_LEVELS:
+            raise ValueError(f"the gfx950 library builds at most {MAX_LEVELS} levels and {MAX_LEVELS} middle / output dilations")
         self.topology_set = 1
         self.n_levels = len(channel_mult)
         for i, m in enumerate(channel_mult):
@@ -67,26 +42,25 @@ class Cfg(C.Structure):
             self.dilations[i] = int(d)
 
 
-EXPORTS = [
-    "vqvs_param_count", "vqvs_param_info", "vqvs_model_create", "vqvs_model_destroy", "vqvs_model_device_bytes",
-    "vqvs_unet_forward", "vqvs_encoder_forward", "vqvs_mfcc_encoder_forward", "vqvs_mfcc_encoder_forward_logmel", "vqvs_model_status", "vqvs_resblock_forward", "vqvs_classifier_forward",
-    "vqvs_classifier_guidance", "vqvs_classifier_features", "vqvs_feature_moments", "vqvs_encpred_forward", "vqvs_encpred_guidance", "vqvs_ddpm_step", "vqvs_ddpm_step_windows", "vqvs_ddim_step", "vqvs_ddim_step_windows", "vqvs_dpmpp_step", "vqvs_dpmpp_step_windows",
-    "vqvs_ddpm_step_windows_packed", "vqvs_ddim_step_windows_packed", "vqvs_dpmpp_step_windows_packed", "vqvs_keep_region", "vqvs_keep_region_windows", "vqvs_ddpm_mean",
-    "vqvs_ddpm_guided_eps", "vqvs_randn", "vqvs_ddpm_noise", "vqvs_ddpm_sqerr", "vqvs_vq_argmin", "vqvs_vq_quantize", "vqvs_vq_embed", "vqvs_xent_score", "vqvs_spectral_distance", "vqvs_pitch_distance", "vqvs_debug_tap_count",
-    "vqvs_debug_tap_info", "vqvs_debug_tap_rows", "vqvs_debug_read_tap", "vqvs_debug_read_embedding", "vqvs_forward_kernel_count", "vqvs_forward_model_bytes",
-    "vqvs_forward_flops", "vqvs_set_profiling", "vqvs_op_info", "vqvs_op_desc", "vqvs_profile_read", "vqvs_last_error", "vqvs_version",
-    "vqvs_unet_embed_grad", "vqvs_embed_adamw", "vqvs_debug_read_dfilm", "vqvs_head_xent_grad", "vqvs_head_adamw",
-    "vqvs_mel_cepstra", "vqvs_dtw_distance", "vqvs_guidance_mix", "vqvs_unet_forward_vec", "vqvs_speaker_mix",
-    "vqvs_debug_read_film", "vqvs_debug_gelu",
-    "vqvs_debug_gn_count", "vqvs_debug_gn_info", "vqvs_debug_gn_read", "vqvs_debug_xform_count", "vqvs_debug_xform_info", "vqvs_debug_xform_read",
-    "vqvs_keep_region_windows_packed", "vqvs_pause_mask", "vqvs_windows_kept",
-]
+def _read_header() -> _abi.Abi:
+    try:
+        with open(HEADER) as f:
+            return _abi.parse(f.read(), Cfg)
+    except OSError as e:
+        raise NativeError(f"cannot read the library's header {HEADER}: {e}") from e
+
+
+# One declaration of the boundary: the prototypes, the VQVS_* constants (KIND_*, PREC_*, DDPM_*, DDIM_*, ERR_*, MAX_LEVELS: bound here
+# under their names without the prefix) and the fields of vqvs_cfg all come from include/vqvs.h.
+ABI = _read_header()
+Cfg._fields_ = ABI.cfg_fields
+EXPORTS = list(ABI.functions)
+globals().update({name[len("VQVS_"):]: value for name, value in ABI.constants.items()})
+STREAM_STEP, STREAM_XT, STREAM_LOSS, STREAM_KEEP = 0, 1, 2, 3  # stream ids of the noise generator (csrc/philox.hpp)
+PRECISIONS = {"fp32": PREC_F32, "f32": PREC_F32, "float32": PREC_F32, "bf16": PREC_BF16, "bfloat16": PREC_BF16,
+              "fp16": PREC_F16, "f16": PREC_F16, "float16": PREC_F16, "half": PREC_F16}
 
 _lib = None
-
-
-class NativeError(RuntimeError):
-    pass
 
 
 class NativeArgumentError(NativeError, ValueError):
@@ -123,85 +97,12 @@ def lib():
                       "sampler starts with loads across PCIe (~2 % slower, DESIGN.md section 7).  Set HIP_FORCE_DEV_KERNARG=1 in the "
                       "process environment before the first HIP call (bench.py and the sample_*.py scripts do).", RuntimeWarning, stacklevel=2)
     L = C.CDLL(LIB_PATH)
-    vp, i32, i64, u32, u64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
-    L.vqvs_last_error.restype = C.c_char_p
-    L.vqvs_version.restype = C.c_char_p
-    L.vqvs_param_count.argtypes = [C.POINTER(Cfg)]
-    L.vqvs_param_info.argtypes = [C.POINTER(Cfg), i32, C.c_char_p, i32, C.POINTER(i64), C.POINTER(i32)]
-    L.vqvs_model_create.argtypes = [C.POINTER(Cfg), C.POINTER(vp), i32, i32, C.POINTER(vp)]
-    L.vqvs_model_destroy.argtypes = [vp]
-    L.vqvs_model_destroy.restype = None
-    L.vqvs_model_device_bytes.argtypes = [vp]
-    L.vqvs_model_device_bytes.restype = i64
-    L.vqvs_unet_forward.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp]
-    L.vqvs_unet_forward_vec.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp]
-    L.vqvs_unet_embed_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
-    L.vqvs_embed_adamw.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp]
-    L.vqvs_debug_read_dfilm.argtypes = [vp, i32, vp]
-    L.vqvs_debug_read_film.argtypes = [vp, i32, vp]
-    L.vqvs_debug_gelu.argtypes = [vp, vp, i32, i32, vp]
-    L.vqvs_debug_gn_count.argtypes = [vp]
-    L.vqvs_debug_gn_info.argtypes = [vp, i32, i32, i32, C.c_char_p, i32, C.POINTER(i64)]
-    L.vqvs_debug_gn_read.argtypes = [vp, i32, i32, i32, i32, i32, vp]
-    L.vqvs_debug_xform_count.argtypes = [vp]
-    L.vqvs_debug_xform_info.argtypes = [vp, i32, i32, i32, C.POINTER(i64)]
-    L.vqvs_debug_xform_read.argtypes = [vp, i32, i32, i32, i32, vp]
-    L.vqvs_head_xent_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    L.vqvs_head_adamw.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp]
-    L.vqvs_encoder_forward.argtypes = [vp, vp, vp, i32, i32, vp]
-    L.vqvs_mfcc_encoder_forward.argtypes = [vp, vp, vp, i32, i32, vp]
-    L.vqvs_mfcc_encoder_forward_logmel.argtypes = [vp, vp, vp, i32, i32, vp]
-    L.vqvs_model_status.argtypes = [vp, vp]
-    L.vqvs_resblock_forward.argtypes = [vp, vp, vp, vp, i32, i32, vp]
-    L.vqvs_classifier_forward.argtypes = [vp, vp, vp, vp, i32, i32, vp]
-    L.vqvs_classifier_guidance.argtypes = [vp, vp, vp, vp, f32, vp, vp, i32, i32, vp]
-    L.vqvs_classifier_features.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp]
-    L.vqvs_feature_moments.argtypes = [vp, i32, i32, vp, vp, vp, vp]
-    L.vqvs_encpred_forward.argtypes = [vp, vp, vp, vp, i32, i32, vp]
-    L.vqvs_encpred_guidance.argtypes = [vp, vp, vp, vp, f32, vp, vp, i32, i32, vp]
-    L.vqvs_ddpm_step.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, u32, f32, u64, u64, u32, vp]
-    L.vqvs_ddpm_step_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, u32, f32, u64, u64, u32, vp]
-    L.vqvs_ddim_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, u32, f32, f32, u64, u64, u32, vp]
-    L.vqvs_ddim_step_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, u32, f32, f32, u64, u64, u32, vp]
-    L.vqvs_dpmpp_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, u32, vp]
-    L.vqvs_dpmpp_step_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, u32, vp]
-    L.vqvs_ddpm_step_windows_packed.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, u32, f32, u64, u64, u32, vp]
-    L.vqvs_ddim_step_windows_packed.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, u32, f32, f32, u64, u64, u32, vp]
-    L.vqvs_dpmpp_step_windows_packed.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, u32, vp]
-    L.vqvs_keep_region.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, u64, u64, u32, vp]
-    L.vqvs_keep_region_windows.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, u64, u64, u32, vp]
-    L.vqvs_keep_region_windows_packed.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, u64, u64, u32, vp]
-    L.vqvs_pause_mask.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i64, i32, i32, vp]
-    L.vqvs_windows_kept.argtypes = [vp, vp, vp, i32, i32, i32, vp]
-    L.vqvs_ddpm_mean.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
-    L.vqvs_ddpm_guided_eps.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, u32, vp]
-    L.vqvs_guidance_mix.argtypes = [vp, vp, i32, i64, i32, f32, f32, vp]
-    L.vqvs_speaker_mix.argtypes = [vp, i32, i32, vp, vp, i32, vp, i32, vp]
-    L.vqvs_randn.argtypes = [vp, i32, i32, u64, u64, u32, vp]
-    L.vqvs_ddpm_noise.argtypes = [vp, i32, vp, vp, i32, vp, vp, i32, i32, u64, u64, vp]
-    L.vqvs_ddpm_sqerr.argtypes = [vp, vp, i32, vp, vp, i32, i32, u64, u64, vp]
-    L.vqvs_vq_argmin.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
-    L.vqvs_vq_quantize.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    L.vqvs_vq_embed.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
-    L.vqvs_xent_score.argtypes = [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp]
-    L.vqvs_spectral_distance.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp]
-    L.vqvs_pitch_distance.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.c_double, vp]
-    L.vqvs_mel_cepstra.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp]
-    L.vqvs_dtw_distance.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    L.vqvs_debug_tap_count.argtypes = [vp]
-    L.vqvs_debug_tap_info.argtypes = [vp, i32, C.c_char_p, i32, C.POINTER(i32), C.POINTER(i32)]
-    L.vqvs_debug_tap_rows.argtypes = [vp, i32, i32]
-    L.vqvs_debug_read_tap.argtypes = [vp, i32, i32, i32, vp]
-    L.vqvs_debug_read_embedding.argtypes = [vp, i32, vp]
-    L.vqvs_forward_kernel_count.argtypes = [vp]
-    L.vqvs_forward_model_bytes.argtypes = [vp, i32, i32]
-    L.vqvs_forward_model_bytes.restype = i64
-    L.vqvs_forward_flops.argtypes = [vp, i32, i32]
-    L.vqvs_forward_flops.restype = i64
-    L.vqvs_set_profiling.argtypes = [vp, i32]
-    L.vqvs_op_info.argtypes = [vp, i32, C.c_char_p, i32, C.POINTER(i64), C.POINTER(i64), i32, i32]
-    L.vqvs_profile_read.argtypes = [vp, vp, i32]
-    L.vqvs_op_desc.argtypes = [vp, i32, C.c_char_p, i32]
+    for name, (restype, argtypes) in ABI.functions.items():
+        try:
+            fn = getattr(L, name)
+        except AttributeError:
+            raise NativeError(f"{LIB_PATH} does not export {name}, which {HEADER} declares: rebuild the library") from None
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -217,7 +118,7 @@ def check(rc: int) -> None:
     if rc == 0:
         return
     msg = last_error()
-    if rc == -1:
+    if rc == ERR_ARG:
         if msg.startswith("must provide"):
             raise AssertionError(msg)
         raise NativeArgumentError(msg)
@@ -359,31 +260,26 @@ class Handle:
             check(r)
         return out[:, :r]
 
-    def read_dfilm(self, B: int):
-        """d mse_b / d (FiLM rows) [B, R] of the last `vqvs_unet_embed_grad` on a predictor-gradient handle: per clip the (d a | d b)
-        rows of every ResBlock in the order down, middle, up."""
+    def _read_film_rows(self, entry, B: int):
         import torch
 
         R = sum(shape[0] for name, shape in param_table(self.cfg) if name.endswith("cond_layers.1.bias"))  # 2 * cout rows per block
         out = torch.empty(B, R, dtype=torch.float32)
-        r = lib().vqvs_debug_read_dfilm(self._h, B, out.data_ptr())
+        r = entry(self._h, B, out.data_ptr())
         if r < 0:
             check(r)
         assert r == R, (r, R)
         return out
+
+    def read_dfilm(self, B: int):
+        """d mse_b / d (FiLM rows) [B, R] of the last `vqvs_unet_embed_grad` on a predictor-gradient handle: per clip the (d a | d b)
+        rows of every ResBlock in the order down, middle, up."""
+        return self._read_film_rows(lib().vqvs_debug_read_dfilm, B)
 
     def read_film(self, B: int):
         """FiLM rows [B, R] of the last forward: per clip the (a | b) rows of every ResBlock in the order down, middle, up (the
         handle's physical widths)."""
-        import torch
-
-        R = sum(shape[0] for name, shape in param_table(self.cfg) if name.endswith("cond_layers.1.bias"))  # 2 * cout rows per block
-        out = torch.empty(B, R, dtype=torch.float32)
-        r = lib().vqvs_debug_read_film(self._h, B, out.data_ptr())
-        if r < 0:
-            check(r)
-        assert r == R, (r, R)
-        return out
+        return self._read_film_rows(lib().vqvs_debug_read_film, B)
 
     # ---- GroupNorm / xform entries of a debug_taps handle, as the last forward at (B, T) ran them (include/vqvs.h)
     def gn_count(self) -> int:

@@ -105,6 +105,12 @@ const char* vqvs_last_error(void) { return g_err.c_str(); }
 #endif
 const char* vqvs_version(void) { return "vqvs-hip 0.1 (gfx950) build " VQVS_BUILD_ID; }  // (build id: hash of the sources, csrc/Makefile)
 
+int vqvs_pad_blocks(int real_base_channels, int* q, int* q_p) {
+  if (real_base_channels < 1 || !q || !q_p) VQVS_FAIL(VQVS_ERR_ARG, "vqvs_pad_blocks: real_base_channels must be positive and q, q_p not NULL");
+  pad_blocks(real_base_channels, q, q_p);
+  return 0;
+}
+
 int vqvs_param_count(const vqvs_cfg* cfg) {
   if (!cfg) VQVS_FAIL(VQVS_ERR_ARG, "cfg is NULL");
   std::vector<ParamDef> p;
@@ -1177,9 +1183,14 @@ int vqvs_profile_read(vqvs_model* m, float* h_ms, int cap) {
 
 }  // extern "C"
 
+// The in-kernel phase counters of the instrumented build (`make timing`, -DVQVS_TIMING); every other build exports the two entries too,
+// so that the header and the library agree in every build, and refuses the call.
 #ifdef VQVS_TIMING
-namespace vqvs { int conv_timing_read(unsigned long long* out16, int reset); }
-extern "C" int vqvs_debug_conv_timing(unsigned long long* h_out16, int reset) { return vqvs::conv_timing_read(h_out16, reset); }
+namespace vqvs { int conv_timing_read(unsigned long long* out24, int reset); }
+extern "C" int vqvs_debug_conv_timing(unsigned long long* h_counters, int reset) { return vqvs::conv_timing_read(h_counters, reset); }
 namespace vqvs { int ws_timing_read(unsigned long long* out32, int reset); }
-extern "C" int vqvs_debug_ws_timing(unsigned long long* h_out32, int reset) { return vqvs::ws_timing_read(h_out32, reset); }
+extern "C" int vqvs_debug_ws_timing(unsigned long long* h_counters, int reset) { return vqvs::ws_timing_read(h_counters, reset); }
+#else
+extern "C" int vqvs_debug_conv_timing(unsigned long long*, int) { VQVS_FAIL(VQVS_ERR_STATE, "this library was built without -DVQVS_TIMING"); }
+extern "C" int vqvs_debug_ws_timing(unsigned long long*, int) { VQVS_FAIL(VQVS_ERR_STATE, "this library was built without -DVQVS_TIMING"); }
 #endif

@@ -1200,6 +1200,10 @@ int padded_base(int real) {
   const PadMap m = pad_map(real);
   return real / m.q * m.qp;
 }
+void pad_blocks(int real, int* q, int* qp) {
+  const PadMap m = pad_map(real);
+  *q = m.q, *qp = m.qp;
+}
 int real_base(const vqvs_cfg& c) {
   const bool unet = c.kind == VQVS_KIND_PREDICTOR || c.kind == VQVS_KIND_ENCODER;
   return unet && c.reserved[4] > 0 ? c.reserved[4] : c.base_channels;

@@ -11,6 +11,7 @@ does not run torch ops -- it hands device pointers to `libvqvs_hip.so`
 from __future__ import annotations
 
 import contextlib
+import ctypes
 import functools
 import os
 import warnings
@@ -29,21 +30,13 @@ SUPPORTED_BASE_CHANNELS = (32, 64, 128)  # the tuned widths (the reference's two
 
 
 def pad_blocks(base_channels: int) -> Tuple[int, int]:
-    """(q, q_p) of a width that is not a multiple of 32 (csrc/net.cpp pad_map): base = 2^k * q with q odd; the handle is built with
-    channels in blocks of q_p -- the next power of two >= q, widened until 2^k * q_p is a multiple of 32 -- whose first q channels
-    are the real ones and the rest stay exactly zero.  Multiples of 32: (q, q): nothing is padded."""
-    k = 0
-    while (base_channels >> k) & 1 == 0 and k < 5:
-        k += 1
-    q = base_channels >> k
-    if base_channels % 32 == 0:
-        return q, q
-    qp = 1
-    while qp < q:
-        qp <<= 1
-    while ((1 << k) * qp) % 32:
-        qp <<= 1
-    return q, qp
+    """(q, q_p) of a width that is not a multiple of 32, as the library states the rule (vqvs_pad_blocks, csrc/net.cpp pad_map):
+    base = 2^k * q with q odd; the handle is built with channels in blocks of q_p -- the next power of two >= q, widened until
+    2^k * q_p is a multiple of 32 -- whose first q channels are the real ones and the rest stay exactly zero.  Multiples of 32:
+    (q, q): nothing is padded."""
+    q, qp = ctypes.c_int(), ctypes.c_int()
+    _native.check(_native.lib().vqvs_pad_blocks(int(base_channels), ctypes.byref(q), ctypes.byref(qp)))
+    return q.value, qp.value
 
 
 def physical_base(base_channels: int) -> int:
