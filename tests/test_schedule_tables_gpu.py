@@ -1,4 +1,5 @@
-"""The static schedule of every handle kind, entry by entry, against a recorded table (tests/schedule_tables.json).
+"""The static schedule of every handle kind, entry by entry, against a recorded table (tests/schedule_tables.json, and
+tests/schedule_tables_xform.json for the handles of XFORM_CASES).
 
 csrc/net.cpp builds, per handle, a list of kernels with their accounting rows, a liveness-planned arena, a packed weight blob and a
 list of debug taps.  All of it is decided on the host when the handle is created, and all of it can be read back without running a
@@ -11,9 +12,11 @@ CASES reaches every branch of the builder with tiny handles (and a two-channel e
 channel): base 32 (24 for the padded widths), 2 clips, the shortest length each
 topology takes (256 for the default nine levels, 512 for the default classifier, the lengths of tests/enroll_ref.py and
 tests/backward_ref.py for the custom ones, 800 for the MFCC front end), in fp32 and, where the kind has a 2-byte mode, fp16.
+None of them is wide enough for the hoisted prologue (`xform` entries): XFORM_CASES reaches it, in a table of its own so that the first
+one stays as it was recorded, byte for byte.
 
-The table is written by `python tests/test_schedule_tables_gpu.py --record` (handles are created on the device, so on a GPU machine) and
-never by the test.  Equal rows are stored once (`rows`) and referred to by index, which keeps the file small."""
+The tables are written by `python tests/test_schedule_tables_gpu.py --record` (handles are created on the device, so on a GPU machine)
+and never by the test.  Equal rows are stored once per file (`rows`) and referred to by index, which keeps the files small."""
 import json
 import os
 import sys
@@ -27,6 +30,7 @@ if ROOT not in sys.path:
 
 pytestmark = pytest.mark.gpu
 TABLES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "schedule_tables.json")
+XFORM_TABLES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "schedule_tables_xform.json")
 B = 2
 SMALL = dict(channel_mult=(1, 2, 2), depth_mult=1, middle_dilations=(4,))
 BOTH, F32 = ("fp32", "fp16"), ("fp32",)
@@ -66,7 +70,22 @@ CASES = [
     ("grad_plain", "pred", (32,), dict(num_labels=4, **SMALL), 592, F32, dict(grad=True)),
     ("grad_cond", "pred", (32,), dict(num_labels=4, cond_channels=32), 256, F32, dict(grad=True, cond_code=0)),
 ]
-CASE_IDS = [f"{c[0]}.{p}" for c in CASES for p in c[5]]
+# The hoisted prologue (`xform` entries).  pred_wide: widths of 512 from level 1 -- fp32 hoists both convolutions of every block from
+# 512 output channels up (the x0.5 block at 512: an `avg` entry), fp16 only conv 1 of the up blocks whose concatenated input is 1024
+# wide (no `avg`: a resizing block never concatenates).  rb_avg1024: the one place fp16 hoists WITH the average pool, a x0.5 block more
+# than 640 channels wide.
+XFORM_CASES = [
+    ("pred_wide", "pred", (32,), dict(channel_mult=(1, 16, 16), depth_mult=1, middle_dilations=(4,)), 256, BOTH, {}),
+    ("rb_avg1024", "rb", (1024,), dict(scale_factor=0.5), 256, BOTH, {}),
+]
+FILES = ((TABLES, CASES), (XFORM_TABLES, XFORM_CASES))
+
+
+def ids(cases):
+    return [f"{c[0]}.{p}" for c in cases for p in c[5]]
+
+
+CASE_IDS = ids(CASES) + ids(XFORM_CASES)
 
 
 def make_module(case, prec):
@@ -98,7 +117,7 @@ def tables(h, T):
 
 def live(cid):
     name, prec = cid.rsplit(".", 1)
-    case = next(c for c in CASES if c[0] == name)
+    case = next(c for c in CASES + XFORM_CASES if c[0] == name)
     assert torch.cuda.is_available(), "GPU tests need an MI355X"
     m = make_module(case, prec)
     got = tables(make_handle(case, m, torch.device("cuda:0")), case[4])
@@ -108,16 +127,19 @@ def live(cid):
 
 @pytest.fixture(scope="module")
 def recorded():
-    with open(TABLES) as f:
-        z = json.load(f)
-    assert sorted(z["cases"]) == sorted(CASE_IDS), "tests/schedule_tables.json does not hold the case list of this file"
-    return z
+    want = {}
+    for path, cases in FILES:
+        with open(path) as f:
+            z = json.load(f)
+        assert sorted(z["cases"]) == sorted(ids(cases)), f"{os.path.basename(path)} does not hold the case list of this file"
+        for cid, t in z["cases"].items():
+            want[cid] = dict(t, ops=[z["rows"][i] for i in t["ops"]])
+    return want
 
 
 @pytest.mark.parametrize("cid", CASE_IDS)
 def test_schedule_tables(cid, recorded):
-    want = dict(recorded["cases"][cid])
-    want["ops"] = [recorded["rows"][i] for i in want["ops"]]
+    want = recorded[cid]
     got = live(cid)
     assert got["kernel_count"] == want["kernel_count"]
     for i, (g, w) in enumerate(zip(got["ops"], want["ops"])):
@@ -128,9 +150,9 @@ def test_schedule_tables(cid, recorded):
     assert got == want
 
 
-def record():
+def record(path, case_ids):
     rows, index, cases = [], {}, {}
-    for cid in CASE_IDS:
+    for cid in case_ids:
         t = live(cid)
         ops = []
         for r in t["ops"]:
@@ -142,14 +164,15 @@ def record():
         t["ops"] = ops
         cases[cid] = t
         print(f"{cid}: {t['kernel_count']} entries, {t['device_bytes']} device bytes, {len(t['taps'])} taps", flush=True)
-    with open(TABLES, "w") as f:
+    with open(path, "w") as f:
         json.dump(dict(rows=rows, cases=cases), f, separators=(",", ":"))
         f.write("\n")
-    print(f"wrote {TABLES}: {len(cases)} handles, {len(rows)} distinct rows")
+    print(f"wrote {path}: {len(cases)} handles, {len(rows)} distinct rows")
 
 
 if __name__ == "__main__":
     if sys.argv[1:] != ["--record"]:
         sys.exit("usage: python tests/test_schedule_tables_gpu.py --record")
     os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
-    record()
+    for path, cases in FILES:
+        record(path, ids(cases))

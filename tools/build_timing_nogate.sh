@@ -6,7 +6,10 @@ set -e
 cd "$(dirname "$0")/../vq_voice_swap_amd/csrc"
 B=build_timing; mkdir -p $B
 FLAGS="-DVQVS_TIMING -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -Wno-unused-result"
-for f in api.cpp net.cpp conv_mfma.hip misc_kernels.hip sampler_kernels.hip backward_kernels.hip mfcc_kernels.hip; do
+SRCS=$(sed -n 's/^SRCS = //p' Makefile)  # the product's source list, so this one cannot fall behind it
+[ -n "$SRCS" ] || { echo "no SRCS line in csrc/Makefile"; exit 1; }
+for f in $SRCS; do
+  [ $f = conv_ws.hip ] && continue  # (below, with its own flags)
   /opt/rocm/bin/hipcc $FLAGS -DVQVS_BUILD_ID=\"timing\" -x hip -c $f -o $B/$f.o &
 done
 /opt/rocm/bin/hipcc $FLAGS -fno-slp-vectorize -Rpass-analysis=kernel-resource-usage -x hip -c conv_ws.hip -o $B/conv_ws.hip.o 2> $B/conv_ws.resource.txt

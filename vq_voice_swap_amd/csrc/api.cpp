@@ -935,7 +935,7 @@ int vqvs_debug_read_tap(vqvs_model* m, int i, int B, int T, float* h_out) {
   float* d_tmp = nullptr;
   VQVS_HIP(hipSetDevice(m->device));
   VQVS_HIP(hipMalloc(reinterpret_cast<void**>(&d_tmp), n * 4));
-  int e = launch_ntc_to_nct(m->d_arena + t.off, d_tmp, B, t.C, L, t.f32 ? 0 : m->cfg.precision, nullptr);
+  int e = launch_ntc_to_nct(m->act(t.off), d_tmp, B, t.C, L, t.f32 ? 0 : m->cfg.precision, nullptr);
   if (!e) {
     hipError_t he = hipMemcpy(h_out, d_tmp, n * 4, hipMemcpyDeviceToHost);
     if (he != hipSuccess) {
@@ -952,7 +952,7 @@ int vqvs_debug_read_embedding(vqvs_model* m, int B, float* h_out) {
   if (!m->emb_E) VQVS_FAIL(VQVS_ERR_STATE, "this model kind has no timestep embedding");
   VQVS_HIP(hipSetDevice(m->device));
   VQVS_HIP(hipDeviceSynchronize());
-  const float* src = reinterpret_cast<const float*>(m->d_arena + m->misc_off) + m->emb_misc_off;
+  const float* src = m->miscp(m->emb_misc_off);
   VQVS_HIP(hipMemcpy(h_out, src, (size_t)B * m->emb_E * sizeof(float), hipMemcpyDeviceToHost));
   return m->emb_E;
 }
@@ -962,7 +962,7 @@ int vqvs_debug_read_dfilm(vqvs_model* m, int B, float* h_out) {
   if (!m->dfilm_R) VQVS_FAIL(VQVS_ERR_STATE, "this model kind has no FiLM-gradient buffer");
   VQVS_HIP(hipSetDevice(m->device));
   VQVS_HIP(hipDeviceSynchronize());
-  const float* src = reinterpret_cast<const float*>(m->d_arena + m->misc_off) + m->dfilm_misc_off;
+  const float* src = m->miscp(m->dfilm_misc_off);
   VQVS_HIP(hipMemcpy(h_out, src, (size_t)B * m->dfilm_R * sizeof(float), hipMemcpyDeviceToHost));
   return m->dfilm_R;
 }
@@ -972,7 +972,7 @@ int vqvs_debug_read_film(vqvs_model* m, int B, float* h_out) {
   if (!m->film_R) VQVS_FAIL(VQVS_ERR_STATE, "this model kind has no FiLM table");
   VQVS_HIP(hipSetDevice(m->device));
   VQVS_HIP(hipDeviceSynchronize());
-  const float* src = reinterpret_cast<const float*>(m->d_arena + m->misc_off) + m->film_misc_off;
+  const float* src = m->miscp(m->film_misc_off);
   VQVS_HIP(hipMemcpy(h_out, src, (size_t)B * m->film_R * sizeof(float), hipMemcpyDeviceToHost));
   return m->film_R;
 }
@@ -998,7 +998,7 @@ int debug_read_tensor(vqvs_model* m, const TensorH& t, int B, int T, float* h_ou
   float* d_tmp = nullptr;
   VQVS_HIP(hipSetDevice(m->device));
   VQVS_HIP(hipMalloc(reinterpret_cast<void**>(&d_tmp), n * 4));
-  int e = launch_ntc_to_nct(m->d_arena + t.off, d_tmp, B, t.C, L, t.f32 ? 0 : m->cfg.precision, nullptr);
+  int e = launch_ntc_to_nct(m->act(t.off), d_tmp, B, t.C, L, t.f32 ? 0 : m->cfg.precision, nullptr);
   if (!e && hipMemcpy(h_out, d_tmp, n * 4, hipMemcpyDeviceToHost) != hipSuccess) {
     set_error("hipMemcpy failed");
     e = VQVS_ERR_HIP;
@@ -1051,7 +1051,7 @@ int vqvs_debug_gn_read(vqvs_model* m, int i, int B, int T, int what, int src, fl
   if (what == 1) {
     const TensorH& t = g.srcs[src];
     const int rows = tensor_rows(T, t.lshift), nt = (rows + g.tile_rows[src] - 1) / g.tile_rows[src];
-    const float* p = reinterpret_cast<const float*>(m->d_arena + m->stats_off) + t.stats_off;
+    const float* p = m->statp(t.stats_off);
     VQVS_HIP(hipMemcpy(h_out, p, (size_t)B * nt * t.C * 2 * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
   }
@@ -1076,7 +1076,7 @@ int vqvs_debug_gn_read(vqvs_model* m, int i, int B, int T, int what, int src, fl
     (void)hipFree(d_tmp);
     return e;
   }
-  const float* p = reinterpret_cast<const float*>(m->d_arena + m->ss_off) + (what == 2 ? g.ss_off : g.mr_off);
+  const float* p = m->ssp(what == 2 ? g.ss_off : g.mr_off);
   VQVS_HIP(hipMemcpy(h_out, p, bytes, hipMemcpyDeviceToHost));
   return 0;
 }
@@ -1164,7 +1164,7 @@ int vqvs_model_status(vqvs_model* m, unsigned* h_status) {
   if (!m || !h_status) VQVS_FAIL(VQVS_ERR_ARG, "NULL argument");
   *h_status = 0;
   if (m->status_misc_off == (size_t)-1) return 0;
-  unsigned* d = reinterpret_cast<unsigned*>(reinterpret_cast<float*>(m->d_arena + m->misc_off) + m->status_misc_off);
+  unsigned* d = reinterpret_cast<unsigned*>(m->miscp(m->status_misc_off));
   VQVS_HIP(hipDeviceSynchronize());  // (forwards run on the caller's stream; a blocking copy on the null stream alone does not wait for a non-blocking one)
   VQVS_HIP(hipMemcpy(h_status, d, sizeof(unsigned), hipMemcpyDeviceToHost));
   if (*h_status) VQVS_HIP(hipMemset(d, 0, sizeof(unsigned)));

@@ -14,6 +14,7 @@
 #include <cstring>
 #include <functional>
 #include <memory>
+#include <optional>
 
 namespace vqvs {
 
@@ -357,16 +358,6 @@ class Builder {
   }
   size_t status_off_ = (size_t)-1;
 
-  // ---- pointer resolution at run time ------------------------------------------------
-  // (regions are laid out after planning: [activations | stats | ss | misc])
-  char* act(size_t off) const { return m_->d_arena + off; }
-  float* statp(size_t foff) const { return reinterpret_cast<float*>(m_->d_arena + m_->stats_off) + foff; }
-  float* ssp(size_t foff) const { return reinterpret_cast<float*>(m_->d_arena + m_->ss_off) + foff; }
-  float* miscp(size_t foff) const { return reinterpret_cast<float*>(m_->d_arena + m_->misc_off) + foff; }
-  char* wp(size_t off) const { return m_->d_weights + off; }
-  const float* wf(size_t off) const { return reinterpret_cast<const float*>(wp(off)); }  // a float32 entry of the weight blob
-  float2* ssf2(size_t foff) const { return reinterpret_cast<float2*>(ssp(foff)); }       // a (scale, shift) / (mean, rstd) table
-
   // ---- ops ---------------------------------------------------------------------------
   // The one place a schedule entry is made: its accounting row, its function and its phase go in together (run_model, vqvs_op_info and
   // vqvs_profile_read index all three with one number).  `fn` itself becomes the std::function: nothing is wrapped around it.
@@ -386,8 +377,27 @@ class Builder {
     std::function<bool(const RunCtx&)> fused;
     std::function<void(const RunCtx&, GnArgs&)> fill;
   };
-  std::shared_ptr<GnLink> add_gn(const std::vector<TensorH>& srcs, const std::string& gn_name, bool film, int film_off, int film_stride,
-              size_t film_misc_off, size_t ss_off, bool want_mr = false, size_t mr_off = 0) {
+  // Where one block's FiLM rows (a | b) lie: the [max_batch][stride] table of all blocks' rows in the misc region, and the block's
+  // first row in it.  A GroupNorm without FiLM (GroupNorm 1, the encoder's blocks, the heads) is given none.
+  struct FilmRows {
+    size_t misc_off = 0;
+    int off = 0, stride = 0;
+  };
+  // A GroupNorm's coefficient tables in the ss region: (scale, shift), and (mean, rstd) where a backward schedule wants them kept
+  struct GnTables {
+    size_t ss = 0, mr = 0;
+    bool want_mr = false;
+  };
+  GnTables alloc_gn_tables(int C, bool want_mr) {
+    GnTables t;
+    t.ss = alloc_ss(C);
+    t.mr = want_mr ? alloc_ss(C) : 0;
+    t.want_mr = want_mr;
+    return t;
+  }
+  std::shared_ptr<GnLink> add_gn(const std::vector<TensorH>& srcs, const std::string& gn_name, const std::optional<FilmRows>& film,
+                                 const GnTables& tb) {
+    const FilmRows fr = film.value_or(FilmRows{});
     int Ctot = 0;
     for (auto& s : srcs) Ctot += s.C;
     const size_t g_off = blob_f32(gn_name + ".weight");
@@ -396,7 +406,7 @@ class Builder {
     const int Creal = (int)((long long)Ctot * real_base(m_->cfg) / m_->cfg.base_channels);
     const int groups = gn_groups(Creal);
     const int lshift = srcs[0].lshift;
-    Builder* self = this;
+    const vqvs_model* const m = m_;
     std::vector<TensorH> S = srcs;
     std::vector<int> SR;
     for (auto& t : srcs) SR.push_back(stat_rows(t));
@@ -406,18 +416,18 @@ class Builder {
     link->fill = [=](const RunCtx& c, GnArgs& a) {
       const int L = shiftL(c.Lbase, lshift);
       a.nsrc = (int)S.size();
-      for (int i = 0; i < a.nsrc; ++i) a.src[i] = GnSrc{self->statp(S[i].stats_off), ntiles_of(L, SR[i]), S[i].C};
+      for (int i = 0; i < a.nsrc; ++i) a.src[i] = GnSrc{m->statp(S[i].stats_off), ntiles_of(L, SR[i]), S[i].C};
       a.Ctot = Ctot;
       a.groups = groups;
       a.inv_count = 1.0 / ((double)(Creal / groups) * (double)L);
-      a.gamma = self->wf(g_off);
-      a.beta = self->wf(b_off);
-      a.film = film ? self->miscp(film_misc_off) : nullptr;
-      a.film_stride = film_stride;
-      a.film_off = film_off;
-      a.ss = self->ssf2(ss_off);
-      a.mr = want_mr ? self->ssf2(mr_off) : nullptr;
-      a.status = reinterpret_cast<unsigned*>(self->miscp(st_off));
+      a.gamma = m->wf(g_off);
+      a.beta = m->wf(b_off);
+      a.film = film ? m->miscp(fr.misc_off) : nullptr;
+      a.film_stride = fr.stride;
+      a.film_off = fr.off;
+      a.ss = m->ssf2(tb.ss);
+      a.mr = tb.want_mr ? m->ssf2(tb.mr) : nullptr;
+      a.status = reinterpret_cast<unsigned*>(m->miscp(st_off));
       a.guard = guard;
     };
     if (m_->cfg.debug_taps) {  // (read-only record for vqvs_debug_gn_*: nothing the schedule runs depends on it)
@@ -434,12 +444,12 @@ class Builder {
       d.groups = groups;
       d.cpg_real = Creal / groups;
       d.lshift = lshift;
-      d.film = film;
-      d.film_off = film_off;
-      d.film_stride = film_stride;
-      d.ss_off = ss_off;
-      d.mr_off = mr_off;
-      d.has_mr = want_mr;
+      d.film = film.has_value();
+      d.film_off = fr.off;
+      d.film_stride = fr.stride;
+      d.ss_off = tb.ss;
+      d.mr_off = tb.mr;
+      d.has_mr = tb.want_mr;
       d.fused = [link](const RunCtx& c) { return link->fused && link->fused(c); };
       d.fill = [link](const RunCtx& c, GnArgs& a) { link->fill(c, a); };
       m_->gns.push_back(std::move(d));
@@ -456,7 +466,7 @@ class Builder {
   // g = gelu(GN(x)) [avg-pooled] written once (deep levels, see XformArgs)
   TensorH add_xform(const TensorH& src, size_t ss_off, int ss_stride, int ss_c0, bool avg) {
     TensorH g = new_tensor(src.C, src.lshift + (avg ? 1 : 0), false, false);
-    Builder* self = this;
+    const vqvs_model* const m = m_;
     const int prec = m_->cfg.precision;
     const TensorH S = src;
     if (m_->cfg.debug_taps) {
@@ -473,9 +483,9 @@ class Builder {
     op("xform", "C=" + std::to_string(src.C) + " L>>" + std::to_string(g.lshift) + (avg ? " avg" : ""),
        src.C * (lscale(src.lshift) + lscale(g.lshift)), 0, 0, [=](const RunCtx& c) -> int {
       XformArgs a{};
-      a.in = self->act(S.off);
-      a.ss = self->ssf2(ss_off);
-      a.out = self->act(g.off);
+      a.in = m->act(S.off);
+      a.ss = m->ssf2(ss_off);
+      a.out = m->act(g.off);
       a.C = S.C;
       a.Lin = shiftL(c.Lbase, S.lshift);
       a.Lout = shiftL(c.Lbase, g.lshift);
@@ -487,18 +497,36 @@ class Builder {
     return g;
   }
 
+  // One source of a convolution: channels [c0, c0 + C) of `t` through `ntaps` taps.  Made by raw_seg / norm_seg; what differs from
+  // the defaults is then set by name.
   struct SegSpec {
     TensorH t;
-    int c0, C, ntaps, dil, resize;
-    bool xform;
-    size_t ss_off;
-    int ss_stride, ss_c0;
-    long long w_off;
+    int c0 = 0, C = 0, ntaps = 3, dil = 1, resize = RESIZE_NONE;
+    bool xform = false;  // the rows go through the GroupNorm + GELU prologue: (scale, shift) rows of ss_stride channels at ss_off (ss
+    size_t ss_off = 0;   // region), of which this source's begin at channel ss_c0
+    int ss_stride = 0, ss_c0 = 0;
+    long long w_off = 0;  // where PackedConv::append put its weights
     // two-tensor affine prologue (kernels.hpp SegDesc.src2): staged row = P * t + Q * t2 + R with (P, Q, R, 0) rows at coef_off (misc region)
     bool aff2 = false;
     TensorH t2{};
     size_t coef_off = 0;
   };
+  // every channel of `t`, read as stored ...
+  static SegSpec raw_seg(const TensorH& t) {
+    SegSpec g;
+    g.t = t;
+    g.C = t.C;
+    return g;
+  }
+  // ... or normalised on the way in by the table `ss_off`, whose rows are ss_stride channels wide and hold `t` from channel ss_c0 on
+  static SegSpec norm_seg(const TensorH& t, size_t ss_off, int ss_stride, int ss_c0 = 0) {
+    SegSpec g = raw_seg(t);
+    g.xform = true;
+    g.ss_off = ss_off;
+    g.ss_stride = ss_stride;
+    g.ss_c0 = ss_c0;
+    return g;
+  }
 
   // GELU backward fused into a transposed convolution's epilogue (kernels.hpp BwActFuse): forward tensors covering the output
   // channels in order, the forward (scale, shift) table and the partial-sum block the GroupNorm backward reads
@@ -517,38 +545,62 @@ class Builder {
     return v != 0;
   }
 
-  // out_lshift: logical output length when it differs from the allocation of `out` (padding rows); epi_gelu: out = skip + gelu(acc).
+  // One convolution entry: out = bias + sum over segs [+ skip].  The weights are appended to `pk` segment by segment as `segs` is filled.
+  struct ConvSpec {
+    explicit ConvSpec(int precision) : pk(precision) {}
+    std::vector<SegSpec> segs;
+    PackedConv pk;
+    std::vector<float> bias;
+    int Cout = 0;
+    TensorH out;
+    std::optional<TensorH> skip;       // identity skip added in the epilogue, read through skip_resize
+    int skip_resize = RESIZE_NONE;
+    std::optional<int> out_lshift;     // logical output length where it differs from the allocation of `out` (padding rows)
+    bool epi_gelu = false;             // out = skip + gelu(acc)
+    std::optional<BwFuse> fuse;
+    std::shared_ptr<GnLink> gn;        // the GroupNorm of the prologue, where this convolution may build its table itself
+  };
+  ConvSpec conv_spec(int Cout, const TensorH& out) const {
+    ConvSpec cv(m_->cfg.precision);
+    cv.Cout = Cout;
+    cv.out = out;
+    return cv;
+  }
   // Returns the rows per workgroup tile (= rows per statistics / partial-sum tile of the output).
-  int add_conv(const std::vector<SegSpec>& segs, const PackedConv& pk, const std::vector<float>& bias, int Cout, const TensorH& out,
-               const TensorH* skip, int skip_resize, int out_lshift = -1000, bool epi_gelu = false, const BwFuse* fuse = nullptr,
-               std::shared_ptr<GnLink> gn = nullptr) {
-    const size_t hi_off = blob.add(pk.hi.data(), pk.hi.size() * 2);
-    const size_t lo_off = m_->cfg.precision == VQVS_PREC_F32 ? blob.add(pk.lo.data(), pk.lo.size() * 2) : 0;
-    const size_t bias_off = blob.add(bias.data(), bias.size() * 4);
-    const long long w_bytes = (long long)pk.hi.size() * 2;
+  int add_conv(const ConvSpec& cv) {
+    // (what the entries below capture is copied out of the spec: they outlive it, and must not carry its packed weights)
+    const std::vector<SegSpec>& segs = cv.segs;
+    const TensorH& out = cv.out;
+    const int Cout = cv.Cout, skip_resize = cv.skip_resize, out_lshift = cv.out_lshift.value_or(out.lshift);
+    const bool epi_gelu = cv.epi_gelu;
+    const std::shared_ptr<GnLink> gn = cv.gn;
+    const size_t hi_off = blob.add(cv.pk.hi.data(), cv.pk.hi.size() * 2);
+    const size_t lo_off = m_->cfg.precision == VQVS_PREC_F32 ? blob.add(cv.pk.lo.data(), cv.pk.lo.size() * 2) : 0;
+    const size_t bias_off = blob.add(cv.bias.data(), cv.bias.size() * 4);
+    const long long w_bytes = (long long)cv.pk.hi.size() * 2;
     const bool x3 = m_->cfg.precision == VQVS_PREC_F32;
     const int prec = m_->cfg.precision;
-    Builder* self = this;
+    const vqvs_model* const m = m_;
     std::vector<SegSpec> S = segs;
     const TensorH O = out;
-    const bool has_skip = skip != nullptr;
-    const TensorH K = skip ? *skip : TensorH{};
+    const bool has_skip = cv.skip.has_value();
+    const TensorH K = cv.skip.value_or(TensorH{});
     int dmax = 0;
     for (auto& g : segs)
       if (g.ntaps == 3 && g.dil > dmax) dmax = g.dil;
-    int kchunks = skip ? 2 : 0;  // (K chunks of 32 channels per tile: a one-chunk tile is only covered at 32 output channels)
+    int kchunks = has_skip ? 2 : 0;  // (K chunks of 32 channels per tile: a one-chunk tile is only covered at 32 output channels)
     for (auto& g : segs) kchunks += g.C / 32;
-    bool ws_ok = !out.f32 && !epi_gelu && fuse == nullptr && out_lshift == -1000 && kchunks >= 2;
+    bool ws_ok = !out.f32 && !epi_gelu && !cv.fuse && !cv.out_lshift && kchunks >= 2;
     for (auto& g : segs) ws_ok = ws_ok && !g.aff2;  // (conv_mfma_kernel's two-tensor prologue)
     if (m_->cfg.precision == VQVS_PREC_F32) {
       // fp32 storage: a tile geometry other than the default one may only be chosen where conv_ws_kernel is certain to take the
       // launch (conv_mfma_kernel has one geometry): its fp32 form has no avg-pooled sources, wants 32-channel chunks, and
       // addresses a clip's rows through 32-bit descriptors -- checked here against the model's largest clip
       const bool kind_ok = ws_f32_kind;
-      bool ok = kind_ok && Cout % 64 == 0 && !(skip && skip_resize == RESIZE_AVG2);
+      bool ok = kind_ok && Cout % 64 == 0 && !(has_skip && skip_resize == RESIZE_AVG2);
       auto clip_bytes = [&](const TensorH& t) { return (long long)shiftL(m_->cfg.max_T, t.lshift) * t.C * 4; };
       for (auto& g : segs) ok = ok && g.resize != RESIZE_AVG2 && g.C % 32 == 0 && (g.ntaps == 1 || g.ntaps == 3) && clip_bytes(g.t) < (1LL << 29);
-      if (skip) ok = ok && skip->C == Cout && clip_bytes(*skip) < (1LL << 29);
+      if (has_skip) ok = ok && K.C == Cout && clip_bytes(K) < (1LL << 29);
       ok = ok && clip_bytes(out) < (1LL << 31);
       ws_ok = ws_ok && ok;
     }
@@ -561,24 +613,24 @@ class Builder {
       conv_elems += s.C * lscale(s.t.lshift) * (s.aff2 ? 2 : 1);
       ktot += (double)s.C * s.ntaps;
     }
-    if (skip) conv_elems += K.C * lscale(K.lshift);
-    if (fuse) conv_elems += Cout * lscale(out.lshift);  // the forward tensor(s) read by the fused GELU backward
-    const bool has_fuse = fuse != nullptr;
-    const BwFuse F = fuse ? *fuse : BwFuse{};
+    if (has_skip) conv_elems += K.C * lscale(K.lshift);
+    if (cv.fuse) conv_elems += Cout * lscale(out.lshift);  // the forward tensor(s) read by the fused GELU backward
+    const bool has_fuse = cv.fuse.has_value();
+    const BwFuse F = cv.fuse.value_or(BwFuse{});
     if (out.f32) conv_f32 += 4.0 * Cout * lscale(out.lshift);
     else conv_elems += Cout * lscale(out.lshift);
     const double conv_flops = 2.0 * Cout * ktot * lscale(out.lshift);
     std::string desc;
     for (auto& s : segs) desc += (desc.empty() ? "" : "+") + std::to_string(s.C) + "x" + std::to_string(s.ntaps) + (s.resize == RESIZE_AVG2 ? "v" : s.resize == RESIZE_UP2 ? "^" : "") + (s.ntaps == 3 && s.dil > 1 ? "d" + std::to_string(s.dil) : "");
-    desc += "->" + std::to_string(Cout) + " L>>" + std::to_string(out.lshift) + (skip ? " +id" : "");
+    desc += "->" + std::to_string(Cout) + " L>>" + std::to_string(out.lshift) + (has_skip ? " +id" : "");
     const int ws_f32 = ws_f32_kind ? 1 : 0;
     const int rev = (conv_seq_++) & 1;  // consecutive convolutions walk their tiles in opposite directions (ConvArgs.rev)
     auto build = [=](const RunCtx& c, ConvArgs& a) {
       a.nseg = (int)S.size();
       for (int i = 0; i < a.nseg; ++i) {
         SegDesc& g = a.seg[i];
-        g.src = self->act(S[i].t.off);
-        g.ss = S[i].xform ? self->ssf2(S[i].ss_off) : nullptr;
+        g.src = m->act(S[i].t.off);
+        g.ss = S[i].xform ? m->ssf2(S[i].ss_off) : nullptr;
         g.w_off = S[i].w_off;
         g.Csrc = S[i].t.C;
         g.c0 = S[i].c0;
@@ -590,29 +642,29 @@ class Builder {
         g.ss_stride = S[i].ss_stride;
         g.ss_c0 = S[i].ss_c0;
         if (S[i].aff2) {
-          g.src2 = self->act(S[i].t2.off);
-          g.coef = reinterpret_cast<const float4*>(self->miscp(S[i].coef_off));
+          g.src2 = m->act(S[i].t2.off);
+          g.coef = reinterpret_cast<const float4*>(m->miscp(S[i].coef_off));
           g.coef_stride = S[i].C;
           g.coef_c0 = 0;
         }
       }
-      a.w_hi = reinterpret_cast<const bf16_t*>(self->wp(hi_off));
-      a.w_lo = x3 ? reinterpret_cast<const bf16_t*>(self->wp(lo_off)) : nullptr;
+      a.w_hi = reinterpret_cast<const bf16_t*>(m->wp(hi_off));
+      a.w_lo = x3 ? reinterpret_cast<const bf16_t*>(m->wp(lo_off)) : nullptr;
       a.w_bytes = w_bytes;
-      a.bias = self->wf(bias_off);
+      a.bias = m->wf(bias_off);
       a.Cout = Cout;
-      a.Lout = shiftL(c.Lbase, out_lshift == -1000 ? O.lshift : out_lshift);
+      a.Lout = shiftL(c.Lbase, out_lshift);
       a.out_rows = shiftL(c.Lbase, O.lshift);
       a.epi_gelu = epi_gelu ? 1 : 0;
       if (has_skip) {
-        a.skip = self->act(K.off);
+        a.skip = m->act(K.off);
         a.skip_C = K.C;
         a.skip_L = shiftL(c.Lbase, K.lshift);
         a.skip_resize = skip_resize;
       }
-      a.out = self->act(O.off);
+      a.out = m->act(O.off);
       a.out_f32 = O.f32 ? 1 : 0;
-      a.stats = O.has_stats ? self->statp(O.stats_off) : nullptr;
+      a.stats = O.has_stats ? m->statp(O.stats_off) : nullptr;
       a.ntiles = ntiles_of(a.Lout, tile_rows);
       a.tile_rows = tile_rows;
       a.rev = rev;
@@ -621,56 +673,54 @@ class Builder {
         a.nbw = (int)F.xf.size();
         int c0 = 0;
         for (int i = 0; i < a.nbw; ++i) {
-          a.bw[i] = BwActFuse{self->act(F.xf[i].off), F.xf[i].C, c0};
+          a.bw[i] = BwActFuse{m->act(F.xf[i].off), F.xf[i].C, c0};
           c0 += F.xf[i].C;
         }
-        a.bw_ss = self->ssf2(F.ss_off);
+        a.bw_ss = m->ssf2(F.ss_off);
         a.bw_ss_stride = F.ss_stride;
-        a.stats = self->statp(F.part_off);
+        a.stats = m->statp(F.part_off);
       }
     };
+    // The launch at this (B, L), as all three users below see it: `a` with the GroupNorm `g` of link `gl` hung in where
+    // conv_ws_kernel builds the table itself (otherwise the gn_prepare entry before this one has run)
+    auto launch_args = [=](const RunCtx& c, ConvArgs& a, GnArgs& g, const GnLink* gl) {
+      build(c, a);
+      if (!gl) return;
+      gl->fill(c, g);
+      a.gn = &g;
+      if (!ws_fuses_gn(a, c.B, prec)) a.gn = nullptr;
+    };
     if (gn) {
-      GnLink* const gl = gn.get();
+      GnLink* const gl = gn.get();  // (`fused` is stored INSIDE the link: holding the shared_ptr there would be a cycle)
       gl->fused = [=](const RunCtx& c) -> bool {
         ConvArgs a{};
-        build(c, a);
         GnArgs g{};
-        gl->fill(c, g);
-        a.gn = &g;
-        return ws_fuses_gn(a, c.B, prec);
+        launch_args(c, a, g, gl);
+        return a.gn != nullptr;
       };
     }
     if (m_->cfg.debug_taps && out.has_stats)  // (for vqvs_debug_gn_info: which kernel this launch's statistics come from)
       sums_stored_[out.id] = [=](const RunCtx& c) -> bool {
         if (x3) return true;  // (float32 storage: the accumulators are what is stored)
         ConvArgs a{};
-        build(c, a);
         GnArgs g{};
-        if (gn) {
-          gn->fill(c, g);
-          a.gn = &g;
-          if (!ws_fuses_gn(a, c.B, prec)) a.gn = nullptr;
-        }
+        launch_args(c, a, g, gn.get());
         return ws_takes(a, c.B, prec);
       };
     op("conv", desc, conv_elems, conv_f32, conv_flops, [=](const RunCtx& c) -> int {
       ConvArgs a{};
-      build(c, a);
       GnArgs g{};
-      if (gn) {
-        gn->fill(c, g);
-        a.gn = &g;
-        if (!ws_fuses_gn(a, c.B, prec)) a.gn = nullptr;  // (then the gn_prepare entry before this one has run)
-      }
+      launch_args(c, a, g, gn.get());
       return launch_conv(a, c.B, prec, c.st);
     });
     return tile_rows;
   }
 
   // One reference ResBlock (unet.py:248-316).  `ins` = 1 tensor, or 2 for torch.cat([h, skip], 1).
-  // film_misc_off/film_off/film_stride locate this block's (a|b) rows; emb = false for the encoder.
-  TensorH resblock(const std::string& p, const BlockSpec& s, const std::vector<TensorH>& ins, bool emb, int film_off, int film_stride,
-                   size_t film_misc_off, BlockRec* rec = nullptr) {
+  // film: this block's (a | b) rows, none for a block without an embedding (the encoder's).  rec: filled for a backward schedule,
+  // which also keeps the (mean, rstd) tables.
+  TensorH resblock(const std::string& p, const BlockSpec& s, const std::vector<TensorH>& ins, const std::optional<FilmRows>& film,
+                   BlockRec* rec = nullptr) {
     const std::string pre = p.empty() ? "" : p + ".";
     const int cin = s.cin, cout = s.cout;
     const int in_shift = ins[0].lshift;
@@ -685,73 +735,78 @@ class Builder {
     const bool pre_xform1 = pre_xform_min > 0 ? cout >= pre_xform_min : (two_byte ? cin > 640 : cout >= 512);  // (2 x 8 B x cin of table beside the tiles)
     const bool pre_xform2 = pre_xform_min > 0 ? cout >= pre_xform_min : (two_byte ? false : cout >= 512);
     // GroupNorm 1 coefficients over the (virtually concatenated) input
-    const size_t ss1 = alloc_ss(cin);
-    const size_t mr1 = rec ? alloc_ss(cin) : 0;
+    const GnTables t1 = alloc_gn_tables(cin, rec != nullptr);
+    const size_t ss1 = t1.ss, mr1 = t1.mr;
     // (a model with a backward pass keeps every table in memory: no fusion there)
-    auto gn1 = add_gn(ins, pre + "pre_cond.0.0", false, 0, 0, 0, ss1, rec != nullptr, mr1);
+    auto gn1 = add_gn(ins, pre + "pre_cond.0.0", std::nullopt, t1);
     const bool fuse_gn = rec == nullptr && two_byte;
     // conv 1
     TensorH h1 = new_tensor(cout, out_shift, false, true);
     {
-      PackedConv pk(m_->cfg.precision);
-      std::vector<SegSpec> segs;
+      ConvSpec cv = conv_spec(cout, h1);
       const float* W = P(pre + "pre_cond.2.weight");
       int cb = 0;
       std::vector<TensorH> tmp;
       for (auto& t : ins) {
-        SegSpec g{t, 0, t.C, 3, 1, s.resize, true, ss1, cin, cb, 0};
+        SegSpec g = norm_seg(t, ss1, cin, cb);
+        g.resize = s.resize;
         if (pre_xform1) {  // prologue hoisted out of the GEMM: the conv reads g raw
           g.t = add_xform(t, ss1, cin, cb, s.resize == RESIZE_AVG2);
           g.xform = false;
           if (s.resize == RESIZE_AVG2) g.resize = RESIZE_NONE;
           tmp.push_back(g.t);
         }
-        g.w_off = pk.append(W, cout, cin, 3, cb, t.C);
-        segs.push_back(g);
+        g.w_off = cv.pk.append(W, cout, cin, 3, cb, t.C);
+        cv.segs.push_back(g);
         cb += t.C;
       }
       const float* b = P(pre + "pre_cond.2.bias");
-      add_conv(segs, pk, std::vector<float>(b, b + cout), cout, h1, nullptr, 0, -1000, false, nullptr, fuse_gn && !pre_xform1 ? gn1 : nullptr);
+      cv.bias.assign(b, b + cout);
+      if (fuse_gn && !pre_xform1) cv.gn = gn1;
+      add_conv(cv);
       for (auto& t : tmp) release(t);
     }
     // GroupNorm 2 (+FiLM) coefficients
-    const size_t ss2 = alloc_ss(cout);
-    const size_t mr2 = rec ? alloc_ss(cout) : 0;
-    auto gn2 = add_gn({h1}, pre + "pre_cond.3", emb, film_off, film_stride, film_misc_off, ss2, rec != nullptr, mr2);
-    const std::shared_ptr<GnLink> gl2 = fuse_gn && !pre_xform2 ? gn2 : nullptr;
+    const GnTables t2 = alloc_gn_tables(cout, rec != nullptr);
+    const size_t ss2 = t2.ss, mr2 = t2.mr;
+    auto gn2 = add_gn({h1}, pre + "pre_cond.3", film, t2);
     // conv 2 + skip
     TensorH out = new_tensor(cout, out_shift, false, true);
     {
-      PackedConv pk(m_->cfg.precision);
-      std::vector<SegSpec> segs;
+      ConvSpec cv = conv_spec(cout, out);
+      if (fuse_gn && !pre_xform2) cv.gn = gn2;
       const std::string c2 = pre + (cfg_dropout(m_->cfg) ? "post_cond.2" : "post_cond.1");
       const float* W = P(c2 + ".weight");
       const float* b = P(c2 + ".bias");
-      std::vector<float> bias(b, b + cout);
-      SegSpec g{h1, 0, cout, 3, s.dil, RESIZE_NONE, true, ss2, cout, 0, 0};
+      std::vector<float>& bias = cv.bias;
+      bias.assign(b, b + cout);
+      SegSpec g = norm_seg(h1, ss2, cout);
+      g.dil = s.dil;
       TensorH g2{};
       if (pre_xform2) {
         g2 = add_xform(h1, ss2, cout, 0, false);
         g.t = g2;
         g.xform = false;
       }
-      g.w_off = pk.append(W, cout, cout, 3, 0, cout);
-      segs.push_back(g);
+      g.w_off = cv.pk.append(W, cout, cout, 3, 0, cout);
+      cv.segs.push_back(g);
       if (cin != cout) {  // 1x1 skip conv folded into the same GEMM as raw 1-tap segments
         const float* Ws = P(pre + "skip.1.weight");
         const float* bs = P(pre + "skip.1.bias");
         for (int i = 0; i < cout; ++i) bias[i] += bs[i];
         int cb = 0;
         for (auto& t : ins) {
-          SegSpec r{t, 0, t.C, 1, 1, RESIZE_NONE, false, 0, 0, 0, 0};
-          r.w_off = pk.append(Ws, cout, cin, 1, cb, t.C);
-          segs.push_back(r);
+          SegSpec r = raw_seg(t);
+          r.ntaps = 1;
+          r.w_off = cv.pk.append(Ws, cout, cin, 1, cb, t.C);
+          cv.segs.push_back(r);
           cb += t.C;
         }
-        add_conv(segs, pk, bias, cout, out, nullptr, 0, -1000, false, nullptr, gl2);
       } else {  // identity skip (never together with a concatenated input in this topology)
-        add_conv(segs, pk, bias, cout, out, &ins[0], s.resize, -1000, false, nullptr, gl2);
+        cv.skip = ins[0];
+        cv.skip_resize = s.resize;
       }
+      add_conv(cv);
       if (pre_xform2) release(g2);
     }
     release(h1);
@@ -764,18 +819,18 @@ class Builder {
   // [c0, c0 + xf.C) of a partials block that is Ctot channels wide
   void add_bw_act(const TensorH& t, int resize, const TensorH& xf, size_t ss_off, const TensorH& du, size_t part_off, int c0 = 0,
                   int Ctot = 0) {
-    Builder* self = this;
+    const vqvs_model* const m = m_;
     const int prec = m_->cfg.precision;
     if (Ctot == 0) Ctot = xf.C;
     op("bw_act", "C=" + std::to_string(xf.C) + " L>>" + std::to_string(xf.lshift) +
                      (resize == BW_FROM_HALF ? " from L/2" : resize == BW_FROM_DOUBLE ? " from 2L" : ""),
        xf.C * (2 * lscale(xf.lshift) + lscale(t.lshift)), 0, 0, [=](const RunCtx& c) -> int {
       BwActArgs a{};
-      a.t = self->act(t.off);
-      a.xf = self->act(xf.off);
-      a.ss = self->ssf2(ss_off);
-      a.du = self->act(du.off);
-      a.partials = self->statp(part_off);
+      a.t = m->act(t.off);
+      a.xf = m->act(xf.off);
+      a.ss = m->ssf2(ss_off);
+      a.du = m->act(du.off);
+      a.partials = m->statp(part_off);
       a.C = xf.C;
       a.L = shiftL(c.Lbase, xf.lshift);
       a.resize = resize;
@@ -792,19 +847,19 @@ class Builder {
   }
   size_t add_gn_bw(int C, int lshift, size_t part_off, size_t ss_off, size_t mr_off, int tile_rows = STAT_TILE) {
     const size_t coef = alloc_misc((size_t)maxB_ * C * 4);
-    Builder* self = this;
+    const vqvs_model* const m = m_;
     const int groups = gn_groups(C);
     op("gn_bw", "C=" + std::to_string(C) + " L>>" + std::to_string(lshift), 0, 0, 0, [=](const RunCtx& c) -> int {
       GnBwArgs a{};
       const int L = shiftL(c.Lbase, lshift);
-      a.partials = self->statp(part_off);
+      a.partials = m->statp(part_off);
       a.ntiles = ntiles_of(L, tile_rows);
       a.C = C;
       a.groups = groups;
       a.inv_count = 1.0 / ((double)(C / groups) * (double)L);
-      a.ss = self->ssf2(ss_off);
-      a.mr = self->ssf2(mr_off);
-      a.coef = reinterpret_cast<float4*>(self->miscp(coef));
+      a.ss = m->ssf2(ss_off);
+      a.mr = m->ssf2(mr_off);
+      a.coef = reinterpret_cast<float4*>(m->miscp(coef));
       return launch_gn_bw(a, c.B, c.st);
     });
     return coef;
@@ -812,7 +867,7 @@ class Builder {
   // out = P*du + Q*xf + R (+ skip) (+ extra); du / extra / coef may be slices [c0, c0 + xf.C) of Ctot-wide buffers
   void add_bw_affine(const TensorH& du, const TensorH& xf, size_t coef, const TensorH* skip, int skip_mode, const TensorH* extra,
                      const TensorH& out, int c0 = 0, int Ctot = 0) {
-    Builder* self = this;
+    const vqvs_model* const m = m_;
     const int prec = m_->cfg.precision;
     if (Ctot == 0) Ctot = xf.C;
     const bool has_skip = skip != nullptr, has_extra = extra != nullptr;
@@ -820,13 +875,13 @@ class Builder {
     op("bw_affine", "C=" + std::to_string(xf.C) + " L>>" + std::to_string(xf.lshift),
        xf.C * lscale(xf.lshift) * (3 + (has_extra ? 1 : 0)) + (has_skip ? K.C * lscale(K.lshift) : 0.0), 0, 0, [=](const RunCtx& c) -> int {
       BwAffineArgs a{};
-      a.du = self->act(du.off);
-      a.xf = self->act(xf.off);
-      a.coef = reinterpret_cast<const float4*>(self->miscp(coef));
-      a.skip = has_skip ? self->act(K.off) : nullptr;
+      a.du = m->act(du.off);
+      a.xf = m->act(xf.off);
+      a.coef = reinterpret_cast<const float4*>(m->miscp(coef));
+      a.skip = has_skip ? m->act(K.off) : nullptr;
       a.skip_mode = skip_mode;
-      a.extra = has_extra ? self->act(E.off) : nullptr;
-      a.out = self->act(out.off);
+      a.extra = has_extra ? m->act(E.off) : nullptr;
+      a.out = m->act(out.off);
       a.C = xf.C;
       a.L = shiftL(c.Lbase, xf.lshift);
       a.du_C = du.C;
@@ -839,11 +894,11 @@ class Builder {
     });
   }
   void add_bw_add(const TensorH& x, const TensorH& y, const TensorH& out) {  // out = x + y (same shape)
-    Builder* self = this;
+    const vqvs_model* const m = m_;
     const int prec = m_->cfg.precision;
     op("bw_add", "C=" + std::to_string(x.C) + " L>>" + std::to_string(x.lshift), 3 * x.C * lscale(x.lshift), 0, 0, [=](const RunCtx& c) -> int {
       const long long n = (long long)c.B * shiftL(c.Lbase, x.lshift) * x.C;
-      return launch_bw_add(self->act(x.off), self->act(y.off), self->act(out.off), n, prec, c.st);
+      return launch_bw_add(m->act(x.off), m->act(y.off), m->act(out.off), n, prec, c.st);
     });
   }
   // plain convolution of a raw tensor with transposed weights (no prologue, no statistics, zero bias)
@@ -852,15 +907,21 @@ class Builder {
   int add_conv_t(const TensorH& src, const float* W, int Cout_fwd, int Cin_fwd, int ktaps, int dil, const TensorH& out,
                  const BwFuse* fuse = nullptr, const TensorH* aff_xf = nullptr, size_t aff_coef = 0) {
     const std::vector<float> Wt = transpose_flip(W, Cout_fwd, Cin_fwd, ktaps);
-    PackedConv pk(m_->cfg.precision);
-    SegSpec g{src, 0, Cout_fwd, ktaps, dil, RESIZE_NONE, false, 0, 0, 0, 0};
+    ConvSpec cv = conv_spec(Cin_fwd, out);
+    SegSpec g = raw_seg(src);
+    g.C = Cout_fwd;
+    g.ntaps = ktaps;
+    g.dil = dil;
     if (aff_xf) {
       g.aff2 = true;
       g.t2 = *aff_xf;
       g.coef_off = aff_coef;
     }
-    g.w_off = pk.append(Wt.data(), Cin_fwd, Cout_fwd, ktaps, 0, Cout_fwd);
-    return add_conv({g}, pk, std::vector<float>(Cin_fwd, 0.f), Cin_fwd, out, nullptr, 0, -1000, false, fuse);
+    g.w_off = cv.pk.append(Wt.data(), Cin_fwd, Cout_fwd, ktaps, 0, Cout_fwd);
+    cv.segs.push_back(g);
+    cv.bias.assign(Cin_fwd, 0.f);
+    if (fuse) cv.fuse = *fuse;
+    return add_conv(cv);
   }
 
   // Gradient of one ResBlock with respect to its input(s):
@@ -1000,22 +1061,22 @@ class Builder {
     const size_t gemb_off = alloc_misc((size_t)maxB_ * E);
     m_->emb_misc_off = emb_off;
     m_->emb_E = E;
-    Builder* self = this;
+    const vqvs_model* const m = m_;
     op("time_embed", "", 0, 0, 0, [=](const RunCtx& r) -> int {
       TimeEmbedArgs a{};
       a.ts = r.ts;
-      a.freqs = self->wf(freq_off);
-      a.w1 = self->wf(w1);
-      a.b1 = self->wf(b1);
-      a.w2 = self->wf(w2);
-      a.b2 = self->wf(b2);
+      a.freqs = m->wf(freq_off);
+      a.w1 = m->wf(w1);
+      a.b1 = m->wf(b1);
+      a.w2 = m->wf(w2);
+      a.b2 = m->wf(b2);
       // an explicit vector per clip (vqvs_unet_forward_vec, vqvs_unet_embed_grad) takes the table's place: the kernel adds one or the other
-      a.class_embed = class_table && !r.class_vec ? self->wf(ce) : nullptr;
+      a.class_embed = class_table && !r.class_vec ? m->wf(ce) : nullptr;
       a.labels = r.labels;  // (read beside class_embed only)
       a.class_vec = class_vec ? r.class_vec : nullptr;
       a.num_labels = num_labels;
-      a.emb = self->miscp(emb_off);
-      a.gemb = self->miscp(gemb_off);
+      a.emb = m->miscp(emb_off);
+      a.gemb = m->miscp(gemb_off);
       a.E = E;
       return launch_time_embed(a, r.B, r.st);
     });
@@ -1027,6 +1088,13 @@ class Builder {
     std::vector<int> row;  // first row of block i
     int R = 0;
     size_t wall_off = 0, film_off = 0;  // the stacked weights (transposed, weight blob) and the rows (misc region)
+    FilmRows rows(size_t i) const {     // block i's
+      FilmRows r;
+      r.misc_off = film_off;
+      r.off = row[i];
+      r.stride = R;
+      return r;
+    }
   };
   Film film_table(const std::vector<BlockSpec>& blocks, int E, size_t gemb_off) {
     Film f;
@@ -1046,9 +1114,9 @@ class Builder {
     const size_t film_off = f.film_off = alloc_misc((size_t)maxB_ * R);
     m_->film_misc_off = film_off;
     m_->film_R = R;
-    Builder* self = this;
+    const vqvs_model* const m = m_;
     op("film", "", 0, 0, 0, [=](const RunCtx& r) -> int {
-      FilmArgs a{self->miscp(gemb_off), self->wf(wall_off), self->wf(ball_off), self->miscp(film_off), E, R};
+      FilmArgs a{m->miscp(gemb_off), m->wf(wall_off), m->wf(ball_off), m->miscp(film_off), E, R};
       return launch_film(a, r.B, r.st);
     });
     return f;
@@ -1065,19 +1133,19 @@ class Builder {
     if (w_off) *w_off = w;
     const bool has_cond = condp != nullptr;
     const TensorH cp = condp ? *condp : TensorH{};
-    Builder* self = this;
+    const vqvs_model* const m = m_;
     if (m_->cfg.debug_taps) sums_stored_[h.id] = [prec](const RunCtx&) { return prec == VQVS_PREC_F32; };
     op("in_conv", std::to_string(row_cin) + "->" + std::to_string(base), base + (has_cond ? base * lscale(cp.lshift) : 0.0), 4.0 * row_cin, 0,
        [=](const RunCtx& r) -> int {
       InConvArgs a{};
       a.x = r.x;
       a.Cin = Cin;
-      a.w = self->wf(w);
-      a.bias = self->wf(bi);
-      a.condp = has_cond ? self->act(cp.off) : nullptr;
+      a.w = m->wf(w);
+      a.bias = m->wf(bi);
+      a.condp = has_cond ? m->act(cp.off) : nullptr;
       a.cond_len = has_cond ? shiftL(r.Lbase, cp.lshift) : 0;
-      a.out = self->act(h.off);
-      a.stats = self->statp(h.stats_off);
+      a.out = m->act(h.off);
+      a.stats = m->statp(h.stats_off);
       a.C = base;
       a.T = r.Lbase;
       a.ntiles = ntiles_of(r.Lbase);
@@ -1088,11 +1156,11 @@ class Builder {
   // ... and its transpose, the last kernel of a guidance schedule: grad_out = (gscale / grad_scale) * in_conv^T(g)
   void in_conv_bw(const TensorH& g, size_t w_off) {
     const int base = m_->cfg.base_channels, prec = m_->cfg.precision;
-    Builder* self = this;
+    const vqvs_model* const m = m_;
     op("in_conv_bw", std::to_string(base) + "->1", (double)base, 4.0, 0, [=](const RunCtx& r) -> int {
       InConvBwArgs a{};
-      a.dh = self->act(g.off);
-      a.w = self->wf(w_off);
+      a.dh = m->act(g.off);
+      a.w = m->wf(w_off);
       a.out = r.grad_out;
       a.C = base;
       a.T = r.Lbase;
@@ -1103,32 +1171,29 @@ class Builder {
 
   // Output heads begin with GroupNorm + GELU over the last block's output (unet.py:113-116, classifier.py:94): its coefficient
   // tables (mr: mean / rstd, kept for a backward schedule) and the gn_prepare entry
-  struct GnHead {
-    size_t ss = 0, mr = 0;
-  };
-  GnHead head_gn(const TensorH& h, const std::string& gn_name, bool want_mr) {
-    GnHead g;
-    g.ss = alloc_ss(h.C);
-    g.mr = want_mr ? alloc_ss(h.C) : 0;
-    add_gn({h}, gn_name, false, 0, 0, 0, g.ss, want_mr, g.mr);
+  GnTables head_gn(const TensorH& h, const std::string& gn_name, bool want_mr) {
+    const GnTables g = alloc_gn_tables(h.C, want_mr);
+    add_gn({h}, gn_name, std::nullopt, g);
     return g;
   }
   // ... followed, in the UNets, by a 3-tap convolution into a float32 boundary tensor
-  TensorH head_conv(const TensorH& h, const GnHead& gh, const std::string& conv_name, int Cout, int out_lshift) {
+  TensorH head_conv(const TensorH& h, const GnTables& gh, const std::string& conv_name, int Cout, int out_lshift) {
     TensorH o = new_tensor(Cout, out_lshift, true, false);
-    PackedConv pk(m_->cfg.precision);
-    SegSpec g{h, 0, h.C, 3, 1, RESIZE_NONE, true, gh.ss, h.C, 0, 0};
-    g.w_off = pk.append(P(conv_name + ".weight"), Cout, h.C, 3, 0, h.C);
+    ConvSpec cv = conv_spec(Cout, o);
+    SegSpec g = norm_seg(h, gh.ss, h.C);
+    g.w_off = cv.pk.append(P(conv_name + ".weight"), Cout, h.C, 3, 0, h.C);
+    cv.segs.push_back(g);
     const float* bb = P(conv_name + ".bias");
-    add_conv({g}, pk, std::vector<float>(bb, bb + Cout), Cout, o, nullptr, 0);
+    cv.bias.assign(bb, bb + Cout);
+    add_conv(cv);
     return o;
   }
   // the handle's output in the boundary's NCT layout
   void to_nct(const TensorH& o) {
     const int prec = o.f32 ? 0 : m_->cfg.precision;
-    Builder* self = this;
+    const vqvs_model* const m = m_;
     op("ntc_to_nct", "", 0, 0, 0, [=](const RunCtx& r) -> int {
-      return launch_ntc_to_nct(self->act(o.off), r.out, r.B, o.C, shiftL(r.Lbase, o.lshift), prec, r.st);
+      return launch_ntc_to_nct(m->act(o.off), r.out, r.B, o.C, shiftL(r.Lbase, o.lshift), prec, r.st);
     });
   }
 
@@ -1163,10 +1228,7 @@ class Builder {
       if (!merged.empty() && merged.back().first + merged.back().second == f.first) merged.back().second += f.second;
       else merged.push_back(f);
     }
-    // a free block that ends at the high-water mark is given back
-    if (!merged.empty() && merged.back().first + merged.back().second == act_high) {
-      // keep the high-water mark (arena size is the maximum ever needed)
-    }
+    // (a free block that ends at the high-water mark stays in the list: the arena's size is the maximum ever needed)
     free_ = merged;
   }
 
@@ -1419,34 +1481,34 @@ static int check_cfg(const vqvs_cfg& c) {
 }
 
 // ---- one schedule builder per kind -----------------------------------------------------------------------------------------------
-// (the ops capture the Builder by pointer for pointer resolution: build_model keeps it alive beside the handle)
+// (the ops capture the vqvs_model* for pointer resolution, never the Builder: it is gone when build_model returns)
 
 // A single ResBlock (unit-test granularity): NCT in, the external embedding through GELU + cond_layers.1, the block, NCT out
 static void build_resblock(vqvs_model* m, Builder& b) {
   const vqvs_cfg& c = m->cfg;
-  Builder* bp = &b;
   const int prec = c.precision, Cin = c.rb_cin, E = c.rb_emb_channels, R = 2 * c.rb_cout;
   const BlockSpec s{"", c.rb_cin, c.rb_cout, c.rb_resize, c.rb_dilation, false};
   TensorH x = b.new_tensor(Cin, 0, false, true);
   b.op("nct_to_ntc", "", 0, 0, 0, [=](const RunCtx& r) -> int {
-    return launch_nct_to_ntc(r.x, bp->act(x.off), bp->statp(x.stats_off), r.B, Cin, r.Lbase, ntiles_of(r.Lbase), prec, r.st);
+    return launch_nct_to_ntc(r.x, m->act(x.off), m->statp(x.stats_off), r.B, Cin, r.Lbase, ntiles_of(r.Lbase), prec, r.st);
   });
-  size_t film_misc = 0;
+  std::optional<Builder::FilmRows> film;
   if (E) {
     const size_t gemb = b.alloc_misc((size_t)c.max_batch * E);
-    film_misc = b.alloc_misc((size_t)c.max_batch * R);
+    const size_t film_misc = b.alloc_misc((size_t)c.max_batch * R);
+    film = Builder::FilmRows{film_misc, 0, R};  // (the one block's rows are the whole table)
     m->film_misc_off = film_misc;
     m->film_R = R;
     const size_t w_off = b.blob_f32_transposed(b.P("cond_layers.1.weight"), R, E);
     const size_t bias_off = b.blob_f32("cond_layers.1.bias");
     b.op("film", "", 0, 0, 0, [=](const RunCtx& r) -> int {
       if (!r.emb) VQVS_FAIL(VQVS_ERR_ARG, "resblock handle was built with an embedding; d_emb is NULL");
-      if (int e = launch_gelu_rows(r.emb, bp->miscp(gemb), r.B * E, r.st)) return e;
-      FilmArgs f{bp->miscp(gemb), bp->wf(w_off), bp->wf(bias_off), bp->miscp(film_misc), E, R};
+      if (int e = launch_gelu_rows(r.emb, m->miscp(gemb), r.B * E, r.st)) return e;
+      FilmArgs f{m->miscp(gemb), m->wf(w_off), m->wf(bias_off), m->miscp(film_misc), E, R};
       return launch_film(f, r.B, r.st);
     });
   }
-  TensorH y = b.resblock("", s, {x}, E != 0, 0, R, film_misc);
+  TensorH y = b.resblock("", s, {x}, film);
   b.to_nct(y);
   b.tap("out", y);
 }
@@ -1455,9 +1517,8 @@ static void build_resblock(vqvs_model* m, Builder& b) {
 // (phase 1): d mse_b / d v_b for every clip b.  out_w: the output convolution's [3][base] weights; pred: where the prediction of a
 // call that does not ask for it goes.
 static void unet_embed_grad_tail(vqvs_model* m, Builder& b, const std::vector<Builder::BlockRec>& recs, const Builder::TimeEmb& te,
-                                 const Builder::Film& film, const TensorH& h, const Builder::GnHead& gh, size_t out_w, const TensorH& pred) {
+                                 const Builder::Film& film, const TensorH& h, const Builder::GnTables& gh, size_t out_w, const TensorH& pred) {
   const vqvs_cfg& c = m->cfg;
-  Builder* bp = &b;
   const int base = c.base_channels, E = te.E, R = film.R;
   const bool ws_f32_kind = b.ws_f32_kind;
   b.ws_f32_kind = false;  // (the transposed convolutions run where the guidance schedules' run)
@@ -1465,8 +1526,8 @@ static void unet_embed_grad_tail(vqvs_model* m, Builder& b, const std::vector<Bu
   TensorH dout = b.new_tensor(1, 0, true, false);
   const size_t sq_off = b.alloc_misc(2 * (size_t)mse_head_scratch_doubles(c.max_batch, c.max_T));
   b.op("mse_head", "", 0, 12.0, 0, [=](const RunCtx& r) -> int {
-    const float* p = r.out ? r.out : reinterpret_cast<const float*>(bp->act(pred.off));
-    return run_mse_head(p, r.eps, reinterpret_cast<float*>(bp->act(dout.off)), r.mse, reinterpret_cast<double*>(bp->miscp(sq_off)), r.B,
+    const float* p = r.out ? r.out : reinterpret_cast<const float*>(m->act(pred.off));
+    return run_mse_head(p, r.eps, reinterpret_cast<float*>(m->act(dout.off)), r.mse, reinterpret_cast<double*>(m->miscp(sq_off)), r.B,
                         r.Lbase, r.st);
   });
   // out.1 (3-tap conv base -> 1 over gelu(GN(h))) backwards: conv^T and gelu' in one kernel, then GroupNorm backward
@@ -1475,12 +1536,12 @@ static void unet_embed_grad_tail(vqvs_model* m, Builder& b, const std::vector<Bu
   const size_t ss = gh.ss;
   b.op("out_conv_bw", "1->" + std::to_string(base), 2.0 * base, 4.0, 0, [=](const RunCtx& r) -> int {
     OutConvBwArgs a{};
-    a.dout = reinterpret_cast<const float*>(bp->act(dout.off));
-    a.xf = bp->act(h.off);
-    a.ss = bp->ssf2(ss);
-    a.w = bp->wf(out_w);
-    a.du = bp->act(t.off);
-    a.partials = bp->statp(po);
+    a.dout = reinterpret_cast<const float*>(m->act(dout.off));
+    a.xf = m->act(h.off);
+    a.ss = m->ssf2(ss);
+    a.w = m->wf(out_w);
+    a.du = m->act(t.off);
+    a.partials = m->statp(po);
     a.C = base;
     a.L = r.Lbase;
     return launch_out_conv_bw(a, r.B, r.st);
@@ -1502,13 +1563,13 @@ static void unet_embed_grad_tail(vqvs_model* m, Builder& b, const std::vector<Bu
     const size_t mr2 = rec.mr2;
     b.op("film_grad", "C=" + std::to_string(C) + " L>>" + std::to_string(ls), 2.0 * C * lscale(ls), 0, 0, [=](const RunCtx& r) -> int {
       FilmGradArgs a{};
-      a.du = bp->act(D.off);
-      a.h1 = bp->act(H1.off);
-      a.mr = bp->ssf2(mr2);
-      a.gamma = bp->wf(g_off);
-      a.beta = bp->wf(be_off);
-      a.partials = bp->statp(pf);
-      a.dfilm = bp->miscp(dfilm_off);
+      a.du = m->act(D.off);
+      a.h1 = m->act(H1.off);
+      a.mr = m->ssf2(mr2);
+      a.gamma = m->wf(g_off);
+      a.beta = m->wf(be_off);
+      a.partials = m->statp(pf);
+      a.dfilm = m->miscp(dfilm_off);
       a.film_stride = R;
       a.film_off = row;
       a.C = C;
@@ -1521,7 +1582,7 @@ static void unet_embed_grad_tail(vqvs_model* m, Builder& b, const std::vector<Bu
   // d v = gelu'(emb) * Wall^T dfilm
   const size_t wall_off = film.wall_off, emb_off = te.emb_off;
   b.op("film_bw", "", 0, 0, 0, [=](const RunCtx& r) -> int {
-    FilmBwArgs a{bp->miscp(dfilm_off), bp->wf(wall_off), bp->miscp(emb_off), r.egrad, E, R};
+    FilmBwArgs a{m->miscp(dfilm_off), m->wf(wall_off), m->miscp(emb_off), r.egrad, E, R};
     return launch_film_bw(a, r.B, r.st);
   });
   b.phase = 0;
@@ -1531,23 +1592,22 @@ static void unet_embed_grad_tail(vqvs_model* m, Builder& b, const std::vector<Bu
 // EncoderPredictor (encoder_predictor.py:25-58), behind the forward of build_unet with a bottleneck output `o`: the 1x1 head with its
 // cross-entropy gradient (vq_vae.py:125-130: grads of the summed cross-entropy), then the backward schedule (phase 1) down to the input
 static void unet_encpred_tail(vqvs_model* m, Builder& b, const std::vector<Builder::BlockRec>& recs, const TensorH& h,
-                              const Builder::GnHead& gh, const TensorH& o) {
+                              const Builder::GnTables& gh, const TensorH& o) {
   const vqvs_cfg& c = m->cfg;
-  Builder* bp = &b;
   const int prec = c.precision, base = c.base_channels, OC = c.out_channels, D = c.reserved[2], rate = c.reserved[1];
   const size_t hw = b.blob_f32("out.weight"), hb = b.blob_f32("out.bias");
   TensorH dO = b.new_tensor(OC, 0, false, false);
   const int es = b.es();
   b.op("enc_head", "D=" + std::to_string(D), 0, 0, 0, [=](const RunCtx& r) -> int {
-    if (r.backward) VQVS_HIP(hipMemsetAsync(bp->act(dO.off), 0, (size_t)r.B * r.Lbase * OC * es, r.st));
+    if (r.backward) VQVS_HIP(hipMemsetAsync(m->act(dO.off), 0, (size_t)r.B * r.Lbase * OC * es, r.st));
     EncHeadArgs a{};
-    a.o = reinterpret_cast<const float*>(bp->act(o.off));
-    a.w = bp->wf(hw);
-    a.bias = bp->wf(hb);
+    a.o = reinterpret_cast<const float*>(m->act(o.off));
+    a.w = m->wf(hw);
+    a.bias = m->wf(hb);
     a.logits = r.out;
     a.targets = r.backward ? r.labels : nullptr;
     a.gscale = grad_scale(prec);  // (the caller's scale multiplies the finished gradient in fp32, in_conv_bw: the 2-byte gradient tensors never see it)
-    a.dO = bp->act(dO.off);
+    a.dO = m->act(dO.off);
     a.Cb = OC;
     a.D = D;
     a.T = r.Lbase;
@@ -1579,7 +1639,6 @@ static void unet_encpred_tail(vqvs_model* m, Builder& b, const std::vector<Build
 //                       intermediate kept resident too, and unet_embed_grad_tail behind the output convolution.
 static void build_unet(vqvs_model* m, Builder& b) {
   const vqvs_cfg& c = m->cfg;
-  Builder* bp = &b;
   const int prec = c.precision, base = c.base_channels, NL = c.num_labels;
   const bool encpred = c.kind == VQVS_KIND_ENCPRED, gradk = c.kind == VQVS_KIND_PREDICTOR_GRAD;
   const bool keep_bw = encpred || gradk;
@@ -1605,14 +1664,16 @@ static void build_unet(vqvs_model* m, Builder& b) {
     const int CC = c.cond_channels;
     TensorH ct = b.new_tensor(CC, cond_ls, false, false);
     b.op("nct_to_ntc", "", 0, 0, 0, [=](const RunCtx& r) -> int {
-      return launch_nct_to_ntc(r.cond, bp->act(ct.off), nullptr, r.B, CC, shiftL(r.Lbase, cond_ls), 0, prec, r.st);
+      return launch_nct_to_ntc(r.cond, m->act(ct.off), nullptr, r.B, CC, shiftL(r.Lbase, cond_ls), 0, prec, r.st);
     });
     condp = b.new_tensor(base, cond_ls, false, false);
-    PackedConv pk(prec);
-    Builder::SegSpec g{ct, 0, CC, 3, 1, RESIZE_NONE, false, 0, 0, 0, 0};
-    g.w_off = pk.append(b.P(px + "cond_proj.weight"), base, CC, 3, 0, CC);
+    Builder::ConvSpec cv = b.conv_spec(base, condp);
+    Builder::SegSpec g = Builder::raw_seg(ct);
+    g.w_off = cv.pk.append(b.P(px + "cond_proj.weight"), base, CC, 3, 0, CC);
+    cv.segs.push_back(g);
     const float* bb = b.P(px + "cond_proj.bias");
-    b.add_conv({g}, pk, std::vector<float>(bb, bb + base), base, condp, nullptr, 0);
+    cv.bias.assign(bb, bb + base);
+    b.add_conv(cv);
     b.release(ct);
   }
   TensorH h = b.in_conv(px, c.in_channels, has_cond ? &condp : nullptr);
@@ -1629,7 +1690,7 @@ static void build_unet(vqvs_model* m, Builder& b) {
       ins.push_back(skips.back());
       skips.pop_back();
     }
-    TensorH o = b.resblock(s.prefix, s, ins, true, film.row[i], film.R, film.film_off, keep_bw ? &recs[i] : nullptr);
+    TensorH o = b.resblock(s.prefix, s, ins, film.rows(i), keep_bw ? &recs[i] : nullptr);
     if (s.cat) b.release(ins[1]);
     b.release(h);
     h = o;
@@ -1640,7 +1701,7 @@ static void build_unet(vqvs_model* m, Builder& b) {
     b.tap(s.prefix, h);
   }
   // ---- output head (unet.py:113-116, 162)
-  const Builder::GnHead gh = b.head_gn(h, px + "out.0.0", keep_bw);
+  const Builder::GnTables gh = b.head_gn(h, px + "out.0.0", keep_bw);
   // (persist is read by release() alone, and nothing between here and the tails releases -- new_tensor, blob entries and add_conv do
   //  not -- so the forward ends here for every kind, although the tails allocate a little more before their first release)
   b.persist = false;
@@ -1660,11 +1721,11 @@ static void build_unet(vqvs_model* m, Builder& b) {
   const size_t ss = gh.ss;
   b.op("out_conv", std::to_string(base) + "->1", (double)base, 4.0, 0, [=](const RunCtx& r) -> int {
     OutConvArgs a{};
-    a.in = bp->act(h.off);
-    a.ss = bp->ssf2(ss);
-    a.w = bp->wf(w);
+    a.in = m->act(h.off);
+    a.ss = m->ssf2(ss);
+    a.w = m->wf(w);
     a.bias = bias;
-    a.out = gradk && !r.out ? reinterpret_cast<float*>(bp->act(pred.off)) : r.out;
+    a.out = gradk && !r.out ? reinterpret_cast<float*>(m->act(pred.off)) : r.out;
     a.C = base;
     a.L = r.Lbase;
     return launch_out_conv(a, r.B, prec, r.st);
@@ -1675,7 +1736,6 @@ static void build_unet(vqvs_model* m, Builder& b) {
 // Classifier.forward (classifier.py:31-36, 111-121) + the input gradient used by cond_fn (sample_diffusion.py:34-42)
 static void build_classifier(vqvs_model* m, Builder& b) {
   const vqvs_cfg& c = m->cfg;
-  Builder* bp = &b;
   const int prec = c.precision, base = c.base_channels, F = classifier_output_mult(c) * base, NL = c.num_labels;
   std::vector<BlockSpec> blocks;
   const int cur = classifier_blocks(base, topo_of(c), blocks);
@@ -1687,11 +1747,11 @@ static void build_classifier(vqvs_model* m, Builder& b) {
   b.tap("stem.in_conv", h);
   std::vector<Builder::BlockRec> recs(blocks.size());
   for (size_t i = 0; i < blocks.size(); ++i) {
-    h = b.resblock(blocks[i].prefix, blocks[i], {h}, true, film.row[i], film.R, film.film_off, &recs[i]);
+    h = b.resblock(blocks[i].prefix, blocks[i], {h}, film.rows(i), &recs[i]);
     b.tap(blocks[i].prefix, h);
   }
   // ---- head: GroupNorm + GELU + attention pool (query token only) + c_proj + GELU + Linear, and its backward
-  const Builder::GnHead gh = b.head_gn(h, "stem.out.0.0", true);
+  const Builder::GnTables gh = b.head_gn(h, "stem.out.0.0", true);
   const int ch = std::min(cur, 64), heads = cur / ch;
   const float* Wqkv = b.P("stem.out.1.qkv_proj.weight");  // [3*cur][cur][1]: q rows, k rows, v rows
   const float* bqkv = b.P("stem.out.1.qkv_proj.bias");
@@ -1720,9 +1780,9 @@ static void build_classifier(vqvs_model* m, Builder& b) {
   const int groups_h = gn_groups(cur);
   b.op("cls_head", "C=" + std::to_string(cur), 0, 0, 0, [=](const RunCtx& r) -> int {
     HeadArgs a{};
-    a.h = bp->act(h.off);
-    a.ss = bp->ssf2(gh.ss);
-    a.mr = bp->ssf2(gh.mr);
+    a.h = m->act(h.off);
+    a.ss = m->ssf2(gh.ss);
+    a.mr = m->ssf2(gh.mr);
     a.C = cur;
     a.L = shiftL(r.Lbase, h.lshift);
     a.heads = heads;
@@ -1730,23 +1790,23 @@ static void build_classifier(vqvs_model* m, Builder& b) {
     a.NL = NL;
     a.groups = groups_h;
     a.inv_count = 1.0 / ((double)(cur / groups_h) * (double)a.L);
-    a.r = bp->wf(r_off);
-    a.c0 = bp->wf(c0_off);
-    a.wv = bp->wf(wv_off);
-    a.wvT = bp->wf(wvT_off);
-    a.wcT = bp->wf(wcT_off);
-    a.wlT = bp->wf(wlT_off);
-    a.bv = bp->wf(bv_off);
-    a.wc = bp->wf(wc_off);
-    a.bc = bp->wf(bc_off);
-    a.wl = bp->wf(wl_off);
-    a.bl = bp->wf(bl_off);
+    a.r = m->wf(r_off);
+    a.c0 = m->wf(c0_off);
+    a.wv = m->wf(wv_off);
+    a.wvT = m->wf(wvT_off);
+    a.wcT = m->wf(wcT_off);
+    a.wlT = m->wf(wlT_off);
+    a.bv = m->wf(bv_off);
+    a.wc = m->wf(wc_off);
+    a.bc = m->wf(bc_off);
+    a.wl = m->wf(wl_off);
+    a.bl = m->wf(bl_off);
     a.logits = r.out;
     a.feat = r.feat;
     a.probs = r.probs;
     a.labels = r.backward ? r.labels : nullptr;
     a.gscale = grad_scale(prec);  // (the caller's scale multiplies the finished gradient in fp32, in_conv_bw: the 2-byte gradient tensors never see it)
-    a.dh = bp->act(dh.off);
+    a.dh = m->act(dh.off);
     return launch_cls_head(a, r.B, prec, r.st);
   });
   // ---- backward schedule (phase 1): blocks in reverse, then the 1 -> base input convolution
@@ -1764,8 +1824,7 @@ static void build_classifier(vqvs_model* m, Builder& b) {
 //   even half: (0, W1, W3), odd half: (W0, W2, 0).
 static void build_mfcc_encoder(vqvs_model* m, Builder& b) {
   const vqvs_cfg& c = m->cfg;
-  Builder* bp = &b;
-  const int prec = c.precision, base = c.base_channels;
+  const int base = c.base_channels;
   const int version = c.reserved[1], ulaw = c.reserved[2] ? 1 : 0;
   const int n_fft = version == 2 ? 400 : 2 * MFCC_HOP, n_mels = version == 2 ? 80 : 40, n_freqs = n_fft / 2 + 1, mid = 12 * base;
   const int OC = c.out_channels;
@@ -1788,17 +1847,17 @@ static void build_mfcc_encoder(vqvs_model* m, Builder& b) {
   b.op("mfcc_logmel", "n_fft=" + std::to_string(n_fft) + " mels=" + std::to_string(n_mels), 0, 4.0, 0, [=](const RunCtx& r) -> int {
     if (r.logmel != nullptr) {  // testing entry (vqvs_mfcc_encoder_forward_logmel): injected log-mel rows, the transform is skipped
       if (db) VQVS_FAIL(-1, "the injected log-mel entry exists for the log_mels (version 1) front end only");
-      VQVS_HIP(hipMemcpyAsync(bp->miscp(logmel_off), r.logmel, (size_t)r.B * shiftL(r.Lbase, LEN_FRAMES) * n_mels * sizeof(float),
+      VQVS_HIP(hipMemcpyAsync(m->miscp(logmel_off), r.logmel, (size_t)r.B * shiftL(r.Lbase, LEN_FRAMES) * n_mels * sizeof(float),
                               hipMemcpyDeviceToDevice, r.st));
       return 0;
     }
     MfccArgs a{};
     a.x = r.x;
-    a.twiddle = reinterpret_cast<const double*>(bp->wp(tw_off));
-    a.window = bp->wf(win_off);
-    a.fb = bp->wf(fb_off);
-    a.logmel = bp->miscp(logmel_off);
-    a.wgmax = db ? bp->miscp(wgmax_off) + 64 : nullptr;
+    a.twiddle = reinterpret_cast<const double*>(m->wp(tw_off));
+    a.window = m->wf(win_off);
+    a.fb = m->wf(fb_off);
+    a.logmel = m->miscp(logmel_off);
+    a.wgmax = db ? m->miscp(wgmax_off) + 64 : nullptr;
     a.T = r.Lbase;
     a.n_fft = n_fft;
     a.hop = MFCC_HOP;
@@ -1809,15 +1868,15 @@ static void build_mfcc_encoder(vqvs_model* m, Builder& b) {
     a.log_mels = db ? 0 : 1;
     a.power_scale = power_scale;
     if (int e = launch_mfcc_logmel(a, r.B, r.st)) return e;
-    if (db) return launch_mfcc_batch_max(bp->miscp(wgmax_off) + 64, r.B * mfcc_groups(a.frames), bp->miscp(wgmax_off), r.st);
+    if (db) return launch_mfcc_batch_max(m->miscp(wgmax_off) + 64, r.B * mfcc_groups(a.frames), m->miscp(wgmax_off), r.st);
     return 0;
   });
   b.op("mfcc_features", "13 x 3 -> 64 channels", 64.0 / MFCC_HOP, 0, 0, [=](const RunCtx& r) -> int {
     MfccFeatArgs a{};
-    a.logmel = bp->miscp(logmel_off);
-    a.dct = bp->wf(dct_off);
-    a.batch_max = db ? bp->miscp(wgmax_off) : nullptr;
-    a.feat = reinterpret_cast<float*>(bp->act(feat.off));
+    a.logmel = m->miscp(logmel_off);
+    a.dct = m->wf(dct_off);
+    a.batch_max = db ? m->miscp(wgmax_off) : nullptr;
+    a.feat = reinterpret_cast<float*>(m->act(feat.off));
     a.frames = shiftL(r.Lbase, LEN_FRAMES);
     a.rows_alloc = a.frames;
     a.n_mels = n_mels;
@@ -1829,10 +1888,16 @@ static void build_mfcc_encoder(vqvs_model* m, Builder& b) {
     TensorH view = in;
     view.C = in_C;
     view.lshift = in_lshift;
-    PackedConv pk(prec);
-    Builder::SegSpec g{view, 0, in_C, ktaps, 1, RESIZE_NONE, false, 0, 0, 0, 0};
-    g.w_off = pk.append(W.data(), cout, cin, ktaps, 0, in_C);
-    b.add_conv({g}, pk, std::vector<float>(bias, bias + cout), cout, out, skip, RESIZE_NONE, out_lshift, gelu);
+    Builder::ConvSpec cv = b.conv_spec(cout, out);
+    Builder::SegSpec g = Builder::raw_seg(view);
+    g.ntaps = ktaps;
+    g.w_off = cv.pk.append(W.data(), cout, cin, ktaps, 0, in_C);
+    cv.segs.push_back(g);
+    cv.bias.assign(bias, bias + cout);
+    if (skip) cv.skip = *skip;
+    cv.out_lshift = out_lshift;  // (the allocation of `out` may hold a padding row more)
+    cv.epi_gelu = gelu;
+    b.add_conv(cv);
   };
   auto wvec = [&](const std::string& name, size_t n) { return std::vector<float>(b.P(name), b.P(name) + n); };
   // blocks.0: Conv1d(39 -> mid, 3) + GELU over the zero-padded 64-channel feature rows
@@ -1852,7 +1917,7 @@ static void build_mfcc_encoder(vqvs_model* m, Builder& b) {
   b.op("pad_row", "", 0, 0, 0, [=](const RunCtx& r) -> int {
     const int frames = shiftL(r.Lbase, LEN_FRAMES), rows = shiftL(r.Lbase, LEN_FRAMES_PAD);
     if (rows == frames) return 0;
-    VQVS_HIP(hipMemset2DAsync(bp->act(h1.off) + (size_t)frames * mid * 4, (size_t)rows * mid * 4, 0, (size_t)mid * 4, r.B, r.st));
+    VQVS_HIP(hipMemset2DAsync(m->act(h1.off) + (size_t)frames * mid * 4, (size_t)rows * mid * 4, 0, (size_t)mid * 4, r.B, r.st));
     return 0;
   });
   conv_layer(h0, mid, LEN_FRAMES, wvec("blocks.1.conv.weight", (size_t)mid * mid * 3), mid, mid, 3, b.P("blocks.1.conv.bias"), h1,
@@ -1901,12 +1966,12 @@ static void build_encoder(vqvs_model* m, Builder& b) {
   TensorH h = b.in_conv("", c.in_channels, nullptr, nullptr, 1);
   b.tap("in_conv", h);
   for (auto& s : blocks) {
-    TensorH o = b.resblock(s.prefix, s, {h}, false, 0, 0, 0);
+    TensorH o = b.resblock(s.prefix, s, {h}, std::nullopt);
     b.release(h);
     h = o;
     b.tap(s.prefix, h);
   }
-  const Builder::GnHead gh = b.head_gn(h, "out.0.0", false);
+  const Builder::GnTables gh = b.head_gn(h, "out.0.0", false);
   b.to_nct(b.head_conv(h, gh, "out.1", c.out_channels, topo_of(c).levels() - 1));
 }
 
@@ -1914,10 +1979,7 @@ int build_model(vqvs_model* m, const float* const* hp) {
   const vqvs_cfg& c = m->cfg;
   if (int e = check_cfg(c)) return e;
   if (int e = enumerate_params(c, m->params)) return e;
-  // NOTE: the builder object must outlive the ops (lambdas capture it for pointer resolution).
-  auto keep = std::make_shared<Builder>(m, hp);
-  m->keepalive = keep;
-  Builder& b = *keep;
+  Builder b(m, hp);
   switch (c.kind) {
     case VQVS_KIND_RESBLOCK: build_resblock(m, b); break;
     case VQVS_KIND_PREDICTOR:
@@ -1948,8 +2010,6 @@ int build_model(vqvs_model* m, const float* const* hp) {
   VQVS_HIP(hipMemcpy(m->d_weights, b.blob.data.data(), b.blob.data.size(), hipMemcpyHostToDevice));
   VQVS_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_arena), m->arena_bytes));
   VQVS_HIP(hipMemset(m->d_arena, 0, m->arena_bytes));
-  b.blob.data.clear();
-  b.blob.data.shrink_to_fit();
   return 0;
 }
 

@@ -102,8 +102,17 @@ struct vqvs_model {
   size_t weights_bytes = 0;
   char* d_arena = nullptr;
   size_t arena_bytes = 0;
-  // arena regions
+  // arena regions, laid out by build_model after planning: [activations | stats | ss | misc]
   size_t act_bytes = 0, stats_off = 0, stats_floats = 0, ss_off = 0, ss_floats = 0, misc_off = 0, misc_floats = 0;
+  // ---- pointer resolution at run time: the one statement of that layout (the schedule entries and the debug readers of api.cpp hold
+  // byte offsets into the activations and the weight blob, float offsets into the other three regions)
+  char* act(size_t off) const { return d_arena + off; }
+  float* statp(size_t foff) const { return reinterpret_cast<float*>(d_arena + stats_off) + foff; }
+  float* ssp(size_t foff) const { return reinterpret_cast<float*>(d_arena + ss_off) + foff; }
+  float* miscp(size_t foff) const { return reinterpret_cast<float*>(d_arena + misc_off) + foff; }
+  char* wp(size_t off) const { return d_weights + off; }
+  const float* wf(size_t off) const { return reinterpret_cast<const float*>(wp(off)); }  // a float32 entry of the weight blob
+  float2* ssf2(size_t foff) const { return reinterpret_cast<float2*>(ssp(foff)); }       // a (scale, shift) / (mean, rstd) table
   std::vector<std::function<int(const vqvs::RunCtx&)>> ops;
   struct OpMeta {
     std::string kind;      // "conv", "gn_prepare", "in_conv", ...
@@ -135,7 +144,6 @@ struct vqvs_model {
   int dfilm_R = 0;
   size_t film_misc_off = 0;  // FiLM rows [max_batch][film_R] of the last forward, the `film` op's output (misc region, floats); film_R = 0: none
   int film_R = 0;
-  std::shared_ptr<void> keepalive;  // schedule builder (resolves arena/weight offsets for the ops)
 };
 
 namespace vqvs {
